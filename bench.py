@@ -8,6 +8,11 @@ KKTSystem::solve.  Inputs (problem matrices, the interior (s,z) state, the right
 in HBM before the timed region starts; calls go through the C-ABI in PQ_MEM_DEVICE pointer mode.
 
   python bench.py --gpus N --steps K --warmup W        (N>1: under torch.distributed.run, or alone -- it then starts the N ranks itself)
+  python bench.py ... --dump-outputs DIR               (also writes the solutions of the last timed step to DIR/*.npy, float64)
+  python bench.py ... --full                           (also every secondary leg: CPU baselines, the other dense solvers, the per-kernel pass and
+                                                        roofline, the batched / sparse / small-QP legs, the size sweep, at N > 1 the stage-partitioned leg)
+
+A plain run (no --full) sets up, warms up, times the K steps of the headline and prints its result line, nothing else.
 
 Multi-GPU: the dense single-QP path does not shard (SURVEY.md 8e "replicas only"); with N ranks every
 rank factors+solves its own independent QP instance of the same shape (weak scaling, no data-path
@@ -71,8 +76,9 @@ def pmc_traffic(kernel_key, n, m, p):
     return None, None
 
 
-def dense_leg(piqp_amd, pd, torch, np, q, n, p, m, kkt_solver, refine, steps, warmup, rank, world, local_rank, dev, kernel_pass=0):
-    """times `steps` KKT steps (1 update_scalings_and_factor + 2 KKTSystem::solve) with every input resident in HBM; returns the raw figures"""
+def dense_leg(piqp_amd, pd, torch, np, q, n, p, m, kkt_solver, refine, steps, warmup, rank, world, local_rank, dev, kernel_pass=0, capture=False):
+    """times `steps` KKT steps (1 update_scalings_and_factor + 2 KKTSystem::solve) with every input resident in HBM; returns the raw figures
+    (capture: also the predictor and corrector solutions of the last timed step, as host arrays, under "outputs")"""
     from qp_gen import random_vars
     ksys = piqp_amd.KKTSystem(piqp_amd.Data(**q), piqp_amd.default_settings(kkt_solver=kkt_solver), device=local_rank)
     backend = ksys.backend()
@@ -80,13 +86,15 @@ def dense_leg(piqp_amd, pd, torch, np, q, n, p, m, kkt_solver, refine, steps, wa
     # two interior IPM states and rhs sets, alternated so no step re-reads its predecessor's vectors
     states = [{k: torch.from_numpy(v).to(dev) for k, v in random_vars(n, p, m, rng, positive=True).items()} for _ in range(2)]
     rhss = [{k: torch.from_numpy(v).to(dev) for k, v in random_vars(n, p, m, rng).items()} for _ in range(4)]
-    lhs = {k: torch.zeros_like(v) for k, v in rhss[0].items()}
+    # the predictor and the corrector each write their own solution, so that both are still there after the last step
+    lhs_p = {k: torch.zeros_like(v) for k, v in rhss[0].items()}
+    lhs_c = {k: torch.zeros_like(v) for k, v in rhss[0].items()}
     rho, delta = 1e-6, 1e-4
 
     def step(i):
         ok = ksys.update_scalings_and_factor(refine, rho, delta, states[i & 1])
-        ok1, _ = ksys.solve(rhss[(2 * i) & 3], lhs)       # predictor
-        ok2, _ = ksys.solve(rhss[(2 * i + 1) & 3], lhs)   # corrector
+        ok1, _ = ksys.solve(rhss[(2 * i) & 3], lhs_p)     # predictor
+        ok2, _ = ksys.solve(rhss[(2 * i + 1) & 3], lhs_c)  # corrector
         return ok and ok1 and ok2
 
     def barrier():
@@ -96,9 +104,6 @@ def dense_leg(piqp_amd, pd, torch, np, q, n, p, m, kkt_solver, refine, steps, wa
 
     for i in range(warmup):
         assert step(i), "factorisation failed in warmup"
-    res, nrm = ksys.condensed_residual()  # parity gate: relative KKT residual of the last solve
-    rel_res = res / nrm
-    assert rel_res <= 1e-10, f"KKT residual {rel_res:.3e} above 1e-10"
     backend.set_profiling(1)
     # Python's cyclic collector stays out of the timed region: a generation-2 collection of a process that has torch imported takes 35-75 ms and lands inside
     # whichever call is running when the allocation counter trips -- that, not the library or the device, was every multi-millisecond step of the round-5 size
@@ -118,10 +123,15 @@ def dense_leg(piqp_amd, pd, torch, np, q, n, p, m, kkt_solver, refine, steps, wa
         gc.enable()
     assert ok
     backend.set_profiling(0)
+    res, nrm = ksys.condensed_residual()  # parity gate: relative KKT residual of the last timed solve
+    rel_res = res / nrm
+    assert rel_res <= 1e-10, f"KKT residual {rel_res:.3e} above 1e-10"
     elapsed = pd.max_over_ranks(t1 - t0, device=dev if world > 1 else None)
     prof = [backend.get_profile(s) for s in range(3)]
     out = {"elapsed": elapsed, "rel_res": rel_res, "asm_ms": prof[0][0] / max(prof[0][1], 1), "fac_ms": prof[1][0] / max(prof[1][1], 1),
            "sol_ms": prof[2][0] / max(prof[2][1], 1), "backend_solves_per_step": prof[2][1] / steps, "refine": ksys.last_solve_stats()}
+    if capture:  # before the kernel pass below, which runs the steps again into the same buffers
+        out["outputs"] = {f"{tag}_{k}": v.cpu().numpy() for tag, lhs in (("predictor", lhs_p), ("corrector", lhs_c)) for k, v in lhs.items()}
     if kernel_pass > 0:
         # kernel-level brackets (hipEvents around every fused-update / panel-solve / sweep launch on the backend's stream) in a SEPARATE
         # pass of the same steps right after the timed region: 62 extra event markers between dependent launches would cost the timed
@@ -155,8 +165,14 @@ def main():
     ap.add_argument("--cpu-steps", type=int, default=0, help="0 = auto (about 10-30 s of CPU work)")
     ap.add_argument("--no-size-sweep", action="store_true", help="skip the dense size sweep n = 64 .. 4096 (device vs CPU oracle, the crossover)")
     ap.add_argument("--no-dist-c5", action="store_true", help="N > 1 only: skip the stage-partitioned single-QP leg (BASELINE configs[4])")
+    ap.add_argument("--full", action="store_true", help="also run every secondary leg (CPU baselines, other dense solvers, per-kernel pass and roofline, batched / "
+                                                        "sparse / small-QP legs, size sweep, stage-partitioned leg at N > 1); off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the predictor and corrector solutions of the last timed step (rank 0) to DIR/<name>.npy, float64")
     ap.add_argument("--cpu-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.cpu_child:
         return cpu_child(args)
     self_launch(args)
@@ -166,7 +182,7 @@ def main():
     # itself so that the oracle threads of the later single-thread sparse checks never spin behind a device leg (round-4 advice: the passive policy and the cold
     # calibration call biased the CPU numbers downwards).
     cpu_dense = None
-    if int(os.environ.get("WORLD_SIZE", "1")) <= 1 and args.gpus <= 1 and not args.no_cpu_baseline:
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) <= 1 and args.gpus <= 1 and not args.no_cpu_baseline:
         import subprocess
         env = {k: v for k, v in os.environ.items() if k != "OMP_WAIT_POLICY"}
         try:
@@ -181,7 +197,7 @@ def main():
     # processes with their own process group so that nothing in there can cost this run its JSON line; the children are started here,
     # before this process touches the GPU, and wait on stdin until the other legs are done.
     c5_child = c5_native_child = None
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1 and not args.no_dist_c5 and not args.no_sparse_legs:
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) > 1 and not args.no_dist_c5 and not args.no_sparse_legs:
         import importlib.util
         spec = importlib.util.spec_from_file_location("_pq_dist_spawn", os.path.join(ROOT, "piqp_amd", "dist.py"))
         spawn_mod = importlib.util.module_from_spec(spec); spec.loader.exec_module(spawn_mod)
@@ -198,8 +214,8 @@ def main():
 
     assert torch.cuda.is_available(), "bench.py needs a GPU (no CPU fallback)"
     rank, world, local_rank = pd.init()  # RCCL ("nccl") process group when WORLD_SIZE > 1; local_rank = device index of this rank
-    if world > 1:
-        args.no_cpu_baseline = True  # the CPU baseline is a rank-0, N = 1 figure (torch.distributed.run also pins OMP_NUM_THREADS=1)
+    if world > 1 or not args.full:
+        args.no_cpu_baseline = True  # the CPU baseline is a rank-0, N = 1 figure (torch.distributed.run also pins OMP_NUM_THREADS=1), and a --full one
     dev = torch.device("cuda", local_rank)
     from qp_gen import dense_strongly_convex_qp
 
@@ -209,9 +225,12 @@ def main():
     # round 1 ran torch.linalg.eigvalsh here and its rocSOLVER kernels polluted the rocprofv3 summaries of this command)
     q = dense_strongly_convex_qp(n, p, m, seed=43 + rank, double_sided=True, exact_shift=False)
     solver_name = {0: "dense_cholesky", 16: "dense_ldlt_no_pivot"}
-    main_leg = dense_leg(piqp_amd, pd, torch, np, q, n, p, m, args.kkt_solver, False, args.steps, args.warmup, rank, world, local_rank, dev, kernel_pass=5)
+    main_leg = dense_leg(piqp_amd, pd, torch, np, q, n, p, m, args.kkt_solver, False, args.steps, args.warmup, rank, world, local_rank, dev,
+                         kernel_pass=5 if args.full else 0, capture=args.dump_outputs is not None and rank == 0)
+    if "outputs" in main_leg:
+        dump_outputs(args.dump_outputs, main_leg.pop("outputs"))
     extra = {}
-    if not args.no_extra_dense_legs:
+    if args.full and not args.no_extra_dense_legs:
         other = 16 if args.kkt_solver == 0 else 0
         for key, ks, refine in ((solver_name[other], other, False), (solver_name[args.kkt_solver] + "+iterative_refinement", args.kkt_solver, True)):
             extra[key] = dense_leg(piqp_amd, pd, torch, np, q, n, p, m, ks, refine, max(5, args.steps // 2), 2, rank, world, local_rank, dev, kernel_pass=3)
@@ -223,39 +242,11 @@ def main():
         elapsed = main_leg["elapsed"]
         ms_per_step = elapsed / args.steps * 1e3
         value = world * args.steps / elapsed
-        kk = main_leg["kernels"]
+        kk = main_leg.get("kernels")  # the separate per-kernel pass: --full only
         flops_asm = float(n) * (n + 1) * m                    # k_syrk_lower<EPI_ASSEMBLE>, SURVEY.md 8d (C2)
         flops_upd, upd_launches = panel_update_flops(n)       # all fused trailing-update launches of one factorisation
         flops_llt = n ** 3 / 3.0
         asm_s = main_leg["asm_ms"] * 1e-3
-        upd_s = kk["fused_ms_per_step"] * 1e-3
-
-        def roof(kernel, flops_per_step, secs_per_step, launches_per_step, key):
-            traffic, src = pmc_traffic(key, n, m, p)
-            ach = flops_per_step / secs_per_step / 1e12 if secs_per_step > 0 else 0.0
-            return {"bound": "mfma", "kernel": kernel, "achieved": ach, "peak": PEAK_FP64_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": ach / PEAK_FP64_MFMA_TFLOPS,
-                    "traffic": traffic, "traffic_source": src, "alg_flops_per_launch": flops_per_step / max(launches_per_step, 1),
-                    "avg_launch_ms": secs_per_step * 1e3 / max(launches_per_step, 1), "launches_per_step": launches_per_step, "ms_per_step": secs_per_step * 1e3}
-        # the assembly stage is two k_syrk_lower<EPI_ASSEMBLE,2,2> launches (main tiles; split-K tail tiles) + k_syrk_tail_reduce (launch_syrk_t in dense_kernels.hip)
-        r_asm = roof("k_syrk_lower<EPI_ASSEMBLE> (dense/kkt.hpp:140-160 update_kkt): 2 launches per factorisation (main tiles, split-K tail) + k_syrk_tail_reduce; "
-                     "stage hipEvent-bracketed in the timed region, per-launch figures = stage / 2", flops_asm, asm_s, 2, "assembly")
-        persistent = kk["fused_launches_per_step"] < 1.5  # round 3: every round of the factorisation after the first diagonal block / panel in ONE launch
-        if persistent:
-            r_upd = roof("k_chol_persistent = the whole blocked factorisation after its first diagonal block and panel in ONE persistent launch: for every panel the "
-                         "trailing (panel) update, the factorisation of the next diagonal block and the substitution of the next panel behind it, as a ticket-ordered "
-                         "task list with look-ahead (dense/ldlt_no_pivot.hpp:313-354, Eigen::LLT at dense/kkt.hpp:82); hipEvent-bracketed in a separate pass of "
-                         "the same steps", flops_upd, upd_s, 1, "panel_update")
-        else:
-            r_upd = roof("k_syrk_lower<EPI_SUBTRACT_POTRF> = one launch per panel: trailing (panel) update of the factorisation + factorisation of the next diagonal "
-                         "block + substitution of the next panel behind it (dense/ldlt_no_pivot.hpp:313-354, Eigen::LLT at dense/kkt.hpp:82); hipEvent-bracketed per "
-                         "launch in a separate pass of the same steps", flops_upd, upd_s, upd_launches, "panel_update")
-        # `roofline` is the factorisation launch: the kernel the north star names ("MFMA panel update"), the longest single launch of the step and the one
-        # furthest from its bound.  The assembly STAGE (three unequal launches: main tiles, split-K tail, tail reduce -- bracketed as one) takes about as long
-        # per step; it is reported beside it with its own fraction, and `longest_stage` says which of the two stages took more of this run's step (round-5
-        # advice: the choice must not hide that)
-        dominant, secondary = r_upd, r_asm
-        longest = {"stage": "assembly" if asm_s > upd_s else "factorisation", "assembly_ms_per_step": asm_s * 1e3, "factorisation_launch_ms_per_step": upd_s * 1e3,
-                   "assembly_frac_of_peak": r_asm["frac"], "factorisation_frac_of_peak": r_upd["frac"]}
         out = {
             "metric": "KKT factor+solve/sec (per IPM iter)",
             "value": value,
@@ -270,14 +261,9 @@ def main():
             "config": {"workload": f"dense QP n={n} p={p} m_ineq={m} (BASELINE configs[1]), kkt_solver={solver_name[args.kkt_solver]}, "
                                    "1 update_scalings_and_factor + 2 KKTSystem::solve per step, inputs resident in HBM",
                        "n": n, "p": p, "m": m, "parallelism": f"independent QP replicas x{world}"},
-            "roofline": dominant,            # the factorisation launch (see above)
-            "roofline_secondary": secondary,
-            "longest_stage": longest,
             "stages": {"assembly_ms": main_leg["asm_ms"], "factorisation_ms": main_leg["fac_ms"],
                        "factorisation_tflops": flops_llt / (main_leg["fac_ms"] * 1e-3) / 1e12 if main_leg["fac_ms"] > 0 else 0.0,
-                       "backend_solve_ms": main_leg["sol_ms"], "panel_update_ms": kk["fused_ms_per_step"], "panel_solve_ms": kk["trsm_ms_per_step"],
-                       "triangular_sweeps_ms_per_solve": kk["sweeps_ms_per_solve"],
-                       "step_tflops": (flops_asm + flops_llt) / (ms_per_step * 1e-3) / 1e12},
+                       "backend_solve_ms": main_leg["sol_ms"], "step_tflops": (flops_asm + flops_llt) / (ms_per_step * 1e-3) / 1e12},
             "parity": {"rel_kkt_residual": main_leg["rel_res"], "tolerance": 1e-10},
             "process_group": {"collective_backend": (torch.distributed.get_backend() if (world > 1 and torch.distributed.is_initialized()) else "none (single process)"),
                               "ranks_seen": (torch.distributed.get_world_size() if (world > 1 and torch.distributed.is_initialized()) else 1),
@@ -285,6 +271,40 @@ def main():
                               "data_path_collectives": "none in this leg (independent replicas / shards); barrier + MAX of the elapsed time + final gather only",
                               "note": "no multi-GPU figure was measured by the build itself (1-GPU boxes only): every N > 1 number is the driver's"},
         }
+        if kk is not None:
+            upd_s = kk["fused_ms_per_step"] * 1e-3
+
+            def roof(kernel, flops_per_step, secs_per_step, launches_per_step, key):
+                traffic, src = pmc_traffic(key, n, m, p)
+                ach = flops_per_step / secs_per_step / 1e12 if secs_per_step > 0 else 0.0
+                return {"bound": "mfma", "kernel": kernel, "achieved": ach, "peak": PEAK_FP64_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": ach / PEAK_FP64_MFMA_TFLOPS,
+                        "traffic": traffic, "traffic_source": src, "alg_flops_per_launch": flops_per_step / max(launches_per_step, 1),
+                        "avg_launch_ms": secs_per_step * 1e3 / max(launches_per_step, 1), "launches_per_step": launches_per_step, "ms_per_step": secs_per_step * 1e3}
+            # the assembly stage is two k_syrk_lower<EPI_ASSEMBLE,2,2> launches (main tiles; split-K tail tiles) + k_syrk_tail_reduce (launch_syrk_t in dense_kernels.hip)
+            r_asm = roof("k_syrk_lower<EPI_ASSEMBLE> (dense/kkt.hpp:140-160 update_kkt): 2 launches per factorisation (main tiles, split-K tail) + k_syrk_tail_reduce; "
+                         "stage hipEvent-bracketed in the timed region, per-launch figures = stage / 2", flops_asm, asm_s, 2, "assembly")
+            persistent = kk["fused_launches_per_step"] < 1.5  # round 3: every round of the factorisation after the first diagonal block / panel in ONE launch
+            if persistent:
+                r_upd = roof("k_chol_persistent = the whole blocked factorisation after its first diagonal block and panel in ONE persistent launch: for every panel the "
+                             "trailing (panel) update, the factorisation of the next diagonal block and the substitution of the next panel behind it, as a ticket-ordered "
+                             "task list with look-ahead (dense/ldlt_no_pivot.hpp:313-354, Eigen::LLT at dense/kkt.hpp:82); hipEvent-bracketed in a separate pass of "
+                             "the same steps", flops_upd, upd_s, 1, "panel_update")
+            else:
+                r_upd = roof("k_syrk_lower<EPI_SUBTRACT_POTRF> = one launch per panel: trailing (panel) update of the factorisation + factorisation of the next diagonal "
+                             "block + substitution of the next panel behind it (dense/ldlt_no_pivot.hpp:313-354, Eigen::LLT at dense/kkt.hpp:82); hipEvent-bracketed per "
+                             "launch in a separate pass of the same steps", flops_upd, upd_s, upd_launches, "panel_update")
+            # `roofline` is the factorisation launch: the kernel the north star names ("MFMA panel update"), the longest single launch of the step and the one
+            # furthest from its bound.  The assembly STAGE (three unequal launches: main tiles, split-K tail, tail reduce -- bracketed as one) takes about as long
+            # per step; it is reported beside it with its own fraction, and `longest_stage` says which of the two stages took more of this run's step (round-5
+            # advice: the choice must not hide that)
+            dominant, secondary = r_upd, r_asm
+            longest = {"stage": "assembly" if asm_s > upd_s else "factorisation", "assembly_ms_per_step": asm_s * 1e3, "factorisation_launch_ms_per_step": upd_s * 1e3,
+                       "assembly_frac_of_peak": r_asm["frac"], "factorisation_frac_of_peak": r_upd["frac"]}
+            out["roofline"] = dominant  # the factorisation launch (see above)
+            out["roofline_secondary"] = secondary
+            out["longest_stage"] = longest
+            out["stages"].update({"panel_update_ms": kk["fused_ms_per_step"], "panel_solve_ms": kk["trsm_ms_per_step"],
+                                  "triangular_sweeps_ms_per_solve": kk["sweeps_ms_per_solve"]})
         for key, leg in extra.items():
             st = max(5, args.steps // 2)
             out.setdefault("dense_legs", {})[key] = {
@@ -300,27 +320,27 @@ def main():
         out = None
     # second half of BASELINE.json's metric ("QP solves/sec at 1/2/4/8 GPUs"): the batched sparse_multistage leg
     # (the secondary legs must never cost the run its JSON line: a failure is reported in place of the leg)
-    if args.batch_total > 0:
+    if args.full and args.batch_total > 0:
         try:
             bq = batched_qp(args, rank, world, local_rank, dev, pd)
         except Exception as e:  # noqa: BLE001
             bq = {"error": f"{type(e).__name__}: {e}"}
         if rank == 0:
             out["batched_qp"] = bq
-    if world == 1 and not args.no_size_sweep:
+    if args.full and world == 1 and not args.no_size_sweep:
         try:
             sw = dense_size_sweep(piqp_amd, pd, torch, np, args, rank, world, local_rank, dev, (cpu_dense or {}).get("sweep"))
         except Exception as e:  # noqa: BLE001
             sw = {"error": f"{type(e).__name__}: {e}"}
         out["dense_size_sweep"] = sw
-    if not args.no_sparse_legs:
+    if args.full and not args.no_sparse_legs:
         try:
             sl = sparse_legs(args, rank, world, local_rank, dev, pd)
         except Exception as e:  # noqa: BLE001
             sl = {"error": f"{type(e).__name__}: {e}"}
         if rank == 0:
             out["sparse_kkt"] = sl
-    if world == 1 and not args.no_sparse_legs:
+    if args.full and world == 1 and not args.no_sparse_legs:
         try:
             sq = small_qp_legs(args)
         except Exception as e:  # noqa: BLE001
@@ -352,8 +372,22 @@ def main():
                 out["stage_partitioned_c5"]["native_rccl_transport"] = {"error": f"child returncode {rc} (None = timed out after 180 s)", "stderr_tail": n_err}
         pd.barrier()
     if rank == 0:
-        emit(out)
+        if args.full:
+            emit(out)
+        else:
+            print(contract_line(out, details=False), flush=True)
     pd.finalize()
+
+
+def dump_outputs(d, arrays, limit_bytes=64 << 20):
+    """--dump-outputs: one DIR/<name>.npy (float64) per non-empty solution vector of the last timed step; the inputs are seeded, so two builds
+    run with the same arguments can be compared array for array"""
+    import numpy as np
+    arrays ={k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items() if v.size}
+    assert sum(v.nbytes for v in arrays.values()) <= limit_bytes, "outputs above the dump limit"
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), v)
 
 
 def emit(out, limit=6144):
@@ -368,6 +402,12 @@ def emit(out, limit=6144):
         except OSError:
             pass
     print("#details " + full, flush=True)
+    print(contract_line(out, limit), flush=True)
+
+
+def contract_line(out, limit=6144, details=True):
+    """the result line: the required keys + config + roofline + cpu_baseline + parity + stages + one scalar per secondary leg (the parts a
+    plain run did not measure are left out), at most `limit` bytes"""
 
     def short(v, n=200):
         return v if not isinstance(v, str) or len(v) <= n else v[:n - 3] + "..."
@@ -381,8 +421,9 @@ def emit(out, limit=6144):
 
     line = {k: out[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data") if k in out}
     line["config"] = {k: short(v, 240) for k, v in out.get("config", {}).items()}
-    line["roofline"] = roof_short(out.get("roofline"))
-    line["roofline_secondary"] = roof_short(out.get("roofline_secondary"))
+    for k in ("roofline", "roofline_secondary"):
+        if k in out:
+            line[k] = roof_short(out[k])
     if "longest_stage" in out:
         line["longest_stage"] = out["longest_stage"]
     if "cpu_baseline" in out:
@@ -438,8 +479,10 @@ def emit(out, limit=6144):
         for k, v in sq.items():
             if isinstance(v, (int, float)):
                 legs["small_qp:" + k] = v
-    line["legs"] = legs
-    line["details"] = "bench_details.json (and the '#details' stdout line before this one)"
+    if legs:
+        line["legs"] = legs
+    if details:
+        line["details"] = "bench_details.json (and the '#details' stdout line before this one)"
     txt = json.dumps(line)
     if len(txt) > limit:  # never lose the line to its size: drop the optional parts, largest first
         for k in ("legs", "roofline_secondary", "stages", "process_group"):
@@ -447,7 +490,7 @@ def emit(out, limit=6144):
             txt = json.dumps(line)
             if len(txt) <= limit:
                 break
-    print(txt, flush=True)
+    return txt
 
 
 def sparse_legs(args, rank, world, local_rank, dev, pd):

@@ -8,12 +8,12 @@ cd $R
 ulimit -v 150000000
 timeout 2400 python3 -m pytest tests -m gpu -q -n 2 2>&1 | tail -8 > $O/r06_gpu_tests.txt
 tail -3 $O/r06_gpu_tests.txt
-timeout 1500 python3 bench.py > $O/r06_bench_stdout.txt 2> $O/r06_bench_n1.err
+timeout 1500 python3 bench.py --full > $O/r06_bench_stdout.txt 2> $O/r06_bench_n1.err
 echo "bench rc=$?"
 tail -1 $O/r06_bench_stdout.txt > $O/r06_bench_n1.json
 echo "last line bytes: $(tail -1 $O/r06_bench_stdout.txt | wc -c) (limit 6144)"
 cp bench_details.json $O/r06_bench_details.json 2>/dev/null
-rm -rf $O/ks; timeout 900 rocprofv3 --kernel-trace --stats -d $O/ks -o bench -- python3 bench.py --no-size-sweep > $O/r06_bench_under_rocprof.txt 2> $O/r06_bench_under_rocprof.err
+rm -rf $O/ks; timeout 900 rocprofv3 --kernel-trace --stats -d $O/ks -o bench -- python3 bench.py --full --no-size-sweep > $O/r06_bench_under_rocprof.txt 2> $O/r06_bench_under_rocprof.err
 echo "rocprof bench rc=$?"
 python3 tools/rocprof_summary.py $O/ks 40 > $O/r06_bench_kernel_stats.txt 2>&1
 rm -rf $O/ks
