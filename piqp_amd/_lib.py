@@ -216,7 +216,7 @@ def load():
     L.pq_solver_set_exchange.argtypes = [vp, EXCHANGE_FN, vp, vp, vp, vp]
     L.pq_debug_alloc_count.restype = C.c_longlong
     L.pq_debug_alloc_count.argtypes = []
-    L.pq_debug_chol_plan.argtypes = [C.c_int, C.c_int, vp, C.c_int]
+    L.pq_debug_chol_plan.argtypes = [C.c_int, vp, C.c_int]
     L.pq_kkt_set_exchange_norm.argtypes = [vp, vp]
     L.pq_solver_set_exchange_norm.argtypes = [vp, vp]
     L.pq_kkt_sharded_calls.argtypes = [vp, C.POINTER(C.c_int * 2)]

@@ -27,7 +27,7 @@ struct SyrkArgs {
     int tile_begin = 0;
     int k_split = 1;
     double* part = nullptr;
-    int first_col_only = 0;  // 1: only the tiles (ti, 0) of the first 128-column strip (panel look-ahead)
+    int fuse_xwant = 0;  // see fuse_xcnt (declared here: the fields the plain SYRK kernels read keep the argument offsets they need the fewest SGPRs with)
     // XCD-aware tile order (set by the launcher for long inner dimensions): tile of linear block b = tile_order[b] = ti << 16 | tj.
     // Workgroups go to the eight XCDs round-robin, so the order hands every XCD a compact 8 x 8 patch of tiles: the 64 tiles it works on at
     // the same time share 16 operand panels in its own L2 instead of nearly all of them
@@ -49,8 +49,7 @@ struct SyrkArgs {
                                     // tile column solve the next panel in this launch, following the factorisation of the diagonal block
     double* fuse_w16 = nullptr;   // inverted 16 x 16 diagonal pieces of the next diagonal block (8 x 256 doubles), kept for the sweeps; nullable
     int* fuse_xpub = nullptr;     // persistent launch only: eight counters, one per 16-column slice, that every strip wave of the first panel row bumps once
-    const int* fuse_xcnt = nullptr; // ... and the counter the crew of the next diagonal block follows (its operand arrives slice by slice), with its base value
-    int fuse_xwant = 0;
+    const int* fuse_xcnt = nullptr; // ... and the counter the crew of the next diagonal block follows (its operand arrives slice by slice), with its base value fuse_xwant
     double* fuse_side = nullptr;    // persistent launch only: the side copy of the panel being solved (same leading dimension and offsets as C)
     long long* fuse_tr2 = nullptr;  // debugging aid (PIQP_AMD_DEBUG=chol_trace): wall-clock stamps of the hand-over between the first panel row and the next crew
     long long* fuse_tr2n = nullptr;
@@ -82,21 +81,9 @@ void launch_trsm_panel(bool ldlt, double* A, int lda, int k0, int nb, int n, con
 bool chol_persistent_supported(int n);
 bool chol_prepare(int n);      // builds the device task list of this size (allocates: call at create time); false = use the launch-per-panel path
 size_t chol_flag_ints(int n);  // ints of flag storage, zeroed once at allocation
-// fused assembly (round 4): the tiles of block columns >= 1 are assembled by tasks of the persistent launch (dense/kkt.hpp:140-160); block column 0 by
-// launch_syrk_first_col before it.  m % 128 == 0, m >= 512 (chol_fused_supported).
-void launch_pack_row_panels(const double* G, int n, int m, double* Gp, hipStream_t s);  // n % 128 == 0: row panel i of G (ld = n) -> Gp + i 128 m, ld = 128
-struct CholAssembly {
-    const double* GT = nullptr; int ldg = 0, m = 0; const double* zinv = nullptr;  // GT: packed as row panels (launch_pack_row_panels), ldg unused
-    const double* Pfull = nullptr; int ldp = 0; const double* x_reg = nullptr; const double* ATA = nullptr; int ldata = 0; double dinv = 0.0;
-    double* part = nullptr;  // chol_prepare_fused(n, m) doubles
-};
-int chol_debug_plan(int T, int mchunks, int* out6, int capacity_tasks);  // host-only: the task list (mchunks > 0: with the fused assembly), 6 ints per task; returns the task count
-bool chol_fused_supported(int n, int m);
-size_t chol_prepare_fused(int n, int m);  // builds the fused task list (allocates: create time); doubles of partial-sum workspace, 0 = not available
-// the assembly of block column 0 alone (tiles (i, 0)), K split over `ks` workgroups per tile with the fixed-order reduce of the tail tiles; ws: T * ks * 128 * 128 doubles
-void launch_syrk_first_col(const SyrkArgs& args, int ks, double* ws, hipStream_t s);
+int chol_debug_plan(int T, int* out5, int capacity_tasks);  // host-only: the task list, 5 ints per task; returns the task count
 bool launch_chol_persistent(bool ldlt, double* A, double* side, int lda, int n, int* info, double* rdiag, double* dvec, double* pack2, double* w16, double* scratch, int* fuse_flags, int* fuse_cnt,
-                            int token_base, int* flags, int gen, int fcount, hipStream_t s, const CholAssembly* fused = nullptr);
+                            int token_base, int* flags, int gen, int fcount, hipStream_t s);
 size_t trsv_poll_doubles(int n);  // scratch of the persistent sweeps (launch_trsv), to be prepared once with launch_trsv_poll_init
 void launch_trsv_poll_init(double* ypoll, int n, hipStream_t s);
 // w16: the inverted 16 x 16 diagonal pieces written by the factorisation (8 x 256 doubles per 128-column panel), nullptr: substitution only

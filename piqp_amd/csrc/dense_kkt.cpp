@@ -78,8 +78,7 @@ public:
         dense::launch_reciprocal(m_, z_reg, z_reg_inv_.p, st_);
         PQ_HIP(hipMemcpyAsync(x_reg_last_.p, x_reg, sizeof(double) * n_, hipMemcpyDeviceToDevice, st_));
         int t0 = prof_.begin(0, st_);
-        if (chol_fused_) assemble_first_block_column(x_reg_last_.p);  // (the other block columns are assembled inside the persistent launch)
-        else update_kkt(x_reg_last_.p, fac_.p);
+        update_kkt(x_reg_last_.p, fac_.p);
         prof_.end(0, t0, st_);
         int t1 = prof_.begin(1, st_);
         launch_factor_panels();
@@ -209,7 +208,7 @@ private:
         alloc();
         auto cp = [&](DBuf<double>& dst, const DBuf<double>& src) { if (src.n) PQ_HIP(hipMemcpyAsync(dst.p, src.p, src.bytes(), hipMemcpyDeviceToDevice, st_)); };
         cp(Pfull_, o.Pfull_); cp(Pdiag_, o.Pdiag_); cp(AT_, o.AT_); cp(GT_, o.GT_); cp(ATA_, o.ATA_); cp(fac_, o.fac_);
-        cp(GTp_, o.GTp_); cp(vinv_, o.vinv_);
+        cp(vinv_, o.vinv_);
         cp(z_reg_inv_, o.z_reg_inv_); cp(x_reg_last_, o.x_reg_last_); cp(rdiag_, o.rdiag_); cp(w16_, o.w16_);
         stream_wait(st_);
     }
@@ -235,18 +234,6 @@ private:
         // PIQP_AMD_DEBUG=chol_launches: the launch-per-panel factorisation for every size (the bitwise comparison of tests/test_dense_gpu.py)
         chol_persistent_ = !debug_token("chol_launches") && dense::chol_prepare(n_);
         if (chol_persistent_) { side_.alloc((size_t)n_ * n_); pack2_.alloc(2 * (size_t)dense::FACTOR_PACK_DOUBLES); chol_flags_.alloc(dense::chol_flag_ints(n_)); chol_flags_.zero(st_); }
-        // round 4, EXPERIMENTAL (PIQP_AMD_DEBUG=chol_fused; default: assembly launch, then the factorisation): the assembly (dense/kkt.hpp:140-160) as tasks of the
-        // persistent launch, overlapped with the factorisation.  Correct (tools/chk_chol_fused.py) and slower at n = 4096: see DESIGN.md section 4.
-        if (chol_persistent_ && m_ > 0 && debug_token("chol_fused")) {
-            const size_t d = dense::chol_prepare_fused(n_, m_);
-            if (d > 0) {
-                chol_fused_ = true;
-                asm_part_.alloc(d);
-                GTp_.alloc((size_t)n_ * m_);
-                col0_ks_ = 8;
-                col0_ws_.alloc((size_t)(n_ / dense::FACTOR_NB) * col0_ks_ * 128 * 128);
-            }
-        }
         flags_.alloc(3); flags_.zero(st_);  // (error word and tickets of the sweeps)
         one_xcd_ = (n_ + 127) / 128 <= 32 && !debug_token("no_one_xcd") && dense::probe_one_xcd_sweeps(st_);
         ypoll_.alloc(dense::trsv_poll_doubles(n_)); dense::launch_trsv_poll_init(ypoll_.p, n_, st_);
@@ -275,7 +262,6 @@ private:
         dense::launch_symmetrize_upper(fac_.p, n_, Pfull_.p, Pdiag_.p, st_);
         copy_in(AT_.p, d->AT, (size_t)n_ * p_ * sizeof(double), d->mem, st_);
         copy_in(GT_.p, d->GT, (size_t)n_ * m_ * sizeof(double), d->mem, st_);
-        if (chol_fused_) dense::launch_pack_row_panels(GT_.p, n_, m_, GTp_.p, st_);
         if (p_ > 0) {
             // dense/kkt.hpp:53 AT_A.lower = AT * AT^T
             dense::SyrkArgs a;
@@ -303,7 +289,6 @@ private:
         a.Pfull = Pfull_.p; a.ldp = n_; a.x_reg = x_reg; a.ATA = p_ > 0 ? ATA_.p : nullptr; a.ldata = n_; a.dinv = 1.0 / delta_;
         return a;
     }
-    void assemble_first_block_column(const double* x_reg) { dense::launch_syrk_first_col(assembly_args(x_reg, fac_.p), col0_ks_, col0_ws_.p, st_); }
 
     // blocked right-looking factorisation of the lower triangle of fac_ (panel width 128): Eigen::LLT::compute (dense/kkt.hpp:82) or
     // LDLTNoPivot::compute (dense/ldlt_no_pivot.hpp:313-354).  One launch per panel: the fused trailing update of panel k also factors the NEXT
@@ -324,13 +309,8 @@ private:
             const int tt = prof_.begin(3, st_);
             // (false = no task list for this size on the current device; chol_prepare() built it at create time, so this is a programming error, not a state
             // to continue from with only the first panel factored)
-            dense::CholAssembly fa;
-            if (chol_fused_) {
-                fa.GT = GTp_.p; fa.ldg = 128; fa.m = m_; fa.zinv = z_reg_inv_.p; fa.Pfull = Pfull_.p; fa.ldp = n_; fa.x_reg = x_reg_last_.p;
-                fa.ATA = p_ > 0 ? ATA_.p : nullptr; fa.ldata = n_; fa.dinv = 1.0 / delta_; fa.part = asm_part_.p;
-            }
             if (!dense::launch_chol_persistent(ldlt_, fac_.p, side_.p, n_, n_, info_.p, rdiag_.p, dvec_.p, pack2_.p, w16_.p, fuse_scratch_.p, fuse_flags_.p, fuse_cnt_.p, fuse_token_, chol_flags_.p,
-                                               chol_gen_, chol_fcount_, st_, chol_fused_ ? &fa : nullptr))
+                                               chol_gen_, chol_fcount_, st_))
                 throw std::runtime_error("dense factorisation: the persistent launch has no plan for this size / device");
             prof_.end(3, tt, st_);
             fuse_token_ += T - 1;
@@ -413,10 +393,7 @@ private:
         inv_pending_ = false;
     }
     DBuf<double> vinv_;  // inverses of the 128-row diagonal blocks of the factor (dense_kernels.hip, launch_block_inverse_dd)
-    bool chol_persistent_ = false, chol_fused_ = false;
-    DBuf<double> GTp_;  // fused assembly: GT once more, as row panels of 128 rows (consecutive operand stages)
-    DBuf<double> asm_part_, col0_ws_;  // fused assembly: partial sums of the K-sliced tiles; of block column 0's launch
-    int col0_ks_ = 1;
+    bool chol_persistent_ = false;
     int chol_gen_ = 0, chol_fcount_ = 0;
     int fuse_token_ = 0;
     DBuf<double> ypoll_;  // the sweeps' hand-over buffers (dense_kernels.hip, launch_trsv)

@@ -6,7 +6,7 @@ import sys
 
 import numpy as np
 
-KIND = {0: "crew helper", 1: "crew owner", 2: "panel row", 3: "bulk tile", 4: "diag half", 5: "diag half", 7: "far visit", 8: "assembly token"}
+KIND = {0: "crew helper", 1: "crew owner", 2: "panel row", 3: "bulk tile", 4: "diag half", 5: "diag half", 7: "far visit"}
 
 
 def main():

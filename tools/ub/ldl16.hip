@@ -198,7 +198,7 @@ __device__ __forceinline__ void follow16(d4& acc, d4& dn, int lane, const lds_vd
     }
 }
 
-// the form the in-kernel attempt used (tools/ub/potrf_block_ldl_attempt.hip.txt): reciprocals kept in registers and written by lane 0 every fourth column, pivots
+// the form the in-kernel attempt used (commit f162613, tools/ub/potrf_block_ldl_attempt.hip.txt): reciprocals kept in registers and written by lane 0 every fourth column, pivots
 // read off the accumulator's diagonal at the end, no per-pivot bookkeeping.  VARIANT bit 0: s_setprio 3 around it; bit 1: column masks precomputed (ballots before the loop)
 template <int VARIANT>
 __device__ __forceinline__ void factor16_k(d4& sn, double& ddiag, int lane, lds_vdouble* Upub, lds_vdouble* rpub, lds_vint* prog, int base)
