@@ -53,7 +53,11 @@ typedef enum {
      * device (sparse/ldlt.hpp:101-218 bit for bit; PQ_SPARSE_LDLT picks it up to 8192 KKT rows and 4e7 flops per factorisation -- 3e9 in the condensed modes) and the
      * supernodal multifrontal LDLt (everything else) */
     PQ_SPARSE_LDLT_EXACT = 17,
-    PQ_SPARSE_LDLT_MULTIFRONTAL = 18
+    PQ_SPARSE_LDLT_MULTIFRONTAL = 18,
+    /* the dense Cholesky backend in the reference's own order of floating-point operations (csrc/dense_exact.hip): assembly, factor, solves and mat-vecs bitwise
+     * the CPU oracle's, whole solves with its iteration counts.  n <= 1024 (PQ_ERR_UNSUPPORTED above); never chosen by default -- the yardstick for
+     * PQ_DENSE_CHOLESKY, as PQ_SPARSE_LDLT_EXACT is for the sparse engines */
+    PQ_DENSE_CHOLESKY_EXACT = 19
 } pq_kkt_solver;
 
 /* kkt_fwd.hpp:23-29 KKTUpdateOptions */
@@ -150,7 +154,7 @@ const char *pq_version(void);
 typedef struct pq_kkt pq_kkt;
 
 /* dense::KKT ctor, dense/kkt.hpp:39-55 (uploads P_utri/AT/GT, builds AT_A = AT*AT^T).
- * kkt_solver: PQ_DENSE_CHOLESKY (Eigen::LLT semantics, dense/kkt.hpp:82-83) or PQ_DENSE_LDLT_NO_PIVOT. */
+ * kkt_solver: PQ_DENSE_CHOLESKY (Eigen::LLT semantics, dense/kkt.hpp:82-83), PQ_DENSE_LDLT_NO_PIVOT or PQ_DENSE_CHOLESKY_EXACT (n <= 1024). */
 int pq_kkt_create_dense(pq_kkt **out, const pq_dense_data *data, int kkt_solver, int device);
 /* sparse::KKT ctor, sparse/kkt.hpp:51-70 (assemble KKT by mode, AMD, permute, symbolic, upload) for
  * kkt_solver = PQ_SPARSE_LDLT; MultistageKKT ctor, sparse/multistage_kkt.hpp:76-135 (arrow-structure
@@ -465,6 +469,9 @@ long long pq_debug_alloc_count(void);
  * k_chol_persistent), five ints per task (kind, round, a, b, gate).
  * Returns the number of tasks (-1: T outside [3, 1024]).  tests/test_chol_plan.py replays the list on the CPU: every task only waits for EARLIER tickets. */
 int pq_debug_chol_plan(int T, int *out5, int capacity_tasks);
+/* testing aid: out[i] = sqrt(in[i]) computed on `device` as the reference-order dense factorisation computes its pivots (csrc/dense_exact.hip); host arrays.
+ * PQ_DENSE_CHOLESKY_EXACT is bitwise the reference only if the device's fp64 square root is correctly rounded: tests/test_dense_exact_gpu.py checks it. */
+int pq_debug_device_sqrt(int device, const double *in, double *out, long long count);
 int pq_microbench_mfma_f64(int device, int iters, double *tflops_out);
 int pq_microbench_hbm_copy(int device, size_t bytes, int iters, double *gbps_out);
 /* debugging aid: average microseconds of the 128 x 128 diagonal-block factorisation kernel and 64 in-kernel shader-clock stamps

@@ -13,8 +13,10 @@ LIB = os.path.join(OUT, "libpiqp_amd.so")
 # x86-64 (no FMA instructions) and like the CPU oracle's restatement (oracle/Makefile: -ffp-contract=off): the interior-point loop, the KKTSystem shell, the
 # sparse mat-vecs, the equilibration and the reference-order sparse engine.  With the sparse_ldlt engine of sparse_exact.hip a whole solve is then the same
 # sequence of IEEE operations as the oracle's (tests/test_exact_gpu.py).  The dense / multifrontal / multistage / batched kernels keep contraction: their
-# sums are re-associated for the matrix cores anyway and they are held to the 1e-10 residual bar, not to bits.
-NO_CONTRACT = {"kkt_system.hip", "device_ipm.hip", "sparse_ops.hip", "sparse_exact.hip", "ruiz_kernels.hip", "solver.cpp"}
+# sums are re-associated for the matrix cores anyway and they are held to the 1e-10 residual bar, not to bits.  dense_exact.hip (kkt_solver =
+# dense_cholesky_exact) replays the one oracle file that IS contracted, oracle/orc_dense.c: it writes each of that file's fused operations as an explicit fma()
+# and must not get any other.
+NO_CONTRACT = {"kkt_system.hip", "device_ipm.hip", "sparse_ops.hip", "sparse_exact.hip", "ruiz_kernels.hip", "solver.cpp", "dense_exact.hip"}
 
 
 def sources():

@@ -138,7 +138,8 @@ int pq_kkt_create_dense(pq_kkt** out, const pq_dense_data* data, int kkt_solver,
 {
     if (!out || !data) return fail(PQ_ERR_INVALID, "null argument");
     *out = nullptr;
-    if (kkt_solver != PQ_DENSE_CHOLESKY && kkt_solver != PQ_DENSE_LDLT_NO_PIVOT) return fail(PQ_ERR_UNSUPPORTED, "kkt solver not supported");
+    if (!dense_kkt_kind(kkt_solver)) return fail(PQ_ERR_UNSUPPORTED, "kkt solver not supported");
+    if (kkt_solver == PQ_DENSE_CHOLESKY_EXACT && data->n > DENSE_EXACT_MAX_N) return fail(PQ_ERR_UNSUPPORTED, "dense_cholesky_exact supports n <= %d (n = %d)", DENSE_EXACT_MAX_N, data->n);
     int rc = check_device(device);
     if (rc < 0) return rc;
     return guarded([&] {
@@ -670,7 +671,8 @@ int pq_kktsys_create_dense(pq_kktsys** out, const pq_dense_data* data, const pq_
     if (!out || !data || !settings) return fail(PQ_ERR_INVALID, "null argument");
     *out = nullptr;
     // KKTSystem::init_kkt_solver<PIQP_DENSE>, kkt_system.hpp:455-468
-    if (settings->kkt_solver != PQ_DENSE_CHOLESKY && settings->kkt_solver != PQ_DENSE_LDLT_NO_PIVOT) return fail(PQ_ERR_UNSUPPORTED, "kkt solver not supported");
+    if (!dense_kkt_kind(settings->kkt_solver)) return fail(PQ_ERR_UNSUPPORTED, "kkt solver not supported");
+    if (settings->kkt_solver == PQ_DENSE_CHOLESKY_EXACT && data->n > DENSE_EXACT_MAX_N) return fail(PQ_ERR_UNSUPPORTED, "dense_cholesky_exact supports n <= %d (n = %d)", DENSE_EXACT_MAX_N, data->n);
     int rc = check_device(device);
     if (rc < 0) return rc;
     return guarded([&] {
@@ -843,6 +845,13 @@ int pq_kktsys_synchronize(pq_kktsys* k)
 
 // ------------------------------------------------------------------------------------ micro-benchmarks
 long long pq_debug_alloc_count(void) { return alloc_counter().load(); }
+int pq_debug_device_sqrt(int device, const double* in, double* out, long long count)
+{
+    if (!in || !out || count <= 0) return fail(PQ_ERR_INVALID, "null argument");
+    int rc = check_device(device);
+    if (rc < 0) return rc;
+    return guarded([&] { pq::debug_device_sqrt(in, out, count, device); return (int)PQ_OK; });
+}
 int pq_debug_chol_plan(int T, int* out5, int capacity_tasks) { return T >= 3 && T <= 1024 ? dense::chol_debug_plan(T, out5, capacity_tasks) : -1; }
 
 int pq_microbench_mfma_f64(int device, int iters, double* tflops_out)

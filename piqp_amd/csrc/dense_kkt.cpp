@@ -436,6 +436,7 @@ private:
 
 KKTSolverBase* make_dense_kkt(const pq_dense_data* data, int kkt_solver, int device)
 {
+    if (kkt_solver == PQ_DENSE_CHOLESKY_EXACT) return make_dense_exact_kkt(data, device);
     if (kkt_solver != PQ_DENSE_CHOLESKY && kkt_solver != PQ_DENSE_LDLT_NO_PIVOT) throw std::runtime_error("kkt solver not supported");
     return new DenseKKT(data, kkt_solver, device);
 }

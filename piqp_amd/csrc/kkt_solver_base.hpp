@@ -102,6 +102,10 @@ public:
 };
 
 KKTSolverBase* make_dense_kkt(const pq_dense_data* data, int kkt_solver, int device);
+KKTSolverBase* make_dense_exact_kkt(const pq_dense_data* data, int device);  // dense_exact.hip: dense_cholesky in the reference's own order of operations, n <= 1024
+inline bool dense_kkt_kind(int k) { return k == PQ_DENSE_CHOLESKY || k == PQ_DENSE_LDLT_NO_PIVOT || k == PQ_DENSE_CHOLESKY_EXACT; }
+constexpr int DENSE_EXACT_MAX_N = 1024;
+void debug_device_sqrt(const double* in_host, double* out_host, long long count, int device);  // dense_exact.hip (pq_debug_device_sqrt)
 KKTSolverBase* make_sparse_kkt(const pq_sparse_data* data, int kkt_solver, int device);
 KKTSolverBase* make_multistage_kkt(const pq_sparse_data* data, int device);
 KKTSolverBase* make_multifrontal_kkt(const pq_sparse_data* data, int mode, int device);  // sparse_kkt.hip: the supernodal multifrontal engine, any KKTMode

@@ -467,7 +467,8 @@ void Solver::make_kkt()
     m_kkt_system.reset();
     KKTSolverBase* backend = nullptr;
     if (!m_data->sparse) {
-        if (m_settings.kkt_solver != PQ_DENSE_CHOLESKY && m_settings.kkt_solver != PQ_DENSE_LDLT_NO_PIVOT) { std::fprintf(stderr, "kkt solver not supported\n"); return; }
+        if (!dense_kkt_kind(m_settings.kkt_solver)) { std::fprintf(stderr, "kkt solver not supported\n"); return; }
+        if (m_settings.kkt_solver == PQ_DENSE_CHOLESKY_EXACT && m_data->n > DENSE_EXACT_MAX_N) { std::fprintf(stderr, "dense_cholesky_exact supports n <= %d\n", DENSE_EXACT_MAX_N); return; }
         pq_dense_data desc = druiz_ ? druiz_->dense_descriptor(*m_data) : m_data->dense_descriptor();
         backend = make_dense_kkt(&desc, m_settings.kkt_solver, device_);
     } else {

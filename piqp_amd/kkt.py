@@ -19,6 +19,7 @@ PIQP_INF = 1e30  # fwd.hpp:54
 DENSE_CHOLESKY, SPARSE_LDLT, SPARSE_LDLT_EQ_COND, SPARSE_LDLT_INEQ_COND, SPARSE_LDLT_COND, SPARSE_MULTISTAGE = range(6)
 SPARSE_LDLT_EXACT, SPARSE_LDLT_MULTIFRONTAL = 17, 18  # the two engines behind SPARSE_LDLT, selectable directly (include/piqp_amd.h)
 DENSE_LDLT_NO_PIVOT = 16
+DENSE_CHOLESKY_EXACT = 19  # dense_cholesky in the reference's own order of operations (csrc/dense_exact.hip), n <= 1024
 KKT_UPDATE_NONE, KKT_UPDATE_P, KKT_UPDATE_A, KKT_UPDATE_G = 0, 1, 2, 4
 MEM_HOST, MEM_DEVICE = 0, 1
 
