@@ -343,6 +343,36 @@ pq_settings *pq_solver_settings(pq_solver *s); /* solver.hpp:65 settings() */
 int pq_solver_setup_dense(pq_solver *s, int n, int p, int m, const double *P, const double *c, const double *A,
                           const double *b, const double *G, const double *h_l, const double *h_u, const double *x_l,
                           const double *x_u);
+/* ---- problem data that already lives in GPU memory, results returned there ----
+ * The *_mem entry points below are the calls above / below them with two more arguments; pq_solver_setup_dense, pq_solver_update_dense, pq_solver_get_result,
+ * pq_batch_update, pq_batch_update_data and pq_batch_get_result forward to them with PQ_MEM_HOST (and PQ_COL_MAJOR).
+ *   mem     PQ_MEM_HOST, or PQ_MEM_DEVICE: EVERY non-NULL array pointer of the call is device memory on the handle's device.
+ *   layout  storage order of the matrices P (n x n), A (p x n), G (m x n) only: PQ_COL_MAJOR, or PQ_ROW_MAJOR (what a contiguous torch tensor is).  The solver
+ *           keeps upper(P), A^T, G^T column-major: a row-major A already is the column-major A^T (plain copy), a column-major one goes through a transpose
+ *           kernel; P goes through a masked copy (column-major) or a masked transpose (row-major).
+ *   Only the upper triangle of P is read (solver.hpp:169-192), in either layout and either memory: whatever lies in the other triangle -- NaN included --
+ *   never reaches the solver.
+ *   Any other value of mem or layout returns PQ_ERR_INVALID and leaves the handle as it was.
+ * Ordering contract: the caller makes the inputs visible before the call (device mode: the work that produces them has completed, e.g. the producing stream was
+ * synchronised).  The call returns only when the library has finished reading them; for results, only when the outputs are written.  Inputs are never modified.
+ * Device mode moves no matrix across the host-device link: the matrices go from the caller's arrays into the solver's own by kernel / device-to-device copy,
+ * HostData::P_utri / AT / GT are never sized.  The vectors c, b, h_l, h_u, x_l, x_u (O(n + p + m)) are fetched into host staging and go through the same host
+ * logic as in host mode (finite-bound index lists, rows of G without a finite bound), so the two modes compute bit for bit the same.  Exception: under
+ * PIQP_AMD_DEBUG=host_ruiz (the debugging path that equilibrates on the host) a device-mode call fetches the matrices to the host.
+ * pq_solver_last_ingest: figures of the last setup / update of a dense solver, computed from the shapes of the matrices each path moves (not counted by the
+ * runtime): out[0] = bytes of matrix data that cross the host-device link (host mode: 8 n (n + p + m) for a setup, 8 n x the columns of the updated matrices for
+ * an update; device mode: 0), out[1] = bytes of matrix data written device-to-device or by kernel. */
+enum { PQ_COL_MAJOR = 0, PQ_ROW_MAJOR = 1 };
+int pq_solver_setup_dense_mem(pq_solver *s, int n, int p, int m, const double *P, const double *c, const double *A,
+                              const double *b, const double *G, const double *h_l, const double *h_u, const double *x_l,
+                              const double *x_u, int mem, int layout);
+int pq_solver_update_dense_mem(pq_solver *s, const double *P, const double *c, const double *A, const double *b,
+                               const double *G, const double *h_l, const double *h_u, const double *x_l,
+                               const double *x_u, int mem, int layout);
+/* the ten solution vectors into host or device buffers (NULL fields skipped).  The dense solver keeps its solution (unscaled, boxes expanded) on the host, so in
+ * device mode these O(n + p + m) doubles cross the link host-to-device; only the batched solver's results (pq_batch_get_result_mem) never leave the GPU. */
+int pq_solver_get_result_mem(const pq_solver *s, pq_vars *out, int mem);
+int pq_solver_last_ingest(const pq_solver *s, long long out[2]);
 /* SparseSolver::setup, solver.hpp:1297-1308: CSC HOST arrays (P full or upper) */
 int pq_solver_setup_sparse(pq_solver *s, int n, int p, int m, const int *Pp, const int *Pi, const double *Px,
                            const double *c, const int *Ap, const int *Ai, const double *Ax, const double *b,
@@ -410,12 +440,21 @@ int pq_batch_update(pq_batch *s, const double *c, const double *b, const double 
  * With all three matrices NULL this is pq_batch_update.  Returns 1. */
 int pq_batch_update_data(pq_batch *s, const double *Px, const double *Ax, const double *Gx, const double *c, const double *b,
                          const double *h_l, const double *h_u, const double *x_l, const double *x_u);
+/* pq_batch_update / pq_batch_update_data with the arrays in host or device memory (mem, ordering contract: see pq_solver_setup_dense_mem).  Device mode: the
+ * kernels read the caller's [batch][len] / [batch][nnz] arrays in place -- no device allocation (pq_debug_alloc_count does not move), no copy across the link; the
+ * check that the set of finite bounds is unchanged runs as a kernel over the caller's arrays and one flag word comes back (same error as in host mode). */
+int pq_batch_update_mem(pq_batch *s, const double *c, const double *b, const double *h_l, const double *h_u,
+                        const double *x_l, const double *x_u, int mem);
+int pq_batch_update_data_mem(pq_batch *s, const double *Px, const double *Ax, const double *Gx, const double *c, const double *b,
+                             const double *h_l, const double *h_u, const double *x_l, const double *x_u, int mem);
 /* solve() of every instance (solver.hpp:69-148); returns the number of instances that ended PQ_SOLVED (>= 0) */
 int pq_batch_solve(pq_batch *s);
 const pq_info *pq_batch_info(const pq_batch *s, int instance); /* result().info of one instance */
 /* result(): field k of Variables (0..9 = x, y, z_l, z_u, z_bl, z_bu, s_l, s_u, s_bl, s_bu) of ALL instances,
  * copied to a HOST array [batch][len] (len = n, p or m) */
 int pq_batch_get_result(pq_batch *s, int field, double *out_host);
+/* the same into a host or a DEVICE array [batch][len] (device mode: one strided device-to-device copy out of the arena, no allocation) */
+int pq_batch_get_result_mem(pq_batch *s, int field, double *out, int mem);
 int pq_batch_dims(const pq_batch *s, int *batch, int *n, int *p, int *m);
 int pq_batch_block_info(const pq_batch *s, int *out_host, int capacity); /* as pq_kkt_multistage_block_info; sparse_multistage only (error otherwise) */
 /* in-kernel device-clock seconds of one instance's last solve: out8 = {KKT assembly, factorisation (chain / LDLt),
@@ -474,6 +513,8 @@ int pq_debug_chol_plan(int T, int *out5, int capacity_tasks);
 int pq_debug_device_sqrt(int device, const double *in, double *out, long long count);
 int pq_microbench_mfma_f64(int device, int iters, double *tflops_out);
 int pq_microbench_hbm_copy(int device, size_t bytes, int iters, double *gbps_out);
+/* read + write GB/s of the fp64 transpose kernel the device-mode setup / update use (csrc/ingest_kernels.hip) on a rows x cols matrix, counted like the copy above */
+int pq_microbench_transpose(int device, int rows, int cols, int iters, double *gbps_out);
 /* debugging aid: average microseconds of the 128 x 128 diagonal-block factorisation kernel and 64 in-kernel shader-clock stamps
  * (step k at stamps64[8 k + q], see potrf_block in csrc/dense_kernels.hip); stamps64 may be NULL */
 int pq_microbench_potrf_block(int device, int ldlt, int reps, double *us_out, long long *stamps64);

@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import VAR_NAMES, check
-from .kkt import _Handle, _ptr
+from .kkt import MEM_DEVICE, _Handle, _ptr, device_call, sync_current_stream, to_device_args
 
 
 class BatchSparseSolver(_Handle):
@@ -22,7 +22,9 @@ class BatchSparseSolver(_Handle):
         h = C.c_void_p()
         check(self.L.pq_batch_create(C.byref(h), device), "pq_batch_create")
         self.h = h
+        self.device = device
         self.batch = self.n = self.p = self.m = 0
+        self._nnz = (0, 0, 0)
         if kkt_solver is not None:
             self.settings.kkt_solver = int(kkt_solver)
 
@@ -64,17 +66,34 @@ class BatchSparseSolver(_Handle):
                 self._stack(x_l, batch, n), self._stack(x_u, batch, n)]
         ok = bool(check(self.L.pq_batch_setup_sparse(self.h, batch, n, p, m, *[_ptr(a) for a in keep]), "pq_batch_setup_sparse"))
         self.batch, self.n, self.p, self.m = batch, n, p, m
+        self._nnz = (Pm.nnz, 0 if Am is None else Am.nnz, 0 if Gm is None else Gm.nnz)
         return ok
 
+    def _device_args(self, args):
+        """torch CUDA tensors (numpy arguments beside them are moved to the GPU), checked and contiguous; torch's current stream is drained"""
+        B = self.batch
+        shapes = dict(P_values=(B, self._nnz[0]), A_values=(B, self._nnz[1]), G_values=(B, self._nnz[2]), c=(B, self.n), b=(B, self.p), h_l=(B, self.m), h_u=(B, self.m),
+                      x_l=(B, self.n), x_u=(B, self.n))
+        keep, _ = to_device_args(args, shapes, self.device)
+        sync_current_stream(self.device)
+        return keep
+
     def update(self, c=None, b=None, h_l=None, h_u=None, x_l=None, x_u=None):
-        """new vectors for every instance ([batch, len] arrays, None = unchanged); matrices and the set of finite bounds stay"""
+        """new vectors for every instance ([batch, len] arrays, None = unchanged); matrices and the set of finite bounds stay.
+        If any argument is a torch CUDA tensor the kernels read the data where it is (pq_batch_update_mem)."""
+        if device_call((c, b, h_l, h_u, x_l, x_u)):
+            keep = self._device_args(dict(c=c, b=b, h_l=h_l, h_u=h_u, x_l=x_l, x_u=x_u))
+            return bool(check(self.L.pq_batch_update_mem(self.h, *[_ptr(a) for a in keep.values()], MEM_DEVICE), "pq_batch_update"))
         keep = [self._stack(c, self.batch, self.n), self._stack(b, self.batch, self.p), self._stack(h_l, self.batch, self.m), self._stack(h_u, self.batch, self.m),
                 self._stack(x_l, self.batch, self.n), self._stack(x_u, self.batch, self.n)]
         return bool(check(self.L.pq_batch_update(self.h, *[_ptr(a) for a in keep]), "pq_batch_update"))
 
     def update_data(self, P_values=None, A_values=None, G_values=None, c=None, b=None, h_l=None, h_u=None, x_l=None, x_u=None):
         """new matrix values ([batch, nnz] in the CSC order of the setup patterns) and / or vectors for every instance, None = unchanged:
-        unscale -> assign -> (fresh) Ruiz equilibration on the device, solver.hpp:218-308"""
+        unscale -> assign -> (fresh) Ruiz equilibration on the device, solver.hpp:218-308.  torch CUDA tensors are read where they are (pq_batch_update_data_mem)."""
+        if device_call((P_values, A_values, G_values, c, b, h_l, h_u, x_l, x_u)):
+            keep = self._device_args(dict(P_values=P_values, A_values=A_values, G_values=G_values, c=c, b=b, h_l=h_l, h_u=h_u, x_l=x_l, x_u=x_u))
+            return bool(check(self.L.pq_batch_update_data_mem(self.h, *[_ptr(a) for a in keep.values()], MEM_DEVICE), "pq_batch_update_data"))
         st = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
         for a in (P_values, A_values, G_values):
             assert a is None or np.asarray(a).shape[0] == self.batch
@@ -98,9 +117,17 @@ class BatchSparseSolver(_Handle):
     def iterations(self):
         return np.array([self.info(i).iter for i in range(self.batch)])
 
-    def result(self, name):
+    def result(self, name, device=False):
+        """[batch, len] numpy array, or (device=True) a torch tensor on the solver's GPU, copied there without leaving it"""
         k = VAR_NAMES.index(name)
         length = {"x": self.n, "y": self.p, "z_bl": self.n, "z_bu": self.n, "s_bl": self.n, "s_bu": self.n}.get(name, self.m)
+        if device:
+            import torch
+            out = torch.zeros((self.batch, length), dtype=torch.float64, device=f"cuda:{self.device}")
+            sync_current_stream(self.device)
+            if length:
+                check(self.L.pq_batch_get_result_mem(self.h, k, out.data_ptr(), MEM_DEVICE), "pq_batch_get_result")
+            return out
         out = np.zeros((self.batch, length))
         if length:
             check(self.L.pq_batch_get_result(self.h, k, out.ctypes.data), "pq_batch_get_result")

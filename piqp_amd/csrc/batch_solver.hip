@@ -24,6 +24,7 @@
 #include <thread>
 #include <type_traits>
 
+#include "ingest_kernels.hpp"
 #include "multistage_device.hpp"
 #include "multistage_symbolic.hpp"
 #include "solver.hpp"
@@ -1664,14 +1665,16 @@ public:
         return solved;
     }
     // update() of every instance, vectors only; the set of finite bounds must be the one given at setup (it is part of the shared structure)
-    bool update_vectors(const double* c, const double* b, const double* h_l, const double* h_u, const double* x_l, const double* x_u)
+    // mem = PQ_MEM_DEVICE: the kernels read the caller's device arrays in place (no staging buffers, no copies)
+    bool update_vectors(const double* c, const double* b, const double* h_l, const double* h_u, const double* x_l, const double* x_u, int mem = PQ_MEM_HOST)
     {
         if (!setup_done_) throw std::runtime_error("batch solver not set up");
         PQ_HIP(hipSetDevice(dev_));
-        check_patterns(h_l, h_u, x_l, x_u);
+        if (mem == PQ_MEM_DEVICE) check_patterns_device(h_l, h_u, x_l, x_u); else check_patterns(h_l, h_u, x_l, x_u);
         DBuf<double> dc, dbv, dhl, dhu, dxl, dxu;
         auto up = [&](DBuf<double>& d, const double* v, int len) -> const double* {
             if (!v || len == 0) return nullptr;
+            if (mem == PQ_MEM_DEVICE) return v;
             d.alloc((size_t)batch_ * len);
             PQ_HIP(hipMemcpyAsync(d.p, v, sizeof(double) * (size_t)batch_ * len, hipMemcpyHostToDevice, st_));
             return d.p;
@@ -1685,15 +1688,16 @@ public:
     // update() of every instance with new matrix values (patterns and the set of finite bounds as given at setup) and / or vectors: per instance
     // unscale_data -> assign -> scale_data (fresh equilibration unless settings.preconditioner_reuse_on_update), all on the device
     bool update_data(const double* Px, const double* Ax, const double* Gx, const double* c, const double* b, const double* h_l, const double* h_u, const double* x_l,
-                     const double* x_u)
+                     const double* x_u, int mem = PQ_MEM_HOST)
     {
-        if (!Px && !Ax && !Gx) return update_vectors(c, b, h_l, h_u, x_l, x_u);
+        if (!Px && !Ax && !Gx) return update_vectors(c, b, h_l, h_u, x_l, x_u, mem);
         if (!setup_done_) throw std::runtime_error("batch solver not set up");
         PQ_HIP(hipSetDevice(dev_));
-        check_patterns(h_l, h_u, x_l, x_u);
+        if (mem == PQ_MEM_DEVICE) check_patterns_device(h_l, h_u, x_l, x_u); else check_patterns(h_l, h_u, x_l, x_u);
         DBuf<double> dP, dA, dG, dc, dbv, dhl, dhu, dxl, dxu;
         auto up = [&](DBuf<double>& d, const double* v, int len) -> const double* {
             if (!v || len == 0) return nullptr;
+            if (mem == PQ_MEM_DEVICE) return v;
             d.alloc((size_t)batch_ * len);
             PQ_HIP(hipMemcpyAsync(d.p, v, sizeof(double) * (size_t)batch_ * len, hipMemcpyHostToDevice, st_));
             return d.p;
@@ -1724,14 +1728,14 @@ public:
     }
     const pq_info& info(int i) const { return infos_h_.at(i); }
 
-    // field k of Variables (x, y, z_l, z_u, z_bl, z_bu, s_l, s_u, s_bl, s_bu) of all instances -> host [batch][len]
-    void get_result(int field, double* out_host)
+    // field k of Variables (x, y, z_l, z_u, z_bl, z_bu, s_l, s_u, s_bl, s_bu) of all instances -> host or device [batch][len]
+    void get_result(int field, double* out, int mem = PQ_MEM_HOST)
     {
         const int len = field_len(field);
         if (len == 0) return;
         PQ_HIP(hipSetDevice(dev_));
-        PQ_HIP(hipMemcpy2DAsync(out_host, sizeof(double) * len, arena_.p + layout_.off[V_R + field], sizeof(double) * layout_.stride, sizeof(double) * len, batch_,
-                                hipMemcpyDeviceToHost, st_));
+        PQ_HIP(hipMemcpy2DAsync(out, sizeof(double) * len, arena_.p + layout_.off[V_R + field], sizeof(double) * layout_.stride, sizeof(double) * len, batch_,
+                                mem == PQ_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st_));
         stream_wait(st_);
     }
     int field_len(int field) const
@@ -1849,6 +1853,21 @@ private:
             throw std::runtime_error("batch update: the set of finite bounds differs from the one given at setup");
     }
 
+    // the same check on the caller's DEVICE arrays: one small kernel per given bound vector, one flag word read back
+    void check_patterns_device(const double* h_l, const double* h_u, const double* x_l, const double* x_u)
+    {
+        if (!h_l && !h_u && !x_l && !x_u) return;
+        PQ_HIP(hipMemsetAsync(fin_flag_, 0, sizeof(int), st_));
+        if (h_l) ingest_check_finite_pattern(h_l, fin_hl_d_, batch_, m_, true, fin_flag_, st_);
+        if (h_u) ingest_check_finite_pattern(h_u, fin_hu_d_, batch_, m_, false, fin_flag_, st_);
+        if (x_l) ingest_check_finite_pattern(x_l, fin_xl_d_, batch_, n_, true, fin_flag_, st_);
+        if (x_u) ingest_check_finite_pattern(x_u, fin_xu_d_, batch_, n_, false, fin_flag_, st_);
+        int flag = 0;
+        PQ_HIP(hipMemcpyAsync(&flag, fin_flag_, sizeof(int), hipMemcpyDeviceToHost, st_));
+        stream_wait(st_);
+        if (flag) throw std::runtime_error("batch update: the set of finite bounds differs from the one given at setup");
+    }
+
     // Where the caller's k-th value of P / A / G lives in the arena: found by pushing the values 1, 2, 3, ... through the same host path the real
     // values took at setup (make_sparse_host_data: upper-triangle extraction, transposes, disabled rows of G zeroed).
     void build_update_maps(int n, int p, int m, const int* Pp, const int* Pi, const double* c, const int* Ap, const int* Ai, const double* b, const int* Gp, const int* Gi,
@@ -1871,6 +1890,11 @@ private:
         std::vector<int> dis(std::max(m_, 1), 0);
         for (int i = 0; i < m_; ++i) dis[i] = !fin_hl_[i] && !fin_hu_[i];
         disabled_d_ = up(ibufs_, dis);
+        auto as_int = [](const std::vector<char>& f) { std::vector<int> v(std::max<size_t>(f.size(), 1), 0); for (size_t i = 0; i < f.size(); ++i) v[i] = f[i] != 0; return v; };
+        fin_hl_d_ = up(ibufs_, as_int(fin_hl_)); fin_hu_d_ = up(ibufs_, as_int(fin_hu_)); fin_xl_d_ = up(ibufs_, as_int(fin_xl_)); fin_xu_d_ = up(ibufs_, as_int(fin_xu_));
+        ibufs_.emplace_back();
+        ibufs_.back().alloc(1);
+        fin_flag_ = ibufs_.back().p;
         rzPp_ = up(ibufs_, d0.sP_utri.colptr);
         rzPi_ = up(ibufs_, d0.sP_utri.rowind.empty() ? std::vector<int>(1, 0) : d0.sP_utri.rowind);
         stream_wait(st_);
@@ -2179,6 +2203,8 @@ private:
     bool ldlt_ = false;  // backend fixed at setup: sparse_ldlt (MODE_LDLT) or sparse_multistage
     sparse::UpLooking ul_;
     std::vector<char> fin_hl_, fin_hu_, fin_xl_, fin_xu_;  // which of the caller's bounds are finite (shared by all instances)
+    const int *fin_hl_d_ = nullptr, *fin_hu_d_ = nullptr, *fin_xl_d_ = nullptr, *fin_xu_d_ = nullptr;  // device copies (0 / 1 per entry) and the flag word of
+    int* fin_flag_ = nullptr;                                                                            // check_patterns_device; owned by ibufs_
     int nzP_in_ = 0, nzA_in_ = 0, nzG_in_ = 0;             // the caller's nonzero counts (P may carry its lower triangle)
     const int *mapP_ = nullptr, *mapA_ = nullptr, *mapG_ = nullptr, *disabled_d_ = nullptr, *rzPp_ = nullptr, *rzPi_ = nullptr;  // device, owned by ibufs_
     double last_kernel_ms_ = 0.0;
@@ -2227,16 +2253,27 @@ int pq_batch_setup_sparse(pq_batch* s, int batch, int n, int p, int m, const int
     if (!s || !Pp || !Pi || !Px || !c) return fail(PQ_ERR_INVALID, "null argument");
     return guarded([&] { return s->impl->setup(batch, n, p, m, Pp, Pi, Px, c, Ap, Ai, Ax, b, Gp, Gi, Gx, h_l, h_u, x_l, x_u) ? 1 : 0; });
 }
-int pq_batch_update(pq_batch* s, const double* c, const double* b, const double* h_l, const double* h_u, const double* x_l, const double* x_u)
+int pq_batch_update_mem(pq_batch* s, const double* c, const double* b, const double* h_l, const double* h_u, const double* x_l, const double* x_u, int mem)
 {
     if (!s) return fail(PQ_ERR_INVALID, "null argument");
-    return guarded([&] { return s->impl->update_vectors(c, b, h_l, h_u, x_l, x_u) ? 1 : 0; });
+    if (mem != PQ_MEM_HOST && mem != PQ_MEM_DEVICE) return fail(PQ_ERR_INVALID, "mem must be PQ_MEM_HOST or PQ_MEM_DEVICE");
+    return guarded([&] { return s->impl->update_vectors(c, b, h_l, h_u, x_l, x_u, mem) ? 1 : 0; });
+}
+int pq_batch_update(pq_batch* s, const double* c, const double* b, const double* h_l, const double* h_u, const double* x_l, const double* x_u)
+{
+    return pq_batch_update_mem(s, c, b, h_l, h_u, x_l, x_u, PQ_MEM_HOST);
+}
+int pq_batch_update_data_mem(pq_batch* s, const double* Px, const double* Ax, const double* Gx, const double* c, const double* b, const double* h_l, const double* h_u,
+                             const double* x_l, const double* x_u, int mem)
+{
+    if (!s) return fail(PQ_ERR_INVALID, "null argument");
+    if (mem != PQ_MEM_HOST && mem != PQ_MEM_DEVICE) return fail(PQ_ERR_INVALID, "mem must be PQ_MEM_HOST or PQ_MEM_DEVICE");
+    return guarded([&] { return s->impl->update_data(Px, Ax, Gx, c, b, h_l, h_u, x_l, x_u, mem) ? 1 : 0; });
 }
 int pq_batch_update_data(pq_batch* s, const double* Px, const double* Ax, const double* Gx, const double* c, const double* b, const double* h_l, const double* h_u,
                          const double* x_l, const double* x_u)
 {
-    if (!s) return fail(PQ_ERR_INVALID, "null argument");
-    return guarded([&] { return s->impl->update_data(Px, Ax, Gx, c, b, h_l, h_u, x_l, x_u) ? 1 : 0; });
+    return pq_batch_update_data_mem(s, Px, Ax, Gx, c, b, h_l, h_u, x_l, x_u, PQ_MEM_HOST);
 }
 int pq_batch_solve(pq_batch* s)
 {
@@ -2248,11 +2285,13 @@ const pq_info* pq_batch_info(const pq_batch* s, int instance)
     if (!s || instance < 0 || instance >= s->impl->batch()) return nullptr;
     return &s->impl->info(instance);
 }
-int pq_batch_get_result(pq_batch* s, int field, double* out_host)
+int pq_batch_get_result_mem(pq_batch* s, int field, double* out, int mem)
 {
-    if (!s || !out_host || field < 0 || field >= 10) return fail(PQ_ERR_INVALID, "bad argument");
-    return guarded([&] { s->impl->get_result(field, out_host); return (int)PQ_OK; });
+    if (!s || !out || field < 0 || field >= 10) return fail(PQ_ERR_INVALID, "bad argument");
+    if (mem != PQ_MEM_HOST && mem != PQ_MEM_DEVICE) return fail(PQ_ERR_INVALID, "mem must be PQ_MEM_HOST or PQ_MEM_DEVICE");
+    return guarded([&] { s->impl->get_result(field, out, mem); return (int)PQ_OK; });
 }
+int pq_batch_get_result(pq_batch* s, int field, double* out_host) { return pq_batch_get_result_mem(s, field, out_host, PQ_MEM_HOST); }
 int pq_batch_dims(const pq_batch* s, int* batch, int* n, int* p, int* m)
 {
     if (!s) return fail(PQ_ERR_INVALID, "null argument");

@@ -7,6 +7,7 @@
 #include <stdexcept>
 
 #include "dense_kernels.hpp"
+#include "ingest_kernels.hpp"
 #include "kkt_solver_base.hpp"
 #include "rccl_transport.hpp"
 #include "kkt_system.hpp"
@@ -879,6 +880,14 @@ int pq_microbench_hbm_copy(int device, size_t bytes, int iters, double* gbps_out
     int rc = check_device(device);
     if (rc < 0) return rc;
     return guarded([&] { PQ_HIP(hipSetDevice(device)); *gbps_out = dense::microbench_hbm_copy(bytes, iters, nullptr); return (int)PQ_OK; });
+}
+
+int pq_microbench_transpose(int device, int rows, int cols, int iters, double* gbps_out)
+{
+    if (!gbps_out || rows <= 0 || cols <= 0 || iters <= 0) return fail(PQ_ERR_INVALID, "bad argument");
+    int rc = check_device(device);
+    if (rc < 0) return rc;
+    return guarded([&] { PQ_HIP(hipSetDevice(device)); *gbps_out = pq::microbench_transpose(rows, cols, iters, nullptr); return (int)PQ_OK; });
 }
 
 }  // extern "C"

@@ -51,6 +51,9 @@ public:
 
     // dense: (re)load the unscaled matrices named by `options` (PQ_KKT_UPDATE_*) from the host staging copies in d
     void upload_dense(const HostData& d, int options);
+    // dense: the same from the caller's DEVICE arrays P (n x n), A (p x n), G (m x n) in storage order `layout` (PQ_COL_MAJOR: transpose kernel for A and G, masked
+    // copy for P; PQ_ROW_MAJOR: plain copies of A and G, masked transpose for P).  The sources are only read; returns the bytes written.
+    long long ingest_dense(const double* P, const double* A, const double* G, int layout, int options);
     void zero_G_rows(const std::vector<int>& rows);  // dense: rows of G disabled by data.hpp:144-169 after the upload
     // scale_data / unscale_data of the matrices, c and x_b_scaling; the scalings land in rz, c / x_b_scaling in d (sparse: the matrix values too)
     void scale(HostData& d, Ruiz& rz, bool reuse_prev_scaling, bool scale_cost, int max_iter, double eps = 1e-3);

@@ -1,5 +1,6 @@
 // piqp_amd/csrc/ruiz_kernels.hip -- device Ruiz equilibration (see ruiz_device.hpp).  HBM-bound byte pushing: no matrix cores here.
 #include "ruiz_device.hpp"
+#include "ingest_kernels.hpp"
 
 #include <memory>
 #include <stdexcept>
@@ -442,6 +443,30 @@ void DeviceRuiz::upload_dense(const HostData& d, int options)
     if ((options & PQ_KKT_UPDATE_A) && s.AT.n) PQ_HIP(hipMemcpyAsync(s.AT.p, d.AT.data(), n * s.p * sizeof(double), hipMemcpyHostToDevice, s.st));
     if ((options & PQ_KKT_UPDATE_G) && s.GT.n) PQ_HIP(hipMemcpyAsync(s.GT.p, d.GT.data(), n * s.m * sizeof(double), hipMemcpyHostToDevice, s.st));
     stream_wait(s.st);
+}
+
+long long DeviceRuiz::ingest_dense(const double* P, const double* A, const double* G, int layout, int options)
+{
+    Impl& s = *I;
+    if (s.sparse) throw std::runtime_error("DeviceRuiz::ingest_dense on a sparse problem");
+    PQ_HIP(hipSetDevice(s.device));
+    const int n = s.n;
+    long long moved = 0;
+    if ((options & PQ_KKT_UPDATE_P) && P && s.P.n) {
+        if (layout == PQ_ROW_MAJOR) ingest_transpose(s.P.p, P, n, n, true, s.st);  // a row-major P is the column-major P^T
+        else ingest_copy_upper(s.P.p, P, n, s.st);
+        moved += (long long)s.P.bytes();
+    }
+    auto mat = [&](DBuf<double>& dst, const double* src, int rows) {  // src rows x n -> dst = src^T, column-major n x rows
+        if (!src || !dst.n) return;
+        if (layout == PQ_ROW_MAJOR) PQ_HIP(hipMemcpyAsync(dst.p, src, dst.bytes(), hipMemcpyDeviceToDevice, s.st));
+        else ingest_transpose(dst.p, src, rows, n, false, s.st);
+        moved += (long long)dst.bytes();
+    };
+    if (options & PQ_KKT_UPDATE_A) mat(s.AT, A, s.p);
+    if (options & PQ_KKT_UPDATE_G) mat(s.GT, G, s.m);
+    stream_wait(s.st);
+    return moved;
 }
 
 void DeviceRuiz::zero_G_rows(const std::vector<int>& rows)

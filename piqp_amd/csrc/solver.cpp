@@ -116,11 +116,11 @@ pq_sparse_data HostData::sparse_descriptor() const
     return d;
 }
 
-static void finish_data(HostData& d, const double* c, const double* b, const double* h_l, const double* h_u, const double* x_l, const double* x_u)
+static void finish_data(HostData& d, const double* c, const double* b, const double* h_l, const double* h_u, const double* x_l, const double* x_u, IVec* zeroed_rows = nullptr)
 {
     std::copy(c, c + d.n, d.c.begin());
     if (b && d.p) std::copy(b, b + d.p, d.b.begin());
-    d.set_h_l(h_l); d.set_h_u(h_u); d.disable_inf_constraints(); d.set_x_l(x_l); d.set_x_u(x_u);
+    d.set_h_l(h_l); d.set_h_u(h_u); d.disable_inf_constraints(zeroed_rows); d.set_x_l(x_l); d.set_x_u(x_u);
 }
 
 // MT(i, k) = M(k, i) for a rows x n column-major M: 32 x 32 tiles keep both sides of the transpose in cache
@@ -135,19 +135,41 @@ static void transpose_into(int n, const double* M, int rows, Vec& MT)
     });
 }
 
-// solver.hpp:169-192 (DenseSolver): P_utri = upper(P), AT = A^T, GT = G^T
+// P_utri = upper(P), zeros strictly below the diagonal; P column-major or row-major (only its upper triangle is read in either)
+static void upper_into(int n, const double* P, int layout, Vec& U)
+{
+    U.resize((size_t)n * n);
+    parallel_for(n, n, [&](int lo, int hi, int) {
+        for (int j = lo; j < hi; ++j) {
+            double* col = U.data() + (size_t)j * n;
+            if (layout == PQ_ROW_MAJOR) for (int i = 0; i <= j; ++i) col[i] = P[(size_t)i * n + j];
+            else for (int i = 0; i <= j; ++i) col[i] = P[i + (size_t)j * n];
+            for (int i = j + 1; i < n; ++i) col[i] = 0.0;
+        }
+    });
+}
+// MT = M^T column-major for a rows x n matrix M: a row-major M already is that
+static void transposed_into(int n, const double* M, int rows, int layout, Vec& MT)
+{
+    if (layout == PQ_ROW_MAJOR) MT.assign(M, M + (size_t)n * rows);
+    else transpose_into(n, M, rows, MT);
+}
+
+// solver.hpp:169-192 (DenseSolver): P_utri = upper(P), AT = A^T, GT = G^T.  matrices_on_device: P, A, G only say which matrices exist; the three stay empty
+// (DeviceRuiz::ingest_dense fills the device copies) and the rows of G without a finite bound come back in *zeroed_rows
 std::unique_ptr<HostData> make_dense_host_data(int n, int p, int m, const double* P, const double* c, const double* A, const double* b, const double* G, const double* h_l,
-                                               const double* h_u, const double* x_l, const double* x_u)
+                                               const double* h_u, const double* x_l, const double* x_u, int layout, bool matrices_on_device, IVec* zeroed_rows)
 {
     auto d = std::make_unique<HostData>();
     d->sparse = false; d->n = n; d->p = A ? p : 0; d->m = G ? m : 0;
     p = d->p; m = d->m;
-    d->P_utri.assign((size_t)n * n, 0.0);
-    parallel_for(n, n, [&](int lo, int hi, int) { for (int j = lo; j < hi; ++j) for (int i = 0; i <= j; ++i) d->P_utri[i + (size_t)j * n] = P[i + (size_t)j * n]; });
-    if (p > 0) transpose_into(n, A, p, d->AT); else d->AT.clear();
-    if (m > 0) transpose_into(n, G, m, d->GT); else d->GT.clear();
+    if (!matrices_on_device) {
+        upper_into(n, P, layout, d->P_utri);
+        if (p > 0) transposed_into(n, A, p, layout, d->AT); else d->AT.clear();
+        if (m > 0) transposed_into(n, G, m, layout, d->GT); else d->GT.clear();
+    }
     d->resize_vectors();
-    finish_data(*d, c, b, h_l, h_u, x_l, x_u);
+    finish_data(*d, c, b, h_l, h_u, x_l, x_u, zeroed_rows);
     return d;
 }
 
@@ -482,11 +504,14 @@ void Solver::make_kkt()
 }
 
 // solver.hpp:151-216
-bool Solver::setup(std::unique_ptr<HostData> data)
+bool Solver::device_ingest() { return debug_token("host_ruiz") == nullptr; }
+
+bool Solver::setup(std::unique_ptr<HostData> data, const DenseDeviceSource* dev, const IVec* zeroed_rows)
 {
     const double t0 = now_s();
     m_data = std::move(data);
     const int n = m_data->n, p = m_data->p, m = m_data->m;
+    ingest_[0] = ingest_[1] = 0;
     // init_workspace :361-377
     m_result.resize(n, p, m); res_nr.resize(n, p, m); res.resize(n, p, m); step.resize(n, p, m); prox_vars.resize(n, p, m);
     m_info = pq_info{};
@@ -496,8 +521,12 @@ bool Solver::setup(std::unique_ptr<HostData> data)
     druiz_.reset();
     if (!debug_token("host_ruiz")) {
         druiz_ = std::make_unique<DeviceRuiz>(device_, *m_data);
-        if (!m_data->sparse) { druiz_->upload_dense(*m_data, PQ_KKT_UPDATE_P | PQ_KKT_UPDATE_A | PQ_KKT_UPDATE_G); release_dense_staging(); }
-    }
+        if (!m_data->sparse && dev) {
+            ingest_[1] = druiz_->ingest_dense(dev->P, dev->A, dev->G, dev->layout, PQ_KKT_UPDATE_P | PQ_KKT_UPDATE_A | PQ_KKT_UPDATE_G);
+            if (zeroed_rows) druiz_->zero_G_rows(*zeroed_rows);
+        } else if (!m_data->sparse) { druiz_->upload_dense(*m_data, PQ_KKT_UPDATE_P | PQ_KKT_UPDATE_A | PQ_KKT_UPDATE_G); release_dense_staging(); }
+    } else if (dev) throw std::runtime_error("device matrices need the device preconditioner");
+    if (!m_data->sparse && !dev) ingest_[0] = 8LL * n * ((long long)n + p + m);  // P, A^T, G^T go up once (here, or in the KKT backend under host_ruiz)
     scale_problem(false);
     make_kkt();
     if (!m_kkt_system) { m_setup_done = false; return false; }
@@ -568,6 +597,7 @@ static void refresh_kkt(const DeviceRuiz* dr, KKTSystem& k, const HostData& d, i
 bool Solver::update_vectors_only(const double* c, const double* b, const double* h_l, const double* h_u, const double* x_l, const double* x_u, double t0)
 {
     HostData& d = *m_data;
+    ingest_[0] = ingest_[1] = 0;
     m_preconditioner.unscale_vectors(d);
     if (c) std::copy(c, c + d.n, d.c.begin());
     if (b) std::copy(b, b + d.p, d.b.begin());
@@ -588,28 +618,22 @@ bool Solver::update_vectors_only(const double* c, const double* b, const double*
 
 // solver.hpp:218-308 with the dense update_P/A/G of :311-351
 bool Solver::update_dense(const double* P, const double* c, const double* A, const double* b, const double* G, const double* h_l, const double* h_u, const double* x_l,
-                          const double* x_u)
+                          const double* x_u, int mat_mem, int layout)
 {
     if (!m_setup_done) { std::fprintf(stderr, "Solver not setup yet\n"); return false; }
     const double t0 = now_s();
     HostData& d = *m_data;
     const int n = d.n, p = d.p, m = d.m;
     if (!P && !A && !G) return update_vectors_only(c, b, h_l, h_u, x_l, x_u, t0);
+    const bool on_device = mat_mem == PQ_MEM_DEVICE;
+    if (on_device && !druiz_) throw std::runtime_error("device matrices need the device preconditioner");
     unscale_problem();
     int opt = PQ_KKT_UPDATE_NONE;
-    if (P) {
-        d.P_utri.resize((size_t)n * n);
-        parallel_for(n, n, [&](int lo, int hi, int) {
-            for (int j = lo; j < hi; ++j) {
-                double* col = d.P_utri.data() + (size_t)j * n;
-                for (int i = 0; i <= j; ++i) col[i] = P[i + (size_t)j * n];
-                for (int i = j + 1; i < n; ++i) col[i] = 0.0;
-            }
-        });
-        opt |= PQ_KKT_UPDATE_P;
-    }
-    if (A) { transpose_into(n, A, p, d.AT); opt |= PQ_KKT_UPDATE_A; }
-    if (G) { transpose_into(n, G, m, d.GT); opt |= PQ_KKT_UPDATE_G; }
+    if (P) { if (!on_device) upper_into(n, P, layout, d.P_utri); opt |= PQ_KKT_UPDATE_P; }
+    if (A) { if (!on_device) transposed_into(n, A, p, layout, d.AT); opt |= PQ_KKT_UPDATE_A; }
+    if (G) { if (!on_device) transposed_into(n, G, m, layout, d.GT); opt |= PQ_KKT_UPDATE_G; }
+    ingest_[0] = ingest_[1] = 0;
+    if (!on_device) ingest_[0] = 8LL * n * ((P ? (long long)n : 0) + (A ? p : 0) + (G ? m : 0));
     if (c) std::copy(c, c + n, d.c.begin());
     if (b) std::copy(b, b + p, d.b.begin());
     if (h_l) d.set_h_l(h_l);
@@ -618,7 +642,8 @@ bool Solver::update_dense(const double* P, const double* c, const double* A, con
     if (h_l || h_u) d.disable_inf_constraints(&zeroed);
     if (x_l) d.set_x_l(x_l);
     if (x_u) d.set_x_u(x_u);
-    if (druiz_) { druiz_->upload_dense(d, opt); druiz_->zero_G_rows(zeroed); release_dense_staging(); }
+    if (druiz_ && on_device) { ingest_[1] = druiz_->ingest_dense(P, A, G, layout, opt); druiz_->zero_G_rows(zeroed); }
+    else if (druiz_) { druiz_->upload_dense(d, opt); druiz_->zero_G_rows(zeroed); release_dense_staging(); }
     bool reuse = m_settings.preconditioner_reuse_on_update != 0;
     if (opt == PQ_KKT_UPDATE_NONE) reuse = true;
     scale_problem(reuse);
@@ -1245,13 +1270,62 @@ int pq_solver_clone(const pq_solver* s, pq_solver** out)
 }
 pq_settings* pq_solver_settings(pq_solver* s) { return s ? &s->impl->settings() : nullptr; }
 
+namespace {
+bool bad_mem_or_layout(int mem, int layout) { return (mem != PQ_MEM_HOST && mem != PQ_MEM_DEVICE) || (layout != PQ_COL_MAJOR && layout != PQ_ROW_MAJOR); }
+// device-mode calls: the O(n + p + m) vectors are fetched into host staging and go through the host logic (bound lists, disabled rows of G) unchanged
+struct FetchedVectors {
+    Vec buf[6];
+    const double* fetch(int k, const double* dev, int len)
+    {
+        if (!dev || len <= 0) return dev;
+        buf[k].resize((size_t)len);
+        PQ_HIP(hipMemcpy(buf[k].data(), dev, sizeof(double) * (size_t)len, hipMemcpyDeviceToHost));
+        return buf[k].data();
+    }
+};
+// PIQP_AMD_DEBUG=host_ruiz only: a device matrix comes to the host
+const double* fetch_matrix(Vec& buf, const double* dev, size_t count, long long& bytes)
+{
+    if (!dev || !count) return dev;
+    buf.resize(count);
+    PQ_HIP(hipMemcpy(buf.data(), dev, sizeof(double) * count, hipMemcpyDeviceToHost));
+    bytes += (long long)(sizeof(double) * count);
+    return buf.data();
+}
+}  // namespace
+
+int pq_solver_setup_dense_mem(pq_solver* s, int n, int p, int m, const double* P, const double* c, const double* A, const double* b, const double* G, const double* h_l,
+                              const double* h_u, const double* x_l, const double* x_u, int mem, int layout)
+{
+    if (!s || !P || !c || n <= 0) return fail(PQ_ERR_INVALID, "bad argument");
+    if (bad_mem_or_layout(mem, layout)) return fail(PQ_ERR_INVALID, "mem must be PQ_MEM_HOST or PQ_MEM_DEVICE, layout PQ_COL_MAJOR or PQ_ROW_MAJOR");
+    // solver.hpp:175-178 argument checks
+    if ((A && !b && p > 0) || (!h_l && !h_u && G && m > 0)) return fail(PQ_ERR_INVALID, "b / h_l or h_u must be provided");
+    if (mem == PQ_MEM_HOST) return guarded([&] { return s->impl->setup(make_dense_host_data(n, p, m, P, c, A, b, G, h_l, h_u, x_l, x_u, layout)) ? 1 : 0; });
+    return guarded([&] {
+        PQ_HIP(hipSetDevice(s->impl->device()));
+        const int pp = A ? p : 0, mm = G ? m : 0;
+        FetchedVectors v;
+        c = v.fetch(0, c, n); b = v.fetch(1, b, pp); h_l = v.fetch(2, h_l, mm); h_u = v.fetch(3, h_u, mm); x_l = v.fetch(4, x_l, n); x_u = v.fetch(5, x_u, n);
+        if (!Solver::device_ingest()) {
+            Vec hP, hA, hG;
+            long long bytes = 0;
+            P = fetch_matrix(hP, P, (size_t)n * n, bytes); A = fetch_matrix(hA, A, (size_t)n * pp, bytes); G = fetch_matrix(hG, G, (size_t)n * mm, bytes);
+            const bool ok = s->impl->setup(make_dense_host_data(n, p, m, P, c, A, b, G, h_l, h_u, x_l, x_u, layout));
+            s->impl->add_link_bytes(bytes);
+            return ok ? 1 : 0;
+        }
+        IVec zeroed;
+        auto data = make_dense_host_data(n, p, m, P, c, A, b, G, h_l, h_u, x_l, x_u, layout, true, &zeroed);
+        DenseDeviceSource src;
+        src.P = P; src.A = A; src.G = G; src.layout = layout;
+        return s->impl->setup(std::move(data), &src, &zeroed) ? 1 : 0;
+    });
+}
 int pq_solver_setup_dense(pq_solver* s, int n, int p, int m, const double* P, const double* c, const double* A, const double* b, const double* G, const double* h_l,
                           const double* h_u, const double* x_l, const double* x_u)
 {
-    if (!s || !P || !c || n <= 0) return fail(PQ_ERR_INVALID, "bad argument");
-    // solver.hpp:175-178 argument checks
-    if ((A && !b && p > 0) || (!h_l && !h_u && G && m > 0)) return fail(PQ_ERR_INVALID, "b / h_l or h_u must be provided");
-    return guarded([&] { return s->impl->setup(make_dense_host_data(n, p, m, P, c, A, b, G, h_l, h_u, x_l, x_u)) ? 1 : 0; });
+    return pq_solver_setup_dense_mem(s, n, p, m, P, c, A, b, G, h_l, h_u, x_l, x_u, PQ_MEM_HOST, PQ_COL_MAJOR);
 }
 int pq_solver_setup_sparse(pq_solver* s, int n, int p, int m, const int* Pp, const int* Pi, const double* Px, const double* c, const int* Ap, const int* Ai, const double* Ax,
                            const double* b, const int* Gp, const int* Gi, const double* Gx, const double* h_l, const double* h_u, const double* x_l, const double* x_u)
@@ -1260,11 +1334,40 @@ int pq_solver_setup_sparse(pq_solver* s, int n, int p, int m, const int* Pp, con
     if ((Ap && !b && p > 0) || (!h_l && !h_u && Gp && m > 0)) return fail(PQ_ERR_INVALID, "b / h_l or h_u must be provided");
     return guarded([&] { return s->impl->setup(make_sparse_host_data(n, p, m, Pp, Pi, Px, c, Ap, Ai, Ax, b, Gp, Gi, Gx, h_l, h_u, x_l, x_u)) ? 1 : 0; });
 }
+int pq_solver_update_dense_mem(pq_solver* s, const double* P, const double* c, const double* A, const double* b, const double* G, const double* h_l, const double* h_u,
+                               const double* x_l, const double* x_u, int mem, int layout)
+{
+    if (!s) return fail(PQ_ERR_INVALID, "null argument");
+    if (bad_mem_or_layout(mem, layout)) return fail(PQ_ERR_INVALID, "mem must be PQ_MEM_HOST or PQ_MEM_DEVICE, layout PQ_COL_MAJOR or PQ_ROW_MAJOR");
+    if (mem == PQ_MEM_HOST) return guarded([&] { return s->impl->update_dense(P, c, A, b, G, h_l, h_u, x_l, x_u, PQ_MEM_HOST, layout) ? 1 : 0; });
+    return guarded([&] {
+        const HostData* d = s->impl->data();
+        if (!d || d->sparse) { std::fprintf(stderr, "Solver not setup yet\n"); return 0; }
+        PQ_HIP(hipSetDevice(s->impl->device()));
+        const int n = d->n, p = d->p, m = d->m;
+        FetchedVectors v;
+        c = v.fetch(0, c, n); b = v.fetch(1, b, p); h_l = v.fetch(2, h_l, m); h_u = v.fetch(3, h_u, m); x_l = v.fetch(4, x_l, n); x_u = v.fetch(5, x_u, n);
+        if (!Solver::device_ingest()) {
+            Vec hP, hA, hG;
+            long long bytes = 0;
+            P = fetch_matrix(hP, P, (size_t)n * n, bytes); A = fetch_matrix(hA, A, (size_t)n * p, bytes); G = fetch_matrix(hG, G, (size_t)n * m, bytes);
+            const bool ok = s->impl->update_dense(P, c, A, b, G, h_l, h_u, x_l, x_u, PQ_MEM_HOST, layout);
+            s->impl->add_link_bytes(bytes);
+            return ok ? 1 : 0;
+        }
+        return s->impl->update_dense(P, c, A, b, G, h_l, h_u, x_l, x_u, PQ_MEM_DEVICE, layout) ? 1 : 0;
+    });
+}
 int pq_solver_update_dense(pq_solver* s, const double* P, const double* c, const double* A, const double* b, const double* G, const double* h_l, const double* h_u,
                            const double* x_l, const double* x_u)
 {
-    if (!s) return fail(PQ_ERR_INVALID, "null argument");
-    return guarded([&] { return s->impl->update_dense(P, c, A, b, G, h_l, h_u, x_l, x_u) ? 1 : 0; });
+    return pq_solver_update_dense_mem(s, P, c, A, b, G, h_l, h_u, x_l, x_u, PQ_MEM_HOST, PQ_COL_MAJOR);
+}
+int pq_solver_last_ingest(const pq_solver* s, long long out[2])
+{
+    if (!s || !out) return fail(PQ_ERR_INVALID, "null argument");
+    out[0] = s->impl->last_ingest()[0]; out[1] = s->impl->last_ingest()[1];
+    return PQ_OK;
 }
 int pq_solver_update_sparse(pq_solver* s, const int* Pp, const int* Pi, const double* Px, const double* c, const int* Ap, const int* Ai, const double* Ax, const double* b,
                             const int* Gp, const int* Gi, const double* Gx, const double* h_l, const double* h_u, const double* x_l, const double* x_u)
@@ -1280,14 +1383,24 @@ int pq_solver_solve(pq_solver* s)
     return rc < 0 ? PQ_NUMERICS : status;
 }
 const pq_info* pq_solver_info(const pq_solver* s) { return s ? &s->impl->info() : nullptr; }
-int pq_solver_get_result(const pq_solver* s, pq_vars* out)
+int pq_solver_get_result_mem(const pq_solver* s, pq_vars* out, int mem)
 {
     if (!s || !out) return fail(PQ_ERR_INVALID, "null argument");
+    if (mem != PQ_MEM_HOST && mem != PQ_MEM_DEVICE) return fail(PQ_ERR_INVALID, "mem must be PQ_MEM_HOST or PQ_MEM_DEVICE");
     const HostVars& r = s->impl->result();
     double* dst[10] = {out->x, out->y, out->z_l, out->z_u, out->z_bl, out->z_bu, out->s_l, out->s_u, out->s_bl, out->s_bu};
-    for (int k = 0; k < 10; ++k) if (dst[k]) std::copy(r.field(k).begin(), r.field(k).end(), dst[k]);
-    return PQ_OK;
+    if (mem == PQ_MEM_HOST) {
+        for (int k = 0; k < 10; ++k) if (dst[k]) std::copy(r.field(k).begin(), r.field(k).end(), dst[k]);
+        return PQ_OK;
+    }
+    // the solution the solve left in result() (unscaled, boxes expanded), O(n + p + m); blocking copies: the outputs are written when this returns
+    return guarded([&] {
+        PQ_HIP(hipSetDevice(s->impl->device()));
+        for (int k = 0; k < 10; ++k) if (dst[k] && !r.field(k).empty()) PQ_HIP(hipMemcpy(dst[k], r.field(k).data(), sizeof(double) * r.field(k).size(), hipMemcpyHostToDevice));
+        return (int)PQ_OK;
+    });
 }
+int pq_solver_get_result(const pq_solver* s, pq_vars* out) { return pq_solver_get_result_mem(s, out, PQ_MEM_HOST); }
 int pq_solver_dims(const pq_solver* s, int* n, int* p, int* m)
 {
     if (!s || !s->impl->data()) return fail(PQ_ERR_INVALID, "solver not set up");

@@ -81,6 +81,13 @@ private:
     std::unique_ptr<Impl> I;
 };
 
+// the dense matrices of a setup / update that already live in HBM on the solver's device: P n x n, A p x n, G m x n in storage order `layout`
+// (PQ_COL_MAJOR / PQ_ROW_MAJOR); nullptr = absent (setup) / unchanged (update).  They go to DeviceRuiz by kernel (ingest_kernels.hip), never through HostData.
+struct DenseDeviceSource {
+    const double *P = nullptr, *A = nullptr, *G = nullptr;
+    int layout = PQ_COL_MAJOR;
+};
+
 class Solver {
 public:
     explicit Solver(int device);
@@ -88,9 +95,16 @@ public:
     Solver* clone() const;
 
     pq_settings& settings() { return m_settings; }
-    bool setup(std::unique_ptr<HostData> data);  // solver.hpp:151-216
+    // solver.hpp:151-216.  dev: the matrices of a dense problem come from device memory (data then carries vectors and bound lists only, and
+    // zeroed_rows the rows of G that data.hpp:144-169 disables); requires device_ingest()
+    bool setup(std::unique_ptr<HostData> data, const DenseDeviceSource* dev = nullptr, const IVec* zeroed_rows = nullptr);
+    // solver.hpp:218-308.  The vectors are host arrays; P, A, G are host arrays (mat_mem = PQ_MEM_HOST) or device arrays (PQ_MEM_DEVICE, requires device_ingest())
+    // in storage order `layout`
     bool update_dense(const double* P, const double* c, const double* A, const double* b, const double* G, const double* h_l, const double* h_u, const double* x_l,
-                      const double* x_u);  // solver.hpp:218-308
+                      const double* x_u, int mat_mem = PQ_MEM_HOST, int layout = PQ_COL_MAJOR);
+    static bool device_ingest();                                  // false under PIQP_AMD_DEBUG=host_ruiz: the matrices are scaled on the host there
+    const long long* last_ingest() const { return ingest_; }      // pq_solver_last_ingest
+    void add_link_bytes(long long bytes) { ingest_[0] += bytes; }  // matrix bytes the C-ABI layer itself moved across the link for the last setup / update
     bool update_sparse(const int* Pp, const int* Pi, const double* Px, const double* c, const int* Ap, const int* Ai, const double* Ax, const double* b, const int* Gp,
                        const int* Gi, const double* Gx, const double* h_l, const double* h_u, const double* x_l, const double* x_u);
     int solve();  // solver.hpp:69-148
@@ -145,12 +159,14 @@ private:
     std::unique_ptr<DeviceIpm> dipm_;  // null when PIQP_AMD_HOST_IPM=1
     double* trace_ = nullptr;
     int trace_max_ = 0, trace_rows_ = 0;
+    long long ingest_[2] = {0, 0};  // matrix bytes of the last setup / update: across the host-device link, device to device
 };
 
 bool verify_settings(const pq_settings& s);  // settings.hpp:84-106
 
 std::unique_ptr<HostData> make_dense_host_data(int n, int p, int m, const double* P, const double* c, const double* A, const double* b, const double* G, const double* h_l,
-                                               const double* h_u, const double* x_l, const double* x_u);
+                                               const double* h_u, const double* x_l, const double* x_u, int layout = PQ_COL_MAJOR, bool matrices_on_device = false,
+                                               IVec* zeroed_rows = nullptr);
 std::unique_ptr<HostData> make_sparse_host_data(int n, int p, int m, const int* Pp, const int* Pi, const double* Px, const double* c, const int* Ap, const int* Ai,
                                                 const double* Ax, const double* b, const int* Gp, const int* Gi, const double* Gx, const double* h_l, const double* h_u,
                                                 const double* x_l, const double* x_u);

@@ -22,6 +22,7 @@ DENSE_LDLT_NO_PIVOT = 16
 DENSE_CHOLESKY_EXACT = 19  # dense_cholesky in the reference's own order of operations (csrc/dense_exact.hip), n <= 1024
 KKT_UPDATE_NONE, KKT_UPDATE_P, KKT_UPDATE_A, KKT_UPDATE_G = 0, 1, 2, 4
 MEM_HOST, MEM_DEVICE = 0, 1
+COL_MAJOR, ROW_MAJOR = 0, 1  # storage order of P, A, G for the *_mem entry points (include/piqp_amd.h)
 
 
 def _is_torch(a):
@@ -47,6 +48,71 @@ def _f64(a, order="C"):
 
 def _i32(a):
     return np.ascontiguousarray(a, dtype=np.int32)
+
+
+# ---- problem data in GPU memory (pq_solver_*_mem, pq_batch_*_mem): pure argument handling, no library call in here ----
+def tensor_layout(t):
+    """(tensor to pass, layout) for a 2-D torch tensor: a contiguous tensor is ROW_MAJOR, a transposed view of one is COL_MAJOR,
+    anything else (slices, strided views) is made contiguous first"""
+    if t.is_contiguous():
+        return t, ROW_MAJOR
+    if t.t().is_contiguous():
+        return t, COL_MAJOR
+    return t.contiguous(), ROW_MAJOR
+
+
+def device_call(args):
+    """True if a call with these arguments takes its data from GPU memory: any of them is a torch CUDA tensor"""
+    return any(a is not None and _is_torch(a) and a.is_cuda for a in args)
+
+
+def check_device_tensor(name, t, shape, device):
+    """refuses, before the library is called, a torch tensor that cannot be handed over as device memory of GPU `device`"""
+    import torch
+    if t.dtype != torch.float64:
+        raise TypeError(f"{name}: dtype {t.dtype}, the solvers take float64")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
+    if not t.is_cuda:
+        raise TypeError(f"{name}: a CPU torch tensor beside GPU data; pass a numpy array (moved to the GPU for you) or a CUDA tensor")
+    if t.device.index != device:
+        raise ValueError(f"{name}: lives on cuda:{t.device.index}, the solver on cuda:{device}")
+    return t
+
+
+def to_device_args(args, shapes, device, matrices=()):
+    """args: dict name -> None / numpy array / torch tensor.  Returns (dict of CUDA tensors ready to pass, layout of the matrices).
+    numpy arguments are moved to the GPU; vectors are made contiguous; the matrices named in `matrices` end up in ONE storage order."""
+    import torch
+    out = {}
+    for k, a in args.items():
+        if a is None:
+            out[k] = None
+        elif _is_torch(a):
+            out[k] = check_device_tensor(k, a, shapes[k], device)
+        else:
+            h = np.ascontiguousarray(a, dtype=np.float64)
+            if h.shape != tuple(shapes[k]):
+                raise ValueError(f"{k}: shape {h.shape}, expected {tuple(shapes[k])}")
+            out[k] = torch.as_tensor(h).to(f"cuda:{device}")
+    lay = {}
+    for k in matrices:
+        if out[k] is not None:
+            out[k], lay[k] = tensor_layout(out[k])
+    layout = COL_MAJOR if lay and all(v == COL_MAJOR for v in lay.values()) else ROW_MAJOR
+    for k, v in lay.items():
+        if v != layout:
+            out[k] = out[k].contiguous()
+    for k in out:
+        if k not in matrices and out[k] is not None:
+            out[k] = out[k].contiguous()
+    return out, layout
+
+
+def sync_current_stream(device):
+    """the caller's half of the ordering contract: everything torch has queued on its current stream for `device` is complete"""
+    import torch
+    torch.cuda.current_stream(device).synchronize()
 
 
 def var_sizes(n, p, m):
@@ -466,6 +532,7 @@ class DenseSolver(_Handle):
             h = C.c_void_p()
             check(self.L.pq_solver_create(C.byref(h), device), "pq_solver_create")
             self.h = h
+        self.device = device
         self._trace = None
 
     @property
@@ -475,7 +542,7 @@ class DenseSolver(_Handle):
     def clone(self):
         h = C.c_void_p()
         check(self.L.pq_solver_clone(self.h, C.byref(h)))
-        return type(self)(_h=h)
+        return type(self)(device=self.device, _h=h)
 
     @staticmethod
     def _col(a):
@@ -485,7 +552,28 @@ class DenseSolver(_Handle):
     def _vec(a):
         return None if a is None else np.ascontiguousarray(a, dtype=np.float64)
 
+    _NAMES = ("P", "c", "A", "b", "G", "h_l", "h_u", "x_l", "x_u")
+
+    def _device_args(self, args, n, p, m):
+        shapes = dict(P=(n, n), c=(n,), A=(p, n), b=(p,), G=(m, n), h_l=(m,), h_u=(m,), x_l=(n,), x_u=(n,))
+        keep, layout = to_device_args(dict(zip(self._NAMES, args)), shapes, self.device, matrices=("P", "A", "G"))
+        sync_current_stream(self.device)
+        return [keep[k] for k in self._NAMES], layout
+
+    def last_ingest(self):
+        """(matrix bytes that crossed the host-device link, matrix bytes moved on the device) of the last setup / update"""
+        out = (C.c_longlong * 2)()
+        check(self.L.pq_solver_last_ingest(self.h, out), "last_ingest")
+        return out[0], out[1]
+
     def setup(self, P, c, A=None, b=None, G=None, h_l=None, h_u=None, x_l=None, x_u=None):
+        """numpy arrays, or torch CUDA float64 tensors (any argument; the data then stays on the GPU: pq_solver_setup_dense_mem)"""
+        args = (P, c, A, b, G, h_l, h_u, x_l, x_u)
+        if device_call(args):
+            rows = lambda M: 0 if M is None else (M if _is_torch(M) else np.asarray(M)).shape[0]
+            n, p, m = rows(P), rows(A), rows(G)
+            keep, layout = self._device_args(args, n, p, m)
+            return bool(check(self.L.pq_solver_setup_dense_mem(self.h, n, p, m, *[_ptr(a) for a in keep], MEM_DEVICE, layout), "setup"))
         P = self._col(P)
         n = P.shape[0]
         p = 0 if A is None else np.asarray(A).shape[0]
@@ -493,7 +581,16 @@ class DenseSolver(_Handle):
         keep = [P, self._vec(c), self._col(A), self._vec(b), self._col(G), self._vec(h_l), self._vec(h_u), self._vec(x_l), self._vec(x_u)]
         return bool(check(self.L.pq_solver_setup_dense(self.h, n, p, m, *[_ptr(a) for a in keep]), "setup"))
 
+    def _dims(self):
+        n, p, m = C.c_int(), C.c_int(), C.c_int()
+        check(self.L.pq_solver_dims(self.h, C.byref(n), C.byref(p), C.byref(m)))
+        return n.value, p.value, m.value
+
     def update(self, P=None, c=None, A=None, b=None, G=None, h_l=None, h_u=None, x_l=None, x_u=None):
+        args = (P, c, A, b, G, h_l, h_u, x_l, x_u)
+        if device_call(args):
+            keep, layout = self._device_args(args, *self._dims())
+            return bool(check(self.L.pq_solver_update_dense_mem(self.h, *[_ptr(a) for a in keep], MEM_DEVICE, layout), "update"))
         keep = [self._col(P), self._vec(c), self._col(A), self._vec(b), self._col(G), self._vec(h_l), self._vec(h_u), self._vec(x_l), self._vec(x_u)]
         return bool(check(self.L.pq_solver_update_dense(self.h, *[_ptr(a) for a in keep]), "update"))
 
@@ -511,10 +608,17 @@ class DenseSolver(_Handle):
     def info(self):
         return self.L.pq_solver_info(self.h).contents
 
-    def result(self):
-        n, p, m = C.c_int(), C.c_int(), C.c_int()
-        check(self.L.pq_solver_dims(self.h, C.byref(n), C.byref(p), C.byref(m)))
-        out = Variables.zeros(n.value, p.value, m.value)
+    def result(self, device=False):
+        """the ten solution vectors as numpy arrays, or (device=True) as torch tensors on the solver's GPU"""
+        n, p, m = self._dims()
+        if device:
+            import torch
+            out = Variables({k: torch.zeros(sz, dtype=torch.float64, device=f"cuda:{self.device}") for k, sz in var_sizes(n, p, m).items()})
+            sync_current_stream(self.device)
+            vs = Variables.to_struct(out)
+            check(self.L.pq_solver_get_result_mem(self.h, C.byref(vs), MEM_DEVICE))
+            return out
+        out = Variables.zeros(n, p, m)
         vs = Variables.to_struct(out)
         check(self.L.pq_solver_get_result(self.h, C.byref(vs)))
         return out
