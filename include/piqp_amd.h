@@ -508,6 +508,14 @@ long long pq_debug_alloc_count(void);
  * k_chol_persistent), five ints per task (kind, round, a, b, gate).
  * Returns the number of tasks (-1: T outside [3, 1024]).  tests/test_chol_plan.py replays the list on the CPU: every task only waits for EARLIER tickets. */
 int pq_debug_chol_plan(int T, int *out5, int capacity_tasks);
+/* host-only (no device needed): the launch plan of the SYRK behind the dense KKT assembly and A^T A (csrc/dense_kernels.hip launch_syrk) for an n x n result with
+ * inner dimension kdim, with (the G' W G assembly) or without (A^T A) the split-K workspace: out = { T = ceil(n / 128), tiles of the lower triangle, 1 if the 16-wave
+ * low-latency shape runs (kdim <= 256), 1 if the launch asks for the XCD-aware tile-order table (if its allocation fails the launch falls back to the triangular
+ * block -> tile map: the hook allocates nothing and cannot tell), rem = tiles of the split-K tail (0: none), k_split = K slices per tail tile }.
+ * Computed by the functions the launcher itself uses; without a visible device the plan is that of 256 CUs.  Returns 0, or < 0 for a null out, n <= 0, kdim < 0 or
+ * n > 32767 * 128.  tests/test_syrk_plan.py pins it for the shapes of
+ * tests/test_dense_assembly_gpu.py. */
+int pq_debug_syrk_plan(int n, int kdim, int with_workspace, int out[6]);
 /* testing aid: out[i] = sqrt(in[i]) computed on `device` as the reference-order dense factorisation computes its pivots (csrc/dense_exact.hip); host arrays.
  * PQ_DENSE_CHOLESKY_EXACT is bitwise the reference only if the device's fp64 square root is correctly rounded: tests/test_dense_exact_gpu.py checks it. */
 int pq_debug_device_sqrt(int device, const double *in, double *out, long long count);

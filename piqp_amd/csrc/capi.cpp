@@ -853,6 +853,13 @@ int pq_debug_device_sqrt(int device, const double* in, double* out, long long co
     if (rc < 0) return rc;
     return guarded([&] { pq::debug_device_sqrt(in, out, count, device); return (int)PQ_OK; });
 }
+int pq_debug_syrk_plan(int n, int kdim, int with_workspace, int out[6])
+{
+    if (!out || n <= 0 || kdim < 0) return fail(PQ_ERR_INVALID, "bad argument");
+    if (n > 32767 * 128) return fail(PQ_ERR_INVALID, "n = %d: more than 32767 tile rows", n);  // (the tile count stays an int, a tile index fits the table's 16 bits)
+    dense::syrk_debug_plan(n, kdim, with_workspace != 0, out);
+    return (int)PQ_OK;
+}
 int pq_debug_chol_plan(int T, int* out5, int capacity_tasks) { return T >= 3 && T <= 1024 ? dense::chol_debug_plan(T, out5, capacity_tasks) : -1; }
 
 int pq_microbench_mfma_f64(int device, int iters, double* tflops_out)

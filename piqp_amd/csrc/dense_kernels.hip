@@ -754,12 +754,41 @@ size_t syrk_split_workspace_doubles(int n, int kdim)
     return (size_t)rem * ks * TS * TS;
 }
 
+// The launch plan of launch_syrk_t: everything it decides from (n, kdim, split workspace, CU count).  The launcher reads it from here and so does
+// syrk_debug_plan (pq_debug_syrk_plan, tests/test_syrk_plan.py), so the two cannot disagree.
+struct SyrkPlan {
+    int T, ntiles;
+    bool low_latency;  // short inner dimension (factorisation trailing updates, K = 128): latency-bound per tile -> 16-wave shape
+    bool tile_order;   // the XCD-aware order table is asked for (long inner dimension, T x T grid of at least two patches a side)
+    int rem, k_split;  // the last `rem` tiles run as k_split K-slices each + k_syrk_tail_reduce (0, 1: no tail)
+};
+static bool syrk_wants_tile_order(int T) { return T >= 16; }
+static SyrkPlan syrk_plan(int n, int kdim, bool with_ws, size_t ws_doubles)
+{
+    SyrkPlan p;
+    p.T = div_up(n, TS);
+    p.ntiles = p.T * (p.T + 1) / 2;
+    p.rem = 0; p.k_split = 1;
+    if (with_ws) syrk_tail_plan(n, kdim, p.rem, p.k_split);
+    if (p.rem > 0 && (size_t)p.rem * p.k_split * TS * TS > ws_doubles) { p.rem = 0; p.k_split = 1; }
+    p.low_latency = kdim <= 256;
+    p.tile_order = !p.low_latency && syrk_wants_tile_order(p.T);
+    return p;
+}
+// host-only: { T, ntiles, low_latency, tile_order, rem, k_split } of a launch with (with_workspace) or without the split workspace of
+// syrk_split_workspace_doubles(n, kdim).  Allocates nothing, launches nothing, builds no table; without a visible device the plan is that of 256 CUs
+void syrk_debug_plan(int n, int kdim, bool with_workspace, int out[6])
+{
+    const SyrkPlan p = syrk_plan(n, kdim, with_workspace, ~(size_t)0);
+    out[0] = p.T; out[1] = p.ntiles; out[2] = p.low_latency ? 1 : 0; out[3] = p.tile_order ? 1 : 0; out[4] = p.rem; out[5] = p.k_split;
+}
+
 // device copy of the XCD-aware tile order for a T x T lower-triangular tile grid (built once per device and T, never freed: a few KB)
 static const int* syrk_tile_order(int T)
 {
     static std::mutex mu;
     static std::map<std::pair<int, int>, int*> cache;
-    if (T < 16) return nullptr;
+    if (!syrk_wants_tile_order(T)) return nullptr;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return nullptr;
     std::lock_guard<std::mutex> lk(mu);
@@ -789,22 +818,16 @@ void syrk_prepare(int n) { (void)syrk_tile_order(div_up(n, TS)); }  // the per-d
 template <int EPI>
 static void launch_syrk_t(SyrkArgs a, hipStream_t s, double* ws, size_t ws_doubles)
 {
-    const int T = div_up(a.n, TS);
-    const int ntiles = T * (T + 1) / 2;
-    int rem = 0, ks = 1;
-    if (ws) syrk_tail_plan(a.n, a.kdim, rem, ks);
-    if (rem > 0 && (size_t)rem * ks * TS * TS > ws_doubles) { rem = 0; ks = 1; }
-    const int main_tiles = ntiles - rem;
+    const SyrkPlan pl = syrk_plan(a.n, a.kdim, ws != nullptr, ws_doubles);
+    const int main_tiles = pl.ntiles - pl.rem;
     a.tile_begin = 0; a.k_split = 1; a.part = nullptr;
-    // short inner dimension (factorisation trailing updates, K = 128): latency-bound per tile -> 16-wave shape
-    const bool low_latency = a.kdim <= 256;
-    a.tile_order = !low_latency ? syrk_tile_order(T) : nullptr;
-    if (low_latency) hipLaunchKernelGGL((k_syrk_lower<EPI, 4, 4>), dim3(main_tiles), dim3(1024), SYRK_LDS_BYTES, s, a);
+    a.tile_order = pl.tile_order ? syrk_tile_order(pl.T) : nullptr;
+    if (pl.low_latency) hipLaunchKernelGGL((k_syrk_lower<EPI, 4, 4>), dim3(main_tiles), dim3(1024), SYRK_LDS_BYTES, s, a);
     else hipLaunchKernelGGL((k_syrk_lower<EPI, 2, 2>), dim3(main_tiles), dim3(256), SYRK_LDS_BYTES, s, a);
-    if (rem > 0) {
-        a.tile_begin = main_tiles; a.k_split = ks; a.part = ws;
-        hipLaunchKernelGGL((k_syrk_lower<EPI, 2, 2>), dim3(rem * ks), dim3(256), SYRK_LDS_BYTES, s, a);
-        hipLaunchKernelGGL(k_syrk_tail_reduce<EPI>, dim3(rem, TS * TS / 256), dim3(256), 0, s, a);
+    if (pl.rem > 0) {
+        a.tile_begin = main_tiles; a.k_split = pl.k_split; a.part = ws;
+        hipLaunchKernelGGL((k_syrk_lower<EPI, 2, 2>), dim3(pl.rem * pl.k_split), dim3(256), SYRK_LDS_BYTES, s, a);
+        hipLaunchKernelGGL(k_syrk_tail_reduce<EPI>, dim3(pl.rem, TS * TS / 256), dim3(256), 0, s, a);
     }
 }
 

@@ -64,6 +64,7 @@ struct SyrkArgs {
 
 void launch_syrk(int epi, const SyrkArgs& args, hipStream_t s, double* split_ws = nullptr, size_t split_ws_doubles = 0);
 size_t syrk_split_workspace_doubles(int n, int kdim);
+void syrk_debug_plan(int n, int kdim, bool with_workspace, int out[6]);  // host-only: { T, ntiles, low_latency, tile_order, rem, k_split } as launch_syrk decides them
 void syrk_prepare(int n);  // allocates what launch_syrk(EPI_ASSEMBLE, n) would otherwise allocate on first use
 void launch_assemble_no_g(int n, const double* Pf, const double* x_reg, const double* ATA, double dinv, double* C, hipStream_t s);
 // diagonal block of order nb <= 128 at A: factor in place, reciprocal pivots to rdiag[kglobal..], D to dvec[0..nb) (LDLT, nullable), and the
