@@ -1505,13 +1505,7 @@ public:
     {
         pq_settings_default(&settings_);
         settings_.kkt_solver = PQ_SPARSE_MULTISTAGE;
-        PQ_HIP(hipSetDevice(dev_));
-        PQ_HIP(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
-    }
-    ~BatchSolver()
-    {
-        (void)hipSetDevice(dev_);
-        if (st_) { (void)hipStreamSynchronize(st_); (void)hipStreamDestroy(st_); }
+        st_ = Stream(dev_);
     }
     pq_settings& settings() { return settings_; }
     int batch() const { return batch_; }
@@ -2209,7 +2203,6 @@ private:
     const int *mapP_ = nullptr, *mapA_ = nullptr, *mapG_ = nullptr, *disabled_d_ = nullptr, *rzPp_ = nullptr, *rzPi_ = nullptr;  // device, owned by ibufs_
     double last_kernel_ms_ = 0.0;
     bool lpt_ = true;
-    hipStream_t st_ = nullptr;
     pq_settings settings_;
     multistage::Symbolic sym_;
     Layout layout_;
@@ -2222,6 +2215,7 @@ private:
     DBuf<int> order_;            // block -> instance of the next launch
     std::vector<int> order_h_;
     std::vector<pq_info> infos_h_;
+    Stream st_;  // last, so it goes first: drained and destroyed before the buffers its work uses
 };
 
 }  // namespace pq

@@ -151,6 +151,46 @@ struct DBuf {
     size_t bytes() const { return n * sizeof(T); }
 };
 
+// RAII owner of one hipStream_t on one device; move-only, empty by default.  The destructor waits for the stream before destroying it.  Members go in reverse order of
+// declaration, so where a class declares its Stream decides what the stream outlives: last = it is drained and destroyed before any buffer goes; first = it goes last, and
+// the class's destructor waits on it itself before it releases events or a communicator.  Either way a constructor that throws once the stream exists no longer leaks it.
+// (Api: the create / destroy pair; anything but HipStreamApi is tests/c/stream_raii_kat.cpp counting the calls.)
+struct HipStreamApi {
+    static hipStream_t create(int device)
+    {
+        hipStream_t s = nullptr;
+        PQ_HIP(hipSetDevice(device));
+        PQ_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        return s;
+    }
+    static void destroy(int device, hipStream_t s) noexcept { (void)hipSetDevice(device); (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
+};
+template <class Api>
+class BasicStream {
+public:
+    BasicStream() = default;
+    explicit BasicStream(int device) : dev_(device), s_(Api::create(device)) {}
+    BasicStream(int device, hipStream_t adopt) : dev_(device), s_(adopt) {}
+    BasicStream(const BasicStream&) = delete;
+    BasicStream& operator=(const BasicStream&) = delete;
+    BasicStream(BasicStream&& o) noexcept : dev_(o.dev_), s_(o.release()) {}
+    BasicStream& operator=(BasicStream&& o) noexcept
+    {
+        if (this != &o) { reset(); dev_ = o.dev_; s_ = o.release(); }
+        return *this;
+    }
+    ~BasicStream() { reset(); }
+    hipStream_t get() const { return s_; }
+    operator hipStream_t() const { return s_; }
+    hipStream_t release() noexcept { hipStream_t s = s_; s_ = nullptr; return s; }  // the caller owns it from here on
+
+private:
+    void reset() noexcept { if (s_) Api::destroy(dev_, release()); }
+    int dev_ = 0;
+    hipStream_t s_ = nullptr;
+};
+using Stream = BasicStream<HipStreamApi>;
+
 // pinned host staging buffer
 template <class T>
 struct HBuf {

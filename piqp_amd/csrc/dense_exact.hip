@@ -332,15 +332,9 @@ public:
     {
         if (n_ <= 0 || p_ < 0 || m_ < 0) throw std::runtime_error("dense KKT: bad dimensions");
         if (n_ > EX_MAX_N) throw std::runtime_error("dense_cholesky_exact: n <= 1024 only");
-        PQ_HIP(hipSetDevice(dev_));
-        PQ_HIP(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
-        // (the destructor does not run for a constructor that throws: the buffers release themselves, the stream does not)
-        try { alloc(); upload(d); } catch (...) { drop_stream(); throw; }
-    }
-    ~DenseExactKKT() override
-    {
-        (void)hipSetDevice(dev_);
-        drop_stream();
+        st_ = Stream(dev_);
+        alloc();
+        upload(d);
     }
 
     KKTSolverBase* clone() const override
@@ -449,14 +443,9 @@ public:
 private:
     DenseExactKKT(const DenseExactKKT& o, int) : dev_(o.dev_), n_(o.n_), p_(o.p_), m_(o.m_), delta_(o.delta_)
     {
-        PQ_HIP(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
-        try { alloc(); copy_state(o); } catch (...) { drop_stream(); throw; }
-    }
-
-    void drop_stream()
-    {
-        if (st_) { (void)hipStreamSynchronize(st_); (void)hipStreamDestroy(st_); }
-        st_ = nullptr;
+        st_ = Stream(dev_);
+        alloc();
+        copy_state(o);
     }
 
     void copy_state(const DenseExactKKT& o)
@@ -509,11 +498,11 @@ private:
 
     int dev_, n_, p_, m_;
     double delta_ = 1.0;
-    hipStream_t st_ = nullptr;
     DBuf<double> Pu_, Pdiag_, AT_, GT_, ATA_, kkt_, fac_, z_reg_inv_;
     DBuf<int> info_;
     HBuf<int> info_h_;
     StageProfiler prof_;
+    Stream st_;  // last, so it goes first: drained and destroyed before the profiler's events and the buffers its work uses
 };
 
 }  // namespace

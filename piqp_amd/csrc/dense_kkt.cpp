@@ -29,11 +29,9 @@ namespace {
 
 class DenseKKT final : public KKTSolverBase {
 public:
-    DenseKKT(const pq_dense_data* d, int kkt_solver, int device) : dev_(device), n_(d->n), p_(d->p), m_(d->m), ldlt_(kkt_solver == PQ_DENSE_LDLT_NO_PIVOT)
+    DenseKKT(const pq_dense_data* d, int kkt_solver, int device) : dev_(device), n_(d->n), p_(d->p), m_(d->m), ldlt_(kkt_solver == PQ_DENSE_LDLT_NO_PIVOT), st_(device)
     {
         if (n_ <= 0 || p_ < 0 || m_ < 0) throw std::runtime_error("dense KKT: bad dimensions");
-        PQ_HIP(hipSetDevice(dev_));
-        PQ_HIP(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
         alloc();
         upload(d);
     }
@@ -41,10 +39,10 @@ public:
     ~DenseKKT() override
     {
         (void)hipSetDevice(dev_);
-        if (st_inv_) { (void)hipStreamSynchronize(st_inv_); (void)hipStreamDestroy(st_inv_); }
+        if (st_inv_) (void)hipStreamSynchronize(st_inv_);
+        if (st_) (void)hipStreamSynchronize(st_);
         if (ev_fac_) (void)hipEventDestroy(ev_fac_);
         if (ev_inv_) (void)hipEventDestroy(ev_inv_);
-        if (st_) { (void)hipStreamSynchronize(st_); (void)hipStreamDestroy(st_); }
     }
 
     // dense/kkt.hpp:57-60
@@ -202,9 +200,8 @@ public:
 
 private:
     // copy-construction for clone(): same device, fresh stream, deep copies of all state
-    DenseKKT(const DenseKKT& o, int) : dev_(o.dev_), n_(o.n_), p_(o.p_), m_(o.m_), ldlt_(o.ldlt_), class_semantics_(o.class_semantics_), delta_(o.delta_)
+    DenseKKT(const DenseKKT& o, int) : dev_(o.dev_), n_(o.n_), p_(o.p_), m_(o.m_), ldlt_(o.ldlt_), class_semantics_(o.class_semantics_), delta_(o.delta_), st_(o.dev_)
     {
-        PQ_HIP(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
         alloc();
         auto cp = [&](DBuf<double>& dst, const DBuf<double>& src) { if (src.n) PQ_HIP(hipMemcpyAsync(dst.p, src.p, src.bytes(), hipMemcpyDeviceToDevice, st_)); };
         cp(Pfull_, o.Pfull_); cp(Pdiag_, o.Pdiag_); cp(AT_, o.AT_); cp(GT_, o.GT_); cp(ATA_, o.ATA_); cp(fac_, o.fac_);
@@ -244,7 +241,7 @@ private:
         if (const char* e = debug_token("inv_sweeps")) inv_sweeps_ = std::atoi(e) != 0 && (n_ + 127) / 128 <= 224;
         if (inv_sweeps_) {
             vinv_.alloc(dense::block_inverse_dd_doubles(n_));
-            PQ_HIP(hipStreamCreateWithFlags(&st_inv_, hipStreamNonBlocking));
+            st_inv_ = Stream(dev_);
             PQ_HIP(hipEventCreateWithFlags(&ev_fac_, hipEventDisableTiming));
             PQ_HIP(hipEventCreateWithFlags(&ev_inv_, hipEventDisableTiming));
         }
@@ -379,12 +376,11 @@ private:
     bool ldlt_;
     bool class_semantics_ = false;  // see KKTSolverBase::set_class_failure_semantics
     double delta_ = 1.0;
-    hipStream_t st_ = nullptr;
+    Stream st_, st_inv_;  // before every buffer, so they go last: the destructor waits on both, then the events go, then the buffers (st_inv_: the block inverses)
     DBuf<double> Pfull_, Pdiag_, AT_, GT_, ATA_, fac_, z_reg_inv_, x_reg_last_, dvec_, part_, rdiag_, split_ws_, pack_, w16_, fuse_scratch_;
     DBuf<int> info_, flags_, fuse_flags_, fuse_cnt_, chol_flags_;
     DBuf<double> pack2_, side_;  // side_: the solved panels once more, at addresses the persistent launch has never read before (dense_kernels.hip)
     bool inv_sweeps_ = false, inv_pending_ = false;
-    hipStream_t st_inv_ = nullptr;
     hipEvent_t ev_fac_ = nullptr, ev_inv_ = nullptr;
     void join_inverses()
     {

@@ -108,7 +108,9 @@ constexpr int DENSE_EXACT_MAX_N = 1024;
 void debug_device_sqrt(const double* in_host, double* out_host, long long count, int device);  // dense_exact.hip (pq_debug_device_sqrt)
 KKTSolverBase* make_sparse_kkt(const pq_sparse_data* data, int kkt_solver, int device);
 KKTSolverBase* make_multistage_kkt(const pq_sparse_data* data, int device);
-KKTSolverBase* make_multifrontal_kkt(const pq_sparse_data* data, int mode, int device);  // sparse_kkt.hip: the supernodal multifrontal engine, any KKTMode
+// sparse_kkt.hip: the supernodal multifrontal engine, any KKTMode.  adopt: a stream the engine runs on and owns from the moment this returns (if it throws, the caller still owns it)
+KKTSolverBase* make_multifrontal_kkt(const pq_sparse_data* data, int mode, int device, hipStream_t adopt = nullptr);
 KKTSolverBase* make_exact_sparse_kkt(const pq_sparse_data* data, int mode, int device, double max_flops = 0.0);  // sparse_exact.hip: any KKTMode in the reference's own elimination order
+hipStream_t release_exact_sparse_stream(KKTSolverBase* exact);  // an engine of make_exact_sparse_kkt gives its (idle) stream away; all it can do afterwards is be deleted
 
 }  // namespace pq

@@ -93,8 +93,7 @@ public:
     MultistageKKT(const pq_sparse_data* d, int device) : dev_(device)
     {
         if (d->mem != PQ_MEM_HOST) throw std::runtime_error("sparse data must be host-resident");
-        PQ_HIP(hipSetDevice(dev_));
-        PQ_HIP(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
+        st_ = Stream(dev_);
         multistage::analyse(d, S_);
         n_ = S_.n; p_ = S_.p; m_ = S_.m;
         plan_lds();
@@ -113,12 +112,6 @@ public:
         ops_.init(d, st_);
         scatter_values(KKT_ALL);
     }
-    ~MultistageKKT() override
-    {
-        (void)hipSetDevice(dev_);
-        if (st_) { (void)hipStreamSynchronize(st_); (void)hipStreamDestroy(st_); }
-    }
-
     KKTSolverBase* clone() const override
     {
         PQ_HIP(hipSetDevice(dev_));
@@ -309,7 +302,7 @@ private:
         : dev_(o.dev_), n_(o.n_), p_(o.p_), m_(o.m_), delta_(o.delta_), S_(o.S_), factor_in_lds_(o.factor_in_lds_), li_in_lds_(o.li_in_lds_), solve_in_lds_(o.solve_in_lds_),
           factor_lds_bytes_(o.factor_lds_bytes_), solve_lds_bytes_(o.solve_lds_bytes_), fcap_(o.fcap_), ucap_(o.ucap_), pcap_(o.pcap_), hcap_(o.hcap_), asm_chunks_(o.asm_chunks_)
     {
-        PQ_HIP(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
+        st_ = Stream(dev_);
         ops_.clone_from(o.ops_, st_);
         clone_buf(w_, o.w_, st_); clone_buf(off_, o.off_, st_); clone_buf(h_, o.h_, st_); clone_buf(start_, o.start_, st_);
         clone_buf(front_off_, o.front_off_, st_); clone_buf(pan_off_, o.pan_off_, st_);
@@ -372,7 +365,6 @@ private:
 
     int dev_, n_ = 0, p_ = 0, m_ = 0;
     double delta_ = 1.0;
-    hipStream_t st_ = nullptr;
     multistage::Symbolic S_;
     bool factor_in_lds_ = true, li_in_lds_ = true, solve_in_lds_ = true;
     int factor_lds_bytes_ = 0, solve_lds_bytes_ = 0, fcap_ = 0, ucap_ = 0, pcap_ = 0, hcap_ = 1, asm_chunks_ = 1;
@@ -382,6 +374,7 @@ private:
     DBuf<double> Pf_, AtAf_, F_, pan_, XA_, XG_, zinv_;
     StageProfiler prof_;
     std::unique_ptr<KKTSolverBase> tree_;
+    Stream st_;  // last, so it goes first: drained and destroyed before the tree engine, the profiler's events and the buffers its work uses
 };
 
 // MultistageKKT ctor (multistage_kkt.hpp:76-135).  Chains of 16+ stages get both elimination orders analysed and a SYMBOLIC cost

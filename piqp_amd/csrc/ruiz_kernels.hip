@@ -367,7 +367,6 @@ size_t ruiz_grid_ws_words() { return RUIZ_WS_WORDS; }
 struct DeviceRuiz::Impl {
     int device = 0, n = 0, p = 0, m = 0;
     bool sparse = false;
-    hipStream_t st = nullptr;
     // dense: the matrices (scaled once scale() ran); sparse: value staging
     DBuf<double> P, AT, GT;
     DBuf<int> Pp, Pi, ATp, ATi, GTp, GTi;
@@ -378,19 +377,14 @@ struct DeviceRuiz::Impl {
     HBuf<double> hvec;
     double *c = nullptr, *xbs = nullptr, *delta = nullptr, *delta_inv = nullptr, *delta_b = nullptr, *delta_b_inv = nullptr, *tmp = nullptr;
     size_t vec_len = 0;
-    ~Impl()
-    {
-        (void)hipSetDevice(device);
-        if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-    }
+    Stream st;  // last, so it goes first: drained and destroyed before the buffers its work uses
 };
 
 DeviceRuiz::DeviceRuiz(int device, const HostData& d) : I(new Impl)
 {
     Impl& s = *I;
     s.device = device; s.n = d.n; s.p = d.p; s.m = d.m; s.sparse = d.sparse;
-    PQ_HIP(hipSetDevice(device));
-    PQ_HIP(hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
+    s.st = Stream(device);
     const size_t n = d.n, N = (size_t)d.n + d.p + d.m;
     s.vec_len = 5 * n + 2 * N;
     s.vec.alloc(s.vec_len);

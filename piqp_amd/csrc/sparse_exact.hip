@@ -898,8 +898,7 @@ public:
         sparse::analyse_kkt_pattern(d, mode_, S);
         sparse::analyse_uplooking(S, d, U_);
         if (max_flops > 0.0 && U_.flops > max_flops) throw TooCostly{};
-        PQ_HIP(hipSetDevice(dev_));
-        PQ_HIP(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
+        st_ = Stream(dev_);
         n_ = U_.n; p_ = U_.p; m_ = U_.m; N_ = U_.N;
         if (mode_ != 0) {
             // eliminated blocks: entry -> value index of P K P' and the product-term lists (kkt_all_eliminated.hpp:184-223)
@@ -922,10 +921,10 @@ public:
     ~ExactSparseKKT() override
     {
         (void)hipSetDevice(dev_);
-        if (st_) { (void)hipStreamSynchronize(st_); }
+        if (st_) (void)hipStreamSynchronize(st_);
         if (xq_event_) { xq_launch_order().forget(dev_, xq_event_); (void)hipEventDestroy(xq_event_); }
-        if (st_) (void)hipStreamDestroy(st_);
     }
+    hipStream_t release_stream() { return st_.release(); }  // (release_exact_sparse_stream)
     KKTSolverBase* clone() const override
     {
         PQ_HIP(hipSetDevice(dev_));
@@ -1142,7 +1141,7 @@ public:
 private:
     ExactSparseKKT(const ExactSparseKKT& o, int) : dev_(o.dev_), mode_(o.mode_), nzAA_(o.nzAA_), nzGG_(o.nzGG_), n_(o.n_), p_(o.p_), m_(o.m_), N_(o.N_), nnzK_(o.nnzK_), delta_(o.delta_), U_(o.U_)
     {
-        PQ_HIP(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
+        st_ = Stream(dev_);
         build_device();
         auto cpi = [&](DBuf<int>& d, const DBuf<int>& sc) { d.alloc(sc.n ? sc.n : 1); if (sc.n) PQ_HIP(hipMemcpyAsync(d.p, sc.p, sc.bytes(), hipMemcpyDeviceToDevice, st_)); };
         auto cpd = [&](DBuf<double>& d, const DBuf<double>& sc) { d.alloc(sc.n ? sc.n : 1); if (sc.n) PQ_HIP(hipMemcpyAsync(d.p, sc.p, sc.bytes(), hipMemcpyDeviceToDevice, st_)); };
@@ -1341,10 +1340,10 @@ private:
 
     int dev_, mode_ = 0, nzAA_ = 0, nzGG_ = 0, n_ = 0, p_ = 0, m_ = 0, N_ = 0, nnzK_ = 0, ntask_ = 0, nticket_ = 0, grid_ = 1, nbgroup_ = 0, epoch_ = 0;
     double delta_ = 1.0;
+    Stream st_;  // before every buffer, so it goes last: the destructor waits on it, then the launch-order event goes, then the buffers (empty once the stream was handed on)
     DBuf<int> mapAA_, mapGG_, aa_ptr_, aa_q1_, aa_q2_, aa_k_, gg_ptr_, gg_q1_, gg_q2_, gg_k_;
     DBuf<double> ata_vals_, zinv_, rhs_top_;
     bool lds_y_ = true, lds_x_ = true;
-    hipStream_t st_ = nullptr;
     sparse::UpLooking U_;
     CscOperators ops_;
     DBuf<int> perm_, Cp_, Ci_, diag_pos_, mapP_, mapA_, mapG_, Lp_, Li_, Lcol_, Rp_, Rcol_, Rpos_, tk_kind_, tk_id_, task_rows_, dep_, rowrec_, taskrec_, E4_, Etab_, done_, p1done_, ctl_, bgroup_;
@@ -1382,5 +1381,7 @@ KKTSolverBase* make_exact_sparse_kkt(const pq_sparse_data* data, int mode, int d
         return nullptr;
     }
 }
+
+hipStream_t release_exact_sparse_stream(KKTSolverBase* exact) { return static_cast<ExactSparseKKT*>(exact)->release_stream(); }
 
 }  // namespace pq

@@ -14,8 +14,10 @@
 // No atomics anywhere: children are merged into their parent in a fixed order, so results are bitwise
 // reproducible (the reference's clone test needs that).
 #include <algorithm>
+#include <array>
 #include <cstdio>
 #include <cstdlib>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <type_traits>
@@ -2230,17 +2232,22 @@ inline dim3 g1(int n) { return dim3(n > 0 ? (n + 255) / 256 : 1); }
 
 class SparseKKT final : public KKTSolverBase {
 public:
-    SparseKKT(const pq_sparse_data* d, int mode, int device) : dev_(device), mode_(mode)
+    SparseKKT(const pq_sparse_data* d, int mode, int device, hipStream_t adopt = nullptr) : dev_(device), mode_(mode)
     {
         if (d->mem != PQ_MEM_HOST) throw std::runtime_error("sparse data must be host-resident");
         PQ_HIP(hipSetDevice(dev_));
-        PQ_HIP(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
-        PQ_HIP(hipStreamCreateWithFlags(&st2_, hipStreamNonBlocking));
-        PQ_HIP(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming)); PQ_HIP(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming));
-        sparse::analyse_kkt(d, mode, S_);
-        n_ = S_.n; p_ = S_.p; m_ = S_.m; N_ = S_.N;
-        compute_level_lds();
-        build_device(d);
+        st_ = adopt ? Stream(dev_, adopt) : Stream(dev_);
+        try {
+            st2_ = Stream(dev_);
+            PQ_HIP(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming)); PQ_HIP(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming));
+            sparse::analyse_kkt(d, mode, S_);
+            n_ = S_.n; p_ = S_.p; m_ = S_.m; N_ = S_.N;
+            compute_level_lds();
+            build_device(d);
+        } catch (...) {
+            if (adopt) { (void)hipStreamSynchronize(st_); (void)st_.release(); }  // (an adopted stream is the caller's again: make_multifrontal_kkt)
+            throw;
+        }
     }
     ~SparseKKT() override
     {
@@ -2249,8 +2256,6 @@ public:
         if (comm_) rccl::comm_destroy(comm_);
         if (ev_fork_) (void)hipEventDestroy(ev_fork_);
         if (ev_join_) (void)hipEventDestroy(ev_join_);
-        if (st2_) (void)hipStreamDestroy(st2_);
-        if (st_) (void)hipStreamDestroy(st_);
     }
 
     KKTSolverBase* clone() const override
@@ -2740,8 +2745,7 @@ private:
     SparseKKT(const SparseKKT& o, int) : dev_(o.dev_), mode_(o.mode_), nzAA_(o.nzAA_), nzGG_(o.nzGG_), n_(o.n_), p_(o.p_), m_(o.m_), N_(o.N_), nnzK_(o.nnzK_), delta_(o.delta_), S_(o.S_), level_lds_(o.level_lds_), sub_lds_(o.sub_lds_), ntop_(o.ntop_), top_grid_(o.top_grid_), top_lds_(o.top_lds_), top_l0_(o.top_l0_), top_start_(o.top_start_), top_nper_(o.top_nper_), top_persistent_(o.top_persistent_)
     {
         ref_mode_ = o.ref_mode_;
-        PQ_HIP(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
-        PQ_HIP(hipStreamCreateWithFlags(&st2_, hipStreamNonBlocking));
+        st_ = Stream(dev_); st2_ = Stream(dev_);
         PQ_HIP(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming)); PQ_HIP(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming));
         auto cpd = [&](DBuf<double>& d, const DBuf<double>& s) { d.alloc(s.n ? s.n : 1); if (s.n) PQ_HIP(hipMemcpyAsync(d.p, s.p, s.bytes(), hipMemcpyDeviceToDevice, st_)); };
         auto cpi = [&](DBuf<int>& d, const DBuf<int>& s) { d.alloc(s.n ? s.n : 1); if (s.n) PQ_HIP(hipMemcpyAsync(d.p, s.p, s.bytes(), hipMemcpyDeviceToDevice, st_)); };
@@ -3506,7 +3510,8 @@ private:
 
     int dev_, mode_ = 0, nzAA_ = 0, nzGG_ = 0, n_ = 0, p_ = 0, m_ = 0, N_ = 0, nnzK_ = 0;
     double delta_ = 1.0;
-    hipStream_t st_ = nullptr, st2_ = nullptr;  // st2_: the one-workgroup fronts of a level next to its big fronts' diagonal blocks (factor_levels)
+    // before every buffer, so they go last: the destructor waits on st_ (which st2_'s work joins), then the communicator and the events go, then the buffers
+    Stream st_, st2_;  // st2_: the one-workgroup fronts of a level next to its big fronts' diagonal blocks (factor_levels)
     hipEvent_t ev_fork_ = nullptr, ev_join_ = nullptr;
     sparse::Symbolic S_;
     std::vector<int> level_lds_;
@@ -3577,53 +3582,56 @@ private:
 
 }  // namespace
 
-KKTSolverBase* make_multifrontal_kkt(const pq_sparse_data* data, int mode, int device) { return new SparseKKT(data, mode, device); }
+KKTSolverBase* make_multifrontal_kkt(const pq_sparse_data* data, int mode, int device, hipStream_t adopt) { return new SparseKKT(data, mode, device, adopt); }
 
 namespace {
-// A host copy of the matrices a sparse backend is built from (the C-ABI lends them for the duration of a call only).
+// A host copy of the matrices a sparse backend is built from (the C-ABI lends them for the duration of a call only).  A PIQP update never changes a pattern: the patterns
+// are copied once, refresh() takes the values, the bound lists and x_b_scaling.
 struct SparseDataCopy {
     std::vector<int> pc, pr, ac, ar, gc, gr, hl, hu, xl, xu;
     std::vector<double> pv, av, gv, xb;
     pq_sparse_data d{};
-    bool has_xb = false;
-    void take(const pq_sparse_data* s)
+    explicit SparseDataCopy(const pq_sparse_data* s)
+        : pc(s->P_colptr, s->P_colptr + s->n + 1), pr(s->P_rowind, s->P_rowind + pc.back()), ac(s->AT_colptr, s->AT_colptr + s->p + 1), ar(s->AT_rowind, s->AT_rowind + ac.back()),
+          gc(s->GT_colptr, s->GT_colptr + s->m + 1), gr(s->GT_rowind, s->GT_rowind + gc.back())
     {
-        auto csc = [](int cols, const int* cp, const int* ri, const double* v, std::vector<int>& c, std::vector<int>& r, std::vector<double>& x) {
-            c.assign(cp, cp + cols + 1);
-            r.assign(ri, ri + c[cols]);
-            x.assign(v, v + c[cols]);
-        };
-        csc(s->n, s->P_colptr, s->P_rowind, s->P_val, pc, pr, pv);
-        csc(s->p, s->AT_colptr, s->AT_rowind, s->AT_val, ac, ar, av);
-        csc(s->m, s->GT_colptr, s->GT_rowind, s->GT_val, gc, gr, gv);
+        refresh(s);
+    }
+    SparseDataCopy(const SparseDataCopy&) = delete;  // (d points into this object)
+    void refresh(const pq_sparse_data* s)  // same dimensions and nonzero counts as at construction (the caller checks)
+    {
+        pv.assign(s->P_val, s->P_val + pr.size()); av.assign(s->AT_val, s->AT_val + ar.size()); gv.assign(s->GT_val, s->GT_val + gr.size());
         auto idx = [](const int* p, int k, std::vector<int>& o) { if (p && k > 0) o.assign(p, p + k); else o.clear(); };
         idx(s->h_l_idx, s->n_h_l, hl); idx(s->h_u_idx, s->n_h_u, hu); idx(s->x_l_idx, s->n_x_l, xl); idx(s->x_u_idx, s->n_x_u, xu);
-        has_xb = s->x_b_scaling != nullptr;
-        if (has_xb) xb.assign(s->x_b_scaling, s->x_b_scaling + s->n);
+        if (s->x_b_scaling) xb.assign(s->x_b_scaling, s->x_b_scaling + s->n);
         d = *s;
         d.P_colptr = pc.data(); d.P_rowind = pr.data(); d.P_val = pv.data();
         d.AT_colptr = ac.data(); d.AT_rowind = ar.data(); d.AT_val = av.data();
         d.GT_colptr = gc.data(); d.GT_rowind = gr.data(); d.GT_val = gv.data();
         d.h_l_idx = hl.data(); d.h_u_idx = hu.data(); d.x_l_idx = xl.data(); d.x_u_idx = xu.data();
-        d.x_b_scaling = has_xb ? xb.data() : nullptr;
+        d.x_b_scaling = s->x_b_scaling ? xb.data() : nullptr;
         d.mem = PQ_MEM_HOST;
     }
 };
 
 // kkt_solver = sparse_ldlt (or a condensed mode) on a system small enough for the reference-order engine -- which has no stage partition: a caller that asks for one
 // (pq_kkt_partition) gets the multifrontal engine from there on, built from this wrapper's copy of the data, instead of "not supported" (round-5 advice).  Everything
-// else is forwarded to the engine in use.
+// else is forwarded to the engine in use.  stream() is the same value from construction to destruction: the new engine takes the old one's stream over.
 class EngineSwitchKKT final : public KKTSolverBase {
 public:
-    EngineSwitchKKT(KKTSolverBase* exact, const pq_sparse_data* data, int mode, int device) : cur_(exact), mode_(mode), dev_(device) { copy_.take(data); }
-    ~EngineSwitchKKT() override { delete cur_; }
-    KKTSolverBase* clone() const override
+    EngineSwitchKKT(std::unique_ptr<KKTSolverBase> exact, const pq_sparse_data* data, int mode, int device)
+        : cur_(std::move(exact)), copy_(new SparseDataCopy(data)), nnz_{data->P_colptr[data->n], data->AT_colptr[data->p], data->GT_colptr[data->m]}, mode_(mode), dev_(device)
     {
-        auto* c = new EngineSwitchKKT(cur_->clone(), &copy_.d, mode_, dev_);
-        c->switched_ = switched_;
-        return c;
     }
-    void update_data_sparse(const pq_sparse_data* data, int options) override { copy_.take(data); cur_->update_data_sparse(data, options); }
+    KKTSolverBase* clone() const override { return new EngineSwitchKKT(*this, std::unique_ptr<KKTSolverBase>(cur_->clone())); }
+    void update_data_sparse(const pq_sparse_data* data, int options) override
+    {
+        if (data->n != n() || data->p != p() || data->m != m()) throw std::runtime_error("update_data: dimension mismatch");
+        if (data->P_colptr[data->n] != nnz_[0] || data->AT_colptr[data->p] != nnz_[1] || data->GT_colptr[data->m] != nnz_[2])
+            throw std::runtime_error("update_data: the number of nonzeros differs from the pattern the handle was built with");
+        if (copy_) copy_->refresh(data);
+        cur_->update_data_sparse(data, options);
+    }
     bool update_scalings_and_factor(double delta, const double* x_reg, const double* z_reg) override { return cur_->update_scalings_and_factor(delta, x_reg, z_reg); }
     void solve(const double* rx, const double* ry, const double* rz, double* lx, double* ly, double* lz) override { cur_->solve(rx, ry, rz, lx, ly, lz); }
     void eval_P_x(double alpha, const double* x, double* z) override { cur_->eval_P_x(alpha, x, z); }
@@ -3640,13 +3648,15 @@ public:
     int sparse_ordering(int* fill_perm, int* elim_perm) const override { return cur_->sparse_ordering(fill_perm, elim_perm); }
     void partition(int rank, int world, long long sizes[3]) override
     {
-        if (!switched_) {
-            // (the streams of the two engines are their own: whatever the caller queued on the old one is finished before it goes)
-            stream_wait(cur_->stream());
-            KKTSolverBase* mf = make_multifrontal_kkt(&copy_.d, mode_, dev_);
-            delete cur_;
-            cur_ = mf;
-            switched_ = true;
+        if (copy_) {
+            // The multifrontal engine is built on the old engine's stream, idle by then, and owns it from there on; only then does the old engine let go of it and leave.
+            // (If the build throws, nothing has changed hands and this handle works on as before.)
+            const hipStream_t st = cur_->stream();
+            stream_wait(st);
+            std::unique_ptr<KKTSolverBase> mf(make_multifrontal_kkt(&copy_->d, mode_, dev_, st));
+            (void)release_exact_sparse_stream(cur_.get());
+            cur_ = std::move(mf);
+            copy_.reset();
         }
         cur_->partition(rank, world, sizes);
     }
@@ -3671,10 +3681,14 @@ public:
     void get_profile(int stage, double* total_ms, int* count) override { cur_->get_profile(stage, total_ms, count); }
 
 private:
-    KKTSolverBase* cur_;
-    SparseDataCopy copy_;
+    EngineSwitchKKT(const EngineSwitchKKT& o, std::unique_ptr<KKTSolverBase> engine)
+        : cur_(std::move(engine)), copy_(o.copy_ ? new SparseDataCopy(&o.copy_->d) : nullptr), nnz_(o.nnz_), mode_(o.mode_), dev_(o.dev_)
+    {
+    }
+    std::unique_ptr<KKTSolverBase> cur_;
+    std::unique_ptr<SparseDataCopy> copy_;  // what the multifrontal engine would be built from; gone once it has been
+    std::array<int, 3> nnz_;                // nonzeros of P, A', G'
     int mode_, dev_;
-    bool switched_ = false;
 };
 }  // namespace
 
@@ -3699,7 +3713,8 @@ KKTSolverBase* make_sparse_kkt(const pq_sparse_data* data, int kkt_solver, int d
             const char* mf = std::getenv("PIQP_AMD_EXACT_MAX_FLOPS");
             // (the condensed modes' systems are denser -- nl_czprob 2.1e9 flops, eleven fixtures above 2e8 -- and keep their bitwise contract too: limit 3e9 there)
             const double max_flops = eng ? 0.0 : (mf ? std::atof(mf) : (mode == 0 ? 4e7 : 3e9));
-            if (KKTSolverBase* k = make_exact_sparse_kkt(data, mode, device, max_flops)) return new EngineSwitchKKT(k, data, mode, device);
+            std::unique_ptr<KKTSolverBase> k(make_exact_sparse_kkt(data, mode, device, max_flops));
+            if (k) return new EngineSwitchKKT(std::move(k), data, mode, device);
         }
         return new SparseKKT(data, mode, device);
     }

@@ -98,6 +98,12 @@ def gather_stats(local_rows, device=None):
     return rows
 
 
+def _handle_of(obj):
+    """(is it a solver, the C handle the partition calls take) for what a StagePartition wraps: a solver, a KKTSystem (its backend's handle) or a backend"""
+    is_solver = hasattr(obj, "solve") and hasattr(obj, "setup")
+    return is_solver, obj.h if is_solver else (obj.backend().h if hasattr(obj, "backend") else obj.h)
+
+
 class StagePartition:
     """Stage-partitioned execution of ONE KKT system / solver over the ranks of a process group (BASELINE configs[4]).
 
@@ -119,8 +125,7 @@ class StagePartition:
         self.rank = rank if rank is not None else (dist.get_rank(group) if on else 0)
         self.world = world if world is not None else (dist.get_world_size(group) if on else 1)
         self.backend = dist.get_backend(group) if on else None
-        is_solver = hasattr(obj, "solve") and hasattr(obj, "setup")
-        h = obj.h if is_solver else (obj.backend().h if hasattr(obj, "backend") else obj.h)
+        is_solver, h = _handle_of(obj)
         part = L.pq_solver_partition if is_solver else L.pq_kkt_partition
         setx = L.pq_solver_set_exchange if is_solver else L.pq_kkt_set_exchange
         sizes = (C.c_longlong * 3)()
@@ -213,9 +218,7 @@ class StagePartition:
 
         from . import _lib
         L = _lib.load()
-        obj = self._obj
-        is_solver = hasattr(obj, "solve") and hasattr(obj, "setup")
-        h = obj.h if is_solver else (obj.backend().h if hasattr(obj, "backend") else obj.h)
+        is_solver, h = _handle_of(self._obj)
         out = (C.c_int * 3)()
         _lib.check((L.pq_solver_native_exchange_calls if is_solver else L.pq_kkt_native_exchange_calls)(h, out), "native_exchange_calls")
         return [int(v) for v in out]
@@ -226,9 +229,7 @@ class StagePartition:
 
         from . import _lib
         L = _lib.load()
-        obj = self._obj
-        is_solver = hasattr(obj, "solve") and hasattr(obj, "setup")
-        h = obj.h if is_solver else (obj.backend().h if hasattr(obj, "backend") else obj.h)
+        is_solver, h = _handle_of(self._obj)
         out = (C.c_int * 2)()
         _lib.check((L.pq_solver_sharded_calls if is_solver else L.pq_kkt_sharded_calls)(h, C.byref(out)), "sharded_calls")
         return [int(out[0]), int(out[1])]
@@ -240,9 +241,7 @@ class StagePartition:
 
         from . import _lib
         L = _lib.load()
-        obj = self._obj
-        is_solver = hasattr(obj, "solve") and hasattr(obj, "setup")
-        h = obj.h if is_solver else (obj.backend().h if hasattr(obj, "backend") else obj.h)
+        is_solver, h = _handle_of(self._obj)
         out = (C.c_int * 6)()
         _lib.check((L.pq_solver_sharded_solve_calls if is_solver else L.pq_kkt_sharded_solve_calls)(h, C.byref(out)), "sharded_solve_calls")
         return [int(v) for v in out]
@@ -254,9 +253,7 @@ class StagePartition:
 
         from . import _lib
         L = _lib.load()
-        obj = self._obj
-        is_solver = hasattr(obj, "solve") and hasattr(obj, "setup")
-        h = obj.h if is_solver else (obj.backend().h if hasattr(obj, "backend") else obj.h)
+        is_solver, h = _handle_of(self._obj)
         out = (C.c_int * 4)()
         _lib.check((L.pq_solver_comm_info if is_solver else L.pq_kkt_comm_info)(h, out), "comm_info")
         on = self.dist.is_available() and self.dist.is_initialized()
@@ -269,10 +266,9 @@ class StagePartition:
 
         from . import _lib
         L = _lib.load()
-        obj = self._obj
-        if hasattr(obj, "solve") and hasattr(obj, "setup"):
+        is_solver, h = _handle_of(self._obj)
+        if is_solver:
             return None
-        h = obj.backend().h if hasattr(obj, "backend") else obj.h
         out = (C.c_int * 8)()
         _lib.check(L.pq_kkt_partition_info(h, out), "partition_info")
         return dict(owned_supernodes=out[0], shared_supernodes=out[1], boundary_roots=out[2], span=(out[3], out[4]), work_permille=out[5],

@@ -187,10 +187,17 @@ def test_partition_of_a_system_small_enough_for_the_reference_order_engine(ks):
     k = hip.SparseKKT(d, kkt_solver=ks)
     assert k.update_scalings_and_factor(0.7, x_reg, z_reg)
     ref_order = k.solve(*r)                                  # (the reference-order engine's answer, before the switch)
+    stream = k.stream()
     part = StagePartition(k, rank=0, world=1)
     assert part.sizes[2] >= 0
+    assert stream and k.stream() == stream                   # the new engine took the old one's stream over: whoever cached it still holds a live stream
     assert k.update_scalings_and_factor(0.7, x_reg, z_reg)
     got = k.solve(*r)
+    kc = k.clone()                                           # (a clone taken after the switch: the multifrontal engine on a stream of its own)
+    assert kc.stream() and kc.stream() != stream
+    assert kc.update_scalings_and_factor(0.7, x_reg, z_reg)
+    for a, b in zip(kc.solve(*r), got):
+        assert np.array_equal(a, b)
     env_ks = {1: hip.SPARSE_LDLT_MULTIFRONTAL, 4: 4}[ks]
     import os
     os.environ["PIQP_AMD_SPARSE_LDLT"] = "multifrontal"
@@ -203,6 +210,106 @@ def test_partition_of_a_system_small_enough_for_the_reference_order_engine(ks):
     for a, b, c in zip(got, want, ref_order):
         assert np.array_equal(a, b)
         assert np.allclose(a, c, rtol=1e-8, atol=1e-10)
+
+
+def _multifrontal(build):
+    """build() with PIQP_AMD_SPARSE_LDLT=multifrontal in the environment: the multifrontal engine from the start"""
+    os.environ["PIQP_AMD_SPARSE_LDLT"] = "multifrontal"
+    try:
+        return build()
+    finally:
+        del os.environ["PIQP_AMD_SPARSE_LDLT"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ks", [1, 4])
+def test_partition_through_a_kkt_system_that_caches_the_stream(ks):
+    """KKTSystem reads its backend's stream once, in its constructor, and launches its own kernels on it.  A partition that switches the backend's engine must leave
+    that stream alive and the one the new engine runs on: factor + solve after the switch equal, bit for bit, those of a KKTSystem on the multifrontal engine from the
+    start.  (The shell's own arithmetic does not depend on the engine -- nothing in kkt_system.hip asks for reference_order() -- so bits are owed.)"""
+    import piqp_amd as hip
+    from piqp_amd.dist import StagePartition
+    from qp_gen import c3_problem, random_vars
+    d = hip.SparseData(*c3_problem(n=900, p=300, m=500, seed=11, spread=40))
+    rng = np.random.default_rng(3)
+    state = random_vars(d.n, d.p, d.m, rng, positive=True)
+    rhs = random_vars(d.n, d.p, d.m, rng)
+    ksys = hip.KKTSystem(d, hip.default_settings(kkt_solver=ks))
+    stream = ksys.backend().stream()
+    assert ksys.update_scalings_and_factor(False, 1e-6, 1e-4, state) and ksys.solve(rhs)[0]
+    part = StagePartition(ksys, rank=0, world=1)
+    assert part.sizes[2] >= 0
+    assert stream and ksys.backend().stream() == stream
+    assert ksys.update_scalings_and_factor(False, 1e-6, 1e-4, state)
+    ok, got = ksys.solve(rhs)
+    assert ok
+    fresh = _multifrontal(lambda: hip.KKTSystem(d, hip.default_settings(kkt_solver=ks)))
+    assert fresh.update_scalings_and_factor(False, 1e-6, 1e-4, state)
+    ok, want = fresh.solve(rhs)
+    assert ok
+    for key in want:
+        assert np.array_equal(got[key], want[key]), key
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["mm_CVXQP1_S", "qp_chain_mass_sqp"])
+def test_solver_partitioned_between_setup_and_solve(hip, orc, name):
+    """the whole solver: its interior-point loop is set up on the stream of the reference-order engine and runs on the multifrontal one after the partition.  Status and
+    objective are the oracle's (the tolerance of test_fixture_iteration_parity_sparse); the iteration counts are printed, not asserted -- the loop finishes on another
+    engine than the one the oracle's arithmetic mirrors."""
+    from piqp_amd.dist import StagePartition
+    from qp_io import load_qp
+    q = load_qp(name)
+    args = (q["P"], q["c"], q["A"], q["b"], q["G"], q["h_l"], q["h_u"], q["x_l"], q["x_u"])
+    sh = hip.SparseSolver(); sh.settings.kkt_solver = hip.SPARSE_LDLT
+    so = orc.Solver(); so.settings.kkt_solver = orc.SPARSE_LDLT
+    assert sh.setup(*args) and so.setup(*args, sparse=True)
+    part = StagePartition(sh, rank=0, world=1)
+    assert part.sizes[2] >= 0
+    st_h, st_o = sh.solve(), so.solve()
+    print(f"{name}: status {st_h} / {st_o}, iterations {sh.info.iter} / {so.info.iter}, primal objective {sh.info.primal_obj!r} / {so.info.primal_obj!r}")
+    assert st_h == st_o
+    assert abs(sh.info.primal_obj - so.info.primal_obj) <= 1e-6 * (1 + abs(so.info.primal_obj))
+
+
+@pytest.mark.gpu
+def test_update_data_before_the_switch_reaches_the_engine_built_at_the_switch():
+    """the wrapper keeps the patterns from construction and takes only values from update_data: new values given BEFORE the partition are what the multifrontal engine
+    is built from -- bitwise a multifrontal handle built fresh from them -- and an update whose number of nonzeros differs is an error, before and after the switch"""
+    import piqp_amd as hip
+    from piqp_amd.dist import StagePartition
+    from qp_gen import c3_problem
+    P, c, A, b, G, h_l, h_u, x_l, x_u = c3_problem(n=900, p=300, m=500, seed=11, spread=40)
+    rng = np.random.default_rng(17)
+
+    def perturbed(M):
+        M = M.copy()
+        M.data = M.data * (1 + 0.1 * rng.standard_normal(M.nnz))
+        return M
+    P2, A2, G2 = perturbed(P), perturbed(A), perturbed(G)
+    P2.setdiag(np.abs(P2.diagonal()))                         # (P's diagonal stays positive; the entries are there already, the pattern does not change)
+    assert P2.nnz == P.nnz
+    d, d2 = hip.SparseData(P, c, A, b, G, h_l, h_u, x_l, x_u), hip.SparseData(P2, c, A2, b, G2, h_l, h_u, x_l, x_u)
+    A3 = A2.copy(); A3.data[0] = 0.0; A3.eliminate_zeros()
+    d3 = hip.SparseData(P2, c, A3, b, G2, h_l, h_u, x_l, x_u)
+    n, p, m = d.n, d.p, d.m
+    x_reg = rng.uniform(0.5, 2.0, n); z_reg = rng.uniform(0.1, 3.0, m)
+    r = [rng.standard_normal(k) for k in (n, p, m)]
+    everything = hip.KKT_UPDATE_P | hip.KKT_UPDATE_A | hip.KKT_UPDATE_G
+    k = hip.SparseKKT(d, kkt_solver=1)
+    with pytest.raises(RuntimeError, match="nonzeros"):
+        k.update_data(d3, everything)
+    k.update_data(d2, everything)
+    part = StagePartition(k, rank=0, world=1)
+    assert part.sizes[2] >= 0
+    assert k.update_scalings_and_factor(0.7, x_reg, z_reg)
+    got = k.solve(*r)
+    with pytest.raises(RuntimeError, match="nonzeros"):
+        k.update_data(d3, everything)
+    k2 = _multifrontal(lambda: hip.SparseKKT(d2, kkt_solver=1))
+    assert k2.update_scalings_and_factor(0.7, x_reg, z_reg)
+    for a, b_ in zip(got, k2.solve(*r)):
+        assert np.array_equal(a, b_)
 
 
 @pytest.mark.gpu
