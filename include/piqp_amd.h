@@ -88,7 +88,12 @@ typedef struct {
     int mem;                                           /* pq_mem */
 } pq_dense_data;
 
-/* sparse/data.hpp:26-54 -- CSC int32/fp64 (P_utri upper triangle; AT = A^T n x p; GT = G^T n x m) */
+/* sparse/data.hpp:26-54 -- CSC int32/fp64 (P_utri upper triangle; AT = A^T n x p; GT = G^T n x m).
+ * Every index array (*_colptr, *_rowind, *_idx) is HOST memory in either mode: the symbolic analysis runs on the host.  `mem` says where the value arrays P_val,
+ * AT_val, GT_val and x_b_scaling live: PQ_MEM_HOST, or PQ_MEM_DEVICE = device memory on the handle's device (complete before the call, only read, read by the time
+ * the call returns).  Device mode, every sparse backend (PQ_SPARSE_LDLT on either engine, the condensed modes, PQ_SPARSE_MULTISTAGE, selectors 17 and 18): *_create
+ * and *_update_data_sparse move the values device-to-device, nothing crosses the host-device link and no value is ever fetched to the host (a handle that has to
+ * remember its data for pq_kkt_partition keeps a device copy).  Any other value of mem: PQ_ERR_INVALID, the handle stays as it was. */
 typedef struct {
     int n, p, m;
     const int *P_colptr, *P_rowind; const double *P_val;
@@ -97,7 +102,7 @@ typedef struct {
     int n_h_l, n_h_u, n_x_l, n_x_u;
     const int *h_l_idx, *h_u_idx, *x_l_idx, *x_u_idx;
     const double *x_b_scaling;
-    int mem; /* host only in this release */
+    int mem; /* pq_mem: where the VALUE arrays live; the index arrays are host memory always */
 } pq_sparse_data;
 
 /* variables.hpp:19-105 Variables<T>: ten vectors (box vectors length n, compressed to the first
@@ -359,7 +364,7 @@ int pq_solver_setup_dense(pq_solver *s, int n, int p, int m, const double *P, co
  * HostData::P_utri / AT / GT are never sized.  The vectors c, b, h_l, h_u, x_l, x_u (O(n + p + m)) are fetched into host staging and go through the same host
  * logic as in host mode (finite-bound index lists, rows of G without a finite bound), so the two modes compute bit for bit the same.  Exception: under
  * PIQP_AMD_DEBUG=host_ruiz (the debugging path that equilibrates on the host) a device-mode call fetches the matrices to the host.
- * pq_solver_last_ingest: figures of the last setup / update of a dense solver, computed from the shapes of the matrices each path moves (not counted by the
+ * pq_solver_last_ingest: figures of the last setup / update of a dense solver (sparse: see pq_solver_setup_sparse), computed from the shapes of the matrices each path moves (not counted by the
  * runtime): out[0] = bytes of matrix data that cross the host-device link (host mode: 8 n (n + p + m) for a setup, 8 n x the columns of the updated matrices for
  * an update; device mode: 0), out[1] = bytes of matrix data written device-to-device or by kernel. */
 enum { PQ_COL_MAJOR = 0, PQ_ROW_MAJOR = 1 };
@@ -373,7 +378,9 @@ int pq_solver_update_dense_mem(pq_solver *s, const double *P, const double *c, c
  * device mode these O(n + p + m) doubles cross the link host-to-device; only the batched solver's results (pq_batch_get_result_mem) never leave the GPU. */
 int pq_solver_get_result_mem(const pq_solver *s, pq_vars *out, int mem);
 int pq_solver_last_ingest(const pq_solver *s, long long out[2]);
-/* SparseSolver::setup, solver.hpp:1297-1308: CSC HOST arrays (P full or upper) */
+/* out[] of pq_solver_last_ingest for a sparse solver: out[0] = 8 x the stored nonzeros (upper(P), A, G) of the matrices a host-mode setup / update moves, 0 for a
+ * device-mode call; out[1] = bytes written by the gather kernel of a device-mode call.
+ * SparseSolver::setup, solver.hpp:1297-1308: CSC HOST arrays (P full or upper) */
 int pq_solver_setup_sparse(pq_solver *s, int n, int p, int m, const int *Pp, const int *Pi, const double *Px,
                            const double *c, const int *Ap, const int *Ai, const double *Ax, const double *b,
                            const int *Gp, const int *Gi, const double *Gx, const double *h_l, const double *h_u,
@@ -386,6 +393,34 @@ int pq_solver_update_sparse(pq_solver *s, const int *Pp, const int *Pi, const do
                             const int *Ap, const int *Ai, const double *Ax, const double *b, const int *Gp,
                             const int *Gi, const double *Gx, const double *h_l, const double *h_u,
                             const double *x_l, const double *x_u);
+/* ---- sparse problem data whose VALUES already live in GPU memory ----
+ * pq_solver_setup_sparse / pq_solver_update_sparse with one more argument; they forward here with PQ_MEM_HOST.  mem = PQ_MEM_DEVICE: Px, Ax, Gx and the six vectors
+ * are device memory on the handle's device; the index arrays Pp, Pi, Ap, Ai, Gp, Gi are HOST memory in either mode.  Ordering contract, treatment of the vectors
+ * (fetched, same host logic, so both modes compute bit for bit the same) and the PIQP_AMD_DEBUG=host_ruiz exception: as written above pq_solver_setup_dense_mem.
+ * Any other value of mem returns PQ_ERR_INVALID and leaves the handle as it was.
+ * Device mode: at setup, gather maps are built from the patterns alone -- stored entry of upper(P) <- the caller's entry on or above the diagonal (rows ascending
+ * within a column), stored entry of A^T / G^T <- the caller's CSC entry of A / G -- and from then on only values move: a gather kernel (csrc/ingest_kernels.hip)
+ * fills the solver's device arrays, the rows of G without a finite bound are zeroed by a kernel, unscale_data -> assign -> scale_data (sparse/preconditioner.hpp)
+ * run on those arrays, and the KKT backend is refreshed from a device-mode pq_sparse_data.  No matrix value comes to the host or crosses the link; entries of P
+ * below the diagonal are never loaded (NaN there is harmless).  In pq_solver_update_sparse_mem with PQ_MEM_DEVICE the index arrays may be NULL: identical sparsity is
+ * the reference's precondition (solver.hpp:325,341,356), the value arrays are read in the CSC order given at setup.  Lengths: the caller guarantees that Px, Ax,
+ * Gx hold as many entries as the arrays given at setup (Pp[n], Ap[n], Gp[n] of that call); where index arrays are passed their totals are checked against those
+ * counts (the host path's per-column check of P has no counterpart: the map fixes which entries are read), where they are NULL nothing can be checked.
+ * Where the values live is a one-way switch: a host-fed solver keeps a host mirror of its values until its first device-mode update, which drops the mirror for the
+ * rest of the handle's life; from then on, as for a solver set up in device mode, a host-mode update stages the caller's values in device memory and takes the
+ * device path (out[0] of pq_solver_last_ingest counts them; the same length guarantee holds for the host arrays).  Results do not depend on the switch.
+ * pq_debug_sparse_ingest_maps (host-only, no GPU needed): those maps in scatter form for tests -- mapP[k] / mapA[k] / mapG[k] = stored position of the caller's
+ * entry k in upper(P) / A^T / G^T, -1 = never read; NULL Ap / Gp = absent matrix, NULL map = skipped; nnz_out = stored entries of the three.  Returns 0. */
+int pq_solver_setup_sparse_mem(pq_solver *s, int n, int p, int m, const int *Pp, const int *Pi, const double *Px,
+                               const double *c, const int *Ap, const int *Ai, const double *Ax, const double *b,
+                               const int *Gp, const int *Gi, const double *Gx, const double *h_l, const double *h_u,
+                               const double *x_l, const double *x_u, int mem);
+int pq_solver_update_sparse_mem(pq_solver *s, const int *Pp, const int *Pi, const double *Px, const double *c,
+                                const int *Ap, const int *Ai, const double *Ax, const double *b, const int *Gp,
+                                const int *Gi, const double *Gx, const double *h_l, const double *h_u,
+                                const double *x_l, const double *x_u, int mem);
+int pq_debug_sparse_ingest_maps(int n, int p, int m, const int *Pp, const int *Pi, const int *Ap, const int *Ai,
+                                const int *Gp, const int *Gi, int *mapP, int *mapA, int *mapG, int nnz_out[3]);
 int pq_solver_solve(pq_solver *s);               /* solver.hpp:69-148; returns Status */
 const pq_info *pq_solver_info(const pq_solver *s); /* result().info */
 /* result(): copies the ten solution vectors (sizes n,p,m,m,n,n,m,m,n,n) into host buffers (NULL skipped) */

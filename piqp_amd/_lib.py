@@ -86,6 +86,7 @@ SYMBOLS = [
     "pq_batch_kkt_factor", "pq_batch_kkt_solve", "pq_batch_ldlt_factor",
     "pq_dense_factor_create", "pq_dense_factor_destroy", "pq_dense_factor_compute", "pq_dense_factor_info", "pq_dense_factor_solve_in_place", "pq_dense_factor_matrix", "pq_dense_factor_last_ms",
     "pq_debug_alloc_count", "pq_debug_chol_plan", "pq_debug_syrk_plan", "pq_debug_device_sqrt", "pq_kkt_set_exchange_norm", "pq_kkt_sharded_calls", "pq_kkt_sharded_solve_calls", "pq_solver_sharded_solve_calls", "pq_solver_set_exchange_norm", "pq_solver_sharded_calls", "pq_microbench_mfma_f64", "pq_microbench_hbm_copy", "pq_microbench_potrf_block", "pq_debug_potrf_block", "pq_rccl_unique_id", "pq_kkt_set_comm_rccl", "pq_solver_set_comm_rccl", "pq_kkt_native_exchange_calls", "pq_kkt_min_abs_pivot", "pq_solver_native_exchange_calls",
+    "pq_solver_setup_sparse_mem", "pq_solver_update_sparse_mem", "pq_debug_sparse_ingest_maps",
     "pq_solver_setup_dense_mem", "pq_solver_update_dense_mem", "pq_solver_get_result_mem", "pq_solver_last_ingest", "pq_batch_update_mem", "pq_batch_update_data_mem",
     "pq_batch_get_result_mem", "pq_microbench_transpose",
     "pq_sparse_amd_order", "pq_sparse_permute_sym_upper", "pq_sparse_kkt_symbolic", "pq_kkt_sparse_ordering", "pq_kkt_comm_info", "pq_solver_comm_info", "pq_kkt_exact_factor", "pq_sparse_uplooking_plan",
@@ -198,6 +199,9 @@ def load():
     L.pq_solver_update_sparse.argtypes = [vp] + [vp] * 15
     L.pq_solver_setup_dense_mem.argtypes = [vp, C.c_int, C.c_int, C.c_int] + [vp] * 9 + [C.c_int, C.c_int]
     L.pq_solver_update_dense_mem.argtypes = [vp] + [vp] * 9 + [C.c_int, C.c_int]
+    L.pq_solver_setup_sparse_mem.argtypes = [vp, C.c_int, C.c_int, C.c_int] + [vp] * 15 + [C.c_int]
+    L.pq_solver_update_sparse_mem.argtypes = [vp] + [vp] * 15 + [C.c_int]
+    L.pq_debug_sparse_ingest_maps.argtypes = [C.c_int, C.c_int, C.c_int] + [vp] * 9 + [C.POINTER(C.c_int * 3)]
     L.pq_solver_get_result_mem.argtypes = [vp, C.POINTER(Vars), C.c_int]
     L.pq_solver_last_ingest.argtypes = [vp, C.POINTER(C.c_longlong * 2)]
     L.pq_batch_update_mem.argtypes = [vp] + [vp] * 6 + [C.c_int]

@@ -152,10 +152,15 @@ int pq_kkt_create_dense(pq_kkt** out, const pq_dense_data* data, int kkt_solver,
     });
 }
 
+// pq_sparse_data.mem: where P_val / AT_val / GT_val / x_b_scaling live; every index array is host memory in either mode
+static bool bad_sparse_mem(const pq_sparse_data* d) { return d->mem != PQ_MEM_HOST && d->mem != PQ_MEM_DEVICE; }
+static const char* const BAD_SPARSE_MEM = "pq_sparse_data.mem must be PQ_MEM_HOST or PQ_MEM_DEVICE";
+
 int pq_kkt_create_sparse(pq_kkt** out, const pq_sparse_data* data, int kkt_solver, int device)
 {
     if (!out || !data) return fail(PQ_ERR_INVALID, "null argument");
     *out = nullptr;
+    if (bad_sparse_mem(data)) return fail(PQ_ERR_INVALID, BAD_SPARSE_MEM);
     int rc = check_device(device);
     if (rc < 0) return rc;
     return guarded([&] {
@@ -201,6 +206,7 @@ int pq_kkt_update_data_dense(pq_kkt* k, const pq_dense_data* data, int options)
 int pq_kkt_update_data_sparse(pq_kkt* k, const pq_sparse_data* data, int options)
 {
     if (!k || !data) return fail(PQ_ERR_INVALID, "null argument");
+    if (bad_sparse_mem(data)) return fail(PQ_ERR_INVALID, BAD_SPARSE_MEM);
     return guarded([&] { k->impl->update_data_sparse(data, options); return (int)PQ_OK; });
 }
 
@@ -690,6 +696,7 @@ int pq_kktsys_create_sparse(pq_kktsys** out, const pq_sparse_data* data, const p
 {
     if (!out || !data || !settings) return fail(PQ_ERR_INVALID, "null argument");
     *out = nullptr;
+    if (bad_sparse_mem(data)) return fail(PQ_ERR_INVALID, BAD_SPARSE_MEM);
     int rc = check_device(device);
     if (rc < 0) return rc;
     return guarded([&] {
@@ -697,7 +704,7 @@ int pq_kktsys_create_sparse(pq_kktsys** out, const pq_sparse_data* data, const p
         if (!b) return fail(PQ_ERR_UNSUPPORTED, "kkt solver not supported");
         std::unique_ptr<KKTSystem> sys(new KKTSystem(b.get(), *settings));
         b.release();
-        sys->set_bounds(data->n_h_l, data->n_h_u, data->n_x_l, data->n_x_u, data->h_l_idx, data->h_u_idx, data->x_l_idx, data->x_u_idx, data->x_b_scaling, data->mem);
+        sys->set_bounds(data->n_h_l, data->n_h_u, data->n_x_l, data->n_x_u, data->h_l_idx, data->h_u_idx, data->x_l_idx, data->x_u_idx, data->x_b_scaling, PQ_MEM_HOST, data->mem);
         *out = wrap_kktsys(sys.release());
         return (int)PQ_OK;
     });
@@ -739,9 +746,10 @@ int pq_kktsys_update_data_dense(pq_kktsys* k, const pq_dense_data* data, int opt
 int pq_kktsys_update_data_sparse(pq_kktsys* k, const pq_sparse_data* data, int options)
 {
     if (!k || !data) return fail(PQ_ERR_INVALID, "null argument");
+    if (bad_sparse_mem(data)) return fail(PQ_ERR_INVALID, BAD_SPARSE_MEM);
     return guarded([&] {
         k->impl->backend()->update_data_sparse(data, options);
-        k->impl->set_bounds(data->n_h_l, data->n_h_u, data->n_x_l, data->n_x_u, data->h_l_idx, data->h_u_idx, data->x_l_idx, data->x_u_idx, data->x_b_scaling, data->mem);
+        k->impl->set_bounds(data->n_h_l, data->n_h_u, data->n_x_l, data->n_x_u, data->h_l_idx, data->h_u_idx, data->x_l_idx, data->x_u_idx, data->x_b_scaling, PQ_MEM_HOST, data->mem);
         return (int)PQ_OK;
     });
 }

@@ -64,7 +64,38 @@ __global__ __launch_bounds__(256) void k_ingest_check_finite_pattern(const doubl
     if (bad) atomicOr(flag, 1);
 }
 
+// ---- sparse problems: the caller's CSC value arrays -> the stored order of upper(P), A^T, G^T (SparseSolver::setup / update, solver.hpp:169-192,317-358).  The
+// index work is done once on the host (gather maps, Solver setup); per call only values move: one 8-byte load through a 4-byte index and one coalesced 8-byte store
+// per stored entry, plain vector memory instructions.
+// dst[q] = src[src_idx[q]], q < count.  Entries of src no map entry names (the strictly lower triangle of a full P) are never loaded.
+__global__ __launch_bounds__(256) void k_ingest_gather(double* __restrict__ dst, const double* __restrict__ src, const int* __restrict__ src_idx, int count)
+{
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < count; q += (long long)gridDim.x * 256) dst[q] = src[src_idx[q]];  // (64-bit: q + stride may pass 2^31)
+}
+// vals[colptr[c] .. colptr[c + 1]) = 0 for the listed columns c of a CSC matrix (G^T: column c is row c of G); one workgroup per listed column
+__global__ __launch_bounds__(256) void k_ingest_zero_columns(double* __restrict__ vals, const int* __restrict__ colptr, const int* __restrict__ cols, int ncols)
+{
+    for (int k = blockIdx.x; k < ncols; k += gridDim.x) {
+        const int c = cols[k], hi = colptr[c + 1];
+        for (int q = colptr[c] + threadIdx.x; q < hi; q += 256) vals[q] = 0.0;
+    }
+}
+
 }  // namespace
+
+void ingest_gather(double* dst, const double* src, const int* src_idx, int count, hipStream_t st)
+{
+    if (count <= 0) return;
+    hipLaunchKernelGGL(k_ingest_gather, dim3(std::min(div_up(count, 256), 65536)), dim3(256), 0, st, dst, src, src_idx, count);
+    PQ_HIP(hipGetLastError());
+}
+
+void ingest_zero_columns(double* vals, const int* colptr, const int* cols, int ncols, hipStream_t st)
+{
+    if (ncols <= 0) return;
+    hipLaunchKernelGGL(k_ingest_zero_columns, dim3(std::min(ncols, 65536)), dim3(256), 0, st, vals, colptr, cols, ncols);
+    PQ_HIP(hipGetLastError());
+}
 
 void ingest_transpose(double* dst, const double* src, int rows, int cols, bool upper_only, hipStream_t st)
 {

@@ -423,7 +423,7 @@ void KKTSystem::alloc()
 }
 
 // the index-list part of dense::Data / sparse::Data (dense/data.hpp:41-51)
-void KKTSystem::set_bounds(int n_h_l_, int n_h_u_, int n_x_l_, int n_x_u_, const int* hl, const int* hu, const int* xl, const int* xu, const double* xbs, int mem)
+void KKTSystem::set_bounds(int n_h_l_, int n_h_u_, int n_x_l_, int n_x_u_, const int* hl, const int* hu, const int* xl, const int* xu, const double* xbs, int mem, int xbs_mem)
 {
     PQ_HIP(hipSetDevice(dev_));
     n_h_l = n_h_l_; n_h_u = n_h_u_; n_x_l = n_x_l_; n_x_u = n_x_u_;
@@ -432,7 +432,7 @@ void KKTSystem::set_bounds(int n_h_l_, int n_h_u_, int n_x_l_, int n_x_u_, const
     copy_in(h_u_idx.p, hu, sizeof(int) * n_h_u, mem, st_);
     copy_in(x_l_idx.p, xl, sizeof(int) * n_x_l, mem, st_);
     copy_in(x_u_idx.p, xu, sizeof(int) * n_x_u, mem, st_);
-    if (xbs) copy_in(x_b_scaling.p, xbs, sizeof(double) * n_, mem, st_);
+    if (xbs) copy_in(x_b_scaling.p, xbs, sizeof(double) * n_, xbs_mem < 0 ? mem : xbs_mem, st_);
     else LAUNCH1(k_fill, n_, st_, n_, 1.0, x_b_scaling.p);
     LAUNCH1(k_fill_int, m_, st_, m_, -1, has_l.p);
     LAUNCH1(k_fill_int, m_, st_, m_, -1, has_u.p);

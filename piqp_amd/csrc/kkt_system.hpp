@@ -19,8 +19,10 @@ public:
 
     KKTSystem* clone() const;  // kkt_system.hpp:70-95
 
-    // finite-bound index lists + x_b_scaling of dense::Data / sparse::Data (host or device arrays per `mem`)
-    void set_bounds(int n_h_l, int n_h_u, int n_x_l, int n_x_u, const int* h_l_idx, const int* h_u_idx, const int* x_l_idx, const int* x_u_idx, const double* x_b_scaling, int mem);
+    // finite-bound index lists + x_b_scaling of dense::Data / sparse::Data (host or device arrays per `mem`; xbs_mem >= 0: x_b_scaling alone lives there --
+    // a device-mode pq_sparse_data keeps every index array on the host)
+    void set_bounds(int n_h_l, int n_h_u, int n_x_l, int n_x_u, const int* h_l_idx, const int* h_u_idx, const int* x_l_idx, const int* x_u_idx, const double* x_b_scaling, int mem,
+                    int xbs_mem = -1);
 
     // kkt_system.hpp:143-211 (vars: device pointers)
     bool update_scalings_and_factor(bool iterative_refinement, double rho, double delta, const pq_vars& vars);

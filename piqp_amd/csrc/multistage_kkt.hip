@@ -92,7 +92,7 @@ class MultistageKKT final : public KKTSolverBase {
 public:
     MultistageKKT(const pq_sparse_data* d, int device) : dev_(device)
     {
-        if (d->mem != PQ_MEM_HOST) throw std::runtime_error("sparse data must be host-resident");
+        if (d->mem != PQ_MEM_HOST && d->mem != PQ_MEM_DEVICE) throw std::runtime_error("sparse data: mem must be PQ_MEM_HOST or PQ_MEM_DEVICE");  // (index arrays: host either way)
         st_ = Stream(dev_);
         multistage::analyse(d, S_);
         n_ = S_.n; p_ = S_.p; m_ = S_.m;

@@ -40,7 +40,9 @@ struct HostData;
 struct Ruiz;
 
 // Device side of the preconditioner of ONE Solver.  Dense problems: owns the (scaled) device matrices.  Sparse problems: owns device copies
-// of the patterns and a value staging area; the scaled values return to the host mirror (the sparse backends take host CSC).
+// of the patterns and the value arrays.  A host-fed sparse solver uses them as staging: the values go up from and return to the host mirror (HostData::s*.val)
+// around every run.  A device-fed one (HostData::values_on_device) keeps no mirror: the value arrays here are the solver's data, filled by ingest_sparse and
+// handed to the KKT backend through sparse_descriptor.
 class DeviceRuiz {
 public:
     DeviceRuiz(int device, const HostData& d);
@@ -54,7 +56,13 @@ public:
     // dense: the same from the caller's DEVICE arrays P (n x n), A (p x n), G (m x n) in storage order `layout` (PQ_COL_MAJOR: transpose kernel for A and G, masked
     // copy for P; PQ_ROW_MAJOR: plain copies of A and G, masked transpose for P).  The sources are only read; returns the bytes written.
     long long ingest_dense(const double* P, const double* A, const double* G, int layout, int options);
-    void zero_G_rows(const std::vector<int>& rows);  // dense: rows of G disabled by data.hpp:144-169 after the upload
+    // rows of G disabled by data.hpp:144-169 after the upload / ingest (sparse: only where the values live here, HostData::values_on_device)
+    void zero_G_rows(const std::vector<int>& rows);
+    // sparse, values_on_device: the value arrays named by `options` from the caller's DEVICE arrays in the CSC order given at setup, through the gather maps of
+    // d (HostData::srcP / srcA / srcG; ingest_kernels.hip).  The sources are only read; returns the bytes written.
+    long long ingest_sparse(const HostData& d, const double* Px, const double* Ax, const double* Gx, int options);
+    void copy_values_from(const DeviceRuiz& o);               // sparse: the three value arrays of another instance of the same problem (Solver::clone)
+    pq_sparse_data sparse_descriptor(const HostData& d) const;  // device-resident values + x_b_scaling, host index arrays (pq_sparse_data.mem = PQ_MEM_DEVICE)
     // scale_data / unscale_data of the matrices, c and x_b_scaling; the scalings land in rz, c / x_b_scaling in d (sparse: the matrix values too)
     void scale(HostData& d, Ruiz& rz, bool reuse_prev_scaling, bool scale_cost, int max_iter, double eps = 1e-3);
     void unscale(HostData& d, Ruiz& rz);

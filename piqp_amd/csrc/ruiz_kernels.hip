@@ -2,6 +2,7 @@
 #include "ruiz_device.hpp"
 #include "ingest_kernels.hpp"
 
+#include <climits>
 #include <memory>
 #include <stdexcept>
 
@@ -370,6 +371,7 @@ struct DeviceRuiz::Impl {
     // dense: the matrices (scaled once scale() ran); sparse: value staging
     DBuf<double> P, AT, GT;
     DBuf<int> Pp, Pi, ATp, ATi, GTp, GTi;
+    DBuf<int> srcP, srcA, srcG, rows;  // sparse, device-fed: gather maps (stored position -> caller's CSC position), uploaded by the first ingest; disabled rows of G
     DBuf<double> vec;  // c | xbs | delta | delta_inv | delta_b | delta_b_inv | tmp
     DBuf<DenseState> state;
     DBuf<double> cscale;
@@ -402,9 +404,9 @@ DeviceRuiz::DeviceRuiz(int device, const HostData& d) : I(new Impl)
         up(s.Pp, d.sP_utri.colptr); up(s.Pi, d.sP_utri.rowind);
         up(s.ATp, d.sAT.colptr); up(s.ATi, d.sAT.rowind);
         up(s.GTp, d.sGT.colptr); up(s.GTi, d.sGT.rowind);
-        s.P.alloc(std::max<size_t>(d.sP_utri.val.size(), 1));
-        s.AT.alloc(std::max<size_t>(d.sAT.val.size(), 1));
-        s.GT.alloc(std::max<size_t>(d.sGT.val.size(), 1));
+        s.P.alloc(std::max<size_t>(d.sP_utri.rowind.size(), 1));
+        s.AT.alloc(std::max<size_t>(d.sAT.rowind.size(), 1));
+        s.GT.alloc(std::max<size_t>(d.sGT.rowind.size(), 1));
         stream_wait(s.st);
     }
 }
@@ -466,10 +468,66 @@ long long DeviceRuiz::ingest_dense(const double* P, const double* A, const doubl
 void DeviceRuiz::zero_G_rows(const std::vector<int>& rows)
 {
     Impl& s = *I;
-    if (s.sparse || rows.empty()) return;
+    if (rows.empty()) return;
     PQ_HIP(hipSetDevice(s.device));
+    if (s.sparse) {
+        if ((int)rows.size() > s.m) throw std::runtime_error("DeviceRuiz::zero_G_rows: more rows than G has");
+        if (!s.rows.p) s.rows.alloc(std::max(s.m, 1));
+        PQ_HIP(hipMemcpyAsync(s.rows.p, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice, s.st));
+        ingest_zero_columns(s.GT.p, s.GTp.p, s.rows.p, (int)rows.size(), s.st);
+        stream_wait(s.st);  // (`rows` is the caller's)
+        return;
+    }
     for (int r : rows) PQ_HIP(hipMemsetAsync(s.GT.p + (size_t)r * s.n, 0, sizeof(double) * s.n, s.st));
     stream_wait(s.st);
+}
+
+long long DeviceRuiz::ingest_sparse(const HostData& d, const double* Px, const double* Ax, const double* Gx, int options)
+{
+    Impl& s = *I;
+    if (!s.sparse) throw std::runtime_error("DeviceRuiz::ingest_sparse on a dense problem");
+    PQ_HIP(hipSetDevice(s.device));
+    const size_t nzP = d.sP_utri.rowind.size(), nzA = d.sAT.rowind.size(), nzG = d.sGT.rowind.size();
+    if (d.srcP.size() != nzP || d.srcA.size() != nzA || d.srcG.size() != nzG) throw std::runtime_error("DeviceRuiz::ingest_sparse: no gather maps");
+    if (std::max(nzP, std::max(nzA, nzG)) > (size_t)INT_MAX) throw std::runtime_error("DeviceRuiz::ingest_sparse: more than 2^31 - 1 nonzeros");  // (int32 CSC: cannot happen)
+    if (!s.srcP.p) {
+        auto up = [&](DBuf<int>& dst, const IVec& h) { dst.alloc(std::max<size_t>(h.size(), 1)); if (!h.empty()) PQ_HIP(hipMemcpyAsync(dst.p, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice, s.st)); };
+        up(s.srcP, d.srcP); up(s.srcA, d.srcA); up(s.srcG, d.srcG);
+    }
+    long long moved = 0;
+    auto mat = [&](DBuf<double>& dst, const double* src, const DBuf<int>& map, size_t cnt) {
+        if (!src || !cnt) return;
+        ingest_gather(dst.p, src, map.p, (int)cnt, s.st);
+        moved += (long long)(cnt * sizeof(double));
+    };
+    if (options & PQ_KKT_UPDATE_P) mat(s.P, Px, s.srcP, nzP);
+    if (options & PQ_KKT_UPDATE_A) mat(s.AT, Ax, s.srcA, nzA);
+    if (options & PQ_KKT_UPDATE_G) mat(s.GT, Gx, s.srcG, nzG);
+    stream_wait(s.st);
+    return moved;
+}
+
+void DeviceRuiz::copy_values_from(const DeviceRuiz& o)
+{
+    Impl& s = *I;
+    const Impl& t = *o.I;
+    if (!s.sparse || !t.sparse || s.P.n != t.P.n || s.AT.n != t.AT.n || s.GT.n != t.GT.n) throw std::runtime_error("DeviceRuiz::copy_values_from: not the same sparse problem");
+    PQ_HIP(hipSetDevice(s.device));
+    stream_wait(t.st);
+    auto cp = [&](DBuf<double>& dst, const DBuf<double>& src) { PQ_HIP(hipMemcpyAsync(dst.p, src.p, src.bytes(), hipMemcpyDeviceToDevice, s.st)); };
+    cp(s.P, t.P); cp(s.AT, t.AT); cp(s.GT, t.GT); cp(s.vec, t.vec);
+    stream_wait(s.st);
+}
+
+// x_b_scaling: the device copy the last scale / unscale left, which is HostData::x_b_scaling bit for bit -- only those two change it, on the device, and download
+// it (an update of vectors alone rescales c and the bounds, never x_b_scaling)
+pq_sparse_data DeviceRuiz::sparse_descriptor(const HostData& d) const
+{
+    pq_sparse_data desc = d.sparse_descriptor();
+    desc.P_val = I->P.p; desc.AT_val = I->AT.p; desc.GT_val = I->GT.p;
+    desc.x_b_scaling = I->xbs;
+    desc.mem = PQ_MEM_DEVICE;
+    return desc;
 }
 
 pq_dense_data DeviceRuiz::dense_descriptor(const HostData& d) const

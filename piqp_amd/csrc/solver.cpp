@@ -69,7 +69,7 @@ bool HostData::disable_inf_constraints(IVec* rows)
     bool any = false;
     for (int i = 0; i < m; ++i) {
         if (h_l[i] <= -PIQP_INF && h_u[i] >= PIQP_INF) {
-            if (sparse) { for (int k = sGT.colptr[i]; k < sGT.colptr[i + 1]; ++k) sGT.val[k] = 0.0; }
+            if (sparse) { if (!values_on_device) for (int k = sGT.colptr[i]; k < sGT.colptr[i + 1]; ++k) sGT.val[k] = 0.0; }  // (on the device: see `rows`)
             else if (!GT.empty()) std::fill(GT.begin() + (size_t)i * n, GT.begin() + (size_t)(i + 1) * n, 0.0);  // (empty: the matrix lives on the device, see `rows`)
             if (rows) rows->push_back(i);
             h_l[i] = -1.0; h_u[i] = 1.0;
@@ -177,24 +177,58 @@ static void csc_transpose(int rows, int cols, const int* Ap, const int* Ai, cons
 {
     const int nnz = Ap ? Ap[cols] : 0;
     T.rows = cols; T.cols = rows;
-    T.colptr.assign(rows + 1, 0); T.rowind.assign(nnz, 0); T.val.assign(nnz, 0.0);
+    T.colptr.assign(rows + 1, 0); T.rowind.assign(nnz, 0); T.val.assign(Ax ? nnz : 0, 0.0);  // (Ax null: pattern only, the values live on the device)
     for (int k = 0; k < nnz; ++k) T.colptr[Ai[k] + 1]++;
     for (int i = 0; i < rows; ++i) T.colptr[i + 1] += T.colptr[i];
     IVec next(T.colptr.begin(), T.colptr.end() - 1);
-    for (int j = 0; j < cols; ++j) for (int k = Ap[j]; k < Ap[j + 1]; ++k) { const int q = next[Ai[k]]++; T.rowind[q] = j; T.val[q] = Ax[k]; }
+    for (int j = 0; j < cols; ++j) for (int k = Ap[j]; k < Ap[j + 1]; ++k) { const int q = next[Ai[k]]++; T.rowind[q] = j; if (Ax) T.val[q] = Ax[k]; }
+}
+
+void build_sparse_ingest_maps(int n, int p, int m, const int* Pp, const int* Pi, const int* Ap, const int* Ai, const int* Gp, const int* Gi, IVec& srcP, IVec& srcA, IVec& srcG)
+{
+    srcP.clear();
+    std::vector<std::pair<int, int>> col;
+    for (int j = 0; j < n; ++j) {
+        col.clear();
+        for (int k = Pp[j]; k < Pp[j + 1]; ++k) if (Pi[k] <= j) col.emplace_back(Pi[k], k);
+        std::sort(col.begin(), col.end(), [](const auto& a, const auto& b2) { return a.first < b2.first; });  // (the comparison make_sparse_host_data sorts the values with)
+        for (auto& e : col) srcP.push_back(e.second);
+    }
+    auto transposed = [&](int rows, const int* Mp, const int* Mi, IVec& src) {
+        src.clear();
+        if (!Mp || rows <= 0) return;
+        const int nnz = Mp[n];
+        IVec next(rows + 1, 0);
+        for (int k = 0; k < nnz; ++k) next[Mi[k] + 1]++;
+        for (int i = 0; i < rows; ++i) next[i + 1] += next[i];
+        src.assign(nnz, 0);
+        for (int j = 0; j < n; ++j) for (int k = Mp[j]; k < Mp[j + 1]; ++k) src[next[Mi[k]]++] = k;
+    };
+    transposed(p, Ap, Ai, srcA);
+    transposed(m, Gp, Gi, srcG);
 }
 
 // solver.hpp:169-192 (SparseSolver)
 std::unique_ptr<HostData> make_sparse_host_data(int n, int p, int m, const int* Pp, const int* Pi, const double* Px, const double* c, const int* Ap, const int* Ai,
                                                 const double* Ax, const double* b, const int* Gp, const int* Gi, const double* Gx, const double* h_l, const double* h_u,
-                                                const double* x_l, const double* x_u)
+                                                const double* x_l, const double* x_u, bool values_on_device, IVec* zeroed_rows)
 {
     auto d = std::make_unique<HostData>();
     d->sparse = true; d->n = n; d->p = Ap ? p : 0; d->m = Gp ? m : 0;
     p = d->p; m = d->m;
+    d->values_on_device = values_on_device;
+    build_sparse_ingest_maps(n, p, m, Pp, Pi, p > 0 ? Ap : nullptr, Ai, m > 0 ? Gp : nullptr, Gi, d->srcP, d->srcA, d->srcG);
+    d->nnz_in[0] = Pp[n]; d->nnz_in[1] = p > 0 ? Ap[n] : 0; d->nnz_in[2] = m > 0 ? Gp[n] : 0;
     Csc& U = d->sP_utri;
     U.rows = U.cols = n; U.colptr.assign(n + 1, 0);
-    for (int j = 0; j < n; ++j) {
+    if (values_on_device) {
+        // patterns only: Px / Ax / Gx are device pointers, the stored values are gathered on the device through the maps (DeviceRuiz::ingest_sparse)
+        Px = Ax = Gx = nullptr;
+        U.rowind.resize(d->srcP.size());
+        for (size_t t = 0; t < d->srcP.size(); ++t) U.rowind[t] = Pi[d->srcP[t]];
+        for (int j = 0; j < n; ++j) { int cnt = 0; for (int k = Pp[j]; k < Pp[j + 1]; ++k) cnt += Pi[k] <= j; U.colptr[j + 1] = U.colptr[j] + cnt; }
+    }
+    for (int j = 0; !values_on_device && j < n; ++j) {
         std::vector<std::pair<int, double>> col;
         for (int k = Pp[j]; k < Pp[j + 1]; ++k) if (Pi[k] <= j) col.emplace_back(Pi[k], Px[k]);
         std::sort(col.begin(), col.end(), [](const auto& a, const auto& b2) { return a.first < b2.first; });
@@ -204,7 +238,7 @@ std::unique_ptr<HostData> make_sparse_host_data(int n, int p, int m, const int* 
     if (p > 0) csc_transpose(p, n, Ap, Ai, Ax, d->sAT); else { d->sAT.rows = n; d->sAT.cols = 0; d->sAT.colptr.assign(1, 0); }
     if (m > 0) csc_transpose(m, n, Gp, Gi, Gx, d->sGT); else { d->sGT.rows = n; d->sGT.cols = 0; d->sGT.colptr.assign(1, 0); }
     d->resize_vectors();
-    finish_data(*d, c, b, h_l, h_u, x_l, x_u);
+    finish_data(*d, c, b, h_l, h_u, x_l, x_u, zeroed_rows);
     return d;
 }
 
@@ -494,7 +528,7 @@ void Solver::make_kkt()
         pq_dense_data desc = druiz_ ? druiz_->dense_descriptor(*m_data) : m_data->dense_descriptor();
         backend = make_dense_kkt(&desc, m_settings.kkt_solver, device_);
     } else {
-        pq_sparse_data desc = m_data->sparse_descriptor();
+        pq_sparse_data desc = m_data->values_on_device ? druiz_->sparse_descriptor(*m_data) : m_data->sparse_descriptor();
         backend = make_sparse_kkt(&desc, m_settings.kkt_solver, device_);
         if (!backend) { std::fprintf(stderr, "kkt solver not supported\n"); return; }
     }
@@ -506,8 +540,9 @@ void Solver::make_kkt()
 // solver.hpp:151-216
 bool Solver::device_ingest() { return debug_token("host_ruiz") == nullptr; }
 
-bool Solver::setup(std::unique_ptr<HostData> data, const DenseDeviceSource* dev, const IVec* zeroed_rows)
+bool Solver::setup(std::unique_ptr<HostData> data, const DenseDeviceSource* dev, const IVec* zeroed_rows, const SparseDeviceSource* sdev)
 {
+    if (data->sparse ? (dev != nullptr || data->values_on_device != (sdev != nullptr)) : sdev != nullptr) throw std::runtime_error("Solver::setup: device source of the wrong kind");
     const double t0 = now_s();
     m_data = std::move(data);
     const int n = m_data->n, p = m_data->p, m = m_data->m;
@@ -525,8 +560,13 @@ bool Solver::setup(std::unique_ptr<HostData> data, const DenseDeviceSource* dev,
             ingest_[1] = druiz_->ingest_dense(dev->P, dev->A, dev->G, dev->layout, PQ_KKT_UPDATE_P | PQ_KKT_UPDATE_A | PQ_KKT_UPDATE_G);
             if (zeroed_rows) druiz_->zero_G_rows(*zeroed_rows);
         } else if (!m_data->sparse) { druiz_->upload_dense(*m_data, PQ_KKT_UPDATE_P | PQ_KKT_UPDATE_A | PQ_KKT_UPDATE_G); release_dense_staging(); }
-    } else if (dev) throw std::runtime_error("device matrices need the device preconditioner");
+        else if (sdev) {
+            ingest_[1] = druiz_->ingest_sparse(*m_data, sdev->Px, sdev->Ax, sdev->Gx, PQ_KKT_UPDATE_P | PQ_KKT_UPDATE_A | PQ_KKT_UPDATE_G);
+            if (zeroed_rows) druiz_->zero_G_rows(*zeroed_rows);
+        }
+    } else if (dev || sdev) throw std::runtime_error("device matrices need the device preconditioner");
     if (!m_data->sparse && !dev) ingest_[0] = 8LL * n * ((long long)n + p + m);  // P, A^T, G^T go up once (here, or in the KKT backend under host_ruiz)
+    if (m_data->sparse && !sdev) ingest_[0] = 8LL * ((long long)m_data->sP_utri.nnz() + m_data->sAT.nnz() + m_data->sGT.nnz());  // upper(P), A^T, G^T values go up
     scale_problem(false);
     make_kkt();
     if (!m_kkt_system) { m_setup_done = false; return false; }
@@ -574,6 +614,7 @@ Solver* Solver::clone() const
         s->m_data = std::make_unique<HostData>(*m_data);
         s->m_preconditioner = m_preconditioner;
         if (druiz_) s->druiz_ = m_data->sparse ? std::make_unique<DeviceRuiz>(device_, *m_data) : druiz_->clone();
+        if (druiz_ && m_data->sparse && m_data->values_on_device) s->druiz_->copy_values_from(*druiz_);  // (no host mirror to rebuild them from)
         s->m_result = m_result; s->res_nr = res_nr; s->res = res; s->step = step; s->prox_vars = prox_vars;
         if (m_kkt_system) {
             s->m_kkt_system.reset(m_kkt_system->clone()); s->stage_alloc();
@@ -587,7 +628,7 @@ static void refresh_kkt(const DeviceRuiz* dr, KKTSystem& k, const HostData& d, i
 {
     // KKTSystem::update_data, kkt_system.hpp:134-141 (+ bound lists / x_b_scaling, which live in `data` in the reference)
     if (!d.sparse) { pq_dense_data desc = dr ? dr->dense_descriptor(d) : d.dense_descriptor(); k.backend()->update_data_dense(&desc, options); }
-    else { pq_sparse_data desc = d.sparse_descriptor(); k.backend()->update_data_sparse(&desc, options); }
+    else { pq_sparse_data desc = d.values_on_device ? dr->sparse_descriptor(d) : d.sparse_descriptor(); k.backend()->update_data_sparse(&desc, options); }
     k.set_bounds(d.n_h_l, d.n_h_u, d.n_x_l, d.n_x_u, d.h_l_idx.data(), d.h_u_idx.data(), d.x_l_idx.data(), d.x_u_idx.data(), d.x_b_scaling.data(), PQ_MEM_HOST);
 }
 
@@ -605,7 +646,7 @@ bool Solver::update_vectors_only(const double* c, const double* b, const double*
     if (h_u) d.set_h_u(h_u);
     IVec zeroed;
     const bool row_zeroed = (h_l || h_u) && d.disable_inf_constraints(&zeroed);  // a row of G without any finite bound is zeroed: that IS a matrix change
-    if (row_zeroed && druiz_) druiz_->zero_G_rows(zeroed);
+    if (row_zeroed && druiz_ && (!d.sparse || d.values_on_device)) druiz_->zero_G_rows(zeroed);
     if (x_l) d.set_x_l(x_l);
     if (x_u) d.set_x_u(x_u);
     m_preconditioner.scale_vectors(d);
@@ -655,13 +696,17 @@ bool Solver::update_dense(const double* P, const double* c, const double* A, con
 
 // solver.hpp:218-308 with the sparse update_P/A/G of :317-358 (identical sparsity required)
 bool Solver::update_sparse(const int* Pp, const int* Pi, const double* Px, const double* c, const int* Ap, const int* Ai, const double* Ax, const double* b, const int* Gp,
-                           const int* Gi, const double* Gx, const double* h_l, const double* h_u, const double* x_l, const double* x_u)
+                           const int* Gi, const double* Gx, const double* h_l, const double* h_u, const double* x_l, const double* x_u, int mat_mem)
 {
     if (!m_setup_done) { std::fprintf(stderr, "Solver not setup yet\n"); return false; }
     const double t0 = now_s();
     HostData& d = *m_data;
     const int n = d.n, p = d.p, m = d.m;
+    if (!d.sparse) { std::fprintf(stderr, "Solver not setup yet\n"); return false; }
     if (!Px && !Ax && !Gx) return update_vectors_only(c, b, h_l, h_u, x_l, x_u, t0);
+    if (mat_mem == PQ_MEM_DEVICE || d.values_on_device) return update_sparse_on_device(Pp, Px, c, Ap, Ax, b, Gp, Gx, h_l, h_u, x_l, x_u, mat_mem, t0);
+    ingest_[0] = 8LL * ((Px ? (long long)d.sP_utri.nnz() : 0) + (Ax ? d.sAT.nnz() : 0) + (Gx ? d.sGT.nnz() : 0));
+    ingest_[1] = 0;
     unscale_problem();
     int opt = PQ_KKT_UPDATE_NONE;
     (void)Pi;
@@ -685,6 +730,62 @@ bool Solver::update_sparse(const int* Pp, const int* Pi, const double* Px, const
     if (h_l) d.set_h_l(h_l);
     if (h_u) d.set_h_u(h_u);
     if (h_l || h_u) d.disable_inf_constraints();
+    if (x_l) d.set_x_l(x_l);
+    if (x_u) d.set_x_u(x_u);
+    bool reuse = m_settings.preconditioner_reuse_on_update != 0;
+    if (opt == PQ_KKT_UPDATE_NONE) reuse = true;
+    scale_problem(reuse);
+    refresh_kkt(druiz_.get(), *m_kkt_system, d, opt);
+    if (dipm_) dipm_->refresh_data(d, m_preconditioner);
+    m_info.update_time = now_s() - t0;
+    return true;
+}
+
+// The same with the matrix values in DeviceRuiz's arrays (a device-fed solver, or the first device-mode update of a host-fed one): unscale_data -> assign ->
+// scale_data on the device, the KKT system refreshed from a device-mode descriptor; no matrix value comes to the host or goes back.  Px / Ax / Gx: device arrays
+// (mat_mem = PQ_MEM_DEVICE) or host arrays (a host-fed update of a device-fed solver: staged in HBM first) in the CSC order given at setup; the index arrays may be
+// null (identical sparsity is the precondition, the maps of the setup are used) and are only checked for their length.
+bool Solver::update_sparse_on_device(const int* Pp, const double* Px, const double* c, const int* Ap, const double* Ax, const double* b, const int* Gp, const double* Gx,
+                                     const double* h_l, const double* h_u, const double* x_l, const double* x_u, int mat_mem, double t0)
+{
+    HostData& d = *m_data;
+    const int n = d.n, p = d.p, m = d.m;
+    if (!druiz_) throw std::runtime_error("device matrices need the device preconditioner");
+    if (Pp && Px && Pp[n] != d.nnz_in[0]) { std::fprintf(stderr, "P nonzeros missmatch\n"); return false; }
+    if (Ap && Ax && Ap[n] != d.nnz_in[1]) { std::fprintf(stderr, "A nonzeros missmatch\n"); return false; }
+    if (Gp && Gx && Gp[n] != d.nnz_in[2]) { std::fprintf(stderr, "G nonzeros missmatch\n"); return false; }
+    if (p == 0) Ax = nullptr;
+    if (m == 0) Gx = nullptr;
+    PQ_HIP(hipSetDevice(device_));
+    unscale_problem();  // (host-fed so far: the mirror goes up, is unscaled, and comes back for the last time -- the device arrays keep the same values)
+    if (!d.values_on_device) {
+        Vec().swap(d.sP_utri.val); Vec().swap(d.sAT.val); Vec().swap(d.sGT.val);
+        d.values_on_device = true;
+    }
+    ingest_[0] = ingest_[1] = 0;
+    DBuf<double> stage[3];
+    if (mat_mem != PQ_MEM_DEVICE) {
+        const double** src[3] = {&Px, &Ax, &Gx};
+        for (int k = 0; k < 3; ++k) {
+            if (!*src[k] || d.nnz_in[k] <= 0) continue;
+            stage[k].alloc((size_t)d.nnz_in[k]);
+            PQ_HIP(hipMemcpy(stage[k].p, *src[k], sizeof(double) * (size_t)d.nnz_in[k], hipMemcpyHostToDevice));
+            ingest_[0] += 8LL * d.nnz_in[k];
+            *src[k] = stage[k].p;
+        }
+    }
+    int opt = PQ_KKT_UPDATE_NONE;
+    if (Px) opt |= PQ_KKT_UPDATE_P;
+    if (Ax) opt |= PQ_KKT_UPDATE_A;
+    if (Gx) opt |= PQ_KKT_UPDATE_G;
+    ingest_[1] = druiz_->ingest_sparse(d, Px, Ax, Gx, opt);
+    if (c) std::copy(c, c + n, d.c.begin());
+    if (b) std::copy(b, b + p, d.b.begin());
+    if (h_l) d.set_h_l(h_l);
+    if (h_u) d.set_h_u(h_u);
+    IVec zeroed;
+    if (h_l || h_u) d.disable_inf_constraints(&zeroed);
+    druiz_->zero_G_rows(zeroed);
     if (x_l) d.set_x_l(x_l);
     if (x_u) d.set_x_u(x_u);
     bool reuse = m_settings.preconditioner_reuse_on_update != 0;
@@ -1327,12 +1428,39 @@ int pq_solver_setup_dense(pq_solver* s, int n, int p, int m, const double* P, co
 {
     return pq_solver_setup_dense_mem(s, n, p, m, P, c, A, b, G, h_l, h_u, x_l, x_u, PQ_MEM_HOST, PQ_COL_MAJOR);
 }
+int pq_solver_setup_sparse_mem(pq_solver* s, int n, int p, int m, const int* Pp, const int* Pi, const double* Px, const double* c, const int* Ap, const int* Ai,
+                               const double* Ax, const double* b, const int* Gp, const int* Gi, const double* Gx, const double* h_l, const double* h_u, const double* x_l,
+                               const double* x_u, int mem)
+{
+    if (!s || !Pp || !c || n <= 0) return fail(PQ_ERR_INVALID, "bad argument");
+    if (mem != PQ_MEM_HOST && mem != PQ_MEM_DEVICE) return fail(PQ_ERR_INVALID, "mem must be PQ_MEM_HOST or PQ_MEM_DEVICE");
+    if ((Ap && !b && p > 0) || (!h_l && !h_u && Gp && m > 0)) return fail(PQ_ERR_INVALID, "b / h_l or h_u must be provided");
+    if (mem == PQ_MEM_HOST) return guarded([&] { return s->impl->setup(make_sparse_host_data(n, p, m, Pp, Pi, Px, c, Ap, Ai, Ax, b, Gp, Gi, Gx, h_l, h_u, x_l, x_u)) ? 1 : 0; });
+    if (!Pi || (Pp[n] > 0 && !Px) || (Ap && p > 0 && (!Ai || (Ap[n] > 0 && !Ax))) || (Gp && m > 0 && (!Gi || (Gp[n] > 0 && !Gx)))) return fail(PQ_ERR_INVALID, "bad argument");
+    return guarded([&] {
+        PQ_HIP(hipSetDevice(s->impl->device()));
+        const int pp = Ap ? p : 0, mm = Gp ? m : 0;
+        FetchedVectors v;
+        c = v.fetch(0, c, n); b = v.fetch(1, b, pp); h_l = v.fetch(2, h_l, mm); h_u = v.fetch(3, h_u, mm); x_l = v.fetch(4, x_l, n); x_u = v.fetch(5, x_u, n);
+        if (!Solver::device_ingest()) {
+            Vec hP, hA, hG;
+            long long bytes = 0;
+            Px = fetch_matrix(hP, Px, (size_t)Pp[n], bytes); Ax = fetch_matrix(hA, Ax, pp ? (size_t)Ap[n] : 0, bytes); Gx = fetch_matrix(hG, Gx, mm ? (size_t)Gp[n] : 0, bytes);
+            const bool ok = s->impl->setup(make_sparse_host_data(n, p, m, Pp, Pi, Px, c, Ap, Ai, Ax, b, Gp, Gi, Gx, h_l, h_u, x_l, x_u));
+            s->impl->add_link_bytes(bytes);
+            return ok ? 1 : 0;
+        }
+        IVec zeroed;
+        auto data = make_sparse_host_data(n, p, m, Pp, Pi, nullptr, c, Ap, Ai, nullptr, b, Gp, Gi, nullptr, h_l, h_u, x_l, x_u, true, &zeroed);
+        SparseDeviceSource src;
+        src.Px = Px; src.Ax = pp ? Ax : nullptr; src.Gx = mm ? Gx : nullptr;
+        return s->impl->setup(std::move(data), nullptr, &zeroed, &src) ? 1 : 0;
+    });
+}
 int pq_solver_setup_sparse(pq_solver* s, int n, int p, int m, const int* Pp, const int* Pi, const double* Px, const double* c, const int* Ap, const int* Ai, const double* Ax,
                            const double* b, const int* Gp, const int* Gi, const double* Gx, const double* h_l, const double* h_u, const double* x_l, const double* x_u)
 {
-    if (!s || !Pp || !c || n <= 0) return fail(PQ_ERR_INVALID, "bad argument");
-    if ((Ap && !b && p > 0) || (!h_l && !h_u && Gp && m > 0)) return fail(PQ_ERR_INVALID, "b / h_l or h_u must be provided");
-    return guarded([&] { return s->impl->setup(make_sparse_host_data(n, p, m, Pp, Pi, Px, c, Ap, Ai, Ax, b, Gp, Gi, Gx, h_l, h_u, x_l, x_u)) ? 1 : 0; });
+    return pq_solver_setup_sparse_mem(s, n, p, m, Pp, Pi, Px, c, Ap, Ai, Ax, b, Gp, Gi, Gx, h_l, h_u, x_l, x_u, PQ_MEM_HOST);
 }
 int pq_solver_update_dense_mem(pq_solver* s, const double* P, const double* c, const double* A, const double* b, const double* G, const double* h_l, const double* h_u,
                                const double* x_l, const double* x_u, int mem, int layout)
@@ -1369,11 +1497,57 @@ int pq_solver_last_ingest(const pq_solver* s, long long out[2])
     out[0] = s->impl->last_ingest()[0]; out[1] = s->impl->last_ingest()[1];
     return PQ_OK;
 }
+int pq_solver_update_sparse_mem(pq_solver* s, const int* Pp, const int* Pi, const double* Px, const double* c, const int* Ap, const int* Ai, const double* Ax, const double* b,
+                                const int* Gp, const int* Gi, const double* Gx, const double* h_l, const double* h_u, const double* x_l, const double* x_u, int mem)
+{
+    if (!s) return fail(PQ_ERR_INVALID, "null argument");
+    if (mem != PQ_MEM_HOST && mem != PQ_MEM_DEVICE) return fail(PQ_ERR_INVALID, "mem must be PQ_MEM_HOST or PQ_MEM_DEVICE");
+    if (mem == PQ_MEM_HOST) return guarded([&] { return s->impl->update_sparse(Pp, Pi, Px, c, Ap, Ai, Ax, b, Gp, Gi, Gx, h_l, h_u, x_l, x_u) ? 1 : 0; });
+    return guarded([&] {
+        const HostData* d = s->impl->data();
+        if (!d || !d->sparse) { std::fprintf(stderr, "Solver not setup yet\n"); return 0; }
+        PQ_HIP(hipSetDevice(s->impl->device()));
+        const int n = d->n, p = d->p, m = d->m;
+        FetchedVectors v;
+        c = v.fetch(0, c, n); b = v.fetch(1, b, p); h_l = v.fetch(2, h_l, m); h_u = v.fetch(3, h_u, m); x_l = v.fetch(4, x_l, n); x_u = v.fetch(5, x_u, n);
+        if (!Solver::device_ingest()) {
+            // the host path walks the index arrays: they must be given here
+            if ((Px && (!Pp || !Pi)) || (Ax && p > 0 && (!Ap || !Ai)) || (Gx && m > 0 && (!Gp || !Gi))) throw std::runtime_error("PIQP_AMD_DEBUG=host_ruiz: a device-mode update needs the index arrays");
+            Vec hP, hA, hG;
+            long long bytes = 0;
+            Px = fetch_matrix(hP, Px, (size_t)d->nnz_in[0], bytes); Ax = fetch_matrix(hA, Ax, (size_t)d->nnz_in[1], bytes); Gx = fetch_matrix(hG, Gx, (size_t)d->nnz_in[2], bytes);
+            const bool ok = s->impl->update_sparse(Pp, Pi, Px, c, Ap, Ai, Ax, b, Gp, Gi, Gx, h_l, h_u, x_l, x_u);
+            s->impl->add_link_bytes(bytes);
+            return ok ? 1 : 0;
+        }
+        return s->impl->update_sparse(Pp, Pi, Px, c, Ap, Ai, Ax, b, Gp, Gi, Gx, h_l, h_u, x_l, x_u, PQ_MEM_DEVICE) ? 1 : 0;
+    });
+}
 int pq_solver_update_sparse(pq_solver* s, const int* Pp, const int* Pi, const double* Px, const double* c, const int* Ap, const int* Ai, const double* Ax, const double* b,
                             const int* Gp, const int* Gi, const double* Gx, const double* h_l, const double* h_u, const double* x_l, const double* x_u)
 {
-    if (!s) return fail(PQ_ERR_INVALID, "null argument");
-    return guarded([&] { return s->impl->update_sparse(Pp, Pi, Px, c, Ap, Ai, Ax, b, Gp, Gi, Gx, h_l, h_u, x_l, x_u) ? 1 : 0; });
+    return pq_solver_update_sparse_mem(s, Pp, Pi, Px, c, Ap, Ai, Ax, b, Gp, Gi, Gx, h_l, h_u, x_l, x_u, PQ_MEM_HOST);
+}
+// host-only planning hook: the gather maps of a sparse setup in scatter form (mapX[k] = stored position of the caller's entry k, -1 = never read)
+int pq_debug_sparse_ingest_maps(int n, int p, int m, const int* Pp, const int* Pi, const int* Ap, const int* Ai, const int* Gp, const int* Gi, int* mapP, int* mapA, int* mapG,
+                                int nnz_out[3])
+{
+    if (n <= 0 || !Pp || (Pp[n] > 0 && !Pi) || p < 0 || m < 0) return fail(PQ_ERR_INVALID, "bad argument");
+    if ((Ap && p > 0 && Ap[n] > 0 && !Ai) || (Gp && m > 0 && Gp[n] > 0 && !Gi)) return fail(PQ_ERR_INVALID, "bad argument");
+    return guarded([&] {
+        IVec sP, sA, sG;
+        build_sparse_ingest_maps(n, Ap ? p : 0, Gp ? m : 0, Pp, Pi, Ap, Ai, Gp, Gi, sP, sA, sG);
+        auto scatter = [](const IVec& src, int cnt, int* map) {
+            if (!map) return;
+            std::fill(map, map + cnt, -1);
+            for (size_t t = 0; t < src.size(); ++t) map[src[t]] = (int)t;
+        };
+        scatter(sP, Pp[n], mapP);
+        scatter(sA, Ap && p > 0 ? Ap[n] : 0, mapA);
+        scatter(sG, Gp && m > 0 ? Gp[n] : 0, mapG);
+        if (nnz_out) { nnz_out[0] = (int)sP.size(); nnz_out[1] = (int)sA.size(); nnz_out[2] = (int)sG.size(); }
+        return (int)PQ_OK;
+    });
 }
 int pq_solver_solve(pq_solver* s)
 {

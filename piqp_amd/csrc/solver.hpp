@@ -29,6 +29,11 @@ struct HostData {
     int n = 0, p = 0, m = 0;
     Vec P_utri, AT, GT;  // dense, column-major (n x n, n x p, n x m)
     Csc sP_utri, sAT, sGT;
+    // sparse: gather maps from the caller's CSC value arrays (P full or upper, A, G as given at setup, nnz_in entries each) to the stored order of sP_utri / sAT /
+    // sGT: stored value t = caller value src*[t] (build_sparse_ingest_maps).  values_on_device: the stored values live in DeviceRuiz only, s*.val stay empty.
+    IVec srcP, srcA, srcG;
+    int nnz_in[3] = {0, 0, 0};
+    bool values_on_device = false;
     Vec c, b, h_l, h_u, x_l, x_u, x_b_scaling;
     int n_h_l = 0, n_h_u = 0, n_x_l = 0, n_x_u = 0;
     IVec h_l_idx, h_u_idx, x_l_idx, x_u_idx;
@@ -88,6 +93,11 @@ struct DenseDeviceSource {
     int layout = PQ_COL_MAJOR;
 };
 
+// the CSC value arrays of a sparse setup that already live in HBM on the solver's device, in the order of the (host) index arrays of the same call; nullptr = absent
+struct SparseDeviceSource {
+    const double *Px = nullptr, *Ax = nullptr, *Gx = nullptr;
+};
+
 class Solver {
 public:
     explicit Solver(int device);
@@ -97,7 +107,8 @@ public:
     pq_settings& settings() { return m_settings; }
     // solver.hpp:151-216.  dev: the matrices of a dense problem come from device memory (data then carries vectors and bound lists only, and
     // zeroed_rows the rows of G that data.hpp:144-169 disables); requires device_ingest()
-    bool setup(std::unique_ptr<HostData> data, const DenseDeviceSource* dev = nullptr, const IVec* zeroed_rows = nullptr);
+    // sdev: the same for a sparse problem (data built with values_on_device: patterns, gather maps, vectors and bound lists)
+    bool setup(std::unique_ptr<HostData> data, const DenseDeviceSource* dev = nullptr, const IVec* zeroed_rows = nullptr, const SparseDeviceSource* sdev = nullptr);
     // solver.hpp:218-308.  The vectors are host arrays; P, A, G are host arrays (mat_mem = PQ_MEM_HOST) or device arrays (PQ_MEM_DEVICE, requires device_ingest())
     // in storage order `layout`
     bool update_dense(const double* P, const double* c, const double* A, const double* b, const double* G, const double* h_l, const double* h_u, const double* x_l,
@@ -106,7 +117,7 @@ public:
     const long long* last_ingest() const { return ingest_; }      // pq_solver_last_ingest
     void add_link_bytes(long long bytes) { ingest_[0] += bytes; }  // matrix bytes the C-ABI layer itself moved across the link for the last setup / update
     bool update_sparse(const int* Pp, const int* Pi, const double* Px, const double* c, const int* Ap, const int* Ai, const double* Ax, const double* b, const int* Gp,
-                       const int* Gi, const double* Gx, const double* h_l, const double* h_u, const double* x_l, const double* x_u);
+                       const int* Gi, const double* Gx, const double* h_l, const double* h_u, const double* x_l, const double* x_u, int mat_mem = PQ_MEM_HOST);
     int solve();  // solver.hpp:69-148
     const pq_info& info() const { return m_info; }
     const HostVars& result() const { return m_result; }
@@ -118,6 +129,8 @@ public:
 
 private:
     int solve_impl();
+    bool update_sparse_on_device(const int* Pp, const double* Px, const double* c, const int* Ap, const double* Ax, const double* b, const int* Gp, const double* Gx,
+                                 const double* h_l, const double* h_u, const double* x_l, const double* x_u, int mat_mem, double t0);
     bool update_vectors_only(const double* c, const double* b, const double* h_l, const double* h_u, const double* x_l, const double* x_u, double t0);
     bool kkt_factor();
     void kkt_solve(const HostVars& rhs, HostVars& lhs);
@@ -169,6 +182,10 @@ std::unique_ptr<HostData> make_dense_host_data(int n, int p, int m, const double
                                                IVec* zeroed_rows = nullptr);
 std::unique_ptr<HostData> make_sparse_host_data(int n, int p, int m, const int* Pp, const int* Pi, const double* Px, const double* c, const int* Ap, const int* Ai,
                                                 const double* Ax, const double* b, const int* Gp, const int* Gi, const double* Gx, const double* h_l, const double* h_u,
-                                                const double* x_l, const double* x_u);
+                                                const double* x_l, const double* x_u, bool values_on_device = false, IVec* zeroed_rows = nullptr);
+// Gather maps of a sparse setup, from the patterns alone (host-only; pq_debug_sparse_ingest_maps): srcP[t] = position in the caller's P arrays of the t-th stored
+// entry of upper(P) -- per column the entries on or above the diagonal, rows ascending --, srcA[t] / srcG[t] = position in the caller's A / G arrays of the t-th
+// stored entry of A^T / G^T (the order csc_transpose and the retranspose of Solver::update_sparse produce).  Absent matrix: null pattern, empty map.
+void build_sparse_ingest_maps(int n, int p, int m, const int* Pp, const int* Pi, const int* Ap, const int* Ai, const int* Gp, const int* Gi, IVec& srcP, IVec& srcA, IVec& srcG);
 
 }  // namespace pq

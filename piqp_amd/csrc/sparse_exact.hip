@@ -893,7 +893,7 @@ public:
     struct TooCostly {};  // thrown by the constructor before anything is allocated: the factorisation has more flops than the caller's limit
     ExactSparseKKT(const pq_sparse_data* d, int mode, int device, double max_flops) : dev_(device), mode_(mode)
     {
-        if (d->mem != PQ_MEM_HOST) throw std::runtime_error("sparse data must be host-resident");
+        if (d->mem != PQ_MEM_HOST && d->mem != PQ_MEM_DEVICE) throw std::runtime_error("sparse data: mem must be PQ_MEM_HOST or PQ_MEM_DEVICE");  // (index arrays: host either way)
         sparse::Symbolic S;
         sparse::analyse_kkt_pattern(d, mode_, S);
         sparse::analyse_uplooking(S, d, U_);

@@ -2234,7 +2234,7 @@ class SparseKKT final : public KKTSolverBase {
 public:
     SparseKKT(const pq_sparse_data* d, int mode, int device, hipStream_t adopt = nullptr) : dev_(device), mode_(mode)
     {
-        if (d->mem != PQ_MEM_HOST) throw std::runtime_error("sparse data must be host-resident");
+        if (d->mem != PQ_MEM_HOST && d->mem != PQ_MEM_DEVICE) throw std::runtime_error("sparse data: mem must be PQ_MEM_HOST or PQ_MEM_DEVICE");  // (index arrays: host either way)
         PQ_HIP(hipSetDevice(dev_));
         st_ = adopt ? Stream(dev_, adopt) : Stream(dev_);
         try {
@@ -3585,30 +3585,50 @@ private:
 KKTSolverBase* make_multifrontal_kkt(const pq_sparse_data* data, int mode, int device, hipStream_t adopt) { return new SparseKKT(data, mode, device, adopt); }
 
 namespace {
-// A host copy of the matrices a sparse backend is built from (the C-ABI lends them for the duration of a call only).  A PIQP update never changes a pattern: the patterns
-// are copied once, refresh() takes the values, the bound lists and x_b_scaling.
+// A copy of the matrices a sparse backend is built from (the C-ABI lends them for the duration of a call only).  A PIQP update never changes a pattern: the patterns
+// are copied once, refresh() takes the values, the bound lists and x_b_scaling.  The values stay where the caller has them (pq_sparse_data.mem): host values in host
+// vectors, device values in device buffers filled device-to-device -- a device-mode refresh moves nothing across the link.
 struct SparseDataCopy {
     std::vector<int> pc, pr, ac, ar, gc, gr, hl, hu, xl, xu;
     std::vector<double> pv, av, gv, xb;
+    DBuf<double> dpv, dav, dgv, dxb;  // device mode
     pq_sparse_data d{};
-    explicit SparseDataCopy(const pq_sparse_data* s)
+    int dev;
+    SparseDataCopy(const pq_sparse_data* s, int device, hipStream_t st)
         : pc(s->P_colptr, s->P_colptr + s->n + 1), pr(s->P_rowind, s->P_rowind + pc.back()), ac(s->AT_colptr, s->AT_colptr + s->p + 1), ar(s->AT_rowind, s->AT_rowind + ac.back()),
-          gc(s->GT_colptr, s->GT_colptr + s->m + 1), gr(s->GT_rowind, s->GT_rowind + gc.back())
+          gc(s->GT_colptr, s->GT_colptr + s->m + 1), gr(s->GT_rowind, s->GT_rowind + gc.back()), dev(device)
     {
-        refresh(s);
+        refresh(s, st);
     }
     SparseDataCopy(const SparseDataCopy&) = delete;  // (d points into this object)
-    void refresh(const pq_sparse_data* s)  // same dimensions and nonzero counts as at construction (the caller checks)
+    // same dimensions and nonzero counts as at construction (the caller checks).  st: the owning handle's stream; device values are copied on it and the call waits
+    // for it, so the caller's arrays have been read when this returns and the copies are ordered before anything the handle does later
+    void refresh(const pq_sparse_data* s, hipStream_t st)
     {
-        pv.assign(s->P_val, s->P_val + pr.size()); av.assign(s->AT_val, s->AT_val + ar.size()); gv.assign(s->GT_val, s->GT_val + gr.size());
         auto idx = [](const int* p, int k, std::vector<int>& o) { if (p && k > 0) o.assign(p, p + k); else o.clear(); };
         idx(s->h_l_idx, s->n_h_l, hl); idx(s->h_u_idx, s->n_h_u, hu); idx(s->x_l_idx, s->n_x_l, xl); idx(s->x_u_idx, s->n_x_u, xu);
-        if (s->x_b_scaling) xb.assign(s->x_b_scaling, s->x_b_scaling + s->n);
         d = *s;
-        d.P_colptr = pc.data(); d.P_rowind = pr.data(); d.P_val = pv.data();
-        d.AT_colptr = ac.data(); d.AT_rowind = ar.data(); d.AT_val = av.data();
-        d.GT_colptr = gc.data(); d.GT_rowind = gr.data(); d.GT_val = gv.data();
+        d.P_colptr = pc.data(); d.P_rowind = pr.data();
+        d.AT_colptr = ac.data(); d.AT_rowind = ar.data();
+        d.GT_colptr = gc.data(); d.GT_rowind = gr.data();
         d.h_l_idx = hl.data(); d.h_u_idx = hu.data(); d.x_l_idx = xl.data(); d.x_u_idx = xu.data();
+        if (s->mem == PQ_MEM_DEVICE) {
+            PQ_HIP(hipSetDevice(dev));
+            auto keep = [st](DBuf<double>& b, const double* src, size_t cnt) {
+                if (b.n < std::max<size_t>(cnt, 1)) b.alloc(std::max<size_t>(cnt, 1));
+                if (cnt) PQ_HIP(hipMemcpyAsync(b.p, src, sizeof(double) * cnt, hipMemcpyDeviceToDevice, st));
+            };
+            keep(dpv, s->P_val, pr.size()); keep(dav, s->AT_val, ar.size()); keep(dgv, s->GT_val, gr.size());
+            if (s->x_b_scaling) keep(dxb, s->x_b_scaling, (size_t)s->n);
+            stream_wait(st);  // (`src` is the caller's for this call only)
+            d.P_val = dpv.p; d.AT_val = dav.p; d.GT_val = dgv.p;
+            d.x_b_scaling = s->x_b_scaling ? dxb.p : nullptr;
+            d.mem = PQ_MEM_DEVICE;
+            return;
+        }
+        pv.assign(s->P_val, s->P_val + pr.size()); av.assign(s->AT_val, s->AT_val + ar.size()); gv.assign(s->GT_val, s->GT_val + gr.size());
+        if (s->x_b_scaling) xb.assign(s->x_b_scaling, s->x_b_scaling + s->n);
+        d.P_val = pv.data(); d.AT_val = av.data(); d.GT_val = gv.data();
         d.x_b_scaling = s->x_b_scaling ? xb.data() : nullptr;
         d.mem = PQ_MEM_HOST;
     }
@@ -3620,7 +3640,7 @@ struct SparseDataCopy {
 class EngineSwitchKKT final : public KKTSolverBase {
 public:
     EngineSwitchKKT(std::unique_ptr<KKTSolverBase> exact, const pq_sparse_data* data, int mode, int device)
-        : cur_(std::move(exact)), copy_(new SparseDataCopy(data)), nnz_{data->P_colptr[data->n], data->AT_colptr[data->p], data->GT_colptr[data->m]}, mode_(mode), dev_(device)
+        : cur_(std::move(exact)), copy_(new SparseDataCopy(data, device, cur_->stream())), nnz_{data->P_colptr[data->n], data->AT_colptr[data->p], data->GT_colptr[data->m]}, mode_(mode), dev_(device)
     {
     }
     KKTSolverBase* clone() const override { return new EngineSwitchKKT(*this, std::unique_ptr<KKTSolverBase>(cur_->clone())); }
@@ -3629,7 +3649,7 @@ public:
         if (data->n != n() || data->p != p() || data->m != m()) throw std::runtime_error("update_data: dimension mismatch");
         if (data->P_colptr[data->n] != nnz_[0] || data->AT_colptr[data->p] != nnz_[1] || data->GT_colptr[data->m] != nnz_[2])
             throw std::runtime_error("update_data: the number of nonzeros differs from the pattern the handle was built with");
-        if (copy_) copy_->refresh(data);
+        if (copy_) copy_->refresh(data, cur_->stream());
         cur_->update_data_sparse(data, options);
     }
     bool update_scalings_and_factor(double delta, const double* x_reg, const double* z_reg) override { return cur_->update_scalings_and_factor(delta, x_reg, z_reg); }
@@ -3682,7 +3702,7 @@ public:
 
 private:
     EngineSwitchKKT(const EngineSwitchKKT& o, std::unique_ptr<KKTSolverBase> engine)
-        : cur_(std::move(engine)), copy_(o.copy_ ? new SparseDataCopy(&o.copy_->d) : nullptr), nnz_(o.nnz_), mode_(o.mode_), dev_(o.dev_)
+        : cur_(std::move(engine)), copy_(o.copy_ ? new SparseDataCopy(&o.copy_->d, o.dev_, cur_->stream()) : nullptr), nnz_(o.nnz_), mode_(o.mode_), dev_(o.dev_)
     {
     }
     std::unique_ptr<KKTSolverBase> cur_;

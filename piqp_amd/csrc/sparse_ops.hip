@@ -24,6 +24,12 @@ __global__ void k_gather_values(int nnz, const int* __restrict__ src_idx, const 
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q < nnz) dst[q] = src[src_idx[q]];
 }
+// dst[j] = src[src_idx[j]], 0 where src_idx[j] < 0 (the diagonal of P: columns without a structural diagonal entry)
+__global__ void k_gather_or_zero(int cnt, const int* __restrict__ src_idx, const double* __restrict__ src, double* __restrict__ dst)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < cnt) { const int q = src_idx[j]; dst[j] = q >= 0 ? src[q] : 0.0; }
+}
 
 // ---- column dots of a CSC matrix, one column per lane, with COALESCED traffic (round 3).
 // A thread that walks its own column reads val[q], rowind[q] at addresses a whole column apart from its neighbours': every load instruction of the wave
@@ -317,6 +323,12 @@ void CscOperators::init(const pq_sparse_data* d, hipStream_t st)
     }
     P_x_.alloc(nzP_ ? nzP_ : 1);
     Pdiag_.alloc(n_ ? n_ : 1);
+    {
+        // position of the diagonal entry of every column of P_utri (the last one if a column lists it twice), -1 = none
+        std::vector<int> dsrc(n_ ? n_ : 1, -1);
+        for (int j = 0; j < n_; ++j) for (int q = d->P_colptr[j]; q < d->P_colptr[j + 1]; ++q) if (d->P_rowind[q] == j) dsrc[j] = q;
+        upload_vec(Pdiag_src_, dsrc, st);
+    }
     // AT (n x p) and its transpose A (p x n); GT (n x m) and G
     {
         std::vector<int> atp(d->AT_colptr, d->AT_colptr + p_ + 1), ati(d->AT_rowind, d->AT_rowind + nzA_);
@@ -351,23 +363,24 @@ void CscOperators::init(const pq_sparse_data* d, hipStream_t st)
 void CscOperators::upload_values(const pq_sparse_data* d, hipStream_t st)
 {
     if (d->n != n_ || d->p != p_ || d->m != m_) throw std::runtime_error("update_data: dimension mismatch");
+    if (d->mem != PQ_MEM_HOST && d->mem != PQ_MEM_DEVICE) throw std::runtime_error("update_data: mem must be PQ_MEM_HOST or PQ_MEM_DEVICE");
+    // the values come from the caller's host arrays or, device mode, from arrays already in HBM (device-to-device: nothing crosses the link)
+    const hipMemcpyKind kind = d->mem == PQ_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     if (nzP_) {
-        PQ_HIP(hipMemcpyAsync(P_x_.p, d->P_val, sizeof(double) * nzP_, hipMemcpyHostToDevice, st));
+        PQ_HIP(hipMemcpyAsync(P_x_.p, d->P_val, sizeof(double) * nzP_, kind, st));
         launch_gather_values(nzPf_, Pf_src_.p, P_x_.p, Pf_x_.p, st);
     }
-    std::vector<double> pd(n_, 0.0);
-    for (int j = 0; j < n_; ++j) for (int q = d->P_colptr[j]; q < d->P_colptr[j + 1]; ++q) if (d->P_rowind[q] == j) pd[j] = d->P_val[q];
-    if (n_) PQ_HIP(hipMemcpyAsync(Pdiag_.p, pd.data(), sizeof(double) * n_, hipMemcpyHostToDevice, st));
+    if (n_) hipLaunchKernelGGL(k_gather_or_zero, g1(n_), dim3(256), 0, st, n_, Pdiag_src_.p, P_x_.p, Pdiag_.p);
     if (nzA_) {
-        PQ_HIP(hipMemcpyAsync(AT_x_.p, d->AT_val, sizeof(double) * nzA_, hipMemcpyHostToDevice, st));
+        PQ_HIP(hipMemcpyAsync(AT_x_.p, d->AT_val, sizeof(double) * nzA_, kind, st));
         launch_gather_values(nzA_, A_src_.p, AT_x_.p, A_x_.p, st);
     }
     if (nzG_) {
-        PQ_HIP(hipMemcpyAsync(GT_x_.p, d->GT_val, sizeof(double) * nzG_, hipMemcpyHostToDevice, st));
+        PQ_HIP(hipMemcpyAsync(GT_x_.p, d->GT_val, sizeof(double) * nzG_, kind, st));
         launch_gather_values(nzG_, G_src_.p, GT_x_.p, G_x_.p, st);
     }
     PQ_HIP(hipGetLastError());
-    stream_wait(st);  // `pd` and the caller's arrays must outlive the copies
+    stream_wait(st);  // the caller's arrays must outlive the copies
 }
 
 void CscOperators::clone_from(const CscOperators& o, hipStream_t st)
@@ -376,7 +389,7 @@ void CscOperators::clone_from(const CscOperators& o, hipStream_t st)
     auto cpd = [&](DBuf<double>& d, const DBuf<double>& s) { d.alloc(s.n ? s.n : 1); if (s.n) PQ_HIP(hipMemcpyAsync(d.p, s.p, s.bytes(), hipMemcpyDeviceToDevice, st)); };
     auto cpi = [&](DBuf<int>& d, const DBuf<int>& s) { d.alloc(s.n ? s.n : 1); if (s.n) PQ_HIP(hipMemcpyAsync(d.p, s.p, s.bytes(), hipMemcpyDeviceToDevice, st)); };
     cpd(P_x_, o.P_x_); cpd(Pf_x_, o.Pf_x_); cpd(AT_x_, o.AT_x_); cpd(A_x_, o.A_x_); cpd(GT_x_, o.GT_x_); cpd(G_x_, o.G_x_); cpd(Pdiag_, o.Pdiag_);
-    cpi(Pf_p_, o.Pf_p_); cpi(Pf_i_, o.Pf_i_); cpi(Pf_src_, o.Pf_src_); cpi(AT_p_, o.AT_p_); cpi(AT_i_, o.AT_i_); cpi(A_p_, o.A_p_); cpi(A_i_, o.A_i_);
+    cpi(Pf_p_, o.Pf_p_); cpi(Pf_i_, o.Pf_i_); cpi(Pf_src_, o.Pf_src_); cpi(Pdiag_src_, o.Pdiag_src_); cpi(AT_p_, o.AT_p_); cpi(AT_i_, o.AT_i_); cpi(A_p_, o.A_p_); cpi(A_i_, o.A_i_);
     cpi(A_src_, o.A_src_); cpi(GT_p_, o.GT_p_); cpi(GT_i_, o.GT_i_); cpi(G_p_, o.G_p_); cpi(G_i_, o.G_i_); cpi(G_src_, o.G_src_);
     cpi(long_Pf_, o.long_Pf_); cpi(long_AT_, o.long_AT_); cpi(long_A_, o.long_A_); cpi(long_GT_, o.long_GT_); cpi(long_G_, o.long_G_);
     for (int q = 0; q < 5; ++q) nlong_[q] = o.nlong_[q];

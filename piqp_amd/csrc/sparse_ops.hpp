@@ -25,9 +25,10 @@ inline void upload_vec(DBuf<T>& d, const std::vector<T>& h, hipStream_t st)
 
 class CscOperators {
 public:
-    // patterns (host CSC of P_utri n x n, AT n x p, GT n x m) + values; synchronises `st`
+    // patterns (host CSC of P_utri n x n, AT n x p, GT n x m) + values (host or device arrays per d->mem); synchronises `st`
     void init(const pq_sparse_data* d, hipStream_t st);
-    // values only, identical sparsity (solver.hpp:325,341,356); synchronises `st`
+    // values only, identical sparsity (solver.hpp:325,341,356), host or device arrays per d->mem -- device values move device-to-device, the index arrays are not
+    // read at all; synchronises `st`
     void upload_values(const pq_sparse_data* d, hipStream_t st);
     void clone_from(const CscOperators& o, hipStream_t st);
 
@@ -91,7 +92,7 @@ public:
 private:
     int n_ = 0, p_ = 0, m_ = 0, nzP_ = 0, nzA_ = 0, nzG_ = 0, nzPf_ = 0;
     DBuf<double> P_x_, Pf_x_, AT_x_, A_x_, GT_x_, G_x_, Pdiag_;
-    DBuf<int> Pf_p_, Pf_i_, Pf_src_, AT_p_, AT_i_, A_p_, A_i_, A_src_, GT_p_, GT_i_, G_p_, G_i_, G_src_;
+    DBuf<int> Pf_p_, Pf_i_, Pf_src_, Pdiag_src_, AT_p_, AT_i_, A_p_, A_i_, A_src_, GT_p_, GT_i_, G_p_, G_i_, G_src_;
     DBuf<int> long_Pf_, long_AT_, long_A_, long_GT_, long_G_;  // columns with more than SPMV_LONG_COL entries, per copy
     int nlong_[5] = {0, 0, 0, 0, 0};
     bool ref_order_ = false;

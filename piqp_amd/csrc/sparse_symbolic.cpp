@@ -530,9 +530,10 @@ void analyse_kkt_pattern(const pq_sparse_data* d, int mode, Symbolic& S)
     const int N = n + (eq ? 0 : p) + (ineq ? 0 : m);
     S.n = n; S.p = p; S.m = m; S.N = N; S.mode = mode;
     static const int zero_ptr[1] = {0};
-    const int* Pp = d->P_colptr; const int* Pi = d->P_rowind; const double* Px = d->P_val;
-    const int* Atp = p ? d->AT_colptr : zero_ptr; const int* Ati = d->AT_rowind; const double* Atx = d->AT_val;
-    const int* Gtp = m ? d->GT_colptr : zero_ptr; const int* Gti = d->GT_rowind; const double* Gtx = d->GT_val;
+    // (patterns only: the value arrays of `d` may be device memory, pq_sparse_data.mem, and are not touched here)
+    const int* Pp = d->P_colptr; const int* Pi = d->P_rowind;
+    const int* Atp = p ? d->AT_colptr : zero_ptr; const int* Ati = d->AT_rowind;
+    const int* Gtp = m ? d->GT_colptr : zero_ptr; const int* Gti = d->GT_rowind;
     const int nzP = Pp[n], nzA = p ? Atp[p] : 0, nzG = m ? Gtp[m] : 0;
     if (eq) gram_structure(n, p, Atp, Ati, S.gramA); else S.gramA = Symbolic::Gram();
     if (ineq) gram_structure(n, m, Gtp, Gti, S.gramG); else S.gramG = Symbolic::Gram();
@@ -541,7 +542,7 @@ void analyse_kkt_pattern(const pq_sparse_data* d, int mode, Symbolic& S)
     // (kkt_{eq,ineq,all}_eliminated.hpp create_kkt_matrix; kkt_full.hpp:39-170 when nothing is eliminated); then one column
     // per kept constraint: [AT col; -delta] and [GT col; -z_reg]
     S.Kp.assign(N + 1, 0);
-    S.Ki.clear(); S.Kx.clear();
+    S.Ki.clear();
     S.P_utri_to_Ki.assign(nzP, 0); S.AT_to_Ki.assign(eq ? 0 : nzA, 0); S.GT_to_Ki.assign(ineq ? 0 : nzG, 0);
     S.gramA_to_Ki.assign(eq ? S.gramA.rowind.size() : 0, 0); S.gramG_to_Ki.assign(ineq ? S.gramG.rowind.size() : 0, 0);
     for (int j = 0; j < n; ++j) {
@@ -557,27 +558,26 @@ void analyse_kkt_pattern(const pq_sparse_data* d, int mode, Symbolic& S)
             if (!diag_done) r = std::min(r, j);
             if (r > n) break;
             const int at = (int)S.Ki.size();
-            double v = 0.0;
-            if (a < ae && Pi[a] == r) { v = Px[a]; S.P_utri_to_Ki[a++] = at; }
+            if (a < ae && Pi[a] == r) S.P_utri_to_Ki[a++] = at;
             if (b < be && S.gramA.rowind[b] == r) S.gramA_to_Ki[b++] = at;
             if (c < ce && S.gramG.rowind[c] == r) S.gramG_to_Ki[c++] = at;
             if (r == j) diag_done = true;
             if (r > j) throw std::runtime_error("symbolic: P is not upper triangular");
-            S.Ki.push_back(r); S.Kx.push_back(v);
+            S.Ki.push_back(r);
         }
         S.Kp[j + 1] = (int)S.Ki.size();
     }
     int jk = n;
     if (!eq)
         for (int j = 0; j < p; ++j, ++jk) {
-            for (int q = Atp[j]; q < Atp[j + 1]; ++q) { S.AT_to_Ki[q] = (int)S.Ki.size(); S.Ki.push_back(Ati[q]); S.Kx.push_back(Atx[q]); }
-            S.Ki.push_back(jk); S.Kx.push_back(0.0);
+            for (int q = Atp[j]; q < Atp[j + 1]; ++q) { S.AT_to_Ki[q] = (int)S.Ki.size(); S.Ki.push_back(Ati[q]); }
+            S.Ki.push_back(jk);
             S.Kp[jk + 1] = (int)S.Ki.size();
         }
     if (!ineq)
         for (int j = 0; j < m; ++j, ++jk) {
-            for (int q = Gtp[j]; q < Gtp[j + 1]; ++q) { S.GT_to_Ki[q] = (int)S.Ki.size(); S.Ki.push_back(Gti[q]); S.Kx.push_back(Gtx[q]); }
-            S.Ki.push_back(jk); S.Kx.push_back(0.0);
+            for (int q = Gtp[j]; q < Gtp[j + 1]; ++q) { S.GT_to_Ki[q] = (int)S.Ki.size(); S.Ki.push_back(Gti[q]); }
+            S.Ki.push_back(jk);
             S.Kp[jk + 1] = (int)S.Ki.size();
         }
 

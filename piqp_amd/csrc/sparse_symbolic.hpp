@@ -38,8 +38,7 @@ struct Symbolic {
     } gramA, gramG;
     IVec gramA_to_Ki, gramG_to_Ki;
     // K (upper, diagonal last in every column) and the value maps of kkt_full.hpp
-    IVec Kp, Ki;
-    DVec Kx;
+    IVec Kp, Ki;  // (pattern only: the values never come to the host, they may live in device memory)
     IVec P_utri_to_Ki, AT_to_Ki, GT_to_Ki;
     // ordering: P[new] = old, P_inv[old] = new (AMD composed with the etree postorder)
     IVec P, P_inv;

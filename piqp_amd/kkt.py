@@ -244,15 +244,43 @@ class SparseData(Data):
     def disable_inf_constraints(self):
         both = (self.h_l <= -PIQP_INF) & (self.h_u >= PIQP_INF)
         if both.any():
+            self._device = None  # (device copies of the values, if any, are stale now)
             for i in np.nonzero(both)[0]:
                 self.GT.data[self.GT.indptr[i]:self.GT.indptr[i + 1]] = 0.0
             self.h_l[both] = -1.0
             self.h_u[both] = 1.0
             self.set_h_l(self.h_l.copy()); self.set_h_u(self.h_u.copy())
 
+    _device = None
+
+    def to_device(self, device=0):
+        """descriptor() from now on hands out the VALUE arrays (P_utri, AT, GT data and x_b_scaling, as they are now) as torch CUDA tensors on GPU `device`
+        with mem = MEM_DEVICE; the index arrays stay numpy (pq_sparse_data: host indices, device values).  host() goes back."""
+        import torch
+        self._device = [torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(f"cuda:{device}")
+                        for a in (self.P_utri.data, self.AT.data, self.GT.data, self.x_b_scaling)]
+        sync_current_stream(device)
+        return self
+
+    def host(self):
+        self._device = None
+        return self
+
     def descriptor(self):
         d = _lib.SparseData()
         d.n, d.p, d.m = self.n, self.p, self.m
+        if self._device is not None:
+            k = []
+            for M in (self.P_utri, self.AT, self.GT):
+                k += [_i32(M.indptr), _i32(M.indices)]
+            k += [_i32(self.h_l_idx), _i32(self.h_u_idx), _i32(self.x_l_idx), _i32(self.x_u_idx)]
+            self._keep = k + list(self._device)
+            (d.P_colptr, d.P_rowind, d.AT_colptr, d.AT_rowind, d.GT_colptr, d.GT_rowind) = (a.ctypes.data for a in k[:6])
+            d.P_val, d.AT_val, d.GT_val, d.x_b_scaling = (t.data_ptr() for t in self._device)
+            d.n_h_l, d.n_h_u, d.n_x_l, d.n_x_u = self.n_h_l, self.n_h_u, self.n_x_l, self.n_x_u
+            d.h_l_idx, d.h_u_idx, d.x_l_idx, d.x_u_idx = (a.ctypes.data for a in k[6:10])
+            d.mem = MEM_DEVICE
+            return d
         k = []
         for M in (self.P_utri, self.AT, self.GT):
             k += [_i32(M.indptr), _i32(M.indices), np.ascontiguousarray(M.data, dtype=np.float64)]
@@ -630,6 +658,7 @@ class SparseSolver(DenseSolver):
 
     @staticmethod
     def _csc(M):
+        """sorted CSC of a scipy matrix as [indptr, indices, data] (int32 / int32 / float64); None -> three Nones"""
         import scipy.sparse as sp
         if M is None:
             return [None, None, None]
@@ -637,13 +666,105 @@ class SparseSolver(DenseSolver):
         M.sort_indices()
         return [np.ascontiguousarray(M.indptr, dtype=np.int32), np.ascontiguousarray(M.indices, dtype=np.int32), np.ascontiguousarray(M.data, dtype=np.float64)]
 
+    # ---- values in GPU memory (pq_solver_*_sparse_mem): a matrix is (pattern, values) at setup, a bare 1-D CUDA tensor at update ----
+    _nnz = None  # nonzeros of P, A, G as given at setup
+
+    def clone(self):
+        s = super().clone()
+        s._nnz = None if self._nnz is None else dict(self._nnz)
+        return s
+
+    @staticmethod
+    def _split(name, M):
+        """(pattern, values) for a matrix argument: a pair as given, else (M, None) -- the values are then the pattern's own.  A torch tensor where a scipy
+        pattern is meant is refused (a bare tensor of values is an update argument, and only as GPU memory)."""
+        if isinstance(M, tuple):
+            if len(M) != 2:
+                raise TypeError(f"{name}: a sparse matrix with separate values is a pair (pattern, values)")
+            M, v = M
+        else:
+            v = None
+        if M is not None and _is_torch(M):
+            raise TypeError(f"{name}: a torch tensor where a scipy sparse pattern is meant")
+        return M, v
+
+    @staticmethod
+    def _with_values(name, M, v):
+        """host path: the scipy matrix with pattern M and values v (numpy, in the order of M's sorted CSC); v None -> M itself"""
+        if M is None or v is None:
+            return M
+        import scipy.sparse as sp
+        if _is_torch(v):
+            raise TypeError(f"{name}: a CPU torch tensor beside GPU data; pass a numpy array (moved to the GPU for you) or a CUDA tensor")
+        M = sp.csc_matrix(M, copy=True)
+        M.sort_indices()
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        if v.shape != (M.nnz,):
+            raise ValueError(f"{name}: shape {v.shape}, expected {(M.nnz,)}")
+        M.data = v.copy()
+        return M
+
+    def _device_values(self, mats, vecs, nnz, n, p, m):
+        """every value array and vector as a CUDA tensor (checked; numpy ones moved), torch's current stream drained"""
+        args = dict(mats)
+        args.update(vecs)
+        shapes = dict(P=(nnz["P"],), A=(nnz["A"],), G=(nnz["G"],), c=(n,), b=(p,), h_l=(m,), h_u=(m,), x_l=(n,), x_u=(n,))
+        for k, a in args.items():  # every argument is checked before the first one is moved
+            if a is None:
+                continue
+            if _is_torch(a):
+                check_device_tensor(k, a, shapes[k], self.device)
+            elif np.shape(a) != tuple(shapes[k]):
+                raise ValueError(f"{k}: shape {np.shape(a)}, expected {tuple(shapes[k])}")
+        keep, _ = to_device_args(args, shapes, self.device)
+        sync_current_stream(self.device)
+        return keep
+
+    def _host_args(self, P, c, A, b, G, h_l, h_u, x_l, x_u):
+        return self._csc(P) + [self._vec(c)] + self._csc(A) + [self._vec(b)] + self._csc(G) + [self._vec(h_l), self._vec(h_u), self._vec(x_l), self._vec(x_u)]
+
     def setup(self, P, c, A=None, b=None, G=None, h_l=None, h_u=None, x_l=None, x_u=None):
+        """P, A, G: scipy sparse matrices, or pairs (pattern, values) with `values` a 1-D float64 array / torch CUDA tensor of pattern.nnz entries in the order
+        of the pattern's sorted CSC.  Vectors: numpy arrays or torch CUDA tensors.  With any CUDA tensor among the arguments the values stay on the GPU
+        (pq_solver_setup_sparse_mem; numpy arguments beside them are moved there)."""
+        (P, Pv), (A, Av), (G, Gv) = self._split("P", P), self._split("A", A), self._split("G", G)
         n = P.shape[0]
         p = 0 if A is None else A.shape[0]
         m = 0 if G is None else G.shape[0]
-        keep = self._csc(P) + [self._vec(c)] + self._csc(A) + [self._vec(b)] + self._csc(G) + [self._vec(h_l), self._vec(h_u), self._vec(x_l), self._vec(x_u)]
-        return bool(check(self.L.pq_solver_setup_sparse(self.h, n, p, m, *[_ptr(a) for a in keep]), "setup"))
+        vecs = dict(c=c, b=b, h_l=h_l, h_u=h_u, x_l=x_l, x_u=x_u)
+        if not device_call((Pv, Av, Gv) + tuple(vecs.values())):
+            keep = self._host_args(self._with_values("P", P, Pv), c, self._with_values("A", A, Av), b, self._with_values("G", G, Gv), h_l, h_u, x_l, x_u)
+            self._nnz = {k: (0 if keep[i] is None else len(keep[i])) for k, i in (("P", 1), ("A", 5), ("G", 9))}  # (what a later device-mode update reads)
+            return bool(check(self.L.pq_solver_setup_sparse(self.h, n, p, m, *[_ptr(a) for a in keep]), "setup"))
+        pat = {k: (None if M is None else self._csc(M)) for k, M in (("P", P), ("A", A), ("G", G))}
+        nnz = self._nnz = {k: (0 if v is None else len(v[1])) for k, v in pat.items()}
+        mats = {k: (None if pat[k] is None else (v if v is not None else pat[k][2])) for k, v in (("P", Pv), ("A", Av), ("G", Gv))}
+        keep = self._device_values(mats, vecs, nnz, n, p, m)
+        idx = lambda k: [None, None] if pat[k] is None else pat[k][:2]
+        a = idx("P") + [keep["P"], keep["c"]] + idx("A") + [keep["A"], keep["b"]] + idx("G") + [keep["G"], keep["h_l"], keep["h_u"], keep["x_l"], keep["x_u"]]
+        return bool(check(self.L.pq_solver_setup_sparse_mem(self.h, n, p, m, *[_ptr(x) for x in a], MEM_DEVICE), "setup"))
 
     def update(self, P=None, c=None, A=None, b=None, G=None, h_l=None, h_u=None, x_l=None, x_u=None):
-        keep = self._csc(P) + [self._vec(c)] + self._csc(A) + [self._vec(b)] + self._csc(G) + [self._vec(h_l), self._vec(h_u), self._vec(x_l), self._vec(x_u)]
-        return bool(check(self.L.pq_solver_update_sparse(self.h, *[_ptr(a) for a in keep]), "update"))
+        """as setup; a matrix may also be a bare 1-D float64 CUDA tensor: its values in the CSC order given at setup (identical sparsity is required anyway)"""
+        vecs = dict(c=c, b=b, h_l=h_l, h_u=h_u, x_l=x_l, x_u=x_u)
+        mats = dict(P=P, A=A, G=G)
+        bare = {k: M for k, M in mats.items() if M is not None and _is_torch(M)}  # bare tensors of values: GPU memory only
+        if not device_call(tuple(bare.values()) + tuple(v for M in mats.values() if isinstance(M, tuple) for v in M[1:]) + tuple(vecs.values())):
+            for k, M in bare.items():
+                raise TypeError(f"{k}: a CPU torch tensor beside GPU data; pass a numpy array (moved to the GPU for you) or a CUDA tensor")
+            full = {k: self._with_values(k, *self._split(k, M)) for k, M in mats.items()}
+            keep = self._host_args(full["P"], c, full["A"], b, full["G"], h_l, h_u, x_l, x_u)
+            return bool(check(self.L.pq_solver_update_sparse(self.h, *[_ptr(a) for a in keep]), "update"))
+        vals = {}
+        for k, M in mats.items():
+            if M is None or k in bare:
+                vals[k] = M
+            else:
+                pat, v = self._split(k, M)
+                vals[k] = v if v is not None else self._csc(pat)[2]
+        n, p, m = self._dims()
+        if self._nnz is None:
+            raise RuntimeError("update from GPU memory: this object never saw the setup, so the lengths of the value arrays are unknown")
+        keep = self._device_values(vals, vecs, self._nnz, n, p, m)
+        a = [None, None, keep["P"], keep["c"], None, None, keep["A"], keep["b"], None, None, keep["G"], keep["h_l"], keep["h_u"], keep["x_l"], keep["x_u"]]
+        return bool(check(self.L.pq_solver_update_sparse_mem(self.h, *[_ptr(x) for x in a], MEM_DEVICE), "update"))
