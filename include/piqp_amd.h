@@ -533,6 +533,34 @@ int pq_dense_factor_matrix(pq_dense_factor *f, double *out_host, int ldo);
  * factorisation + status read-back), both in ms */
 int pq_dense_factor_last_ms(const pq_dense_factor *f, double out2[2]);
 
+/* ----- the same two classes for a BATCH of small matrices (n <= PQ_DENSE_FACTOR_BATCH_MAX_N), one launch per compute() and per solve ----- */
+/* Every matrix of the batch is factored by one workgroup (n >= 32) or one wave (n < 32) with the matrix resident in LDS, in the reference's own order of
+ * floating-point operations (csrc/dense_factor_batch.hip): per matrix the factor, the status and every solve are those of the CPU oracle's restatement of the
+ * two classes (oracle/orc_dense.c), bit for bit.  The instances share nothing: a failing matrix ends alone. */
+enum { PQ_DENSE_FACTOR_BATCH_MAX_N = 128 };
+typedef struct pq_dense_factor_batch pq_dense_factor_batch;
+/* ldlt_no_pivot.hpp:126-131 (preallocating constructor), `batch` times: everything the handle will ever need, the staging of host-mode calls (up to max_nrhs
+ * right-hand sides per matrix) included -- pq_debug_alloc_count() does not move after it.  Arguments are checked before the device is touched: PQ_ERR_UNSUPPORTED
+ * for n > PQ_DENSE_FACTOR_BATCH_MAX_N, PQ_ERR_INVALID for batch < 1, n < 1, max_nrhs < 1, a kind that is neither PQ_DENSE_CHOLESKY nor PQ_DENSE_LDLT_NO_PIVOT, an
+ * uplo that is neither PQ_LOWER nor PQ_UPPER, a null out. */
+int pq_dense_factor_batch_create(pq_dense_factor_batch **out, int device, int batch, int n, int kind, int uplo, int max_nrhs);
+void pq_dense_factor_batch_destroy(pq_dense_factor_batch *f);
+/* compute(), ldlt_no_pivot.hpp:393-423 / Eigen::LLT::compute, per matrix: matrix i is column-major at A + i * stride (leading dimension lda >= n,
+ * stride >= lda * n doubles; host or device memory per `mem`); only its `uplo` triangle is read.  Returns the number of matrices that ended with Eigen::Success
+ * (negative = PQ_ERR_*), when the factors are complete. */
+int pq_dense_factor_batch_compute(pq_dense_factor_batch *f, const double *A, int lda, long long stride, int mem);
+/* info(), ldlt_no_pivot.hpp:231, per matrix: info_host[batch] = 0 (Eigen::Success) / 1 (Eigen::NumericalIssue); first_bad_col_host[batch] (may be NULL) = -1 or
+ * the column at which the routine gives up (ldlt_no_pivot.hpp:307 an exact zero pivot; Eigen LLT.h unblocked: a pivot that is not positive) */
+int pq_dense_factor_batch_info(const pq_dense_factor_batch *f, int *info_host, int *first_bad_col_host);
+/* solveInPlace(MatrixBase&), ldlt_no_pivot.hpp:464-470 (the sweeps of :432-450 per column) / Eigen::LLT::solveInPlace: matrix i's right-hand sides are n x nrhs
+ * column-major at X + i * stride, leading dimension ldx >= n, stride >= ldx * nrhs; nrhs <= max_nrhs.  The block of a matrix whose factorisation failed is left as
+ * it was.  PQ_ERR_INVALID before the first compute(). */
+int pq_dense_factor_batch_solve_in_place(pq_dense_factor_batch *f, double *X, int ldx, int nrhs, long long stride, int mem);
+/* matrixLDLT() (ldlt_no_pivot.hpp:217) / matrixLLT() of one instance, as pq_dense_factor_matrix: the `uplo` triangle of out_host (column-major, ldo >= n) */
+int pq_dense_factor_batch_matrix(pq_dense_factor_batch *f, int instance, double *out_host, int ldo);
+/* out2[0]: device time of the factorisation launch of the last compute() (hipEvents), out2[1]: wall time of the whole call, both in ms */
+int pq_dense_factor_batch_last_ms(const pq_dense_factor_batch *f, double out2[2]);
+
 /* ===================== small utilities used by the measurement harness ===================== */
 /* fp64 MFMA / HBM micro-benchmarks on `device` (used once by bench.py to report measured peaks) */
 /* number of device / pinned-host allocations the library has made in this process.  Contract (the reference's tests assert allocation-free

@@ -12,5 +12,5 @@ from .kkt import DENSE_CHOLESKY_EXACT, SPARSE_LDLT_EXACT, SPARSE_LDLT_MULTIFRONT
 SPARSE_MULTISTAGE = 5
 MultistageKKT = DenseKKT
 from .batch import BatchSparseSolver  # noqa: E402,F401
-from .factor import LLT, LDLTNoPivot, LOWER, UPPER  # noqa: E402,F401
+from .factor import LLT, LDLTNoPivot, BatchLLT, BatchLDLTNoPivot, LOWER, UPPER  # noqa: E402,F401
 from .kkt import COL_MAJOR, MEM_DEVICE, MEM_HOST, ROW_MAJOR, tensor_layout  # noqa: E402,F401

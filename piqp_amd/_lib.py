@@ -85,6 +85,8 @@ SYMBOLS = [
     "pq_batch_dims", "pq_batch_block_info", "pq_batch_get_profile", "pq_batch_last_kernel_ms", "pq_batch_set_start_order",
     "pq_batch_kkt_factor", "pq_batch_kkt_solve", "pq_batch_ldlt_factor",
     "pq_dense_factor_create", "pq_dense_factor_destroy", "pq_dense_factor_compute", "pq_dense_factor_info", "pq_dense_factor_solve_in_place", "pq_dense_factor_matrix", "pq_dense_factor_last_ms",
+    "pq_dense_factor_batch_create", "pq_dense_factor_batch_destroy", "pq_dense_factor_batch_compute", "pq_dense_factor_batch_info", "pq_dense_factor_batch_solve_in_place",
+    "pq_dense_factor_batch_matrix", "pq_dense_factor_batch_last_ms",
     "pq_debug_alloc_count", "pq_debug_chol_plan", "pq_debug_syrk_plan", "pq_debug_device_sqrt", "pq_kkt_set_exchange_norm", "pq_kkt_sharded_calls", "pq_kkt_sharded_solve_calls", "pq_solver_sharded_solve_calls", "pq_solver_set_exchange_norm", "pq_solver_sharded_calls", "pq_microbench_mfma_f64", "pq_microbench_hbm_copy", "pq_microbench_potrf_block", "pq_debug_potrf_block", "pq_rccl_unique_id", "pq_kkt_set_comm_rccl", "pq_solver_set_comm_rccl", "pq_kkt_native_exchange_calls", "pq_kkt_min_abs_pivot", "pq_solver_native_exchange_calls",
     "pq_solver_setup_sparse_mem", "pq_solver_update_sparse_mem", "pq_debug_sparse_ingest_maps",
     "pq_solver_setup_dense_mem", "pq_solver_update_dense_mem", "pq_solver_get_result_mem", "pq_solver_last_ingest", "pq_batch_update_mem", "pq_batch_update_data_mem",
@@ -169,6 +171,14 @@ def load():
     L.pq_dense_factor_solve_in_place.argtypes = [vp, vp, C.c_int]
     L.pq_dense_factor_matrix.argtypes = [vp, vp, C.c_int]
     L.pq_dense_factor_last_ms.argtypes = [vp, vp]
+    L.pq_dense_factor_batch_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.pq_dense_factor_batch_destroy.argtypes = [vp]
+    L.pq_dense_factor_batch_destroy.restype = None
+    L.pq_dense_factor_batch_compute.argtypes = [vp, vp, C.c_int, C.c_longlong, C.c_int]
+    L.pq_dense_factor_batch_info.argtypes = [vp, vp, vp]
+    L.pq_dense_factor_batch_solve_in_place.argtypes = [vp, vp, C.c_int, C.c_int, C.c_longlong, C.c_int]
+    L.pq_dense_factor_batch_matrix.argtypes = [vp, C.c_int, vp, C.c_int]
+    L.pq_dense_factor_batch_last_ms.argtypes = [vp, vp]
     L.pq_kkt_set_profiling.argtypes = [vp, C.c_int]
     L.pq_kkt_get_profile.argtypes = [vp, C.c_int, _dp, _ip]
     L.pq_kktsys_create_dense.argtypes = [C.POINTER(vp), C.POINTER(DenseData), C.POINTER(Settings), C.c_int]
