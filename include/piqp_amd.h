@@ -561,6 +561,54 @@ int pq_dense_factor_batch_matrix(pq_dense_factor_batch *f, int instance, double 
 /* out2[0]: device time of the factorisation launch of the last compute() (hipEvents), out2[1]: wall time of the whole call, both in ms */
 int pq_dense_factor_batch_last_ms(const pq_dense_factor_batch *f, double out2[2]);
 
+/* ===================== the dense KKT backend for a BATCH of small QPs (n <= PQ_KKT_BATCH_DENSE_MAX_N) ===================== */
+/* `batch` independent instances of piqp::dense::KKT (dense/kkt.hpp:39-160) that share n, p, m and the factorisation kind: kkt_solver = PQ_DENSE_CHOLESKY
+ * (Eigen::LLT) or PQ_DENSE_LDLT_NO_PIVOT, both in the reference's own order of floating-point operations (csrc/dense_kkt_batch.hip).  Per instance the assembled
+ * matrix P + diag(x_reg) + AT AT'/delta + GT diag(1/z_reg) GT', its factor, the success flag, every solve and the three mat-vec evaluators are those of the CPU
+ * oracle's dense backend (oracle/orc_dense.c) bit for bit.  The instances share nothing: a failing instance ends alone.  n <= 128 because the n x n square of an
+ * instance lives in LDS; p >= 0 and m >= 0 are not limited (AT and GT stay in global memory).
+ * Data layout: pq_dense_data's, `batch` times, contiguous: P_utri[i] column-major n x n at P_utri + i n n (only its upper triangle is read: NaN in the other one is
+ * harmless), AT[i] column-major n x p at AT + i n p, GT[i] column-major n x m at GT + i n m.  Vectors are [batch][len], per-instance scalars (delta, alpha*) [batch].
+ * mem (pq_mem) says where EVERY array argument of that call lives; ordering contract: see pq_solver_setup_dense_mem.  The handle keeps its own device copy of the
+ * data (device mode: copied device-to-device, nothing crosses the link). */
+enum { PQ_KKT_BATCH_DENSE_MAX_N = 128 };
+typedef struct pq_kkt_batch pq_kkt_batch;
+/* Arguments are checked before the device is touched: PQ_ERR_UNSUPPORTED for n > PQ_KKT_BATCH_DENSE_MAX_N; PQ_ERR_INVALID for batch < 1, n < 1, p < 0, m < 0, a
+ * kkt_solver other than the two, a mem other than the two, a null out or P_utri, a null AT with p > 0 or a null GT with m > 0.  Allocates everything the handle will
+ * ever need (the staging of host-mode calls included: pq_debug_alloc_count() moves in no later call except pq_kkt_batch_clone) and computes AT_A[i] = AT[i] AT[i]'
+ * (dense/kkt.hpp:53) when p > 0. */
+int pq_kkt_batch_create_dense(pq_kkt_batch **out, int device, int batch, int n, int p, int m, int kkt_solver, const double *P_utri, const double *AT,
+                              const double *GT, int mem);
+void pq_kkt_batch_destroy(pq_kkt_batch *k);
+int pq_kkt_batch_clone(const pq_kkt_batch *k, pq_kkt_batch **out);
+int pq_kkt_batch_dims(const pq_kkt_batch *k, int *batch, int *n, int *p, int *m);
+/* dense/kkt.hpp:62-71, per instance.  options: PQ_KKT_UPDATE_* mask; a flagged matrix is re-read from its argument (null there: PQ_ERR_INVALID, the handle stays as
+ * it was), an unflagged one is ignored and its pointer may be null; PQ_KKT_UPDATE_A recomputes AT_A. */
+int pq_kkt_batch_update_data_dense(pq_kkt_batch *k, const double *P_utri, const double *AT, const double *GT, int options, int mem);
+/* dense/kkt.hpp:73-84, per instance, ONE launch for the batch: z_reg_inv = 1 / z_reg, the assembly straight into the LDS square, its factorisation.  delta[batch],
+ * x_reg[batch][n], z_reg[batch][m].  Returns the number of instances that factored (negative = PQ_ERR_*), when the factors are complete. */
+int pq_kkt_batch_update_scalings_and_factor(pq_kkt_batch *k, const double *delta, const double *x_reg, const double *z_reg, int mem);
+/* of the last factorisation, per instance: ok_host[batch] = 1 / 0, first_bad_col_host[batch] (may be NULL) = -1 or the failing column (LLT: a pivot that is not
+ * positive; LDLT: an exact zero only).  The stored factor of a failed instance is unspecified. */
+int pq_kkt_batch_info(const pq_kkt_batch *k, int *ok_host, int *first_bad_col_host);
+/* dense/kkt.hpp:86-105, per instance, one launch.  The lhs_* blocks of an instance whose last factorisation failed are left untouched.  Outputs must not overlap
+ * inputs.  rhs_y / lhs_y (rhs_z / lhs_z) may be null when p == 0 (m == 0).  PQ_ERR_INVALID before the first factorisation. */
+int pq_kkt_batch_solve(pq_kkt_batch *k, const double *rhs_x, const double *rhs_y, const double *rhs_z, double *lhs_x, double *lhs_y, double *lhs_z, int mem);
+/* dense/kkt.hpp:108-132, per instance, one launch each.  With p == 0 (resp. m == 0) zn is not written and zt is all +0.0. */
+int pq_kkt_batch_eval_P_x(pq_kkt_batch *k, const double *alpha, const double *x, double *z, int mem);
+int pq_kkt_batch_eval_A_xn_and_AT_xt(pq_kkt_batch *k, const double *alpha_n, const double *alpha_t, const double *xn, const double *xt, double *zn, double *zt,
+                                     int mem);
+int pq_kkt_batch_eval_G_xn_and_GT_xt(pq_kkt_batch *k, const double *alpha_n, const double *alpha_t, const double *xn, const double *xt, double *zn, double *zt,
+                                     int mem);
+/* test hooks, out_host n x n column-major, lower triangle meaningful.  internal_kkt_mat RECOMPUTES the matrix of one instance from the stored data and the stored
+ * scalings of the last factorisation (an assemble-only instantiation of the factorisation kernel's code: the hot path never writes the assembled matrix to memory);
+ * internal_factor copies the stored factor. */
+int pq_kkt_batch_internal_kkt_mat(pq_kkt_batch *k, int instance, double *out_host);
+int pq_kkt_batch_internal_factor(pq_kkt_batch *k, int instance, double *out_host);
+/* out3[0]: device time of the last factorisation launch, out3[1]: device time of the last solve launch (hipEvents), out3[2]: wall time of the last
+ * pq_kkt_batch_update_scalings_and_factor call, all in ms */
+int pq_kkt_batch_last_ms(const pq_kkt_batch *k, double out3[3]);
+
 /* ===================== small utilities used by the measurement harness ===================== */
 /* fp64 MFMA / HBM micro-benchmarks on `device` (used once by bench.py to report measured peaks) */
 /* number of device / pinned-host allocations the library has made in this process.  Contract (the reference's tests assert allocation-free

@@ -7,7 +7,7 @@
 // the batch); no matrix instruction is used.  dense_exact.hip replays orc_llt_compute across workgroups (left-looking, one launch per panel); here one workgroup
 // owns the whole matrix, so the replay is right-looking like the oracle itself, block by block, with workgroup barriers between the phases.
 //
-//   oracle (orc_dense.c)                      here (k_dfb_factor; L(i, j) is the LDS copy, column-major, leading dimension n | 1)
+//   oracle (orc_dense.c)                      here (k_dfb_factor -> dfb_factor_in_lds, dense_factor_batch_device.hpp; L(i, j) is the LDS copy, column-major, leading dimension n | 1)
 //   llt_unblocked                             column c of the diagonal block, thread t owns row k + t: the pivot thread  s = 0, s = fma(v, v, s) for ascending j,
 //                                             x = a_cc - s (skipped for the block's first column), fail on !(x > 0), sqrt;  every row below  dst = fma(-L(i, j), L(c, j), dst)
 //                                             for ascending j, after the barrier dst / x
@@ -34,26 +34,14 @@
 #include <memory>
 
 #include "common.hpp"
+#include "dense_factor_batch_device.hpp"
 
 namespace pq {
 
 namespace {
 
-constexpr int DFB_THREADS = 256;
 constexpr int DFB_SOLVE_THREADS = 64;
 constexpr int DFB_NCH = 16;  // right-hand sides per workgroup of the solve
-
-// dense/ldlt_no_pivot.hpp:321-323 == Eigen LLT.h blocked()
-int dfb_block_size_rule(int size)
-{
-    int bs = size / 8;
-    bs = (bs / 16) * 16;
-    if (bs < 8) bs = 8;
-    if (bs > 128) bs = 128;
-    return bs;
-}
-
-inline int dfb_ld(int n) { return n | 1; }
 
 // KIND 0: Eigen::LLT, 1: LDLTNoPivot.  G: threads per matrix (256: one matrix per workgroup, 64: four).  width: n below 32 (unblocked), block_size_rule(n) above.
 // upper != 0: the matrix is read from -- and the factor written to -- the upper triangle, transposed on the way (ldlt_no_pivot.hpp:357-371: the Lower code on the
@@ -80,88 +68,7 @@ __global__ __launch_bounds__(DFB_THREADS) void k_dfb_factor(const double* __rest
         }
     }
     __syncthreads();
-    bool live = have;
-    for (int k = 0; k < n && (G != DFB_THREADS || live); k += width) {
-        const int bs = n - k < width ? n - k : width;
-        const int rs = n - k - bs;
-        // ---- the diagonal block, column by column: thread t owns row k + t
-        for (int kc = 0; kc < bs; ++kc) {
-            const int c = k + kc;
-            double v = 0.0;
-            if (live && t == kc) {
-                if (KIND == 0) {
-                    double x = a[c + c * ld];
-                    if (kc > 0) {
-                        double s = 0.0;
-                        for (int j = k; j < c; ++j) { const double w = a[c + j * ld]; s = fma(w, w, s); }
-                        x = x - s;
-                    }
-                    if (!(x > 0.0)) s_fail[g] = c;
-                    else a[c + c * ld] = sqrt(x);
-                } else {
-                    if (kc > 0) {
-                        double s = 0.0;
-                        for (int j = k; j < c; ++j) { const double w = a[c + j * ld]; const double tj = a[j + j * ld] * w; s = fma(w, tj, s); }
-                        a[c + c * ld] = a[c + c * ld] - s;
-                    }
-                    if (a[c + c * ld] == 0.0) s_fail[g] = c;
-                }
-            } else if (live && t > kc && t < bs) {
-                const int i = k + t;
-                v = a[i + c * ld];
-                if (KIND == 0) {
-                    for (int j = k; j < c; ++j) v = fma(-a[i + j * ld], a[c + j * ld], v);
-                } else {
-                    for (int j = k; j < c; ++j) { const double tj = a[j + j * ld] * a[c + j * ld]; v = fma(-a[i + j * ld], tj, v); }
-                }
-            }
-            __syncthreads();
-            live = have && s_fail[g] < 0;
-            if (G == DFB_THREADS && !live) break;  // (one matrix per workgroup: the same answer in every thread)
-            if (live && t > kc && t < bs) a[(k + t) + c * ld] = v / a[c + c * ld];
-            __syncthreads();
-        }
-        if (G == DFB_THREADS && !live) break;
-        if (rs <= 0) continue;
-        // ---- A21 <- A21 L11^-T (LLT) resp. A21 (L11^T unit-upper)^-1 D11^-1, and t = A21 D11: one thread per row
-        if (live)
-            for (int r = k + bs + t; r < n; r += G) {
-                for (int j = 0; j < bs; ++j) {
-                    double x = a[r + (k + j) * ld];
-                    for (int kk = 0; kk < j; ++kk) x = fma(-a[r + (k + kk) * ld], a[(k + j) + (k + kk) * ld], x);
-                    if (KIND == 0) x = x / a[(k + j) + (k + j) * ld];
-                    a[r + (k + j) * ld] = x;
-                }
-                if (KIND == 1)
-                    for (int j = 0; j < bs; ++j) {
-                        const double d = a[(k + j) + (k + j) * ld];
-                        const double dinv = 1.0 / d;
-                        const double col = a[r + (k + j) * ld] * dinv;
-                        a[r + (k + j) * ld] = col;
-                        a[(k + j) + r * ld] = col * d;  // t, in the upper triangle
-                    }
-            }
-        __syncthreads();
-        // ---- A22_L -= a A21^T: one row and four columns per thread
-        if (live) {
-            const int nq = (rs + 3) / 4;
-            for (int e = t; e < rs * nq; e += G) {
-                const int ii = e % rs, jq = (e / rs) * 4;
-                if (jq > ii) continue;
-                const int i = k + bs + ii;
-                int jc[4];
-                for (int q = 0; q < 4; ++q) jc[q] = k + bs + (jq + q <= ii ? jq + q : jq);
-                double acc[4] = {0.0, 0.0, 0.0, 0.0};
-                for (int kk = 0; kk < bs; ++kk) {
-                    const double av = KIND == 0 ? a[i + (k + kk) * ld] : a[(k + kk) + i * ld];
-                    for (int q = 0; q < 4; ++q) acc[q] = fma(av, 0.0 + a[jc[q] + (k + kk) * ld], acc[q]);  // (0 + b: the micro-kernel's broadcast)
-                }
-                for (int q = 0; q < 4; ++q)
-                    if (jq + q <= ii) a[i + jc[q] * ld] = a[i + jc[q] * ld] - acc[q];
-            }
-        }
-        __syncthreads();
-    }
+    const bool live = dfb_factor_in_lds<KIND, G>(a, n, ld, width, have, g, t, s_fail);
     if (!have) return;
     if (t == 0) { info[mat] = live ? 0 : 1; badcol[mat] = s_fail[g]; }
     if (!live) return;
