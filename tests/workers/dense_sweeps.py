@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
-"""Worker of tests/test_dense_gpu.py::test_sweeps_with_block_inverses_against_the_substitution_sweeps: one dense factorisation, five backend solves on the same
-handle with the sweep schedule PIQP_AMD_DEBUG selects; residual of each against the device's own factor in extended precision.
-   python tests/workers/dense_sweeps.py n kkt_solver tag"""
+"""Worker of the dense sweep tests: one dense factorisation, five backend solves on the same handle with the sweep schedule PIQP_AMD_DEBUG selects.
+   python tests/workers/dense_sweeps.py n kkt_solver tag [recipe]
+recipe "qp" (default; tests/test_dense_gpu.py::test_sweeps_with_block_inverses_against_the_substitution_sweeps): residual of each solve against the device's own
+factor in extended precision.
+recipe "lowrank" (tests/test_dense_factor_componentwise_gpu.py::test_sweeps_componentwise_with_a_schedule_switched_off): K = diag(d) + V V^T on a handle with
+p = m = 0, every solve held to |r_i| <= c s_i (tests/factor_bounds.py: SweepCheck), the fifth solve a bitwise repeat of the first; prints the verdict."""
 import json
 import os
 import sys
@@ -13,9 +16,19 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 
 import piqp_amd as hip
-from qp_gen import dense_strongly_convex_qp
 
 n, ks, tag = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3]
+recipe = sys.argv[4] if len(sys.argv) > 4 else "qp"
+
+if recipe == "lowrank":
+    import factor_bounds as fb
+    from factor_shapes import by_n
+    out = fb.run_sweeps(hip, by_n(n), ks, label=f"{n} kkt_solver {ks} [{tag}; PIQP_AMD_DEBUG={os.environ.get('PIQP_AMD_DEBUG', '')}]")
+    print("RESULT " + json.dumps(out), flush=True)
+    sys.exit(0)
+
+from qp_gen import dense_strongly_convex_qp
+
 q = dense_strongly_convex_qp(n, 0, n // 2, seed=7 + n, double_sided=True, exact_shift=False)
 k = hip.DenseKKT(hip.Data(**q), kkt_solver=ks)
 rng = np.random.default_rng(n)
