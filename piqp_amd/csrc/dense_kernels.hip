@@ -19,6 +19,7 @@
 #include <map>
 #include <mutex>
 #include <stdexcept>
+#include <type_traits>
 #include <utility>
 #include <vector>
 #include <cstdlib>
@@ -189,6 +190,58 @@ __device__ __forceinline__ void scale_tile(const double* __restrict__ w, int k0,
         if (NEG) s = -s;
         v[it].x *= s;
         v[it].y *= s;
+    }
+}
+
+// The K loop of syrk_lower_body: load_tile with the address arithmetic taken out.  `p` = M + r0 + k * ld is the wave's first column of the stage (k = k0 + wave,
+// uniform over the wave: scalar registers), `lane_off` = 16 * lane the lane's byte offset in a column, r = r0 + 2 * lane its first row.  The loads take p (plus
+// the uniform it * NT / 64 columns) as their scalar base and lane_off as their 32-bit vector offset; the caller advances p by BK * ld per stage.
+template <bool CHECK, int NT>
+__device__ __forceinline__ void load_tile_at(const double* p, int ld, int r, int k, int nrows, int kdim, unsigned lane_off, d2 (&v)[1024 / NT])
+{
+    typedef const __attribute__((address_space(1))) char* gbytes;
+    // (an empty statement that keeps the 32-bit offset a 32-bit value HERE: widened once outside the K loop it turns every load's address into a 64-bit
+    // vector add of its own; next to the load it is the load instruction's own offset operand)
+    asm volatile("" : "+v"(lane_off));
+#pragma unroll
+    for (int it = 0; it < 1024 / NT; ++it) {
+        gbytes q = (gbytes)(p + (size_t)(it * (NT / 64)) * ld) + lane_off;
+        if (!CHECK) {
+            v[it] = *reinterpret_cast<const __attribute__((address_space(1))) d2*>(q);
+        } else {
+            d2 t = {0.0, 0.0};
+            if (k + it * (NT / 64) < kdim) {
+                if (r < nrows) t.x = *reinterpret_cast<const __attribute__((address_space(1))) double*>(q);
+                if (r + 1 < nrows) t.y = *reinterpret_cast<const __attribute__((address_space(1))) double*>(q + 8);
+            }
+            v[it] = t;
+        }
+    }
+}
+
+// scale_tile in two halves: the weights of the wave's columns (uniform addresses) are requested with the operands, the multiplication waits until the stage is
+// stored to LDS.  The request is unconditional: a column past kdim reads the last weight (kdim >= 1), and apply_weights<true> gives it the zero of scale_tile.
+template <int NT>
+__device__ __forceinline__ void load_weights(const double* __restrict__ w, int k, int kdim, double (&s)[1024 / NT])
+{
+    // Vector loads (every lane the same address) on purpose.  Fetched once per wave with scalar loads they share the LDS counter: the first matrix operation
+    // of a stage, which waits for its LDS reads, then waits for the weights of the NEXT stage too.  The lane offset (zero) is hidden from the compiler, which
+    // would otherwise turn loads from a uniform address into scalar ones.
+    unsigned zero = 0;
+    asm volatile("" : "+v"(zero));
+#pragma unroll
+    for (int it = 0; it < 1024 / NT; ++it)  // (scalar base w + index, then the lane offset: the load's own two address operands)
+        s[it] = *reinterpret_cast<const __attribute__((address_space(1))) double*>((const __attribute__((address_space(1))) char*)(w + min(k + it * (NT / 64), kdim - 1)) + zero);
+}
+
+template <bool CHECK, int NT>
+__device__ __forceinline__ void apply_weights(const double (&s)[1024 / NT], int k, int kdim, d2 (&v)[1024 / NT])
+{
+#pragma unroll
+    for (int it = 0; it < 1024 / NT; ++it) {
+        const double sv = (!CHECK || k + it * (NT / 64) < kdim) ? s[it] : 0.0;
+        v[it].x *= sv;
+        v[it].y *= sv;
     }
 }
 
@@ -504,50 +557,78 @@ __device__ __forceinline__ void syrk_lower_body(const SyrkArgs& a, const int blo
     const int kt_per = (nkt_all + a.k_split - 1) / a.k_split;
     const int kt_begin = kslice * kt_per;
     const int nkt = max(0, min(nkt_all, kt_begin + kt_per) - kt_begin);
+    // The operand stream of the K loop.  A wave loads whole columns of a stage (column k0 + it * NT / 64 + wave, rows 2 * lane and 2 * lane + 1), so everything
+    // but the lane's row is uniform over the wave: the column pointers pa / pb and the weight index live in scalar registers, go from stage to stage by the
+    // uniform BK * ld with scalar adds (no 64-bit vector multiply-add per load and stage), and the lane adds only its byte offset.  A stage is REQUESTED (operand
+    // and weight loads issued) before the matrix operations of the stage in front of it and FINISHED (scaled by w, stored to LDS) behind them (request_stage / finish_stage below;
+    // tools/syrk_kloop_isa.py prints what the compiler made of it).  Same loads, same products fl(w_k * b), same K order as load_tile + scale_tile.
+    const int wv = __builtin_amdgcn_readfirstlane(wave);
+    const unsigned lane_off = 16u * (unsigned)lane;
+    const int ra = row0 + 2 * lane, rb = col0 + 2 * lane;
+    int kw = kt_begin * BK + wv;  // this wave's first column of the stage requested next
+    const double* pa = a.A + row0 + (size_t)kw * a.lda;
+    const double* pb = a.B + col0 + (size_t)kw * a.ldb;
+    const size_t stage_a = (size_t)BK * a.lda, stage_b = (size_t)BK * a.ldb;
+    // the 4 k-slices of the stage in LDS slot `cur`.  (Reading slice 0 in front of the next stage's request, so that its LDS reads travel while the loads are
+    // issued, was tried on an earlier form of this loop and was slower there: profiles/syrk_kloop_before_after.txt)
+    auto multiply_stage = [&](int cur) {
+        const double* Asb = As + cur * BK * LDS_LD + wr * SUBR + (lane & 15);
+        const double* Bsb = Bs + cur * BK * LDS_LD + wc * SUBC + (lane & 15);
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            const int kk = ks * 4 + (lane >> 4);
+            double af[MTR], bf[MTC];
+#pragma unroll
+            for (int q = 0; q < MTR; ++q) af[q] = Asb[kk * LDS_LD + q * 16];
+#pragma unroll
+            for (int q = 0; q < MTC; ++q) bf[q] = Bsb[kk * LDS_LD + q * 16];
+#pragma unroll
+            for (int x = 0; x < MTC; ++x)
+#pragma unroll
+                for (int y = 0; y < MTR; ++y)
+                    acc[x][y] = __builtin_amdgcn_mfma_f64_16x16x4f64(bf[x], af[y], acc[x][y], 0, 0, 0);
+        }
+    };
+    // Request and finish of a stage.  The weights are requested in ONE place behind the fast / checked branch of the operand loads, from an index clamped into
+    // [0, kdim), and the columns past kdim get their zero weight only in finish_stage: loaded inside the two branches, the weights met in a merge block whose
+    // register copies -- and their waits for every load of the stage -- the compiler put in front of the matrix operations.
     d2 va[1024 / NT], vb[1024 / NT];
+    double ws[1024 / NT];
+    const bool weighted = a.w != nullptr;
+    auto request_stage = [&]() {
+        if (edge || (kw - wv + BK > a.kdim)) {
+            load_tile_at<true, NT>(pa, a.lda, ra, kw, a.n, a.kdim, lane_off, va); load_tile_at<true, NT>(pb, a.ldb, rb, kw, a.n, a.kdim, lane_off, vb);
+        } else {
+            load_tile_at<false, NT>(pa, a.lda, ra, kw, a.n, a.kdim, lane_off, va); load_tile_at<false, NT>(pb, a.ldb, rb, kw, a.n, a.kdim, lane_off, vb);
+        }
+        if (weighted) load_weights<NT>(a.w, kw, a.kdim, ws);
+        kw += BK; pa += stage_a; pb += stage_b;
+    };
+    auto finish_stage = [&](int slot) {  // (kw is already the next stage's)
+        if (weighted) {
+            if (kw - wv > a.kdim) apply_weights<true, NT>(ws, kw - BK, a.kdim, vb);
+            else apply_weights<false, NT>(ws, kw - BK, a.kdim, vb);
+        }
+        store_tile<NT>(As + slot * BK * LDS_LD, tid, va);
+        store_tile<NT>(Bs + slot * BK * LDS_LD, tid, vb);
+    };
     if (nkt > 0) {
-        const int k0 = kt_begin * BK;
-        const bool chk = edge || (k0 + BK > a.kdim);
-        if (chk) { load_tile<true, NT>(a.A, a.lda, row0, k0, a.n, a.kdim, tid, va); load_tile<true, NT>(a.B, a.ldb, col0, k0, a.n, a.kdim, tid, vb); scale_tile<true, NT>(a.w, k0, a.kdim, tid, vb); }
-        else { load_tile<false, NT>(a.A, a.lda, row0, k0, a.n, a.kdim, tid, va); load_tile<false, NT>(a.B, a.ldb, col0, k0, a.n, a.kdim, tid, vb); scale_tile<false, NT>(a.w, k0, a.kdim, tid, vb); }
-        store_tile<NT>(As, tid, va);
-        store_tile<NT>(Bs, tid, vb);
+        request_stage();
+        finish_stage(0);
     }
     __syncthreads();
 
-    for (int kt = 0; kt < nkt; ++kt) {
+    // (the last stage has nothing to request: it stands behind the loop, so that the loop body carries no `is there another stage` test and no value from one
+    // iteration to the next but the addresses)
+    for (int kt = 0; kt + 1 < nkt; ++kt) {
         const int cur = kt & 1;
-        const bool more = (kt + 1 < nkt);
-        if (more) {
-            const int k0 = (kt_begin + kt + 1) * BK;
-            const bool chk = edge || (k0 + BK > a.kdim);
-            if (chk) { load_tile<true, NT>(a.A, a.lda, row0, k0, a.n, a.kdim, tid, va); load_tile<true, NT>(a.B, a.ldb, col0, k0, a.n, a.kdim, tid, vb); scale_tile<true, NT>(a.w, k0, a.kdim, tid, vb); }
-            else { load_tile<false, NT>(a.A, a.lda, row0, k0, a.n, a.kdim, tid, va); load_tile<false, NT>(a.B, a.ldb, col0, k0, a.n, a.kdim, tid, vb); scale_tile<false, NT>(a.w, k0, a.kdim, tid, vb); }
-        }
-        if (!skip_wave) {
-            const double* Asb = As + cur * BK * LDS_LD + wr * SUBR + (lane & 15);
-            const double* Bsb = Bs + cur * BK * LDS_LD + wc * SUBC + (lane & 15);
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const int kk = ks * 4 + (lane >> 4);
-                double af[MTR], bf[MTC];
-#pragma unroll
-                for (int q = 0; q < MTR; ++q) af[q] = Asb[kk * LDS_LD + q * 16];
-#pragma unroll
-                for (int q = 0; q < MTC; ++q) bf[q] = Bsb[kk * LDS_LD + q * 16];
-#pragma unroll
-                for (int x = 0; x < MTC; ++x)
-#pragma unroll
-                    for (int y = 0; y < MTR; ++y)
-                        acc[x][y] = __builtin_amdgcn_mfma_f64_16x16x4f64(bf[x], af[y], acc[x][y], 0, 0, 0);
-            }
-        }
-        if (more) {
-            store_tile<NT>(As + (cur ^ 1) * BK * LDS_LD, tid, va);
-            store_tile<NT>(Bs + (cur ^ 1) * BK * LDS_LD, tid, vb);
-        }
+        request_stage();
+        if (!skip_wave) multiply_stage(cur);
+        finish_stage(cur ^ 1);
         __syncthreads();
     }
+    if (nkt > 0 && !skip_wave) multiply_stage((nkt - 1) & 1);
+    __syncthreads();
 
     if (skip_wave) return;
     if (a.part) {
