@@ -1506,6 +1506,7 @@ public:
         pq_settings_default(&settings_);
         settings_.kkt_solver = PQ_SPARSE_MULTISTAGE;
         st_ = Stream(dev_);
+        ev0_ = Event(0); ev1_ = Event(0);
     }
     pq_settings& settings() { return settings_; }
     int batch() const { return batch_; }
@@ -1628,17 +1629,14 @@ public:
         PQ_HIP(hipSetDevice(dev_));
         shared_h_.set = settings_;
         PQ_HIP(hipMemcpyAsync(shared_.p, &shared_h_, sizeof(BatchShared), hipMemcpyHostToDevice, st_));
-        hipEvent_t e0, e1;
-        PQ_HIP(hipEventCreate(&e0)); PQ_HIP(hipEventCreate(&e1));
-        PQ_HIP(hipEventRecord(e0, st_));
+        PQ_HIP(hipEventRecord(ev0_, st_));
         launch_ipm();
-        PQ_HIP(hipEventRecord(e1, st_));
+        PQ_HIP(hipEventRecord(ev1_, st_));
         PQ_HIP(hipGetLastError());
         PQ_HIP(hipMemcpyAsync(infos_h_.data(), infos_.p, sizeof(pq_info) * batch_, hipMemcpyDeviceToHost, st_));
         stream_wait(st_);
         float ms = 0.f;
-        PQ_HIP(hipEventElapsedTime(&ms, e0, e1));
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+        PQ_HIP(hipEventElapsedTime(&ms, ev0_, ev1_));
         last_kernel_ms_ = ms;
         int solved = 0;
         for (const auto& i : infos_h_) solved += i.status == PQ_SOLVED;
@@ -2215,7 +2213,8 @@ private:
     DBuf<int> order_;            // block -> instance of the next launch
     std::vector<int> order_h_;
     std::vector<pq_info> infos_h_;
-    Stream st_;  // last, so it goes first: drained and destroyed before the buffers its work uses
+    Event ev0_, ev1_;  // the timing bracket of solve() (last_kernel_ms)
+    Stream st_;
 };
 
 }  // namespace pq

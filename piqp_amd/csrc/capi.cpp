@@ -46,8 +46,7 @@ struct VarStage {
 }  // namespace
 
 struct pq_kkt {
-    KKTSolverBase* impl = nullptr;
-    bool owned = true;
+    KKTSolverBase* impl = nullptr;  // the backend in use: `owner`'s, or (owner empty: pq_kktsys::backend_view) the one a KKTSystem owns
     int ptr_mode = PQ_MEM_HOST;
     // staging (host pointer mode)
     DBuf<double> sx, sy, sz, lx, ly, lz, xr, zr;
@@ -61,11 +60,11 @@ struct pq_kkt {
         xr.alloc(n); zr.alloc(m > 0 ? m : 1);
         staged = true;
     }
-    ~pq_kkt() { if (owned) delete impl; }
+    void own(std::unique_ptr<KKTSolverBase> b) { owner = std::move(b); impl = owner.get(); }
+    std::unique_ptr<KKTSolverBase> owner;  // last, like a Stream: it owns the stream the staging buffers are used on
 };
 
 struct pq_kktsys {
-    KKTSystem* impl = nullptr;
     pq_kkt backend_view;
     int ptr_mode = PQ_MEM_HOST;
     VarStage in, out, mul_in, mul_out;  // mul_*: scratch Variables of pq_kktsys_mul (the last solve's staged vectors stay intact)
@@ -80,7 +79,7 @@ struct pq_kktsys {
         in.zero(impl->stream()); out.zero(impl->stream());
         staged = true;
     }
-    ~pq_kktsys() { delete impl; }
+    std::unique_ptr<KKTSystem> impl;  // last, like a Stream: its backend owns the stream the staging buffers are used on
 };
 
 static void h2d(double* dst, const double* src, int n, hipStream_t st)
@@ -145,7 +144,7 @@ int pq_kkt_create_dense(pq_kkt** out, const pq_dense_data* data, int kkt_solver,
     if (rc < 0) return rc;
     return guarded([&] {
         std::unique_ptr<pq_kkt> h(new pq_kkt);
-        h->impl = make_dense_kkt(data, kkt_solver, device);
+        h->own(make_dense_kkt(data, kkt_solver, device));
         h->ensure_staging();  // host-pointer-mode staging: allocated here, never later (pq_debug_alloc_count)
         *out = h.release();
         return (int)PQ_OK;
@@ -165,7 +164,7 @@ int pq_kkt_create_sparse(pq_kkt** out, const pq_sparse_data* data, int kkt_solve
     if (rc < 0) return rc;
     return guarded([&] {
         std::unique_ptr<pq_kkt> h(new pq_kkt);
-        h->impl = make_sparse_kkt(data, kkt_solver, device);
+        h->own(make_sparse_kkt(data, kkt_solver, device));
         if (!h->impl) return fail(PQ_ERR_UNSUPPORTED, "kkt solver not supported");
         h->ensure_staging();
         *out = h.release();
@@ -178,7 +177,7 @@ int pq_kkt_clone(const pq_kkt* k, pq_kkt** out)
     if (!k || !out) return fail(PQ_ERR_INVALID, "null argument");
     return guarded([&] {
         std::unique_ptr<pq_kkt> h(new pq_kkt);
-        h->impl = k->impl->clone();
+        h->own(k->impl->clone());
         h->ptr_mode = k->ptr_mode;
         h->ensure_staging();
         *out = h.release();
@@ -188,7 +187,7 @@ int pq_kkt_clone(const pq_kkt* k, pq_kkt** out)
 
 void pq_kkt_destroy(pq_kkt* k)
 {
-    if (k && k->owned) delete k;
+    if (k && k->owner) delete k;  // (a backend_view goes with its pq_kktsys)
 }
 
 int pq_kkt_set_pointer_mode(pq_kkt* k, int mem)
@@ -326,11 +325,11 @@ int pq_kkt_internal_factor(pq_kkt* k, double* out_host)
 // arithmetic is the dense backend's (a backend with p = m = 0, zero regularisation: its assembly is P + 0); the Upper variants work on the transposed view exactly as
 // ldlt_no_pivot.hpp:357-371 does (Transpose<MatrixType>), so U = L^T bit for bit.
 struct pq_dense_factor {
-    std::unique_ptr<KKTSolverBase> impl;
     int device = 0, n = 0, kind = PQ_DENSE_LDLT_NO_PIVOT, uplo = PQ_LOWER, info = 1;
     DBuf<double> stage, full, zero, xb;
     std::vector<double> host;
     double last_ms[2] = {0.0, 0.0};
+    std::unique_ptr<KKTSolverBase> impl;  // last, like a Stream: it owns the stream the buffers are used on
 };
 
 int pq_dense_factor_create(pq_dense_factor** out, int device, int n, int kind, int uplo)
@@ -368,7 +367,7 @@ int pq_dense_factor_compute(pq_dense_factor* f, const double* A, int lda, int me
             PQ_HIP(hipStreamSynchronize(nullptr));
             pq_dense_data d{};
             d.n = n; d.p = 0; d.m = 0; d.P_utri = f->full.p; d.mem = PQ_MEM_DEVICE;
-            f->impl.reset(make_dense_kkt(&d, f->kind, f->device));
+            f->impl = make_dense_kkt(&d, f->kind, f->device);
             f->impl->set_class_failure_semantics(true);
             f->impl->set_profiling(1);
         }
@@ -662,12 +661,11 @@ int pq_kkt_dims(const pq_kkt* k, int* n, int* p, int* m)
 }
 
 // ------------------------------------------------------------------------------------ KKTSystem
-static pq_kktsys* wrap_kktsys(KKTSystem* sys)
+static std::unique_ptr<pq_kktsys> wrap_kktsys(std::unique_ptr<KKTSystem> sys)
 {
-    pq_kktsys* h = new pq_kktsys;
-    h->impl = sys;
-    h->backend_view.impl = sys->backend();
-    h->backend_view.owned = false;
+    auto h = std::make_unique<pq_kktsys>();
+    h->impl = std::move(sys);
+    h->backend_view.impl = h->impl->backend();
     h->ensure_staging();
     h->backend_view.ensure_staging();
     return h;
@@ -683,11 +681,9 @@ int pq_kktsys_create_dense(pq_kktsys** out, const pq_dense_data* data, const pq_
     int rc = check_device(device);
     if (rc < 0) return rc;
     return guarded([&] {
-        std::unique_ptr<KKTSolverBase> b(make_dense_kkt(data, settings->kkt_solver, device));
-        std::unique_ptr<KKTSystem> sys(new KKTSystem(b.get(), *settings));
-        b.release();
+        auto sys = std::make_unique<KKTSystem>(make_dense_kkt(data, settings->kkt_solver, device), *settings);
         sys->set_bounds(data->n_h_l, data->n_h_u, data->n_x_l, data->n_x_u, data->h_l_idx, data->h_u_idx, data->x_l_idx, data->x_u_idx, data->x_b_scaling, data->mem);
-        *out = wrap_kktsys(sys.release());
+        *out = wrap_kktsys(std::move(sys)).release();
         return (int)PQ_OK;
     });
 }
@@ -700,12 +696,11 @@ int pq_kktsys_create_sparse(pq_kktsys** out, const pq_sparse_data* data, const p
     int rc = check_device(device);
     if (rc < 0) return rc;
     return guarded([&] {
-        std::unique_ptr<KKTSolverBase> b(make_sparse_kkt(data, settings->kkt_solver, device));
+        std::unique_ptr<KKTSolverBase> b = make_sparse_kkt(data, settings->kkt_solver, device);
         if (!b) return fail(PQ_ERR_UNSUPPORTED, "kkt solver not supported");
-        std::unique_ptr<KKTSystem> sys(new KKTSystem(b.get(), *settings));
-        b.release();
+        auto sys = std::make_unique<KKTSystem>(std::move(b), *settings);
         sys->set_bounds(data->n_h_l, data->n_h_u, data->n_x_l, data->n_x_u, data->h_l_idx, data->h_u_idx, data->x_l_idx, data->x_u_idx, data->x_b_scaling, PQ_MEM_HOST, data->mem);
-        *out = wrap_kktsys(sys.release());
+        *out = wrap_kktsys(std::move(sys)).release();
         return (int)PQ_OK;
     });
 }
@@ -714,9 +709,9 @@ int pq_kktsys_clone(const pq_kktsys* k, pq_kktsys** out)
 {
     if (!k || !out) return fail(PQ_ERR_INVALID, "null argument");
     return guarded([&] {
-        pq_kktsys* h = wrap_kktsys(k->impl->clone());
+        std::unique_ptr<pq_kktsys> h = wrap_kktsys(k->impl->clone());
         h->ptr_mode = k->ptr_mode;
-        *out = h;
+        *out = h.release();
         return (int)PQ_OK;
     });
 }

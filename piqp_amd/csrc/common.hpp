@@ -151,9 +151,10 @@ struct DBuf {
     size_t bytes() const { return n * sizeof(T); }
 };
 
-// RAII owner of one hipStream_t on one device; move-only, empty by default.  The destructor waits for the stream before destroying it.  Members go in reverse order of
-// declaration, so where a class declares its Stream decides what the stream outlives: last = it is drained and destroyed before any buffer goes; first = it goes last, and
-// the class's destructor waits on it itself before it releases events or a communicator.  Either way a constructor that throws once the stream exists no longer leaks it.
+// RAII owner of one hipStream_t on one device; move-only, empty by default.  The destructor waits for the stream before destroying it.
+// THE RULE for every handle type: its Streams are declared LAST and everything else it holds is RAII (DBuf, HBuf, Event, rccl::CommPtr, unique_ptr), so it needs no
+// destructor of its own.  Members go in reverse order of declaration: the streams are drained and destroyed first, then a communicator, then the events, then the
+// buffers -- nothing is released while work that uses it may still run, and a constructor that throws half way releases what exists in the same order.
 // (Api: the create / destroy pair; anything but HipStreamApi is tests/c/stream_raii_kat.cpp counting the calls.)
 struct HipStreamApi {
     static hipStream_t create(int device)
@@ -190,6 +191,40 @@ private:
     hipStream_t s_ = nullptr;
 };
 using Stream = BasicStream<HipStreamApi>;
+
+// RAII owner of one hipEvent_t, the same shape: move-only, empty by default.  flags 0: a timing event; hipEventDisableTiming: an ordering one.  The event is created on
+// the current device (every creation site has set it).
+struct HipEventApi {
+    static hipEvent_t create(unsigned flags)
+    {
+        hipEvent_t e = nullptr;
+        PQ_HIP(hipEventCreateWithFlags(&e, flags));
+        return e;
+    }
+    static void destroy(hipEvent_t e) noexcept { (void)hipEventDestroy(e); }
+};
+template <class Api>
+class BasicEvent {
+public:
+    BasicEvent() = default;
+    explicit BasicEvent(unsigned flags) : e_(Api::create(flags)) {}
+    BasicEvent(const BasicEvent&) = delete;
+    BasicEvent& operator=(const BasicEvent&) = delete;
+    BasicEvent(BasicEvent&& o) noexcept : e_(std::exchange(o.e_, nullptr)) {}
+    BasicEvent& operator=(BasicEvent&& o) noexcept
+    {
+        if (this != &o) { reset(); e_ = std::exchange(o.e_, nullptr); }
+        return *this;
+    }
+    ~BasicEvent() { reset(); }
+    hipEvent_t get() const { return e_; }
+    operator hipEvent_t() const { return e_; }
+
+private:
+    void reset() noexcept { if (e_) Api::destroy(std::exchange(e_, nullptr)); }
+    hipEvent_t e_ = nullptr;
+};
+using Event = BasicEvent<HipEventApi>;
 
 // pinned host staging buffer
 template <class T>
@@ -253,27 +288,19 @@ struct StageProfiler {
     static constexpr int NSTAGE = 6;  // 0..2 stages of a backend; 3..5 kernel-level brackets of the dense backend (level 2)
     bool enabled = false;
     int level = 0;  // 2: also bracket individual launches (adds event markers between dependent kernels: measurement passes only)
-    struct Pair { hipEvent_t a, b; };
+    struct Pair { Event a, b; };
     std::vector<Pair> pending[NSTAGE], pool;
-    ~StageProfiler()
-    {
-        for (auto& v : pending) for (auto& pr : v) { (void)hipEventDestroy(pr.a); (void)hipEventDestroy(pr.b); }
-        for (auto& pr : pool) { (void)hipEventDestroy(pr.a); (void)hipEventDestroy(pr.b); }
-    }
     Pair get()
     {
-        if (!pool.empty()) { Pair p = pool.back(); pool.pop_back(); return p; }
-        Pair p;
-        PQ_HIP(hipEventCreate(&p.a));
-        PQ_HIP(hipEventCreate(&p.b));
-        return p;
+        if (!pool.empty()) { Pair p = std::move(pool.back()); pool.pop_back(); return p; }
+        return Pair{Event(0), Event(0)};
     }
     int begin(int stage, hipStream_t s)
     {
         if (!enabled || (stage >= 3 && level < 2)) return -1;
         Pair p = get();
         PQ_HIP(hipEventRecord(p.a, s));
-        pending[stage].push_back(p);
+        pending[stage].push_back(std::move(p));
         return (int)pending[stage].size() - 1;
     }
     void end(int stage, int tok, hipStream_t s)
@@ -288,7 +315,7 @@ struct StageProfiler {
             float ms = 0.f;
             PQ_HIP(hipEventElapsedTime(&ms, pr.a, pr.b));
             tot += ms;
-            pool.push_back(pr);
+            pool.push_back(std::move(pr));
         }
         *count = (int)pending[stage].size();
         *total_ms = tot;

@@ -337,11 +337,11 @@ public:
         upload(d);
     }
 
-    KKTSolverBase* clone() const override
+    std::unique_ptr<KKTSolverBase> clone() const override
     {
         PQ_HIP(hipSetDevice(dev_));
         stream_wait(st_);
-        return new DenseExactKKT(*this, 0);
+        return std::unique_ptr<KKTSolverBase>(new DenseExactKKT(*this, 0));  // (a private constructor)
     }
 
     // dense/kkt.hpp:62-71 (every call refreshes all three matrices and AT_A, like the other dense backend: Solver::update rewrites them even when none is passed)
@@ -502,12 +502,12 @@ private:
     DBuf<int> info_;
     HBuf<int> info_h_;
     StageProfiler prof_;
-    Stream st_;  // last, so it goes first: drained and destroyed before the profiler's events and the buffers its work uses
+    Stream st_;
 };
 
 }  // namespace
 
-KKTSolverBase* make_dense_exact_kkt(const pq_dense_data* data, int device) { return new DenseExactKKT(data, device); }
+std::unique_ptr<KKTSolverBase> make_dense_exact_kkt(const pq_dense_data* data, int device) { return std::make_unique<DenseExactKKT>(data, device); }
 
 void debug_device_sqrt(const double* in_host, double* out_host, long long count, int device)
 {

@@ -148,16 +148,9 @@ struct pq_dense_factor_batch {
     DBuf<int> status;    // [0, batch): info, [batch, 2 batch): first bad column
     HBuf<int> status_h;
     HBuf<double> mat_h;  // n x n, pq_dense_factor_batch_matrix
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    Event ev0, ev1;
     double last_ms[2] = {0.0, 0.0};
-    Stream st;  // last, so it goes first: drained and destroyed before the buffers its work uses (the events: see the destructor)
-    ~pq_dense_factor_batch()
-    {
-        (void)hipSetDevice(device);
-        if (st.get()) (void)hipStreamSynchronize(st);
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-    }
+    Stream st;
 };
 
 extern "C" {
@@ -176,8 +169,8 @@ int pq_dense_factor_batch_create(pq_dense_factor_batch** out, int device, int ba
         const size_t nn = (size_t)n * n;
         f->fac.alloc(nn * batch); f->stage_a.alloc(nn * batch); f->stage_x.alloc((size_t)n * max_nrhs * batch);
         f->status.alloc(2 * (size_t)batch); f->status_h.alloc(2 * (size_t)batch); f->mat_h.alloc(nn);
-        PQ_HIP(hipEventCreate(&f->ev0));
-        PQ_HIP(hipEventCreate(&f->ev1));
+        f->ev0 = Event(0);
+        f->ev1 = Event(0);
         f->fac.zero(f->st);  // the triangle that is not named stays zero for life
         // the matrix at n = 128 (129 KiB, with sixteen right-hand sides 145 KiB) is more than the 64 KiB a launch may ask for by default
         static PerDeviceOnce once;

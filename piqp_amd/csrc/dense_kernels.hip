@@ -3019,14 +3019,12 @@ __global__ void k_xcd_probe(int* __restrict__ count)
 // true when a launch of 8 x 32 workgroups puts exactly 32 on every XCD (eight XCDs served round robin: the mode this device is normally in)
 bool probe_one_xcd_sweeps(hipStream_t s)
 {
-    int* cnt = nullptr;
-    PQ_HIP(hipMalloc(&cnt, 8 * sizeof(int)));
-    PQ_HIP(hipMemsetAsync(cnt, 0, 8 * sizeof(int), s));
-    hipLaunchKernelGGL(k_xcd_probe, dim3(256), dim3(256), 0, s, cnt);
+    DBuf<int> cnt(8);
+    cnt.zero(s);
+    hipLaunchKernelGGL(k_xcd_probe, dim3(256), dim3(256), 0, s, cnt.p);
     int h[8];
-    PQ_HIP(hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, s));
+    PQ_HIP(hipMemcpyAsync(h, cnt.p, sizeof(h), hipMemcpyDeviceToHost, s));
     PQ_HIP(hipStreamSynchronize(s));
-    PQ_HIP(hipFree(cnt));
     for (int q = 0; q < 8; ++q) if (h[q] != 32) return false;
     return true;
 }
@@ -3897,9 +3895,7 @@ static double mfma_variant(int blocks, int iters, double* out, hipStream_t s, hi
 double microbench_mfma_f64(int iters, hipStream_t s)
 {
     DBuf<double> out(8);
-    hipEvent_t e0, e1;
-    PQ_HIP(hipEventCreate(&e0));
-    PQ_HIP(hipEventCreate(&e1));
+    Event e0(0), e1(0);
     const int cus = microbench_cus();
     const bool verbose = debug_token("microbench") != nullptr;
     double best = 0.0;
@@ -3913,8 +3909,6 @@ double microbench_mfma_f64(int iters, hipStream_t s)
             best = std::max(best, v[q]);
         }
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     return best;
 }
 
@@ -3932,9 +3926,7 @@ double microbench_potrf_block(bool ldlt, int reps, long long* stamps64, hipStrea
     hipLaunchKernelGGL(k_fill_spd_block, dim3(n), dim3(n), 0, s, A0.p, n);
     PQ_HIP(hipMemsetAsync(ts.p, 0, 64 * sizeof(long long), s));
     PQ_HIP(hipMemsetAsync(info.p, 0xFF, sizeof(int), s));
-    hipEvent_t e0, e1;
-    PQ_HIP(hipEventCreate(&e0));
-    PQ_HIP(hipEventCreate(&e1));
+    Event e0(0), e1(0);
     float total = 0.f;
     for (int r = 0; r < reps + 1; ++r) {
         PQ_HIP(hipMemcpyAsync(A.p, A0.p, A.bytes(), hipMemcpyDeviceToDevice, s));
@@ -3947,8 +3939,6 @@ double microbench_potrf_block(bool ldlt, int reps, long long* stamps64, hipStrea
         if (r > 0 && r < reps) total += ms;
     }
     if (stamps64) PQ_HIP(hipMemcpy(stamps64, ts.p, 64 * sizeof(long long), hipMemcpyDeviceToHost));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     return reps > 1 ? total / (reps - 1) * 1e3 : 0.0;
 }
 
@@ -4005,9 +3995,7 @@ double microbench_hbm_copy(size_t bytes, int iters, hipStream_t s)
     const size_t n2 = bytes / 16;
     DBuf<d2> a(n2), b(n2);
     PQ_HIP(hipMemsetAsync(a.p, 1, n2 * 16, s));
-    hipEvent_t e0, e1;
-    PQ_HIP(hipEventCreate(&e0));
-    PQ_HIP(hipEventCreate(&e1));
+    Event e0(0), e1(0);
     const int cus = microbench_cus();
     const bool verbose = debug_token("microbench") != nullptr;
     double best = 0.0;
@@ -4021,8 +4009,6 @@ double microbench_hbm_copy(size_t bytes, int iters, hipStream_t s)
             best = std::max(best, v[q]);
         }
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     return best;
 }
 

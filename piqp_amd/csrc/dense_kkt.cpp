@@ -36,23 +36,13 @@ public:
         upload(d);
     }
 
-    ~DenseKKT() override
-    {
-        (void)hipSetDevice(dev_);
-        if (st_inv_) (void)hipStreamSynchronize(st_inv_);
-        if (st_) (void)hipStreamSynchronize(st_);
-        if (ev_fac_) (void)hipEventDestroy(ev_fac_);
-        if (ev_inv_) (void)hipEventDestroy(ev_inv_);
-    }
-
     // dense/kkt.hpp:57-60
-    KKTSolverBase* clone() const override
+    std::unique_ptr<KKTSolverBase> clone() const override
     {
         PQ_HIP(hipSetDevice(dev_));
         const_cast<DenseKKT*>(this)->join_inverses();
         stream_wait(st_);
-        DenseKKT* k = new DenseKKT(*this, 0);
-        return k;
+        return std::unique_ptr<KKTSolverBase>(new DenseKKT(*this, 0));  // (a private constructor)
     }
 
     // dense/kkt.hpp:62-71.  The reference backend re-reads data.P_utri/AT/GT at every factor and solve, and
@@ -242,8 +232,8 @@ private:
         if (inv_sweeps_) {
             vinv_.alloc(dense::block_inverse_dd_doubles(n_));
             st_inv_ = Stream(dev_);
-            PQ_HIP(hipEventCreateWithFlags(&ev_fac_, hipEventDisableTiming));
-            PQ_HIP(hipEventCreateWithFlags(&ev_inv_, hipEventDisableTiming));
+            ev_fac_ = Event(hipEventDisableTiming);
+            ev_inv_ = Event(hipEventDisableTiming);
         }
         if (debug_token("trsv_ts")) { trsv_ts_.alloc(4 * ((n_ + 127) / 128) + 8); trsv_ts_.zero(st_); }
         if (const char* e = debug_token("fused_ts")) { dbg_panel_ = std::atoi(e); dbg_ts_.alloc(96); dbg_ts_.zero(st_); }
@@ -376,12 +366,10 @@ private:
     bool ldlt_;
     bool class_semantics_ = false;  // see KKTSolverBase::set_class_failure_semantics
     double delta_ = 1.0;
-    Stream st_, st_inv_;  // before every buffer, so they go last: the destructor waits on both, then the events go, then the buffers (st_inv_: the block inverses)
     DBuf<double> Pfull_, Pdiag_, AT_, GT_, ATA_, fac_, z_reg_inv_, x_reg_last_, dvec_, part_, rdiag_, split_ws_, pack_, w16_, fuse_scratch_;
     DBuf<int> info_, flags_, fuse_flags_, fuse_cnt_, chol_flags_;
     DBuf<double> pack2_, side_;  // side_: the solved panels once more, at addresses the persistent launch has never read before (dense_kernels.hip)
     bool inv_sweeps_ = false, inv_pending_ = false;
-    hipEvent_t ev_fac_ = nullptr, ev_inv_ = nullptr;
     void join_inverses()
     {
         if (!inv_pending_) return;
@@ -426,15 +414,17 @@ private:
         }
         std::fprintf(stderr, "\n");
     }
+    Event ev_fac_, ev_inv_;
+    Stream st_, st_inv_;  // (st_inv_: the block inverses)
 };
 
 }  // namespace
 
-KKTSolverBase* make_dense_kkt(const pq_dense_data* data, int kkt_solver, int device)
+std::unique_ptr<KKTSolverBase> make_dense_kkt(const pq_dense_data* data, int kkt_solver, int device)
 {
     if (kkt_solver == PQ_DENSE_CHOLESKY_EXACT) return make_dense_exact_kkt(data, device);
     if (kkt_solver != PQ_DENSE_CHOLESKY && kkt_solver != PQ_DENSE_LDLT_NO_PIVOT) throw std::runtime_error("kkt solver not supported");
-    return new DenseKKT(data, kkt_solver, device);
+    return std::make_unique<DenseKKT>(data, kkt_solver, device);
 }
 
 }  // namespace pq

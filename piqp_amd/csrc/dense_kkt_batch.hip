@@ -370,17 +370,10 @@ struct pq_kkt_batch {
     DBuf<int> status;                  // [0, batch): info, [batch, 2 batch): first bad column
     HBuf<int> status_h;
     HBuf<double> mat_h;  // n x n
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // factor begin / end, solve begin / end
+    Event ev[4];  // factor begin / end, solve begin / end
     bool timed[2] = {false, false};
     double wall_ms = 0.0;
-    Stream st;  // last, so it goes first: drained and destroyed before the buffers its work uses (the events: see the destructor)
-    ~pq_kkt_batch()
-    {
-        (void)hipSetDevice(device);
-        if (st.get()) (void)hipStreamSynchronize(st);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
+    Stream st;
 };
 
 namespace {
@@ -408,7 +401,7 @@ void kb_alloc(pq_kkt_batch* k)
     k->fac.alloc(b * nn); k->delta_s.alloc(b); k->x_reg_s.alloc(b * n); k->zinv_s.alloc(b * m); k->mat_d.alloc(nn);
     k->stage_in.alloc(b * (n + p + m + 2)); k->stage_out.alloc(b * (n + p + m));
     k->status.alloc(2 * b); k->status_h.alloc(2 * b); k->mat_h.alloc(nn);
-    for (hipEvent_t& e : k->ev) PQ_HIP(hipEventCreate(&e));
+    for (Event& e : k->ev) e = Event(0);
     k->fac.zero(k->st);  // the upper triangles stay zero for life
     k->mat_d.zero(k->st);
     kb_raise_lds();

@@ -128,9 +128,7 @@ double microbench_transpose(int rows, int cols, int iters, hipStream_t s)
     const size_t cnt = (size_t)rows * cols;
     DBuf<double> a(cnt), b(cnt);
     PQ_HIP(hipMemsetAsync(a.p, 1, cnt * sizeof(double), s));
-    hipEvent_t e0, e1;
-    PQ_HIP(hipEventCreate(&e0));
-    PQ_HIP(hipEventCreate(&e1));
+    Event e0(0), e1(0);
     ingest_transpose(b.p, a.p, rows, cols, false, s);
     stream_wait(s);
     PQ_HIP(hipEventRecord(e0, s));
@@ -139,8 +137,6 @@ double microbench_transpose(int rows, int cols, int iters, hipStream_t s)
     PQ_HIP(hipEventSynchronize(e1));
     float ms = 0;
     PQ_HIP(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     return 2.0 * (double)cnt * sizeof(double) * iters / (ms * 1e-3) * 1e-9;
 }
 

@@ -2,10 +2,13 @@
 // Host-side mirror of piqp::KKTSolverBase<T,I,MatrixType> (reference include/piqp/kkt_solver_base.hpp:20-44)
 // for device-resident data: same seven operations, same argument meaning, same bool/void error
 // convention.  All vector arguments are DEVICE pointers on the backend's stream; the C-ABI layer
-// (capi.cpp) stages host vectors when the caller uses PQ_MEM_HOST.
+// (capi.cpp) stages host vectors when the caller uses PQ_MEM_HOST.  Backends are owned by std::unique_ptr from the
+// moment they exist: clone() and every make_*_kkt factory return one.
 #pragma once
 
+#include <memory>
 #include <stdexcept>
+#include <vector>
 
 #include "common.hpp"
 
@@ -16,7 +19,7 @@ public:
     virtual ~KKTSolverBase() = default;
 
     // kkt_solver_base.hpp:28
-    virtual KKTSolverBase* clone() const = 0;
+    virtual std::unique_ptr<KKTSolverBase> clone() const = 0;
     // kkt_solver_base.hpp:30 -- `data` is the C-ABI descriptor (host or device arrays per data->mem)
     virtual void update_data_dense(const pq_dense_data* data, int options) { (void)data; (void)options; throw std::runtime_error("update_data: wrong matrix type"); }
     virtual void update_data_sparse(const pq_sparse_data* data, int options) { (void)data; (void)options; throw std::runtime_error("update_data: wrong matrix type"); }
@@ -101,16 +104,16 @@ public:
     virtual void get_profile(int stage, double* total_ms, int* count) { (void)stage; *total_ms = 0.0; *count = 0; }
 };
 
-KKTSolverBase* make_dense_kkt(const pq_dense_data* data, int kkt_solver, int device);
-KKTSolverBase* make_dense_exact_kkt(const pq_dense_data* data, int device);  // dense_exact.hip: dense_cholesky in the reference's own order of operations, n <= 1024
+std::unique_ptr<KKTSolverBase> make_dense_kkt(const pq_dense_data* data, int kkt_solver, int device);
+std::unique_ptr<KKTSolverBase> make_dense_exact_kkt(const pq_dense_data* data, int device);  // dense_exact.hip: dense_cholesky in the reference's own order of operations, n <= 1024
 inline bool dense_kkt_kind(int k) { return k == PQ_DENSE_CHOLESKY || k == PQ_DENSE_LDLT_NO_PIVOT || k == PQ_DENSE_CHOLESKY_EXACT; }
 constexpr int DENSE_EXACT_MAX_N = 1024;
 void debug_device_sqrt(const double* in_host, double* out_host, long long count, int device);  // dense_exact.hip (pq_debug_device_sqrt)
-KKTSolverBase* make_sparse_kkt(const pq_sparse_data* data, int kkt_solver, int device);
-KKTSolverBase* make_multistage_kkt(const pq_sparse_data* data, int device);
+std::unique_ptr<KKTSolverBase> make_sparse_kkt(const pq_sparse_data* data, int kkt_solver, int device);
+std::unique_ptr<KKTSolverBase> make_multistage_kkt(const pq_sparse_data* data, int device);
 // sparse_kkt.hip: the supernodal multifrontal engine, any KKTMode.  adopt: a stream the engine runs on and owns from the moment this returns (if it throws, the caller still owns it)
-KKTSolverBase* make_multifrontal_kkt(const pq_sparse_data* data, int mode, int device, hipStream_t adopt = nullptr);
-KKTSolverBase* make_exact_sparse_kkt(const pq_sparse_data* data, int mode, int device, double max_flops = 0.0);  // sparse_exact.hip: any KKTMode in the reference's own elimination order
-hipStream_t release_exact_sparse_stream(KKTSolverBase* exact);  // an engine of make_exact_sparse_kkt gives its (idle) stream away; all it can do afterwards is be deleted
+std::unique_ptr<KKTSolverBase> make_multifrontal_kkt(const pq_sparse_data* data, int mode, int device, hipStream_t adopt = nullptr);
+std::unique_ptr<KKTSolverBase> make_exact_sparse_kkt(const pq_sparse_data* data, int mode, int device, double max_flops = 0.0);  // sparse_exact.hip: any KKTMode in the reference's own elimination order
+hipStream_t release_exact_sparse_stream(KKTSolverBase* exact);  // an engine of make_exact_sparse_kkt gives its (idle) stream away; all it can do afterwards is be destroyed
 
 }  // namespace pq

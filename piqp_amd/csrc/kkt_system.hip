@@ -392,16 +392,14 @@ __global__ __launch_bounds__(256) void k_recover_fused(int n, int p, int m, int 
 
 // =====================================================================================================
 
-KKTSystem::KKTSystem(KKTSolverBase* backend, const pq_settings& settings) : kkt_solver(backend), settings_(settings)
+KKTSystem::KKTSystem(std::unique_ptr<KKTSolverBase> backend, const pq_settings& settings) : settings_(settings), kkt_solver(std::move(backend))
 {
-    n_ = backend->n(); p_ = backend->p(); m_ = backend->m();
-    dev_ = backend->device();
-    st_ = backend->stream();
+    n_ = kkt_solver->n(); p_ = kkt_solver->p(); m_ = kkt_solver->m();
+    dev_ = kkt_solver->device();
+    st_ = kkt_solver->stream();
     PQ_HIP(hipSetDevice(dev_));
     alloc();
 }
-
-KKTSystem::~KKTSystem() { delete kkt_solver; }
 
 void KKTSystem::alloc()
 {
@@ -446,12 +444,11 @@ void KKTSystem::set_bounds(int n_h_l_, int n_h_u_, int n_x_l_, int n_x_u_, const
 }
 
 // kkt_system.hpp:70-95 (copy ctor): state vectors copied, work/refinement buffers fresh
-KKTSystem* KKTSystem::clone() const
+std::unique_ptr<KKTSystem> KKTSystem::clone() const
 {
     PQ_HIP(hipSetDevice(dev_));
     stream_wait(st_);
-    KKTSolverBase* b = kkt_solver->clone();
-    KKTSystem* k = new KKTSystem(b, settings_);
+    auto k = std::make_unique<KKTSystem>(kkt_solver->clone(), settings_);
     k->m_rho = m_rho; k->m_delta = m_delta; k->use_iterative_refinement = use_iterative_refinement;
     k->n_h_l = n_h_l; k->n_h_u = n_h_u; k->n_x_l = n_x_l; k->n_x_u = n_x_u;
     auto cpd = [&](DBuf<double>& d, const DBuf<double>& s) { if (s.n) PQ_HIP(hipMemcpyAsync(d.p, s.p, s.bytes(), hipMemcpyDeviceToDevice, k->st_)); };

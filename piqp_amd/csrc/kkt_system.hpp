@@ -11,13 +11,12 @@ namespace pq {
 
 class KKTSystem {
 public:
-    // takes ownership of `backend` (the reference holds it in a unique_ptr, kkt_system.hpp:65)
-    KKTSystem(KKTSolverBase* backend, const pq_settings& settings);
-    ~KKTSystem();
+    // owns `backend` (as the reference does, kkt_system.hpp:65)
+    KKTSystem(std::unique_ptr<KKTSolverBase> backend, const pq_settings& settings);
     KKTSystem(const KKTSystem&) = delete;
     KKTSystem& operator=(const KKTSystem&) = delete;
 
-    KKTSystem* clone() const;  // kkt_system.hpp:70-95
+    std::unique_ptr<KKTSystem> clone() const;  // kkt_system.hpp:70-95
 
     // finite-bound index lists + x_b_scaling of dense::Data / sparse::Data (host or device arrays per `mem`; xbs_mem >= 0: x_b_scaling alone lives there --
     // a device-mode pq_sparse_data keeps every index array on the host)
@@ -32,7 +31,7 @@ public:
     void mul(const pq_vars& lhs, pq_vars& rhs);
     void condensed_residual(const double* lhs_x, const double* lhs_y, double* res_inf, double* rhs_inf);
 
-    KKTSolverBase* backend() { return kkt_solver; }
+    KKTSolverBase* backend() { return kkt_solver.get(); }
     hipStream_t stream() const { return st_; }
     int device() const { return dev_; }
     int n() const { return n_; }
@@ -52,7 +51,6 @@ private:
     double get_refine_error(const double* lhs_x, const double* lhs_y, const double* lhs_z, const double* rhs_x, const double* rhs_y, const double* rhs_z, double* err_x,
                             double* err_y, double* err_z);
 
-    KKTSolverBase* kkt_solver;  // kkt_system.hpp:65
     pq_settings settings_;
     int n_ = 0, p_ = 0, m_ = 0, dev_ = 0;
     hipStream_t st_ = nullptr;
@@ -72,6 +70,8 @@ private:
     DBuf<double> x_b_scaling;
     DBuf<unsigned long long> scal_d;
     HBuf<unsigned long long> scal_h;
+
+    std::unique_ptr<KKTSolverBase> kkt_solver;  // kkt_system.hpp:65.  It owns the stream all of the above is used on, so, like a Stream, it is declared last
 };
 
 }  // namespace pq

@@ -112,12 +112,12 @@ public:
         ops_.init(d, st_);
         scatter_values(KKT_ALL);
     }
-    KKTSolverBase* clone() const override
+    std::unique_ptr<KKTSolverBase> clone() const override
     {
         PQ_HIP(hipSetDevice(dev_));
         stream_wait(st_);
-        MultistageKKT* c = new MultistageKKT(*this, 0);
-        if (tree_) c->tree_.reset(tree_->clone());
+        std::unique_ptr<MultistageKKT> c(new MultistageKKT(*this, 0));  // (a private constructor)
+        if (tree_) c->tree_ = tree_->clone();
         return c;
     }
 
@@ -126,7 +126,7 @@ public:
     // (segments of stages in parallel, separators last), which is what the multifrontal engine does for
     // KKTMode::KKT_ALL_ELIMINATED on exactly this matrix.  When a tree engine is attached, factor / solve go through it
     // (one stream: the engine runs on its own stream, so calls are bracketed by synchronisation points).
-    void attach_tree_engine(KKTSolverBase* engine) { tree_.reset(engine); }
+    void attach_tree_engine(std::unique_ptr<KKTSolverBase> engine) { tree_ = std::move(engine); }
     bool uses_tree_engine() const { return (bool)tree_; }
 
     // multistage_kkt.hpp:142-178
@@ -374,7 +374,7 @@ private:
     DBuf<double> Pf_, AtAf_, F_, pan_, XA_, XG_, zinv_;
     StageProfiler prof_;
     std::unique_ptr<KKTSolverBase> tree_;
-    Stream st_;  // last, so it goes first: drained and destroyed before the tree engine, the profiler's events and the buffers its work uses
+    Stream st_;
 };
 
 // MultistageKKT ctor (multistage_kkt.hpp:76-135).  Chains of 16+ stages get both elimination orders analysed and a SYMBOLIC cost
@@ -406,24 +406,24 @@ double tree_cost_us(const double st[8])
 
 }  // namespace
 
-KKTSolverBase* make_multistage_kkt(const pq_sparse_data* data, int device)
+std::unique_ptr<KKTSolverBase> make_multistage_kkt(const pq_sparse_data* data, int device)
 {
-    std::unique_ptr<MultistageKKT> ms(new MultistageKKT(data, device));
+    auto ms = std::make_unique<MultistageKKT>(data, device);
     const char* env = std::getenv("PIQP_AMD_MULTISTAGE");
     const std::string want = env ? env : "auto";
     std::vector<int> bi;
     ms->multistage_block_info(bi);
     const int stages = (int)bi.size() / 3 - 1;
-    if (want == "chain" || (want == "auto" && stages < 16)) return ms.release();
-    std::unique_ptr<KKTSolverBase> tree(make_multifrontal_kkt(data, 3, device));  // (KKT_ALL_ELIMINATED on the multifrontal engine: the tree engine of this backend)
-    if (!tree) return ms.release();
+    if (want == "chain" || (want == "auto" && stages < 16)) return ms;
+    std::unique_ptr<KKTSolverBase> tree = make_multifrontal_kkt(data, 3, device);  // (KKT_ALL_ELIMINATED on the multifrontal engine: the tree engine of this backend)
+    if (!tree) return ms;
     if (want != "tree") {
         double st[8];
         tree->sparse_stats(st);
-        if (tree_cost_us(st) > 0.9 * chain_cost_us(bi)) return ms.release();
+        if (tree_cost_us(st) > 0.9 * chain_cost_us(bi)) return ms;
     }
-    ms->attach_tree_engine(tree.release());
-    return ms.release();
+    ms->attach_tree_engine(std::move(tree));
+    return ms;
 }
 
 }  // namespace pq

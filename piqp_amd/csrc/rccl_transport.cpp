@@ -72,15 +72,14 @@ void unique_id(unsigned char out[UNIQUE_ID_BYTES])
     std::memcpy(out, &id, UNIQUE_ID_BYTES);
 }
 
-Comm* comm_create(const unsigned char idb[UNIQUE_ID_BYTES], int rank, int world, int device)
+CommPtr comm_create(const unsigned char idb[UNIQUE_ID_BYTES], int rank, int world, int device)
 {
     ncclUniqueId id;
     std::memcpy(&id, idb, UNIQUE_ID_BYTES);
     PQ_HIP(hipSetDevice(device));
-    Comm* c = new Comm;
+    CommPtr c(new Comm);
     c->device = device;
-    ncclResult_t r = api().CommInitRank(&c->c, world, id, rank);
-    if (r != ncclSuccess) { delete c; check(r, "ncclCommInitRank"); }
+    check(api().CommInitRank(&c->c, world, id, rank), "ncclCommInitRank");
     return c;
 }
 

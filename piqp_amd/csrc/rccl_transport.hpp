@@ -6,6 +6,7 @@
 #pragma once
 
 #include <cstddef>
+#include <memory>
 
 #include "common.hpp"
 
@@ -17,8 +18,12 @@ constexpr int UNIQUE_ID_BYTES = 128;  // NCCL_UNIQUE_ID_BYTES (rccl.h:40)
 struct Comm;  // owns one ncclComm_t
 
 void unique_id(unsigned char out[UNIQUE_ID_BYTES]);                                     // ncclGetUniqueId (rank 0; ship the bytes to the other ranks)
-Comm* comm_create(const unsigned char id[UNIQUE_ID_BYTES], int rank, int world, int device);  // ncclCommInitRank on `device`
-void comm_destroy(Comm* c);
+void comm_destroy(Comm* c);  // ncclCommDestroy; CommPtr's deleter and nobody else calls it
+struct CommDeleter {
+    void operator()(Comm* c) const noexcept { comm_destroy(c); }
+};
+using CommPtr = std::unique_ptr<Comm, CommDeleter>;
+CommPtr comm_create(const unsigned char id[UNIQUE_ID_BYTES], int rank, int world, int device);  // ncclCommInitRank on `device`
 void comm_info(Comm* c, int out[3]);  // what the communicator itself reports: ncclCommCount, ncclCommUserRank, ncclCommCuDevice
 void all_reduce_sum(Comm* c, double* buf, size_t count, hipStream_t s);                 // in place, fp64 sum
 void all_reduce_max(Comm* c, double* buf, size_t count, hipStream_t s);                 // in place, fp64 max (the sharded refinement residual's norm)

@@ -379,7 +379,7 @@ struct DeviceRuiz::Impl {
     HBuf<double> hvec;
     double *c = nullptr, *xbs = nullptr, *delta = nullptr, *delta_inv = nullptr, *delta_b = nullptr, *delta_b_inv = nullptr, *tmp = nullptr;
     size_t vec_len = 0;
-    Stream st;  // last, so it goes first: drained and destroyed before the buffers its work uses
+    Stream st;
 };
 
 DeviceRuiz::DeviceRuiz(int device, const HostData& d) : I(new Impl)

@@ -521,7 +521,7 @@ void Solver::from_device(const pq_vars& d, HostVars& h)
 void Solver::make_kkt()
 {
     m_kkt_system.reset();
-    KKTSolverBase* backend = nullptr;
+    std::unique_ptr<KKTSolverBase> backend;
     if (!m_data->sparse) {
         if (!dense_kkt_kind(m_settings.kkt_solver)) { std::fprintf(stderr, "kkt solver not supported\n"); return; }
         if (m_settings.kkt_solver == PQ_DENSE_CHOLESKY_EXACT && m_data->n > DENSE_EXACT_MAX_N) { std::fprintf(stderr, "dense_cholesky_exact supports n <= %d\n", DENSE_EXACT_MAX_N); return; }
@@ -532,7 +532,7 @@ void Solver::make_kkt()
         backend = make_sparse_kkt(&desc, m_settings.kkt_solver, device_);
         if (!backend) { std::fprintf(stderr, "kkt solver not supported\n"); return; }
     }
-    m_kkt_system = std::make_unique<KKTSystem>(backend, m_settings);
+    m_kkt_system = std::make_unique<KKTSystem>(std::move(backend), m_settings);
     const HostData& d = *m_data;
     m_kkt_system->set_bounds(d.n_h_l, d.n_h_u, d.n_x_l, d.n_x_u, d.h_l_idx.data(), d.h_u_idx.data(), d.x_l_idx.data(), d.x_u_idx.data(), d.x_b_scaling.data(), PQ_MEM_HOST);
 }
@@ -605,9 +605,9 @@ void Solver::unscale_problem()
     m_preconditioner.unscale_bounds(d);
 }
 
-Solver* Solver::clone() const
+std::unique_ptr<Solver> Solver::clone() const
 {
-    std::unique_ptr<Solver> s(new Solver(device_));
+    auto s = std::make_unique<Solver>(device_);
     s->m_settings = m_settings; s->m_info = m_info;
     s->m_first_run = m_first_run; s->m_setup_done = m_setup_done; s->m_enable_iterative_refinement = m_enable_iterative_refinement;
     if (m_data) {
@@ -617,11 +617,11 @@ Solver* Solver::clone() const
         if (druiz_ && m_data->sparse && m_data->values_on_device) s->druiz_->copy_values_from(*druiz_);  // (no host mirror to rebuild them from)
         s->m_result = m_result; s->res_nr = res_nr; s->res = res; s->step = step; s->prox_vars = prox_vars;
         if (m_kkt_system) {
-            s->m_kkt_system.reset(m_kkt_system->clone()); s->stage_alloc();
+            s->m_kkt_system = m_kkt_system->clone(); s->stage_alloc();
             if (dipm_) { s->dipm_ = std::make_unique<DeviceIpm>(); s->dipm_->init(*s->m_data, s->m_preconditioner, s->m_kkt_system->stream()); }
         }
     }
-    return s.release();
+    return s;
 }
 
 static void refresh_kkt(const DeviceRuiz* dr, KKTSystem& k, const HostData& d, int options)
@@ -1361,13 +1361,13 @@ int pq_solver_create(pq_solver** out, int device)
     int cnt = 0;
     if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) return fail(PQ_ERR_HIP, "no HIP device visible: this library has no CPU fallback");
     if (device < 0 || device >= cnt) return fail(PQ_ERR_INVALID, "device %d out of range", device);
-    return guarded([&] { auto* h = new pq_solver; h->impl.reset(new Solver(device)); *out = h; return (int)PQ_OK; });
+    return guarded([&] { auto h = std::make_unique<pq_solver>(); h->impl = std::make_unique<Solver>(device); *out = h.release(); return (int)PQ_OK; });
 }
 void pq_solver_destroy(pq_solver* s) { delete s; }
 int pq_solver_clone(const pq_solver* s, pq_solver** out)
 {
     if (!s || !out) return fail(PQ_ERR_INVALID, "null argument");
-    return guarded([&] { auto* h = new pq_solver; h->impl.reset(s->impl->clone()); *out = h; return (int)PQ_OK; });
+    return guarded([&] { auto h = std::make_unique<pq_solver>(); h->impl = s->impl->clone(); *out = h.release(); return (int)PQ_OK; });
 }
 pq_settings* pq_solver_settings(pq_solver* s) { return s ? &s->impl->settings() : nullptr; }
 

@@ -102,7 +102,7 @@ class Solver {
 public:
     explicit Solver(int device);
     ~Solver();
-    Solver* clone() const;
+    std::unique_ptr<Solver> clone() const;
 
     pq_settings& settings() { return m_settings; }
     // solver.hpp:151-216.  dev: the matrices of a dense problem come from device memory (data then carries vectors and bound lists only, and

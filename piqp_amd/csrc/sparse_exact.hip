@@ -887,6 +887,12 @@ struct XqLaunchOrder {
     }
 };
 inline XqLaunchOrder& xq_launch_order() { static XqLaunchOrder* o = new XqLaunchOrder; return *o; }  // (never destroyed: handles may outlive the statics at process exit)
+// a handle's own event of that order: the registry forgets it before it is destroyed
+struct XqOwnEvent {
+    int dev = 0;
+    Event ev;
+    ~XqOwnEvent() { if (ev) xq_launch_order().forget(dev, ev); }
+};
 
 class ExactSparseKKT final : public KKTSolverBase {
 public:
@@ -918,18 +924,12 @@ public:
         ops_.set_reference_order(true);
         remap_values();
     }
-    ~ExactSparseKKT() override
-    {
-        (void)hipSetDevice(dev_);
-        if (st_) (void)hipStreamSynchronize(st_);
-        if (xq_event_) { xq_launch_order().forget(dev_, xq_event_); (void)hipEventDestroy(xq_event_); }
-    }
     hipStream_t release_stream() { return st_.release(); }  // (release_exact_sparse_stream)
-    KKTSolverBase* clone() const override
+    std::unique_ptr<KKTSolverBase> clone() const override
     {
         PQ_HIP(hipSetDevice(dev_));
         stream_wait(st_);
-        return new ExactSparseKKT(*this, 0);
+        return std::unique_ptr<KKTSolverBase>(new ExactSparseKKT(*this, 0));  // (a private constructor)
     }
     void update_data_sparse(const pq_sparse_data* d, int options) override
     {
@@ -986,7 +986,7 @@ public:
                 if (lds_y_) hipLaunchKernelGGL(k_ul_factor<true>, dim3(grid_), dim3(64), (size_t)N_ * sizeof(double), st_, a);
                 else hipLaunchKernelGGL(k_ul_factor<false>, dim3(grid_), dim3(64), 0, st_, a);
             };
-            if (xq_on_) xq_launch_order().run(dev_, st_, xq_event_, launch);
+            if (xq_on_) xq_launch_order().run(dev_, st_, xq_event_.ev, launch);
             else launch();
         }
         PQ_HIP(hipGetLastError());
@@ -1039,7 +1039,7 @@ public:
             // (with the per-XCD queues the engine's persistent launches of one device run one after the other, the substitutions included: a factorisation then only
             // ever shares the chip with short launches that leave on their own -- see XqLaunchOrder)
             auto launch = [&] { hipLaunchKernelGGL(k_ul_solve2<32>, dim3(sgrid_), dim3(64), (size_t)(xa_cap_ + 64) * sizeof(double), st_, b); };
-            if (xq_on_) xq_launch_order().run(dev_, st_, xq_event_, launch);
+            if (xq_on_) xq_launch_order().run(dev_, st_, xq_event_.ev, launch);
             else launch();
             // a wait of the substitution that ran into its bound leaves tasks undone and stale finite values in the solution: poison it (the dense sweeps do the same),
             // so that KKTSystem's refinement / the solver's finiteness checks fail the step instead of taking it
@@ -1244,7 +1244,7 @@ private:
         ctl_.alloc(4); ctl_h_.alloc(4);
         {   // per-XCD row queues: tasks in the order of their last rows, each to the queue with the least work so far (entries of its rows); rows ascending per queue
             xq_on_ = !serial_path_ && debug_token("exact_one_queue") == nullptr;
-            if (!xq_event_) PQ_HIP(hipEventCreateWithFlags(&xq_event_, hipEventDisableTiming));
+            if (!xq_event_.ev) { xq_event_.dev = dev_; xq_event_.ev = Event(hipEventDisableTiming); }
             std::vector<int> order((size_t)ntask_), qof((size_t)std::max(ntask_, 1), 0);
             for (int t = 0; t < ntask_; ++t) order[t] = t;
             std::sort(order.begin(), order.end(), [&](int x, int y) { return U_.task_rows[U_.task_ptr[x + 1] - 1] < U_.task_rows[U_.task_ptr[y + 1] - 1]; });
@@ -1340,7 +1340,6 @@ private:
 
     int dev_, mode_ = 0, nzAA_ = 0, nzGG_ = 0, n_ = 0, p_ = 0, m_ = 0, N_ = 0, nnzK_ = 0, ntask_ = 0, nticket_ = 0, grid_ = 1, nbgroup_ = 0, epoch_ = 0;
     double delta_ = 1.0;
-    Stream st_;  // before every buffer, so it goes last: the destructor waits on it, then the launch-order event goes, then the buffers (empty once the stream was handed on)
     DBuf<int> mapAA_, mapGG_, aa_ptr_, aa_q1_, aa_q2_, aa_k_, gg_ptr_, gg_q1_, gg_q2_, gg_k_;
     DBuf<double> ata_vals_, zinv_, rhs_top_;
     bool lds_y_ = true, lds_x_ = true;
@@ -1356,7 +1355,6 @@ private:
     DBuf<double> Dloc_;
     bool xq_on_ = false;
     int xq_fallbacks_ = 0;  // factorisations that were run again on the single ticket queue
-    hipEvent_t xq_event_ = nullptr;
     std::vector<int> xq_rows_h_;
     // tasks with fewer entries per row than this run their path pass on ONE wave (ul_path).  0 since the rows of a task hand over by values (one round trip per
     // row): side by side wins at every row length measured (QAFIRO 0.09 -> 0.05 ms, finnis 0.39 -> 0.28, STADAT1 7.9 -> 6.7; 17 before, when a hand-over cost five)
@@ -1368,15 +1366,17 @@ private:
     DBuf<double> vals_, Lx_, D_, Dinv_, Ystash_, Pstash_, Dinit_, Lblock_, yglob_, xglob_;
     HBuf<int> ctl_h_;
     StageProfiler prof_;
+    XqOwnEvent xq_event_;
+    Stream st_;  // (empty once the stream was handed on)
 };
 
 }  // namespace
 
 // max_flops > 0: nullptr when the factorisation would take more flops than that (the caller then builds the multifrontal engine)
-KKTSolverBase* make_exact_sparse_kkt(const pq_sparse_data* data, int mode, int device, double max_flops)
+std::unique_ptr<KKTSolverBase> make_exact_sparse_kkt(const pq_sparse_data* data, int mode, int device, double max_flops)
 {
     try {
-        return new ExactSparseKKT(data, mode, device, max_flops);
+        return std::make_unique<ExactSparseKKT>(data, mode, device, max_flops);
     } catch (const ExactSparseKKT::TooCostly&) {
         return nullptr;
     }

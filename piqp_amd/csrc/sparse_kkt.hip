@@ -2238,8 +2238,7 @@ public:
         PQ_HIP(hipSetDevice(dev_));
         st_ = adopt ? Stream(dev_, adopt) : Stream(dev_);
         try {
-            st2_ = Stream(dev_);
-            PQ_HIP(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming)); PQ_HIP(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming));
+            create_side_stream();
             sparse::analyse_kkt(d, mode, S_);
             n_ = S_.n; p_ = S_.p; m_ = S_.m; N_ = S_.N;
             compute_level_lds();
@@ -2249,20 +2248,12 @@ public:
             throw;
         }
     }
-    ~SparseKKT() override
-    {
-        (void)hipSetDevice(dev_);
-        if (st_) { (void)hipStreamSynchronize(st_); }
-        if (comm_) rccl::comm_destroy(comm_);
-        if (ev_fork_) (void)hipEventDestroy(ev_fork_);
-        if (ev_join_) (void)hipEventDestroy(ev_join_);
-    }
 
-    KKTSolverBase* clone() const override
+    std::unique_ptr<KKTSolverBase> clone() const override
     {
         PQ_HIP(hipSetDevice(dev_));
         stream_wait(st_);
-        return new SparseKKT(*this, 0);
+        return std::unique_ptr<KKTSolverBase>(new SparseKKT(*this, 0));  // (a private constructor)
     }
 
     // sparse/kkt_full.hpp:212-251
@@ -2653,7 +2644,7 @@ public:
     void drop_transport()
     {
         xbuf_norm_ = nullptr; own_norm_.release(); sharded_agreed_ = -1;
-        if (comm_) { stream_wait(st_); rccl::comm_destroy(comm_); comm_ = nullptr; }
+        if (comm_) { stream_wait(st_); comm_.reset(); }
         own_factor_.release(); own_forward_.release(); own_gather_.release();
         xfn_ = nullptr; xuser_ = nullptr; xbuf_factor_ = xbuf_forward_ = xbuf_gather_ = nullptr;
         transport_ = Transport::None;
@@ -2688,7 +2679,7 @@ public:
     {
         out[0] = transport_ == Transport::Native ? 2 : (transport_ == Transport::Callback ? 1 : 0);
         out[1] = out[2] = out[3] = -1;
-        if (transport_ == Transport::Native && comm_) rccl::comm_info(comm_, out + 1);
+        if (transport_ == Transport::Native && comm_) rccl::comm_info(comm_.get(), out + 1);
     }
     void partition_info(int out[8]) const override
     {
@@ -2745,8 +2736,8 @@ private:
     SparseKKT(const SparseKKT& o, int) : dev_(o.dev_), mode_(o.mode_), nzAA_(o.nzAA_), nzGG_(o.nzGG_), n_(o.n_), p_(o.p_), m_(o.m_), N_(o.N_), nnzK_(o.nnzK_), delta_(o.delta_), S_(o.S_), level_lds_(o.level_lds_), sub_lds_(o.sub_lds_), ntop_(o.ntop_), top_grid_(o.top_grid_), top_lds_(o.top_lds_), top_l0_(o.top_l0_), top_start_(o.top_start_), top_nper_(o.top_nper_), top_persistent_(o.top_persistent_)
     {
         ref_mode_ = o.ref_mode_;
-        st_ = Stream(dev_); st2_ = Stream(dev_);
-        PQ_HIP(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming)); PQ_HIP(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming));
+        st_ = Stream(dev_);
+        create_side_stream();
         auto cpd = [&](DBuf<double>& d, const DBuf<double>& s) { d.alloc(s.n ? s.n : 1); if (s.n) PQ_HIP(hipMemcpyAsync(d.p, s.p, s.bytes(), hipMemcpyDeviceToDevice, st_)); };
         auto cpi = [&](DBuf<int>& d, const DBuf<int>& s) { d.alloc(s.n ? s.n : 1); if (s.n) PQ_HIP(hipMemcpyAsync(d.p, s.p, s.bytes(), hipMemcpyDeviceToDevice, st_)); };
         auto cpl = [&](DBuf<long long>& d, const DBuf<long long>& s) { d.alloc(s.n ? s.n : 1); if (s.n) PQ_HIP(hipMemcpyAsync(d.p, s.p, s.bytes(), hipMemcpyDeviceToDevice, st_)); };
@@ -2945,10 +2936,10 @@ private:
         if (world_ == 1 && !(force1 && transport_ != Transport::None)) return;
         if (transport_ == Transport::Native) {
             // native transport: stream-ordered behind the pack kernel, the unpack kernel follows on the same stream
-            if (which == 0) rccl::all_reduce_sum(comm_, xbuf_factor_, (size_t)PT_.bmat_off.back() + 1, st_);
-            else if (which == 1) rccl::all_reduce_sum(comm_, xbuf_forward_, (size_t)std::max(1, PT_.bvec_off.back()), st_);
-            else if (which == 3) rccl::all_reduce_max(comm_, xbuf_norm_, 1, st_);
-            else rccl::all_gather(comm_, xbuf_gather_, (size_t)gather_slot_, rank_, st_);
+            if (which == 0) rccl::all_reduce_sum(comm_.get(), xbuf_factor_, (size_t)PT_.bmat_off.back() + 1, st_);
+            else if (which == 1) rccl::all_reduce_sum(comm_.get(), xbuf_forward_, (size_t)std::max(1, PT_.bvec_off.back()), st_);
+            else if (which == 3) rccl::all_reduce_max(comm_.get(), xbuf_norm_, 1, st_);
+            else rccl::all_gather(comm_.get(), xbuf_gather_, (size_t)gather_slot_, rank_, st_);
             if (which < 3) ++native_calls_[which];
             return;
         }
@@ -3510,9 +3501,6 @@ private:
 
     int dev_, mode_ = 0, nzAA_ = 0, nzGG_ = 0, n_ = 0, p_ = 0, m_ = 0, N_ = 0, nnzK_ = 0;
     double delta_ = 1.0;
-    // before every buffer, so they go last: the destructor waits on st_ (which st2_'s work joins), then the communicator and the events go, then the buffers
-    Stream st_, st2_;  // st2_: the one-workgroup fronts of a level next to its big fronts' diagonal blocks (factor_levels)
-    hipEvent_t ev_fork_ = nullptr, ev_join_ = nullptr;
     sparse::Symbolic S_;
     std::vector<int> level_lds_;
     int sub_lds_ = 0, ntop_ = 0, top_grid_ = 0, top_lds_ = 0, top_l0_ = 0, top_start_ = 0, top_nper_ = 0;
@@ -3573,16 +3561,23 @@ private:
     enum class Transport { None, Callback, Native };  // who performs the three exchanges: nobody yet / the caller's callback / the library's own RCCL calls
     Transport transport_ = Transport::None;
     pq_exchange_fn xfn_ = nullptr;
-    rccl::Comm* comm_ = nullptr;  // native RCCL transport (pq_kkt_set_comm_rccl); the exchange buffers below are then the library's own
-    DBuf<double> own_factor_, own_forward_, own_gather_;
+    DBuf<double> own_factor_, own_forward_, own_gather_;  // the library's own exchange buffers (native transport)
     int native_calls_[3] = {0, 0, 0};
     void* xuser_ = nullptr;
     double *xbuf_factor_ = nullptr, *xbuf_forward_ = nullptr, *xbuf_gather_ = nullptr;
+    void create_side_stream()
+    {
+        st2_ = Stream(dev_);
+        ev_fork_ = Event(hipEventDisableTiming); ev_join_ = Event(hipEventDisableTiming);
+    }
+    Event ev_fork_, ev_join_;
+    rccl::CommPtr comm_;  // native RCCL transport (pq_kkt_set_comm_rccl)
+    Stream st_, st2_;     // st2_: the one-workgroup fronts of a level next to its big fronts' diagonal blocks (factor_levels)
 };
 
 }  // namespace
 
-KKTSolverBase* make_multifrontal_kkt(const pq_sparse_data* data, int mode, int device, hipStream_t adopt) { return new SparseKKT(data, mode, device, adopt); }
+std::unique_ptr<KKTSolverBase> make_multifrontal_kkt(const pq_sparse_data* data, int mode, int device, hipStream_t adopt) { return std::make_unique<SparseKKT>(data, mode, device, adopt); }
 
 namespace {
 // A copy of the matrices a sparse backend is built from (the C-ABI lends them for the duration of a call only).  A PIQP update never changes a pattern: the patterns
@@ -3643,7 +3638,7 @@ public:
         : cur_(std::move(exact)), copy_(new SparseDataCopy(data, device, cur_->stream())), nnz_{data->P_colptr[data->n], data->AT_colptr[data->p], data->GT_colptr[data->m]}, mode_(mode), dev_(device)
     {
     }
-    KKTSolverBase* clone() const override { return new EngineSwitchKKT(*this, std::unique_ptr<KKTSolverBase>(cur_->clone())); }
+    std::unique_ptr<KKTSolverBase> clone() const override { return std::unique_ptr<KKTSolverBase>(new EngineSwitchKKT(*this, cur_->clone())); }  // (a private constructor)
     void update_data_sparse(const pq_sparse_data* data, int options) override
     {
         if (data->n != n() || data->p != p() || data->m != m()) throw std::runtime_error("update_data: dimension mismatch");
@@ -3673,7 +3668,7 @@ public:
             // (If the build throws, nothing has changed hands and this handle works on as before.)
             const hipStream_t st = cur_->stream();
             stream_wait(st);
-            std::unique_ptr<KKTSolverBase> mf(make_multifrontal_kkt(&copy_->d, mode_, dev_, st));
+            std::unique_ptr<KKTSolverBase> mf = make_multifrontal_kkt(&copy_->d, mode_, dev_, st);
             (void)release_exact_sparse_stream(cur_.get());
             cur_ = std::move(mf);
             copy_.reset();
@@ -3713,7 +3708,7 @@ private:
 }  // namespace
 
 // KKTSystem::init_kkt_solver<PIQP_SPARSE> (kkt_system.hpp:470-497): all six sparse backends of the reference
-KKTSolverBase* make_sparse_kkt(const pq_sparse_data* data, int kkt_solver, int device)
+std::unique_ptr<KKTSolverBase> make_sparse_kkt(const pq_sparse_data* data, int kkt_solver, int device)
 {
     switch (kkt_solver) {
     case PQ_SPARSE_MULTISTAGE: return make_multistage_kkt(data, device);
@@ -3733,13 +3728,13 @@ KKTSolverBase* make_sparse_kkt(const pq_sparse_data* data, int kkt_solver, int d
             const char* mf = std::getenv("PIQP_AMD_EXACT_MAX_FLOPS");
             // (the condensed modes' systems are denser -- nl_czprob 2.1e9 flops, eleven fixtures above 2e8 -- and keep their bitwise contract too: limit 3e9 there)
             const double max_flops = eng ? 0.0 : (mf ? std::atof(mf) : (mode == 0 ? 4e7 : 3e9));
-            std::unique_ptr<KKTSolverBase> k(make_exact_sparse_kkt(data, mode, device, max_flops));
-            if (k) return new EngineSwitchKKT(std::move(k), data, mode, device);
+            std::unique_ptr<KKTSolverBase> k = make_exact_sparse_kkt(data, mode, device, max_flops);
+            if (k) return std::make_unique<EngineSwitchKKT>(std::move(k), data, mode, device);
         }
-        return new SparseKKT(data, mode, device);
+        return std::make_unique<SparseKKT>(data, mode, device);
     }
     case PQ_SPARSE_LDLT_EXACT: return make_exact_sparse_kkt(data, 0, device);
-    case PQ_SPARSE_LDLT_MULTIFRONTAL: return new SparseKKT(data, 0, device);
+    case PQ_SPARSE_LDLT_MULTIFRONTAL: return std::make_unique<SparseKKT>(data, 0, device);
     default: return nullptr;
     }
 }

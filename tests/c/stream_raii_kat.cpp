@@ -1,10 +1,14 @@
-// Host-only known answers for pq::BasicStream (piqp_amd/csrc/common.hpp), the owner of every hipStream_t in the library: the class is instantiated with a create /
-// destroy pair that only counts, so no device and no HIP runtime is needed.  Built with -fsanitize=address,undefined by tests/test_stream_raii.py.
+// Host-only known answers for pq::BasicStream and pq::BasicEvent (piqp_amd/csrc/common.hpp), the owners of every hipStream_t and hipEvent_t in the library: the classes
+// are instantiated with create / destroy pairs that only count, so no device and no HIP runtime is needed.  Built with -fsanitize=address,undefined by
+// tests/test_stream_raii.py.
 #include <cstdint>
 #include <cstdio>
+#include <memory>
 #include <set>
 #include <stdexcept>
+#include <string>
 #include <utility>
+#include <vector>
 
 #include "../../piqp_amd/csrc/common.hpp"
 
@@ -15,6 +19,8 @@ int failures = 0;
     do {                                                                         \
         if (!(cond)) { std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); ++failures; } \
     } while (0)
+
+std::vector<std::string> seq;  // what was released, in order: the stream's, the event's and the stand-ins' destroys all log here
 
 struct CountingApi {
     static int created, destroyed, bad_destroys, last_device;
@@ -31,6 +37,7 @@ struct CountingApi {
     static void destroy(int device, hipStream_t s) noexcept
     {
         ++destroyed;
+        seq.push_back("stream");
         last_device = device;
         if (s == nullptr || live.erase(s) != 1) ++bad_destroys;  // a null handle, one destroyed before, or one this Api never made or was told about
     }
@@ -42,6 +49,58 @@ std::set<hipStream_t> CountingApi::live;
 
 using Api = CountingApi;
 using S = pq::BasicStream<CountingApi>;
+
+struct CountingEventApi {
+    static int created, destroyed, bad_destroys;
+    static unsigned last_flags;
+    static int fail_at;  // the create with this number (1-based, since reset) throws; 0: none
+    static std::set<hipEvent_t> live;
+    static hipEvent_t create(unsigned flags)
+    {
+        if (fail_at && created + 1 == fail_at) throw std::runtime_error("event create failed");
+        last_flags = flags;
+        hipEvent_t e = reinterpret_cast<hipEvent_t>(static_cast<std::uintptr_t>(0x8000 + 16 * ++created));
+        live.insert(e);
+        return e;
+    }
+    static void destroy(hipEvent_t e) noexcept
+    {
+        ++destroyed;
+        seq.push_back("event");
+        if (e == nullptr || live.erase(e) != 1) ++bad_destroys;  // a null handle, one destroyed before, or one this Api never made
+    }
+    static void reset() { created = destroyed = bad_destroys = 0; last_flags = ~0u; fail_at = 0; live.clear(); seq.clear(); }
+};
+int CountingEventApi::created = 0, CountingEventApi::destroyed = 0, CountingEventApi::bad_destroys = 0, CountingEventApi::fail_at = 0;
+unsigned CountingEventApi::last_flags = ~0u;
+std::set<hipEvent_t> CountingEventApi::live;
+
+using EApi = CountingEventApi;
+using E = pq::BasicEvent<CountingEventApi>;
+
+struct ThrowsAfterTwoEvents {
+    E a, b;
+    ThrowsAfterTwoEvents() : a(0), b(2) { throw std::runtime_error("the rest of the constructor failed"); }
+};
+struct TwoEvents {
+    E a, b;
+    TwoEvents() : a(0), b(0) {}
+};
+
+// the one declaration order of every handle type: buffers, events, a communicator, the streams last
+struct BufferStandIn {
+    ~BufferStandIn() { seq.push_back("buffer"); }
+};
+struct CommStandIn {};
+struct CommDeleter {
+    void operator()(CommStandIn* c) const noexcept { seq.push_back("communicator"); delete c; }
+};
+struct HandleShape {
+    BufferStandIn buf;
+    E ev{0};
+    std::unique_ptr<CommStandIn, CommDeleter> comm{new CommStandIn};
+    S st{1};
+};
 
 struct ThrowsAfterTheStream {
     S st;
@@ -157,6 +216,71 @@ int main()
         CHECK(Api::destroyed == 1);
     }
     CHECK(Api::created == 1 && Api::destroyed == 1 && Api::bad_destroys == 0 && Api::live.empty());
+
+    // ---- pq::BasicEvent
+    EApi::reset();
+    {   // empty: no calls
+        E e;
+        CHECK(e.get() == nullptr && !e);
+    }
+    CHECK(EApi::created == 0 && EApi::destroyed == 0 && seq.empty());
+
+    {   // construct / destroy: one of each, with the flags asked for
+        E a(2);
+        CHECK(EApi::created == 1 && EApi::last_flags == 2u && a.get() != nullptr && static_cast<hipEvent_t>(a) == a.get());
+        CHECK(EApi::destroyed == 0);
+    }
+    CHECK(EApi::created == 1 && EApi::destroyed == 1 && EApi::bad_destroys == 0 && EApi::live.empty());
+
+    EApi::reset();
+    {   // move construction and move assignment into an empty one: nothing created, nothing destroyed, the source is empty
+        E a(0);
+        const hipEvent_t h = a.get();
+        E b(std::move(a));
+        CHECK(a.get() == nullptr && b.get() == h && EApi::created == 1 && EApi::destroyed == 0);
+        E c;
+        c = std::move(b);
+        CHECK(b.get() == nullptr && c.get() == h && EApi::created == 1 && EApi::destroyed == 0);
+    }
+    CHECK(EApi::created == 1 && EApi::destroyed == 1 && EApi::bad_destroys == 0 && EApi::live.empty());
+
+    EApi::reset();
+    {   // move assignment onto a live event: the old one is destroyed exactly once, at once; onto itself: nothing
+        E a(0), b(0);
+        const hipEvent_t ha = a.get(), hb = b.get();
+        a = std::move(b);
+        CHECK(EApi::destroyed == 1 && EApi::live.count(ha) == 0 && EApi::live.count(hb) == 1 && a.get() == hb && b.get() == nullptr);
+        E& self = a;
+        a = std::move(self);
+        CHECK(EApi::destroyed == 1 && a.get() == hb);
+    }
+    CHECK(EApi::created == 2 && EApi::destroyed == 2 && EApi::bad_destroys == 0 && EApi::live.empty());
+
+    EApi::reset();
+    try {   // a constructor that throws after both events exist: each destroyed once
+        ThrowsAfterTwoEvents t;
+        CHECK(false);
+    } catch (const std::runtime_error&) {
+    }
+    CHECK(EApi::created == 2 && EApi::destroyed == 2 && EApi::bad_destroys == 0 && EApi::live.empty());
+
+    EApi::reset();
+    EApi::fail_at = 2;
+    try {   // the second event's create throws: the first is destroyed, nothing else
+        TwoEvents t;
+        CHECK(false);
+    } catch (const std::runtime_error&) {
+    }
+    CHECK(EApi::created == 1 && EApi::destroyed == 1 && EApi::bad_destroys == 0 && EApi::live.empty());
+
+    Api::reset();
+    EApi::reset();
+    {
+        HandleShape h;
+        CHECK(seq.empty());
+    }
+    CHECK((seq == std::vector<std::string>{"stream", "communicator", "event", "buffer"}));
+    CHECK(Api::bad_destroys == 0 && EApi::bad_destroys == 0 && Api::live.empty() && EApi::live.empty());
 
     if (failures) { std::printf("%d checks failed\n", failures); return 1; }
     std::printf("all checks passed\n");

@@ -1,6 +1,6 @@
-"""pq::Stream (piqp_amd/csrc/common.hpp) owns every hipStream_t of the library.  Its logic -- construct / move / release / destroy, a constructor that throws after the
-stream exists -- is host code: tests/c/stream_raii_kat.cpp instantiates it with a create / destroy pair that only counts, and is built with the address and
-undefined-behaviour sanitizers.  No GPU needed."""
+"""pq::Stream and pq::Event (piqp_amd/csrc/common.hpp) own every hipStream_t and hipEvent_t of the library.  Their logic -- construct / move / release / destroy, a
+constructor that throws after the handle exists, the order in which a handle type's members go -- is host code: tests/c/stream_raii_kat.cpp instantiates them with
+create / destroy pairs that only count, and is built with the address and undefined-behaviour sanitizers.  No GPU needed."""
 import os
 import subprocess
 
