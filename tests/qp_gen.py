@@ -152,6 +152,61 @@ def mpc_chain(nx, nu, T, seed):
     return (P, rng.standard_normal(n), A, np.zeros(p), None, None, None, -np.ones(n), np.ones(n))
 
 
+def edge_qp(n, p, m, nxl, nxu, seed, dense=False):
+    """A QP whose five index spaces (n variables, p equality rows, m general rows, nxl lower- and nxu upper-bounded variables) have exactly the given sizes, for
+    the launch-shape tests of the interior-point loop (tests/test_ipm_shapes.py, tests/test_ipm_loop_gpu.py).  Returns the nine setup arguments.
+    Sparse form: diagonal P in [0.5, 2], A rows with 3 consecutive entries, G rows with 2; the last row of each touches the last variables.  dense=True: a small dense
+    SPD P (upper triangle), dense A and G.  General rows carry all four bound kinds (neither / lower / upper / both; the first four rows are one of each, the last row
+    has both); the bounded variables are drawn at random but the last variable is among them whenever the count is above 0; about a fifth of the row bounds (three
+    tenths of the variable bounds) are active at the planted point x_sol.  Planted maxima, so that the infinity norms behind dual_res_rel and primal_res_rel sit in the
+    LAST element of their index space: c[n-1] = 40; the last equality row with its b entry, and the last general row with its bounds, multiplied by 30 (the
+    general row also by -1 if its activity at x_sol is negative: the reference takes the SIGNED maximum over G x, h and s there, update_residuals_nr, solver.hpp:960-1105)."""
+    import scipy.sparse as sp
+    rng = np.random.default_rng(seed)
+    x_sol = rng.standard_normal(n); c = rng.standard_normal(n)
+
+    def rows(k, w):
+        if k == 0:
+            return None
+        w = min(w, n)
+        start = rng.integers(0, n - w + 1, k); start[-1] = n - w
+        cols = (start[:, None] + np.arange(w)[None, :]).ravel()
+        return sp.csc_matrix((rng.standard_normal(k * w), (np.repeat(np.arange(k), w), cols)), shape=(k, n))
+
+    def plant(M, k, positive=False):  # the last of the k rows times 30 (positive: and with a positive activity at x_sol)
+        if k == 0:
+            return None
+        f = np.ones(k); f[-1] = -30.0 if positive and (M[k - 1:k] @ x_sol)[0] < 0 else 30.0
+        return np.ascontiguousarray(M * f[:, None]) if dense else sp.csc_matrix(sp.diags(f) @ M)
+    if dense:
+        M = rng.standard_normal((n, n)); P = np.triu(M @ M.T / n + 0.5 * np.eye(n))
+        A = rng.standard_normal((p, n)) if p else None; G = rng.standard_normal((m, n)) if m else None
+    else:
+        P = sp.diags(rng.uniform(0.5, 2.0, n), format="csc"); A = rows(p, 3); G = rows(m, 2)
+    A, G = plant(A, p), plant(G, m, positive=True)
+    b = A @ x_sol if p else None
+    h_l = h_u = None
+    if m:
+        Gx = G @ x_sol
+        f = np.ones(m); f[-1] = 30.0
+        kind = rng.integers(0, 4, m); kind[:min(4, m)] = np.arange(4)[:min(4, m)]  # bit 0: lower bound, bit 1: upper bound
+        if m > 4:
+            kind[-1] = 3
+        h_l = np.where(kind & 1, Gx - f * np.where(rng.random(m) < 0.2, 0.0, 0.1 + rng.random(m)), -np.inf)
+        h_u = np.where(kind & 2, Gx + f * np.where(rng.random(m) < 0.2, 0.0, 0.1 + rng.random(m)), np.inf)
+
+    def pick(k):
+        idx = np.zeros(n, bool)
+        if k:
+            idx[rng.choice(n - 1, k - 1, replace=False)] = True; idx[n - 1] = True
+        return idx
+    il, iu = pick(nxl), pick(nxu)
+    x_l = np.where(il, x_sol - np.where(rng.random(n) < 0.3, 0.0, 0.1 + rng.random(n)), -np.inf)
+    x_u = np.where(iu, x_sol + np.where(rng.random(n) < 0.3, 0.0, 0.1 + rng.random(n)), np.inf)
+    c[n - 1] = 40.0
+    return (P, c, A, b, G, h_l, h_u, x_l, x_u)
+
+
 def c3_problem(n=50000, p=20000, m=30000, seed=44, spread=40, row_nnz=5):
     """BASELINE configs[2]: sparse QP, P banded upper-tri (~3 nnz/col + diagonal), A and G rows with `row_nnz` nnz each
     inside a window of `spread` variables; N = n + p + m = 100 000.  Defaults: the banded recipe of rounds 1-3 (nnz(upper K) = 4.9e5, fronts <= 92);
