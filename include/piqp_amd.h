@@ -609,6 +609,52 @@ int pq_kkt_batch_internal_factor(pq_kkt_batch *k, int instance, double *out_host
  * pq_kkt_batch_update_scalings_and_factor call, all in ms */
 int pq_kkt_batch_last_ms(const pq_kkt_batch *k, double out3[3]);
 
+/* ===================== KKTSystem for a BATCH of small dense QPs (over the backend above) ===================== */
+/* `batch` instances of piqp::KKTSystem (kkt_system.hpp) over the dense batch backend (csrc/dense_kktsys_batch.hip): per instance the scalings x_reg / z_reg, the
+ * elimination of the slacks from a right-hand side, the backend solve with the iterative-refinement loop, the recovery of the ten-vector step and mul are those of
+ * the CPU oracle (oracle/orc_kkt_system.c over oracle/orc_dense.c) bit for bit.  update_scalings_and_factor, solve and mul are ONE launch each; solve runs one
+ * workgroup per instance, so every instance takes its own number of refinement steps and the host takes no part in the loop.
+ * The instances share n <= PQ_KKT_BATCH_DENSE_MAX_N, p, m (not limited), the factorisation kind (settings->kkt_solver: PQ_DENSE_CHOLESKY or PQ_DENSE_LDLT_NO_PIVOT),
+ * one pq_settings and the four finite-bound index lists (ascending, HOST memory in either mode; every row of G is in h_l_idx or h_u_idx).  x_b_scaling is per
+ * instance, [batch][n]; NULL = all ones.  Matrices: the layout of pq_kkt_batch_create_dense.  mem (pq_mem) says where EVERY array argument of that call lives.
+ * A batch of variables is a pq_vars whose ten pointers are [batch][len] arrays, len the single-instance length (n, p, m, m, n, n, m, m, n, n); of the box vectors
+ * the first n_x_l / n_x_u entries of each row are meaningful, the rest is neither read nor written.  A pointer whose vector has no meaningful entry may be NULL. */
+typedef struct pq_kktsys_batch pq_kktsys_batch;
+/* Arguments are checked before the device is touched.  Refuses what pq_kkt_batch_create_dense refuses (PQ_ERR_UNSUPPORTED for n > PQ_KKT_BATCH_DENSE_MAX_N), and
+ * with PQ_ERR_INVALID: a NULL settings, iterative_refinement_max_iter outside [0, 64] (a safety cap on the in-kernel loop), a negative count, a count above its
+ * vector's length, a NULL list with a positive count, a list that is not strictly ascending or has an index out of range, a row of G in neither h_l_idx nor
+ * h_u_idx.  Allocates everything the handle will ever need, host-mode staging included: pq_debug_alloc_count() moves in no later call except _clone. */
+int pq_kktsys_batch_create_dense(pq_kktsys_batch **out, int device, int batch, int n, int p, int m, const double *P_utri, const double *AT, const double *GT,
+                                 int n_h_l, int n_h_u, int n_x_l, int n_x_u, const int *h_l_idx, const int *h_u_idx, const int *x_l_idx, const int *x_u_idx,
+                                 const double *x_b_scaling, const pq_settings *settings, int mem);
+void pq_kktsys_batch_destroy(pq_kktsys_batch *k);
+int pq_kktsys_batch_clone(const pq_kktsys_batch *k, pq_kktsys_batch **out); /* kkt_system.hpp:70-95: the scalings state is copied, the backend cloned */
+int pq_kktsys_batch_dims(const pq_kktsys_batch *k, int *batch, int *n, int *p, int *m);
+pq_kkt_batch *pq_kktsys_batch_backend(pq_kktsys_batch *k); /* borrowed; NULL for a NULL handle */
+/* kkt_system.hpp:134-141: pq_kkt_batch_update_data_dense on the backend; a non-NULL x_b_scaling is re-read */
+int pq_kktsys_batch_update_data_dense(pq_kktsys_batch *k, const double *P_utri, const double *AT, const double *GT, const double *x_b_scaling, int options, int mem);
+int pq_kktsys_batch_set_settings(pq_kktsys_batch *k, const pq_settings *settings); /* kkt_solver is not re-read */
+/* kkt_system.hpp:143-211 per instance, ONE launch.  iterative_refinement: int [batch], NULL = off everywhere; rho, delta: double [batch].  Afterwards the borrowed
+ * backend is in the state pq_kkt_batch_update_scalings_and_factor(delta_reg, x_reg, z_reg_iter_ref) would have left.  Returns the number of instances that
+ * factored (negative = PQ_ERR_*). */
+int pq_kktsys_batch_update_scalings_and_factor(pq_kktsys_batch *k, const int *iterative_refinement, const double *rho, const double *delta, const pq_vars *vars,
+                                               int mem);
+/* kkt_system.hpp:213-369 per instance, ONE launch, one workgroup per instance, the refinement loop (:256-301) inside it.  Returns the number of instances that
+ * solved (negative = PQ_ERR_*).  The lhs blocks of an instance whose last factorisation failed are not touched; those of an instance that went non-finite are
+ * unspecified.  Outputs must not overlap inputs.  PQ_ERR_INVALID before the first factorisation. */
+int pq_kktsys_batch_solve(pq_kktsys_batch *k, const pq_vars *rhs, pq_vars *lhs, int mem);
+/* kkt_system.hpp:392-425 per instance, one launch: rhs = K_full lhs with the scalings of the last update_scalings_and_factor */
+int pq_kktsys_batch_mul(pq_kktsys_batch *k, const pq_vars *lhs, pq_vars *rhs, int mem);
+/* of the last solve, host arrays [batch], any may be NULL: solve_ok 1 / 0 (0: a non-finite refine error, a non-finite lhs without refinement, a failed last
+ * factorisation), refinement steps taken, backend solves of that solve, the last refine error and the norm of the condensed right-hand side (refinement only) */
+int pq_kktsys_batch_info(const pq_kktsys_batch *k, int *solve_ok, int *refine_steps, int *backend_solves, double *refine_error, double *rhs_norm);
+/* what: the condensed-system vectors the oracle keeps, copied to HOST memory [batch][len]: x_reg (n; includes the static regularisation), z_reg (m; without it),
+ * rhs_x_bar (n), rhs_z_bar (m) of the last solve */
+enum { PQ_KKTSYS_BATCH_X_REG = 0, PQ_KKTSYS_BATCH_Z_REG = 1, PQ_KKTSYS_BATCH_RHS_X_BAR = 2, PQ_KKTSYS_BATCH_RHS_Z_BAR = 3 };
+int pq_kktsys_batch_state(pq_kktsys_batch *k, int what, double *out_host);
+/* device time (hipEvents) of the last factor, solve and mul launch, ms */
+int pq_kktsys_batch_last_ms(const pq_kktsys_batch *k, double out3[3]);
+
 /* ===================== small utilities used by the measurement harness ===================== */
 /* fp64 MFMA / HBM micro-benchmarks on `device` (used once by bench.py to report measured peaks) */
 /* number of device / pinned-host allocations the library has made in this process.  Contract (the reference's tests assert allocation-free

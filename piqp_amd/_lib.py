@@ -90,6 +90,9 @@ SYMBOLS = [
     "pq_kkt_batch_create_dense", "pq_kkt_batch_destroy", "pq_kkt_batch_clone", "pq_kkt_batch_dims", "pq_kkt_batch_update_data_dense", "pq_kkt_batch_update_scalings_and_factor",
     "pq_kkt_batch_info", "pq_kkt_batch_solve", "pq_kkt_batch_eval_P_x", "pq_kkt_batch_eval_A_xn_and_AT_xt", "pq_kkt_batch_eval_G_xn_and_GT_xt", "pq_kkt_batch_internal_kkt_mat",
     "pq_kkt_batch_internal_factor", "pq_kkt_batch_last_ms",
+    "pq_kktsys_batch_create_dense", "pq_kktsys_batch_destroy", "pq_kktsys_batch_clone", "pq_kktsys_batch_dims", "pq_kktsys_batch_backend", "pq_kktsys_batch_update_data_dense",
+    "pq_kktsys_batch_set_settings", "pq_kktsys_batch_update_scalings_and_factor", "pq_kktsys_batch_solve", "pq_kktsys_batch_mul", "pq_kktsys_batch_info", "pq_kktsys_batch_state",
+    "pq_kktsys_batch_last_ms",
     "pq_debug_alloc_count", "pq_debug_chol_plan", "pq_debug_syrk_plan", "pq_debug_device_sqrt", "pq_kkt_set_exchange_norm", "pq_kkt_sharded_calls", "pq_kkt_sharded_solve_calls", "pq_solver_sharded_solve_calls", "pq_solver_set_exchange_norm", "pq_solver_sharded_calls", "pq_microbench_mfma_f64", "pq_microbench_hbm_copy", "pq_microbench_potrf_block", "pq_debug_potrf_block", "pq_rccl_unique_id", "pq_kkt_set_comm_rccl", "pq_solver_set_comm_rccl", "pq_kkt_native_exchange_calls", "pq_kkt_min_abs_pivot", "pq_solver_native_exchange_calls",
     "pq_solver_setup_sparse_mem", "pq_solver_update_sparse_mem", "pq_debug_sparse_ingest_maps",
     "pq_solver_setup_dense_mem", "pq_solver_update_dense_mem", "pq_solver_get_result_mem", "pq_solver_last_ingest", "pq_batch_update_mem", "pq_batch_update_data_mem",
@@ -197,6 +200,21 @@ def load():
     L.pq_kkt_batch_internal_kkt_mat.argtypes = [vp, C.c_int, vp]
     L.pq_kkt_batch_internal_factor.argtypes = [vp, C.c_int, vp]
     L.pq_kkt_batch_last_ms.argtypes = [vp, vp]
+    L.pq_kktsys_batch_create_dense.argtypes = [C.POINTER(vp)] + [C.c_int] * 5 + [vp, vp, vp] + [C.c_int] * 4 + [vp] * 5 + [C.POINTER(Settings), C.c_int]
+    L.pq_kktsys_batch_destroy.argtypes = [vp]
+    L.pq_kktsys_batch_destroy.restype = None
+    L.pq_kktsys_batch_clone.argtypes = [vp, C.POINTER(vp)]
+    L.pq_kktsys_batch_dims.argtypes = [vp, _ip, _ip, _ip, _ip]
+    L.pq_kktsys_batch_backend.argtypes = [vp]
+    L.pq_kktsys_batch_backend.restype = vp
+    L.pq_kktsys_batch_update_data_dense.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int]
+    L.pq_kktsys_batch_set_settings.argtypes = [vp, C.POINTER(Settings)]
+    L.pq_kktsys_batch_update_scalings_and_factor.argtypes = [vp, vp, vp, vp, C.POINTER(Vars), C.c_int]
+    L.pq_kktsys_batch_solve.argtypes = [vp, C.POINTER(Vars), C.POINTER(Vars), C.c_int]
+    L.pq_kktsys_batch_mul.argtypes = [vp, C.POINTER(Vars), C.POINTER(Vars), C.c_int]
+    L.pq_kktsys_batch_info.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.pq_kktsys_batch_state.argtypes = [vp, C.c_int, vp]
+    L.pq_kktsys_batch_last_ms.argtypes = [vp, vp]
     L.pq_kkt_set_profiling.argtypes = [vp, C.c_int]
     L.pq_kkt_get_profile.argtypes = [vp, C.c_int, _dp, _ip]
     L.pq_kktsys_create_dense.argtypes = [C.POINTER(vp), C.POINTER(DenseData), C.POINTER(Settings), C.c_int]

@@ -16,8 +16,10 @@ LIB = os.path.join(OUT, "libpiqp_amd.so")
 # sums are re-associated for the matrix cores anyway and they are held to the 1e-10 residual bar, not to bits.  dense_exact.hip (kkt_solver =
 # dense_cholesky_exact) replays the one oracle file that IS contracted, oracle/orc_dense.c: it writes each of that file's fused operations as an explicit fma()
 # and must not get any other; dense_factor_batch.hip (pq_dense_factor_batch_*) does the same for the factorisation and solve routines of that file, per matrix of a batch,
-# and dense_kkt_batch.hip (pq_kkt_batch_*) for that file's whole dense KKT backend, per instance of a batch.
-NO_CONTRACT = {"kkt_system.hip", "device_ipm.hip", "sparse_ops.hip", "sparse_exact.hip", "ruiz_kernels.hip", "solver.cpp", "dense_exact.hip", "dense_factor_batch.hip", "dense_kkt_batch.hip"}
+# and dense_kkt_batch.hip (pq_kkt_batch_*) for that file's whole dense KKT backend, per instance of a batch.  dense_kktsys_batch.hip (pq_kktsys_batch_*) is the
+# KKTSystem shell over that backend: its own formulas are the uncontracted ones of kkt_system.hip, the fused ones are the explicit fma() of the shared kb_* pieces.
+NO_CONTRACT = {"kkt_system.hip", "device_ipm.hip", "sparse_ops.hip", "sparse_exact.hip", "ruiz_kernels.hip", "solver.cpp", "dense_exact.hip", "dense_factor_batch.hip", "dense_kkt_batch.hip",
+               "dense_kktsys_batch.hip"}
 
 
 def sources():
