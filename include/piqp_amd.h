@@ -35,7 +35,8 @@ typedef enum {
     PQ_ERR_INVALID = -1,     /* bad argument / size mismatch */
     PQ_ERR_HIP = -2,         /* HIP runtime error (see pq_last_error_string) */
     PQ_ERR_UNSUPPORTED = -3, /* kkt solver not supported (kkt_system.hpp:464-465,493-494) */
-    PQ_ERR_NOMEM = -4
+    PQ_ERR_NOMEM = -4,
+    PQ_ERR_INTERNAL = -5     /* a bounded loop of the library reached its bound (pq_solver_batch_solve) */
 } pq_status;
 
 typedef enum { PQ_MEM_HOST = 0, PQ_MEM_DEVICE = 1 } pq_mem;
@@ -654,6 +655,53 @@ enum { PQ_KKTSYS_BATCH_X_REG = 0, PQ_KKTSYS_BATCH_Z_REG = 1, PQ_KKTSYS_BATCH_RHS
 int pq_kktsys_batch_state(pq_kktsys_batch *k, int what, double *out_host);
 /* device time (hipEvents) of the last factor, solve and mul launch, ms */
 int pq_kktsys_batch_last_ms(const pq_kktsys_batch *k, double out3[3]);
+
+/* ===================== DenseSolver for a BATCH of small dense QPs (over the KKTSystem above) ===================== */
+/* The device equivalent of
+ *     for (i < batch) { DenseSolver s; s.settings() = settings; s.setup(P_i, c_i, A_i, b_i, G_i, h_l_i, h_u_i, x_l_i, x_u_i); s.solve(); }
+ * (csrc/dense_solver_batch.hip): per instance status, iterations, trace, results and every non-time info field are those of the CPU oracle (oracle/orc_solver.c) bit
+ * for bit.  n <= PQ_KKT_BATCH_DENSE_MAX_N; p and m are not limited; settings->kkt_solver is PQ_DENSE_CHOLESKY or PQ_DENSE_LDLT_NO_PIVOT.  The instances share n, p, m,
+ * one pq_settings and the set of finite bounds.  The solve runs in rounds clocked by the host: a small kernel advances every instance to its next KKTSystem call, then
+ * the factor launch and the solve launch of pq_kktsys_batch_* run on the instances that asked for them; the host reads three counters per round.  The instances need
+ * not run in lock step; an instance that has ended is not touched again.
+ * There is no update() and no clone() yet: a changed problem goes through pq_solver_batch_setup_dense again (the reference's update un-scales and re-scales all
+ * three matrices even when only vectors change, and its dense backend then does not recompute A'A; reproducing that bit for bit is left to a later change).
+ * Every argument is checked before the device is touched: PQ_ERR_UNSUPPORTED for n > 128; PQ_ERR_INVALID for batch < 1, n < 1, negative p or m, another kkt_solver,
+ * a NULL P or c, a NULL matrix with a positive count, iterative_refinement_max_iter outside [0, 64], a bad mem or order, a solve before a setup (status PQ_UNSOLVED)
+ * and settings that verify_settings refuses (every instance PQ_INVALID_SETTINGS, no launch). */
+typedef struct pq_solver_batch pq_solver_batch;
+int pq_solver_batch_create(pq_solver_batch **out, int device);
+void pq_solver_batch_destroy(pq_solver_batch *s);
+pq_settings *pq_solver_batch_settings(pq_solver_batch *s); /* shared by all instances; kkt_solver and the preconditioner fields are read by setup */
+/* DenseSolver::setup per instance.  P [batch] n x n, A [batch] p x n, G [batch] m x n: stacks of matrices in the layout `order` (PQ_COL_MAJOR / PQ_ROW_MAJOR) and
+ * under the ordering contract of pq_solver_setup_dense_mem; vectors [batch][len]; NULL optionals as in the single solver.  mem: where EVERY array lives.  The
+ * finite-bound pattern is taken from instance 0; another instance that differs is refused (PQ_ERR_INVALID, as pq_batch_update does).  Rows of G without a finite bound
+ * are zeroed (disable_inf_constraints), the Ruiz equilibration runs per instance (one kernel), and the internal pq_kktsys_batch is created on the scaled data.  May be
+ * called again on the same handle; it is the only call besides create and destroy that may allocate.  Returns 1. */
+int pq_solver_batch_setup_dense(pq_solver_batch *s, int batch, int n, int p, int m, const double *P, const double *c, const double *A, const double *b,
+                                const double *G, const double *h_l, const double *h_u, const double *x_l, const double *x_u, int mem, int order);
+/* solve() of every instance; returns the number of instances that ended PQ_SOLVED (>= 0).  The number of rounds is bounded before the loop starts by
+ * (max_iter + 1) (max_factor_retires + 4); a loop that reaches the bound returns PQ_ERR_INTERNAL and leaves every unfinished instance PQ_UNSOLVED. */
+int pq_solver_batch_solve(pq_solver_batch *s);
+/* result().info of one instance, n_factor and n_solve included; solve_time and run_time are the batch's, the other time fields are 0 */
+const pq_info *pq_solver_batch_info(const pq_solver_batch *s, int instance);
+/* field 0..9 of Variables of ALL instances into a host or device array [batch][len], len as in the single solver's result (the box vectors at full length n,
+ * restore_dual applied).  Device mode makes no allocation. */
+int pq_solver_batch_get_result_mem(pq_solver_batch *s, int field, double *out, int mem);
+/* the 11-column table of solver.hpp:590-602 per instance, kept in device memory during the solve.  set_trace: rows per instance, before the setup (which sizes the
+ * buffer; afterwards only a smaller number is accepted); every solve starts at row 0.  get_trace: rows_out rows of 11 doubles to HOST memory (out_host may be NULL) */
+int pq_solver_batch_set_trace(pq_solver_batch *s, int max_rows);
+int pq_solver_batch_get_trace(pq_solver_batch *s, int instance, double *out_host, int *rows_out);
+int pq_solver_batch_dims(const pq_solver_batch *s, int *batch, int *n, int *p, int *m);
+/* of the last solve: out6 = { wall ms, device ms summed over its launches (hipEvents), rounds, launches, device ms of the factor launches, of the solve launches } */
+int pq_solver_batch_last_ms(const pq_solver_batch *s, double out6[6]);
+/* test hooks.  scaled_data: one item of one instance after setup, to HOST memory: the scaled P_utri (n x n), AT (n x p), GT (n x m), c, b, h_l, h_u, x_l, x_u (the box
+ * bounds compressed to the lists), x_b_scaling, and delta (n + p + m), delta_b (n), c (1) of the preconditioner.  kktsys: the borrowed KKT system; after a solve it is
+ * in the state the last factorisation and the last solve of each instance left. */
+enum { PQ_SOLVER_BATCH_P_UTRI = 0, PQ_SOLVER_BATCH_AT, PQ_SOLVER_BATCH_GT, PQ_SOLVER_BATCH_C, PQ_SOLVER_BATCH_B, PQ_SOLVER_BATCH_H_L, PQ_SOLVER_BATCH_H_U,
+       PQ_SOLVER_BATCH_X_L, PQ_SOLVER_BATCH_X_U, PQ_SOLVER_BATCH_X_B_SCALING, PQ_SOLVER_BATCH_PRECOND_DELTA, PQ_SOLVER_BATCH_PRECOND_DELTA_B, PQ_SOLVER_BATCH_PRECOND_C };
+int pq_solver_batch_scaled_data(pq_solver_batch *s, int instance, int what, double *out_host);
+pq_kktsys_batch *pq_solver_batch_kktsys(pq_solver_batch *s);
 
 /* ===================== small utilities used by the measurement harness ===================== */
 /* fp64 MFMA / HBM micro-benchmarks on `device` (used once by bench.py to report measured peaks) */

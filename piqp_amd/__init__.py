@@ -15,4 +15,5 @@ from .batch import BatchSparseSolver  # noqa: E402,F401
 from .factor import LLT, LDLTNoPivot, BatchLLT, BatchLDLTNoPivot, LOWER, UPPER  # noqa: E402,F401
 from .batch_kkt import KKT_BATCH_DENSE_MAX_N, BatchDenseKKT  # noqa: E402,F401
 from .batch_kktsys import BatchKKTSystem  # noqa: E402,F401
+from .batch_dense import BatchDenseSolver  # noqa: E402,F401
 from .kkt import COL_MAJOR, MEM_DEVICE, MEM_HOST, ROW_MAJOR, tensor_layout  # noqa: E402,F401

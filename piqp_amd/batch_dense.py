@@ -1,0 +1,184 @@
+"""BatchDenseSolver: `batch` small dense QPs (n <= 128) through piqp::DenseSolver's setup() and solve(), behind pq_solver_batch_* (include/piqp_amd.h).  The
+interior-point state of every instance lives on the GPU; the host clocks rounds of three launches (csrc/dense_solver_batch.hip).  Per instance status, iterations,
+trace, results and info are bit for bit the CPU oracle's."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import VAR_NAMES, check
+from .batch_kkt import KKT_BATCH_DENSE_MAX_N
+from .batch_kktsys import BatchKKTSystem
+from .kkt import (COL_MAJOR, DENSE_CHOLESKY, DENSE_LDLT_NO_PIVOT, MEM_DEVICE, MEM_HOST, ROW_MAJOR, _Handle, _is_torch, check_device_tensor, device_call,
+                  sync_current_stream, to_device_args)
+
+SCALED_ITEMS = ("P_utri", "AT", "GT", "c", "b", "h_l", "h_u", "x_l", "x_u", "x_b_scaling", "delta", "delta_b", "c_scale")  # PQ_SOLVER_BATCH_*
+_NAMES = ("P", "c", "A", "b", "G", "h_l", "h_u", "x_l", "x_u")
+
+
+def stack_layout(t):
+    """(tensor to pass, order) for a torch stack [batch, rows, cols]: contiguous is ROW_MAJOR, a stack of transposed views of contiguous matrices is COL_MAJOR,
+    anything else is made contiguous first"""
+    if t.is_contiguous():
+        return t, ROW_MAJOR
+    if t.transpose(1, 2).is_contiguous():
+        return t, COL_MAJOR
+    return t.contiguous(), ROW_MAJOR
+
+
+class BatchDenseSolver(_Handle):
+    """BatchDenseSolver(device=0, kkt_solver=DENSE_CHOLESKY)
+
+    s.settings: the pq_settings shared by the batch.  s.setup(P, c, A=None, b=None, G=None, h_l=None, h_u=None, x_l=None, x_u=None): P [batch, n, n], A [batch, p, n],
+    G [batch, m, n], vectors [batch, len]; NumPy arrays, or torch CUDA float64 tensors (with any CUDA tensor among the arguments the data stays on the GPU and NumPy
+    arguments beside it are moved there).  The instances share the set of finite bounds.  s.solve() returns the number of instances that ended SOLVED.  There is no
+    update(): a changed problem goes through setup() again."""
+    _destroy = "pq_solver_batch_destroy"
+
+    def __init__(self, device=0, kkt_solver=DENSE_CHOLESKY):
+        if kkt_solver not in (DENSE_CHOLESKY, DENSE_LDLT_NO_PIVOT):
+            raise ValueError(f"kkt_solver {kkt_solver}: DENSE_CHOLESKY or DENSE_LDLT_NO_PIVOT")
+        self.L = _lib.load()
+        self.device = int(device)
+        self.kkt_solver = int(kkt_solver)
+        self.batch = self.n = self.p = self.m = None
+        h = C.c_void_p()
+        check(self.L.pq_solver_batch_create(C.byref(h), self.device), "pq_solver_batch_create")
+        self.h = h
+        self.settings.kkt_solver = self.kkt_solver
+
+    @property
+    def settings(self):
+        return self.L.pq_solver_batch_settings(self.h).contents
+
+    # ---- argument handling: no library call in here
+    @staticmethod
+    def shapes(P, A, G):
+        """(batch, n, p, m) and the expected shape of every argument"""
+        shape = tuple(P.shape)
+        if len(shape) != 3 or shape[1] != shape[2]:
+            raise ValueError(f"P: shape {shape}, expected [batch, n, n]")
+        b, n = int(shape[0]), int(shape[1])
+        if n > KKT_BATCH_DENSE_MAX_N:
+            raise ValueError(f"n = {n}: the batched dense solver takes n <= {KKT_BATCH_DENSE_MAX_N}")
+        for name, M in (("A", A), ("G", G)):
+            if M is not None and (len(M.shape) != 3 or M.shape[0] != b or M.shape[2] != n):
+                raise ValueError(f"{name}: shape {tuple(M.shape)}, expected [{b}, rows, {n}]")
+        p = 0 if A is None else int(A.shape[1])
+        m = 0 if G is None else int(G.shape[1])
+        return (b, n, p, m), dict(P=(b, n, n), c=(b, n), A=(b, p, n), b=(b, p), G=(b, m, n), h_l=(b, m), h_u=(b, m), x_l=(b, n), x_u=(b, n))
+
+    def _prepare(self, args):
+        """(dims, mem, order, the arrays to pass in the order of _NAMES); raises before any library call"""
+        a = dict(zip(_NAMES, args))
+        if a["P"] is None or a["c"] is None:
+            raise ValueError("P and c must be given")
+        dims, shapes = self.shapes(a["P"], a["A"], a["G"])
+        if a["A"] is None and a["b"] is not None or a["G"] is None and (a["h_l"] is not None or a["h_u"] is not None):
+            raise ValueError("b without A, or h_l / h_u without G")
+        if device_call(args):
+            mats = {}
+            for k in ("P", "A", "G"):
+                if a[k] is not None and _is_torch(a[k]):
+                    mats[k] = stack_layout(check_device_tensor(k, a[k], shapes[k], self.device))
+                    a[k] = None
+            keep, _ = to_device_args(a, shapes, self.device)
+            orders = {v[1] for v in mats.values()}
+            order = COL_MAJOR if orders == {COL_MAJOR} and all(keep[k] is None for k in ("P", "A", "G")) else ROW_MAJOR
+            for k, (t, o) in mats.items():
+                keep[k] = t if o == order else t.contiguous()
+            return dims, MEM_DEVICE, order, [keep[k] for k in _NAMES]
+        out = []
+        for k in _NAMES:
+            v = a[k]
+            if v is not None:
+                v = np.ascontiguousarray(v, dtype=np.float64)
+                if v.shape != shapes[k]:
+                    raise ValueError(f"{k}: shape {v.shape}, expected {shapes[k]}")
+            out.append(v)
+        return dims, MEM_HOST, ROW_MAJOR, out
+
+    @staticmethod
+    def _p(a):
+        if a is None:
+            return None
+        return a.data_ptr() if _is_torch(a) else a.ctypes.data
+
+    # ---- the DenseSolver surface
+    def enable_trace(self, max_rows=512):
+        """keeps the per-iteration table of every instance in device memory; call before setup()"""
+        check(self.L.pq_solver_batch_set_trace(self.h, int(max_rows)), "pq_solver_batch_set_trace")
+
+    def setup(self, P, c, A=None, b=None, G=None, h_l=None, h_u=None, x_l=None, x_u=None):
+        dims, mem, order, arrs = self._prepare((P, c, A, b, G, h_l, h_u, x_l, x_u))
+        if mem == MEM_DEVICE:
+            sync_current_stream(self.device)
+        check(self.L.pq_solver_batch_setup_dense(self.h, *dims, *[self._p(v) for v in arrs], mem, order), "pq_solver_batch_setup_dense")
+        self.batch, self.n, self.p, self.m = dims
+
+    def solve(self):
+        return check(self.L.pq_solver_batch_solve(self.h), "pq_solver_batch_solve")
+
+    def info(self, i):
+        ptr = self.L.pq_solver_batch_info(self.h, int(i))
+        if not ptr:
+            raise IndexError(self.L.pq_last_error_string().decode())
+        return ptr.contents
+
+    def statuses(self):
+        return np.array([self.info(i).status for i in range(self.batch)], dtype=np.int32)
+
+    def iterations(self):
+        return np.array([self.info(i).iter for i in range(self.batch)], dtype=np.int32)
+
+    def result(self, name, device=False):
+        """field `name` of Variables of all instances, [batch, len]: a NumPy array, or with device=True a torch CUDA tensor (no copy across the link)"""
+        field = VAR_NAMES.index(name)
+        shape = (self.batch, (self.n, self.p, self.m, self.m, self.n, self.n, self.m, self.m, self.n, self.n)[field])
+        if device:
+            import torch
+            out = torch.empty(shape, dtype=torch.float64, device=f"cuda:{self.device}")
+            sync_current_stream(self.device)
+            check(self.L.pq_solver_batch_get_result_mem(self.h, field, out.data_ptr(), MEM_DEVICE), "pq_solver_batch_get_result_mem")
+            return out
+        out = np.zeros(shape)
+        check(self.L.pq_solver_batch_get_result_mem(self.h, field, out.ctypes.data, MEM_HOST), "pq_solver_batch_get_result_mem")
+        return out
+
+    def trace(self, i):
+        rows = C.c_int(0)
+        check(self.L.pq_solver_batch_get_trace(self.h, int(i), None, C.byref(rows)), "pq_solver_batch_get_trace")
+        out = np.zeros((rows.value, 11))
+        if rows.value:
+            check(self.L.pq_solver_batch_get_trace(self.h, int(i), out.ctypes.data, C.byref(rows)), "pq_solver_batch_get_trace")
+        return out
+
+    def last_ms(self):
+        """of the last solve: dict(wall_ms, device_ms, rounds, launches, factor_ms, solve_ms)"""
+        o = np.zeros(6)
+        check(self.L.pq_solver_batch_last_ms(self.h, o.ctypes.data), "pq_solver_batch_last_ms")
+        return dict(wall_ms=float(o[0]), device_ms=float(o[1]), rounds=int(o[2]), launches=int(o[3]), factor_ms=float(o[4]), solve_ms=float(o[5]))
+
+    def max_rounds(self):
+        """the bound on the rounds of a solve with the present settings"""
+        return (self.settings.max_iter + 1) * (self.settings.max_factor_retires + 4)
+
+    # ---- test hooks
+    def scaled_data(self, i, name):
+        n, p, m = self.n, self.p, self.m
+        what = SCALED_ITEMS.index(name)
+        shape = ((n, n), (n, p), (n, m), (n,), (p,), (m,), (m,), (n,), (n,), (n,), (n + p + m,), (n,), (1,))[what]
+        out = np.zeros(shape, order="F")
+        check(self.L.pq_solver_batch_scaled_data(self.h, int(i), what, out.ctypes.data), "pq_solver_batch_scaled_data")
+        return out
+
+    def kktsys(self):
+        """the BatchKKTSystem this solver owns (borrowed: it lives until the next setup() or the end of this object)"""
+        h = self.L.pq_solver_batch_kktsys(self.h)
+        if not h:
+            raise RuntimeError(self.L.pq_last_error_string().decode())
+        k = BatchKKTSystem.__new__(BatchKKTSystem)
+        k.L, k.device, k.h = self.L, self.device, C.c_void_p(h)
+        k.batch, k.n, k.p, k.m, k.kkt_solver = self.batch, self.n, self.p, self.m, self.kkt_solver
+        k._owned, k._parent = False, self
+        return k

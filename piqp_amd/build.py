@@ -18,8 +18,10 @@ LIB = os.path.join(OUT, "libpiqp_amd.so")
 # and must not get any other; dense_factor_batch.hip (pq_dense_factor_batch_*) does the same for the factorisation and solve routines of that file, per matrix of a batch,
 # and dense_kkt_batch.hip (pq_kkt_batch_*) for that file's whole dense KKT backend, per instance of a batch.  dense_kktsys_batch.hip (pq_kktsys_batch_*) is the
 # KKTSystem shell over that backend: its own formulas are the uncontracted ones of kkt_system.hip, the fused ones are the explicit fma() of the shared kb_* pieces.
+# dense_solver_batch.hip (pq_solver_batch_*) is the interior-point loop and the equilibration over that shell, per instance of a batch: oracle/orc_solver.c, which is
+# built without contraction, with the three mat-vec evaluators of the contracted orc_dense.c as explicit fma().
 NO_CONTRACT = {"kkt_system.hip", "device_ipm.hip", "sparse_ops.hip", "sparse_exact.hip", "ruiz_kernels.hip", "solver.cpp", "dense_exact.hip", "dense_factor_batch.hip", "dense_kkt_batch.hip",
-               "dense_kktsys_batch.hip"}
+               "dense_kktsys_batch.hip", "dense_solver_batch.hip"}
 
 
 def sources():

@@ -20,3 +20,15 @@ struct pq_kkt_batch {
     double wall_ms = 0.0;
     pq::Stream st;
 };
+
+// The two heavy launches of a pq_kktsys_batch (dense_kktsys_batch.hip) on their own, for dense_solver_batch.hip, which clocks them in rounds: every pointer is
+// device memory, the launch goes on the handle's stream, nothing is read back and nothing waits.  active: null = every instance; else int [batch], an instance
+// whose word is 0 is left out (it reads nothing, writes nothing, and in the n < 32 variant its wave still reaches every barrier of its workgroup).
+namespace pq {
+void ksb_launch_factor(pq_kktsys_batch* k, const int* flags, const double* rho, const double* delta, const pq_vars& v, const int* active);
+void ksb_launch_solve(pq_kktsys_batch* k, const pq_vars& rhs, const pq_vars& lhs, const int* active);
+hipStream_t ksb_stream(pq_kktsys_batch* k);
+const int* ksb_factor_status(const pq_kktsys_batch* k);  // device, [batch]: 0 = the instance's last factorisation succeeded
+const int* ksb_solve_info(const pq_kktsys_batch* k);     // device, [3][batch]: solve_ok, refine steps, backend solves of the instance's last solve
+void ksb_refresh_host(pq_kktsys_batch* k);               // reads status and diagnostics back as the public calls do, marks the handles factored and solved; waits
+}  // namespace pq

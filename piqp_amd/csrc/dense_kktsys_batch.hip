@@ -66,6 +66,7 @@ struct KsbFactorArgs {
     int n, p, m, ld, width, batch, nxl, nxu;
     const double *Pu, *ATA, *GT;  // the backend's data
     const int* flags;             // [batch] or null (off everywhere)
+    const int* active;            // [batch] or null (every instance): an instance whose word is 0 is left out -- nothing of it is read or written
     const double *rho, *delta;    // [batch]
     const double *v_s_l, *v_z_l, *v_s_u, *v_z_u, *v_s_bl, *v_z_bl, *v_s_bu, *v_z_bu;  // the caller's state, [batch][m] resp. [batch][n]
     const int *has_l, *has_u, *pos_l, *pos_u;  // row i has a lower / upper bound (>= 0); variable i is entry pos of the lower / upper box list (or -1)
@@ -87,7 +88,7 @@ __global__ __launch_bounds__(DFB_THREADS) void k_ksb_factor(const KsbFactorArgs 
     const int n = A.n, m = A.m, ld = A.ld;
     const int g = threadIdx.x / G, t = threadIdx.x % G;
     const long long inst = (long long)blockIdx.x * MPW + g;
-    const bool have = inst < A.batch;
+    const bool have = inst < A.batch && (!A.active || A.active[inst] != 0);  // (an instance left out is an empty slot: it still reaches every barrier)
     double* a = ksb_lds + (size_t)g * ((size_t)n * ld + (size_t)(KB_SLICE + 2) * n + KB_SLICE);
     double* dacc = a + (size_t)n * ld;
     double* gs = dacc + n;
@@ -225,6 +226,7 @@ struct KsbSolveArgs {
     double eps_abs, eps_rel, min_rate;
     const double *Pu, *AT, *GT, *F, *delta_s, *x_reg_s, *zinv_s;  // the backend's data, stored scalings and factors
     const int* info;
+    const int* active;  // [batch] or null (every instance): the workgroup of an instance whose word is 0 returns at once
     const double *s_l, *zinv_l, *s_u, *zinv_u, *s_bl, *zinv_bl, *s_bu, *zinv_bu, *z_reg, *mdelta_s, *xbs;  // the state of the last update_scalings_and_factor
     const int *use_ref, *has_l, *has_u, *pos_l, *pos_u, *xl_idx, *xu_idx;
     pq_vars rhs, lhs;                // [batch][len] each; rhs is only read
@@ -298,6 +300,7 @@ __global__ __launch_bounds__(KB_SOLVE_THREADS) void k_ksb_solve(const KsbSolveAr
     __shared__ double s_red[KB_SOLVE_THREADS / 64];
     const long long inst = blockIdx.x;
     const int n = A.n, p = A.p, m = A.m, ld = A.ld, t = threadIdx.x, T = blockDim.x;
+    if (A.active && A.active[inst] == 0) return;  // (uniform: before any barrier)
     if (A.info[inst] != 0) {  // (uniform: before any barrier) the factorisation failed: the lhs blocks are not touched
         if (t == 0) {
             A.sinfo[inst] = 0; A.sinfo[A.batch + inst] = 0; A.sinfo[2 * (size_t)A.batch + inst] = 0;
@@ -686,6 +689,85 @@ int ksb_check_list(const char* name, int cnt, const int* idx, int len)
 
 }  // namespace
 
+// ---- the two heavy launches on their own, without the read-back of their success counts: what the public calls below do between their staging copies and their
+// read-backs, and what the rounds of dense_solver_batch.hip launch with an activity word per instance.  Every pointer is device memory; the launch goes on the
+// handle's stream and nothing waits for it.
+namespace pq {
+
+void ksb_launch_factor(pq_kktsys_batch* k, const int* flags, const double* rho, const double* delta, const pq_vars& v, const int* active)
+{
+    pq_kkt_batch* kb = k->kb.get();
+    const int n = k->n, batch = k->batch;
+    hipStream_t st = kb->st;
+    KsbFactorArgs a;
+    a.n = n; a.p = k->p; a.m = k->m; a.ld = dfb_ld(n); a.width = n < 32 ? n : dfb_block_size_rule(n); a.batch = batch; a.nxl = k->cnt[2]; a.nxu = k->cnt[3];
+    a.Pu = kb->Pu.p; a.ATA = k->p > 0 ? kb->ATA.p : nullptr; a.GT = kb->GT.p;
+    a.flags = flags; a.active = active; a.rho = rho; a.delta = delta;
+    a.v_s_l = v.s_l; a.v_z_l = v.z_l; a.v_s_u = v.s_u; a.v_z_u = v.z_u; a.v_s_bl = v.s_bl; a.v_z_bl = v.z_bl; a.v_s_bu = v.s_bu; a.v_z_bu = v.z_bu;
+    a.has_l = ksb_has_l(k); a.has_u = ksb_has_u(k); a.pos_l = ksb_pos_l(k); a.pos_u = ksb_pos_u(k);
+    a.xbs = k->state[S_XBS].p;
+    a.reg_eps = k->settings.iterative_refinement_static_regularization_eps; a.reg_rel = k->settings.iterative_refinement_static_regularization_rel;
+    a.s_l = k->state[S_SL].p; a.zinv_l = k->state[S_ZIL].p; a.s_u = k->state[S_SU].p; a.zinv_u = k->state[S_ZIU].p;
+    a.s_bl = k->state[S_SBL].p; a.zinv_bl = k->state[S_ZIBL].p; a.s_bu = k->state[S_SBU].p; a.zinv_bu = k->state[S_ZIBU].p;
+    a.z_reg = k->state[S_ZREG].p; a.rho_s = k->state[S_RHO].p; a.mdelta_s = k->state[S_MDELTA].p; a.use_ref = k->use_ref.p;
+    a.delta_s = kb->delta_s.p; a.x_reg_s = kb->x_reg_s.p; a.zinv_s = kb->zinv_s.p; a.F = kb->fac.p; a.info = kb->status.p; a.badcol = kb->status.p + batch;
+    const size_t lds = ksb_factor_lds_bytes(n);
+    if (n < 32) {
+        const int grid = div_up(batch, DFB_THREADS / 64);
+        if (kb->kind == PQ_DENSE_CHOLESKY) k_ksb_factor<0, 64><<<grid, DFB_THREADS, lds, st>>>(a);
+        else k_ksb_factor<1, 64><<<grid, DFB_THREADS, lds, st>>>(a);
+    } else {
+        if (kb->kind == PQ_DENSE_CHOLESKY) k_ksb_factor<0, DFB_THREADS><<<batch, DFB_THREADS, lds, st>>>(a);
+        else k_ksb_factor<1, DFB_THREADS><<<batch, DFB_THREADS, lds, st>>>(a);
+    }
+    PQ_HIP(hipGetLastError());
+}
+
+void ksb_launch_solve(pq_kktsys_batch* k, const pq_vars& rhs, const pq_vars& lhs, const int* active)
+{
+    pq_kkt_batch* kb = k->kb.get();
+    const int n = k->n, batch = k->batch;
+    hipStream_t st = kb->st;
+    KsbSolveArgs a;
+    a.n = n; a.p = k->p; a.m = k->m; a.ld = dfb_ld(n); a.nxl = k->cnt[2]; a.nxu = k->cnt[3]; a.max_iter = k->settings.iterative_refinement_max_iter; a.batch = batch;
+    a.eps_abs = k->settings.iterative_refinement_eps_abs; a.eps_rel = k->settings.iterative_refinement_eps_rel;
+    a.min_rate = k->settings.iterative_refinement_min_improvement_rate;
+    a.Pu = kb->Pu.p; a.AT = kb->AT.p; a.GT = kb->GT.p; a.F = kb->fac.p; a.delta_s = kb->delta_s.p; a.x_reg_s = kb->x_reg_s.p; a.zinv_s = kb->zinv_s.p; a.info = kb->status.p;
+    a.active = active;
+    a.s_l = k->state[S_SL].p; a.zinv_l = k->state[S_ZIL].p; a.s_u = k->state[S_SU].p; a.zinv_u = k->state[S_ZIU].p;
+    a.s_bl = k->state[S_SBL].p; a.zinv_bl = k->state[S_ZIBL].p; a.s_bu = k->state[S_SBU].p; a.zinv_bu = k->state[S_ZIBU].p;
+    a.z_reg = k->state[S_ZREG].p; a.mdelta_s = k->state[S_MDELTA].p; a.xbs = k->state[S_XBS].p;
+    a.use_ref = k->use_ref.p; a.has_l = ksb_has_l(k); a.has_u = ksb_has_u(k); a.pos_l = ksb_pos_l(k); a.pos_u = ksb_pos_u(k); a.xl_idx = ksb_xl_idx(k); a.xu_idx = ksb_xu_idx(k);
+    a.rhs = rhs; a.lhs = lhs;
+    a.rhs_x_bar = k->state[S_RXB].p; a.rhs_z_bar = k->state[S_RZB].p; a.wy = k->wy.p; a.wz = k->wz.p; a.sinfo = k->sinfo.p; a.dinfo = k->dinfo.p;
+    const int threads = n <= 64 ? 64 : KB_SOLVE_THREADS;
+    if (kb->kind == PQ_DENSE_CHOLESKY) k_ksb_solve<0><<<batch, threads, ksb_solve_lds_bytes(n), st>>>(a);
+    else k_ksb_solve<1><<<batch, threads, ksb_solve_lds_bytes(n), st>>>(a);
+    PQ_HIP(hipGetLastError());
+}
+
+hipStream_t ksb_stream(pq_kktsys_batch* k) { return k->kb->st; }
+const int* ksb_factor_status(const pq_kktsys_batch* k) { return k->kb->status.p; }
+const int* ksb_solve_info(const pq_kktsys_batch* k) { return k->sinfo.p; }
+
+// after launches of the two functions above: the host side of both handles as the public calls leave it (status, counts and diagnostics read back; waits)
+void ksb_refresh_host(pq_kktsys_batch* k)
+{
+    pq_kkt_batch* kb = k->kb.get();
+    const int batch = k->batch;
+    hipStream_t st = kb->st;
+    PQ_HIP(hipMemcpyAsync(kb->status_h.p, kb->status.p, sizeof(int) * 2 * batch, hipMemcpyDeviceToHost, st));
+    PQ_HIP(hipMemcpyAsync(k->sinfo_h.p, k->sinfo.p, sizeof(int) * 3 * batch, hipMemcpyDeviceToHost, st));
+    PQ_HIP(hipMemcpyAsync(k->dinfo_h.p, k->dinfo.p, sizeof(double) * 2 * batch, hipMemcpyDeviceToHost, st));
+    stream_wait(st);
+    int good = 0, solved = 0;
+    for (int b = 0; b < batch; ++b) { good += kb->status_h.p[b] == 0; solved += k->sinfo_h.p[b] != 0; }
+    kb->n_ok = good; kb->computed = true;
+    k->n_solved = solved; k->solved = true;
+}
+
+}  // namespace pq
+
 extern "C" {
 
 int pq_kktsys_batch_create_dense(pq_kktsys_batch** out, int device, int batch, int n, int p, int m, const double* P_utri, const double* AT, const double* GT, int n_h_l,
@@ -813,42 +895,23 @@ int pq_kktsys_batch_update_scalings_and_factor(pq_kktsys_batch* k, const int* it
     const int rc = guarded([&] {
         PQ_HIP(hipSetDevice(k->device));
         pq_kkt_batch* kb = k->kb.get();
-        const int n = k->n, batch = k->batch;
+        const int batch = k->batch;
         const auto w0 = std::chrono::steady_clock::now();
         hipStream_t st = kb->st;
-        KsbFactorArgs a;
-        a.n = n; a.p = k->p; a.m = k->m; a.ld = dfb_ld(n); a.width = n < 32 ? n : dfb_block_size_rule(n); a.batch = batch; a.nxl = k->cnt[2]; a.nxu = k->cnt[3];
-        a.Pu = kb->Pu.p; a.ATA = k->p > 0 ? kb->ATA.p : nullptr; a.GT = kb->GT.p;
+        const int* flags = iterative_refinement;
+        const double *rho_d = rho, *delta_d = delta;
         size_t off = 0;
-        if (mem == PQ_MEM_DEVICE) { a.flags = iterative_refinement; a.rho = rho; a.delta = delta; }
-        else {
-            a.flags = iterative_refinement ? k->flags_d.p : nullptr;
+        if (mem != PQ_MEM_DEVICE) {
+            flags = iterative_refinement ? k->flags_d.p : nullptr;
             if (iterative_refinement) PQ_HIP(hipMemcpyAsync(k->flags_d.p, iterative_refinement, sizeof(int) * batch, hipMemcpyHostToDevice, st));
             PQ_HIP(hipMemcpyAsync(k->stage_in.p, rho, sizeof(double) * batch, hipMemcpyHostToDevice, st));
             PQ_HIP(hipMemcpyAsync(k->stage_in.p + batch, delta, sizeof(double) * batch, hipMemcpyHostToDevice, st));
-            a.rho = k->stage_in.p; a.delta = k->stage_in.p + batch;
+            rho_d = k->stage_in.p; delta_d = k->stage_in.p + batch;
             off = 2 * (size_t)batch;
         }
         const pq_vars v = ksb_vars_in(k, vars, 2, mem, off);
-        a.v_s_l = v.s_l; a.v_z_l = v.z_l; a.v_s_u = v.s_u; a.v_z_u = v.z_u; a.v_s_bl = v.s_bl; a.v_z_bl = v.z_bl; a.v_s_bu = v.s_bu; a.v_z_bu = v.z_bu;
-        a.has_l = ksb_has_l(k); a.has_u = ksb_has_u(k); a.pos_l = ksb_pos_l(k); a.pos_u = ksb_pos_u(k);
-        a.xbs = k->state[S_XBS].p;
-        a.reg_eps = k->settings.iterative_refinement_static_regularization_eps; a.reg_rel = k->settings.iterative_refinement_static_regularization_rel;
-        a.s_l = k->state[S_SL].p; a.zinv_l = k->state[S_ZIL].p; a.s_u = k->state[S_SU].p; a.zinv_u = k->state[S_ZIU].p;
-        a.s_bl = k->state[S_SBL].p; a.zinv_bl = k->state[S_ZIBL].p; a.s_bu = k->state[S_SBU].p; a.zinv_bu = k->state[S_ZIBU].p;
-        a.z_reg = k->state[S_ZREG].p; a.rho_s = k->state[S_RHO].p; a.mdelta_s = k->state[S_MDELTA].p; a.use_ref = k->use_ref.p;
-        a.delta_s = kb->delta_s.p; a.x_reg_s = kb->x_reg_s.p; a.zinv_s = kb->zinv_s.p; a.F = kb->fac.p; a.info = kb->status.p; a.badcol = kb->status.p + batch;
-        const size_t lds = ksb_factor_lds_bytes(n);
         PQ_HIP(hipEventRecord(kb->ev[0], st));
-        if (n < 32) {
-            const int grid = div_up(batch, DFB_THREADS / 64);
-            if (kb->kind == PQ_DENSE_CHOLESKY) k_ksb_factor<0, 64><<<grid, DFB_THREADS, lds, st>>>(a);
-            else k_ksb_factor<1, 64><<<grid, DFB_THREADS, lds, st>>>(a);
-        } else {
-            if (kb->kind == PQ_DENSE_CHOLESKY) k_ksb_factor<0, DFB_THREADS><<<batch, DFB_THREADS, lds, st>>>(a);
-            else k_ksb_factor<1, DFB_THREADS><<<batch, DFB_THREADS, lds, st>>>(a);
-        }
-        PQ_HIP(hipGetLastError());
+        ksb_launch_factor(k, flags, rho_d, delta_d, v, nullptr);
         PQ_HIP(hipEventRecord(kb->ev[1], st));
         PQ_HIP(hipMemcpyAsync(kb->status_h.p, kb->status.p, sizeof(int) * 2 * batch, hipMemcpyDeviceToHost, st));
         stream_wait(st);
@@ -875,28 +938,15 @@ int pq_kktsys_batch_solve(pq_kktsys_batch* k, const pq_vars* rhs, pq_vars* lhs, 
     const int rc = guarded([&] {
         PQ_HIP(hipSetDevice(k->device));
         pq_kkt_batch* kb = k->kb.get();
-        const int n = k->n, batch = k->batch;
+        const int batch = k->batch;
         hipStream_t st = kb->st;
         size_t off = 0;
-        KsbSolveArgs a;
-        a.n = n; a.p = k->p; a.m = k->m; a.ld = dfb_ld(n); a.nxl = k->cnt[2]; a.nxu = k->cnt[3]; a.max_iter = k->settings.iterative_refinement_max_iter; a.batch = batch;
-        a.eps_abs = k->settings.iterative_refinement_eps_abs; a.eps_rel = k->settings.iterative_refinement_eps_rel;
-        a.min_rate = k->settings.iterative_refinement_min_improvement_rate;
-        a.Pu = kb->Pu.p; a.AT = kb->AT.p; a.GT = kb->GT.p; a.F = kb->fac.p; a.delta_s = kb->delta_s.p; a.x_reg_s = kb->x_reg_s.p; a.zinv_s = kb->zinv_s.p; a.info = kb->status.p;
-        a.s_l = k->state[S_SL].p; a.zinv_l = k->state[S_ZIL].p; a.s_u = k->state[S_SU].p; a.zinv_u = k->state[S_ZIU].p;
-        a.s_bl = k->state[S_SBL].p; a.zinv_bl = k->state[S_ZIBL].p; a.s_bu = k->state[S_SBU].p; a.zinv_bu = k->state[S_ZIBU].p;
-        a.z_reg = k->state[S_ZREG].p; a.mdelta_s = k->state[S_MDELTA].p; a.xbs = k->state[S_XBS].p;
-        a.use_ref = k->use_ref.p; a.has_l = ksb_has_l(k); a.has_u = ksb_has_u(k); a.pos_l = ksb_pos_l(k); a.pos_u = ksb_pos_u(k); a.xl_idx = ksb_xl_idx(k); a.xu_idx = ksb_xu_idx(k);
-        a.rhs = ksb_vars_in(k, rhs, 0, mem, off);
-        a.lhs = ksb_vars_out(k, lhs, mem, kb->n_ok < batch);
-        a.rhs_x_bar = k->state[S_RXB].p; a.rhs_z_bar = k->state[S_RZB].p; a.wy = k->wy.p; a.wz = k->wz.p; a.sinfo = k->sinfo.p; a.dinfo = k->dinfo.p;
-        const int threads = n <= 64 ? 64 : KB_SOLVE_THREADS;
+        const pq_vars r = ksb_vars_in(k, rhs, 0, mem, off);
+        const pq_vars l = ksb_vars_out(k, lhs, mem, kb->n_ok < batch);
         PQ_HIP(hipEventRecord(k->ev[0], st));
-        if (kb->kind == PQ_DENSE_CHOLESKY) k_ksb_solve<0><<<batch, threads, ksb_solve_lds_bytes(n), st>>>(a);
-        else k_ksb_solve<1><<<batch, threads, ksb_solve_lds_bytes(n), st>>>(a);
-        PQ_HIP(hipGetLastError());
+        ksb_launch_solve(k, r, l, nullptr);
         PQ_HIP(hipEventRecord(k->ev[1], st));
-        ksb_vars_back(k, lhs, a.lhs, mem);
+        ksb_vars_back(k, lhs, l, mem);
         PQ_HIP(hipMemcpyAsync(k->sinfo_h.p, k->sinfo.p, sizeof(int) * 3 * batch, hipMemcpyDeviceToHost, st));
         PQ_HIP(hipMemcpyAsync(k->dinfo_h.p, k->dinfo.p, sizeof(double) * 2 * batch, hipMemcpyDeviceToHost, st));
         stream_wait(st);
