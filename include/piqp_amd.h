@@ -198,6 +198,12 @@ int pq_kkt_dims(const pq_kkt *k, int *n, int *p, int *m);
  * `capacity` rows of (start, diag_size, off_diag_size) -- the last row is the arrow corner block -- and
  * returns the number of blocks (call with out_host = NULL to size the buffer). */
 int pq_kkt_multistage_block_info(pq_kkt *k, int *out_host, int capacity);
+/* sparse_multistage only (an error for every other backend), read-only: where the chain kernels keep their working set, decided from the block
+ * structure at setup.  out = { engine (0 chain, 1 tree), factor_in_lds, li_in_lds, solve_in_lds, asm_chunks, max_h, max_w, factor_lds_bytes }:
+ * the frontal matrix factored in LDS or in place in HBM, the inverse of the diagonal block staged in LDS or written straight to HBM, the
+ * substitution's panel in LDS or read from HBM, workgroups per stage of the assembly, largest front order, largest panel width, dynamic LDS
+ * of the factorisation kernel. */
+int pq_kkt_multistage_plan(pq_kkt *k, int out[8]);
 /* sparse backends: figures of the symbolic analysis for roofline arithmetic.  out = { N, nnz(PKPt), nnz(L) below
  * the diagonal, supernodes, tree levels, workgroup subtrees, max front order, factorisation flops sum_j (c_j^2 + 3 c_j) } */
 int pq_kkt_sparse_stats(pq_kkt *k, double out[8]);

@@ -460,6 +460,11 @@ int pq_kkt_multistage_block_info(pq_kkt* k, int* out_host, int capacity)
         return N;
     });
 }
+int pq_kkt_multistage_plan(pq_kkt* k, int out[8])
+{
+    if (!k || !out) return fail(PQ_ERR_INVALID, "null argument");
+    return guarded([&] { k->impl->multistage_plan(out); return (int)PQ_OK; });
+}
 int pq_kkt_sparse_stats(pq_kkt* k, double out[8])
 {
     if (!k || !out) return fail(PQ_ERR_INVALID, "null argument");

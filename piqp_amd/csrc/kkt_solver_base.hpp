@@ -52,6 +52,9 @@ public:
     virtual void internal_factor(double* out_host) { (void)out_host; throw std::runtime_error("internal_factor: dense only"); }
     // test hook: rows of (start, diag_size, off_diag_size) of the multistage backend (print_info, multistage_kkt.hpp:385-393)
     virtual void multistage_block_info(std::vector<int>& out) const { (void)out; throw std::runtime_error("block_info: sparse_multistage only"); }
+    // test hook (read-only): where the multistage chain kernels keep their working set -- { engine (0 chain, 1 tree), factor_in_lds, li_in_lds, solve_in_lds,
+    // asm_chunks, max_h, max_w, factor_lds_bytes } (MultistageKKT::plan_lds)
+    virtual void multistage_plan(int out[8]) const { (void)out; throw std::runtime_error("multistage_plan: sparse_multistage only"); }
     // symbolic-analysis figures of the sparse backends for the roofline arithmetic: N, nnz(PKPt), nnz(L) below the
     // diagonal, supernodes, tree levels, workgroup subtrees, max front order, factorisation flops
     virtual void sparse_stats(double out[8]) const { (void)out; throw std::runtime_error("sparse_stats: sparse backends only"); }

@@ -294,6 +294,11 @@ public:
         out.clear();
         for (const auto& b : S_.block_info) { out.push_back(b.start); out.push_back(b.diag_size); out.push_back(b.off_diag_size); }
     }
+    void multistage_plan(int out[8]) const override
+    {
+        const int v[8] = {tree_ ? 1 : 0, factor_in_lds_ ? 1 : 0, li_in_lds_ ? 1 : 0, solve_in_lds_ ? 1 : 0, asm_chunks_, S_.max_h, S_.max_w, factor_lds_bytes_};
+        std::copy(v, v + 8, out);
+    }
 
 private:
     enum { KKT_ALL = 7 };

@@ -437,6 +437,14 @@ class DenseKKT(_Handle):
         check(self.L.pq_kkt_multistage_block_info(self.h, out.ctypes.data, N), "block_info")
         return out
 
+    MULTISTAGE_PLAN_KEYS = ("engine", "factor_in_lds", "li_in_lds", "solve_in_lds", "asm_chunks", "max_h", "max_w", "factor_lds_bytes")
+
+    def multistage_plan(self):
+        """sparse_multistage only: where the chain kernels keep their working set (pq_kkt_multistage_plan), as a dict of ints; engine 0 = chain, 1 = tree."""
+        out = (C.c_int * 8)()
+        check(self.L.pq_kkt_multistage_plan(self.h, out), "multistage_plan")
+        return dict(zip(self.MULTISTAGE_PLAN_KEYS, (int(v) for v in out)))
+
     def internal_kkt_mat(self):
         out = np.zeros((self.n, self.n), order="F")
         check(self.L.pq_kkt_internal_kkt_mat(self.h, out.ctypes.data))

@@ -78,6 +78,36 @@ def test_data_mirror_matches_oracle_data(orc):
     assert np.array_equal(d.x_l[: d.n_x_l], o.vec("x_l")[: d.n_x_l])
 
 
+def test_multistage_plan_refuses_null_handle():
+    """pq_kkt_multistage_plan: a NULL handle is an error, not a crash, and the output is left alone"""
+    import piqp_amd
+    L = piqp_amd._lib.load()
+    out = (C.c_int * 8)(*([-7] * 8))
+    assert L.pq_kkt_multistage_plan(None, out) < 0
+    assert b"null" in L.pq_last_error_string()
+    assert list(out) == [-7] * 8
+
+
+@pytest.mark.gpu
+def test_multistage_plan_refuses_other_backends(hip):
+    """the plan is the multistage backend's: a dense handle and a sparse_ldlt handle answer with an error and leave the output alone"""
+    from qp_gen import dense_strongly_convex_qp, mpc_chain
+    L = hip._lib.load()
+    chain = mpc_chain(4, 2, 5, 1)
+    for k in (hip.DenseKKT(hip.Data(**dense_strongly_convex_qp(12, 3, 5, seed=1))), hip.SparseKKT(hip.SparseData(*chain), kkt_solver=hip.SPARSE_LDLT)):
+        out = (C.c_int * 8)(*([-7] * 8))
+        assert L.pq_kkt_multistage_plan(k.h, out) < 0
+        assert b"sparse_multistage only" in L.pq_last_error_string()
+        assert list(out) == [-7] * 8
+        with pytest.raises(RuntimeError, match="sparse_multistage only"):
+            k.multistage_plan()
+    k = hip.SparseKKT(hip.SparseData(*chain), kkt_solver=hip.SPARSE_MULTISTAGE)
+    assert L.pq_kkt_multistage_plan(k.h, None) < 0
+    plan = k.multistage_plan()
+    assert list(plan) == list(hip.DenseKKT.MULTISTAGE_PLAN_KEYS)
+    assert (plan["engine"], plan["factor_in_lds"], plan["li_in_lds"], plan["solve_in_lds"], plan["asm_chunks"]) == (0, 1, 1, 1, 1)
+
+
 @pytest.mark.gpu
 def test_no_allocation_after_create(hip):
     """fwd.hpp:44-52 / the reference tests' PIQP_EIGEN_MALLOC_NOT_ALLOWED brackets: factor, solve, mat-vecs and the residual allocate nothing.
