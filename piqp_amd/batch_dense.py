@@ -7,9 +7,9 @@ import numpy as np
 
 from . import _lib
 from ._lib import VAR_NAMES, check
-from .batch_kkt import KKT_BATCH_DENSE_MAX_N
-from .batch_kktsys import BatchKKTSystem
-from .kkt import (COL_MAJOR, DENSE_CHOLESKY, DENSE_LDLT_NO_PIVOT, MEM_DEVICE, MEM_HOST, ROW_MAJOR, _Handle, _is_torch, check_device_tensor, device_call,
+from .batch_kkt import KKT_BATCH_DENSE_MAX_N, _BatchHandle, var_shapes
+from .batch_kktsys import BatchKKTSystem, _copy_settings
+from .kkt import (COL_MAJOR, DENSE_CHOLESKY, DENSE_LDLT_NO_PIVOT, MEM_DEVICE, MEM_HOST, ROW_MAJOR, _is_torch, check_device_tensor, device_call,
                   sync_current_stream, to_device_args)
 
 SCALED_ITEMS = ("P_utri", "AT", "GT", "c", "b", "h_l", "h_u", "x_l", "x_u", "x_b_scaling", "delta", "delta_b", "c_scale")  # PQ_SOLVER_BATCH_*
@@ -26,7 +26,7 @@ def stack_layout(t):
     return t.contiguous(), ROW_MAJOR
 
 
-class BatchDenseSolver(_Handle):
+class BatchDenseSolver(_BatchHandle):
     """BatchDenseSolver(device=0, kkt_solver=DENSE_CHOLESKY)
 
     s.settings: the pq_settings shared by the batch.  s.setup(P, c, A=None, b=None, G=None, h_l=None, h_u=None, x_l=None, x_u=None): P [batch, n, n], A [batch, p, n],
@@ -98,12 +98,6 @@ class BatchDenseSolver(_Handle):
             out.append(v)
         return dims, MEM_HOST, ROW_MAJOR, out
 
-    @staticmethod
-    def _p(a):
-        if a is None:
-            return None
-        return a.data_ptr() if _is_torch(a) else a.ctypes.data
-
     # ---- the DenseSolver surface
     def enable_trace(self, max_rows=512):
         """keeps the per-iteration table of every instance in device memory; call before setup()"""
@@ -134,7 +128,7 @@ class BatchDenseSolver(_Handle):
     def result(self, name, device=False):
         """field `name` of Variables of all instances, [batch, len]: a NumPy array, or with device=True a torch CUDA tensor (no copy across the link)"""
         field = VAR_NAMES.index(name)
-        shape = (self.batch, (self.n, self.p, self.m, self.m, self.n, self.n, self.m, self.m, self.n, self.n)[field])
+        shape = var_shapes(self.batch, self.n, self.p, self.m)[name]
         if device:
             import torch
             out = torch.empty(shape, dtype=torch.float64, device=f"cuda:{self.device}")
@@ -173,12 +167,9 @@ class BatchDenseSolver(_Handle):
         return out
 
     def kktsys(self):
-        """the BatchKKTSystem this solver owns (borrowed: it lives until the next setup() or the end of this object)"""
+        """the BatchKKTSystem this solver owns (borrowed: it lives until the next setup() or the end of this object).  The solver keeps the bound lists to itself,
+        so the borrowed system has lists = None: its read-only hooks work, its calls that take variables raise RuntimeError"""
         h = self.L.pq_solver_batch_kktsys(self.h)
         if not h:
             raise RuntimeError(self.L.pq_last_error_string().decode())
-        k = BatchKKTSystem.__new__(BatchKKTSystem)
-        k.L, k.device, k.h = self.L, self.device, C.c_void_p(h)
-        k.batch, k.n, k.p, k.m, k.kkt_solver = self.batch, self.n, self.p, self.m, self.kkt_solver
-        k._owned, k._parent = False, self
-        return k
+        return BatchKKTSystem._adopt(h, self.device, self.kkt_solver, owner=self, lists=None, settings=_copy_settings(self.settings))

@@ -6,33 +6,40 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check
+from ._lib import VAR_NAMES, check
 from .kkt import (DENSE_CHOLESKY, DENSE_LDLT_NO_PIVOT, KKT_UPDATE_A, KKT_UPDATE_G, KKT_UPDATE_P, MEM_DEVICE, MEM_HOST, _Handle, _is_torch,
                   check_device_tensor, sync_current_stream)
 
 KKT_BATCH_DENSE_MAX_N = 128  # PQ_KKT_BATCH_DENSE_MAX_N: the n x n square of an instance lives in LDS
 
 
-class BatchDenseKKT(_Handle):
-    """BatchDenseKKT(P, A=None, G=None, kkt_solver=DENSE_CHOLESKY, device=0)
+def var_shapes(b, n, p, m):
+    """name -> shape of the ten [batch, len] vectors of a batch of piqp_amd.Variables"""
+    return dict(zip(VAR_NAMES, ((b, n), (b, p), (b, m), (b, m), (b, n), (b, n), (b, m), (b, m), (b, n), (b, n))))
 
-    numpy arguments: P [batch, n, n] as written (P[i][r, c] = row r, column c; the upper triangle of each is read), A [batch, p, n], G [batch, m, n], float64;
-    the wrapper makes the column-major copies the library takes.
-    torch CUDA tensors (float64, contiguous, on `device`) are passed by pointer without a copy.  A contiguous A[i] ([p, n], row-major) already is the column-major
-    AT[i].  A contiguous P [batch, n, n] is a batch of ROW-major matrices, which the library reads as their column-major transposes: the upper triangle it reads
-    is that of the TRANSPOSE, i.e. P[i].tril() (the lower triangle of the row-major matrix).  For a symmetric P that is only a question of which half has to be
-    filled in; NaN in the other half is harmless.
-    Vectors are [batch, len], per-instance scalars [batch]; numpy in, numpy out; torch in, torch out on the device.  Every argument of one call lives in the same
-    memory.  Wrong dtype, shape, contiguity or device is refused before any library call."""
-    _destroy = "pq_kkt_batch_destroy"
 
-    def __init__(self, P, A=None, G=None, kkt_solver=DENSE_CHOLESKY, device=0, _h=None, _dims=None):
+class _BatchHandle(_Handle):
+    """what the batched wrappers share: the argument handling and the one way to wrap a handle that exists already"""
+    _dims_fn = None  # the library's getter of (batch, n, p, m) for this kind of handle
+
+    @classmethod
+    def _adopt(cls, h, device, kkt_solver, owner=None, **attrs):
+        """the wrapper of the existing handle `h`, its dimensions read from the library.  owner: None = the new object owns the handle and destroys it (a clone);
+        else the object that owns it, which is kept alive as long as the new one (a borrowed handle)"""
+        k = cls.__new__(cls)
+        k._owned, k._parent = owner is None, owner
+        k.L, k.device, k.kkt_solver, k.h = _lib.load(), int(device), int(kkt_solver), h if isinstance(h, C.c_void_p) else C.c_void_p(h)
+        d = [C.c_int() for _ in range(4)]
+        check(getattr(k.L, cls._dims_fn)(k.h, *[C.byref(x) for x in d]), cls._dims_fn)
+        k.batch, k.n, k.p, k.m = (x.value for x in d)
+        for name, v in attrs.items():
+            setattr(k, name, v)
+        return k
+
+    def _open(self, P, A, G, kkt_solver, device):
+        """the start of a constructor from matrices: the library, the device, the kind and batch, n, p, m from the shapes"""
         self.L = _lib.load()
         self.device = int(device)
-        if _h is not None:
-            self.h = _h
-            self.batch, self.n, self.p, self.m, self.kkt_solver = _dims
-            return
         if kkt_solver not in (DENSE_CHOLESKY, DENSE_LDLT_NO_PIVOT):
             raise ValueError(f"kkt_solver {kkt_solver}: DENSE_CHOLESKY or DENSE_LDLT_NO_PIVOT")
         shape = tuple(P.shape)
@@ -44,13 +51,6 @@ class BatchDenseKKT(_Handle):
         if self.p < 0 or self.m < 0:
             raise ValueError("A: [batch, p, n] and G: [batch, m, n] expected")
         self.kkt_solver = int(kkt_solver)
-        mem, (Pm, Am, Gm) = self._matrices(P, A, G)
-        h = C.c_void_p()
-        if mem == MEM_DEVICE:
-            sync_current_stream(self.device)
-        check(self.L.pq_kkt_batch_create_dense(C.byref(h), self.device, self.batch, self.n, self.p, self.m, self.kkt_solver, self._p(Pm), self._p(Am), self._p(Gm), mem),
-              "pq_kkt_batch_create_dense")
-        self.h = h
 
     # ---- argument handling: no library call in here
     @staticmethod
@@ -92,10 +92,6 @@ class BatchDenseKKT(_Handle):
             raise TypeError("numpy arrays and torch tensors in one call: every argument of a call lives in the same memory")
         return (mems.pop() if mems else MEM_HOST), out
 
-    def _matrices(self, P, A, G):
-        b, n = self.batch, self.n
-        return self._args(("P", P, (b, n, n), True), ("A", A, (b, self.p, n)), ("G", G, (b, self.m, n)))
-
     def _out(self, mem, *shape):
         if mem == MEM_DEVICE:
             import torch
@@ -107,11 +103,41 @@ class BatchDenseKKT(_Handle):
             sync_current_stream(self.device)
         return check(getattr(self.L, fn)(self.h, *[self._p(a) for a in args], mem), fn)
 
+
+class BatchDenseKKT(_BatchHandle):
+    """BatchDenseKKT(P, A=None, G=None, kkt_solver=DENSE_CHOLESKY, device=0)
+
+    numpy arguments: P [batch, n, n] as written (P[i][r, c] = row r, column c; the upper triangle of each is read), A [batch, p, n], G [batch, m, n], float64;
+    the wrapper makes the column-major copies the library takes.
+    torch CUDA tensors (float64, contiguous, on `device`) are passed by pointer without a copy.  A contiguous A[i] ([p, n], row-major) already is the column-major
+    AT[i].  A contiguous P [batch, n, n] is a batch of ROW-major matrices, which the library reads as their column-major transposes: the upper triangle it reads
+    is that of the TRANSPOSE, i.e. P[i].tril() (the lower triangle of the row-major matrix).  For a symmetric P that is only a question of which half has to be
+    filled in; NaN in the other half is harmless.
+    Vectors are [batch, len], per-instance scalars [batch]; numpy in, numpy out; torch in, torch out on the device.  Every argument of one call lives in the same
+    memory.  Wrong dtype, shape, contiguity or device is refused before any library call."""
+    _destroy = "pq_kkt_batch_destroy"
+    _dims_fn = "pq_kkt_batch_dims"
+
+    def __init__(self, P, A=None, G=None, kkt_solver=DENSE_CHOLESKY, device=0):
+        self._open(P, A, G, kkt_solver, device)
+        mem, (Pm, Am, Gm) = self._matrices(P, A, G)
+        h = C.c_void_p()
+        if mem == MEM_DEVICE:
+            sync_current_stream(self.device)
+        check(self.L.pq_kkt_batch_create_dense(C.byref(h), self.device, self.batch, self.n, self.p, self.m, self.kkt_solver, self._p(Pm), self._p(Am), self._p(Gm), mem),
+              "pq_kkt_batch_create_dense")
+        self.h = h
+
+    # ---- argument handling: no library call in here
+    def _matrices(self, P, A, G):
+        b, n = self.batch, self.n
+        return self._args(("P", P, (b, n, n), True), ("A", A, (b, self.p, n)), ("G", G, (b, self.m, n)))
+
     # ---- the KKTSolverBase surface, per instance
     def clone(self):
         h = C.c_void_p()
         check(self.L.pq_kkt_batch_clone(self.h, C.byref(h)), "pq_kkt_batch_clone")
-        return BatchDenseKKT(None, device=self.device, _h=h, _dims=(self.batch, self.n, self.p, self.m, self.kkt_solver))
+        return self._adopt(h, self.device, self.kkt_solver)
 
     def update_data(self, P=None, A=None, G=None):
         """re-reads the matrices that are given (layouts as in the constructor); a new A recomputes A' A"""

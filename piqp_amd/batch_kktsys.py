@@ -7,8 +7,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import VAR_NAMES, check
-from .batch_kkt import BatchDenseKKT
-from .kkt import DENSE_CHOLESKY, DENSE_LDLT_NO_PIVOT, KKT_UPDATE_A, KKT_UPDATE_G, KKT_UPDATE_P, MEM_DEVICE, MEM_HOST, _Handle, _is_torch, default_settings, sync_current_stream
+from .batch_kkt import BatchDenseKKT, _BatchHandle, var_shapes
+from .kkt import DENSE_CHOLESKY, KKT_UPDATE_A, KKT_UPDATE_G, KKT_UPDATE_P, MEM_DEVICE, MEM_HOST, _is_torch, default_settings, sync_current_stream
 
 STATE_X_REG, STATE_Z_REG, STATE_RHS_X_BAR, STATE_RHS_Z_BAR = 0, 1, 2, 3  # PQ_KKTSYS_BATCH_*
 MAX_REFINE_ITER = 64
@@ -20,7 +20,7 @@ def _copy_settings(s):
     return c
 
 
-class BatchKKTSystem(_Handle):
+class BatchKKTSystem(_BatchHandle):
     """BatchKKTSystem(P, A=None, G=None, h_l_idx=None, h_u_idx=None, x_l_idx=None, x_u_idx=None, x_b_scaling=None, settings=None, kkt_solver=DENSE_CHOLESKY, device=0)
 
     Matrices as for BatchDenseKKT: P [batch, n, n], A [batch, p, n], G [batch, m, n].  The four finite-bound index lists are shared by the batch, ascending, host
@@ -31,31 +31,10 @@ class BatchKKTSystem(_Handle):
     missing.  numpy in, numpy out; torch CUDA tensors by pointer, torch out; every array of one call lives in the same memory; wrong dtype, shape, contiguity or device
     is refused before any library call."""
     _destroy = "pq_kktsys_batch_destroy"
-    _p = staticmethod(BatchDenseKKT._p)
-    _one = BatchDenseKKT._one
-    _args = BatchDenseKKT._args
-    _matrices = BatchDenseKKT._matrices
+    _dims_fn = "pq_kktsys_batch_dims"
 
-    def __init__(self, P, A=None, G=None, h_l_idx=None, h_u_idx=None, x_l_idx=None, x_u_idx=None, x_b_scaling=None, settings=None, kkt_solver=DENSE_CHOLESKY, device=0,
-                 _h=None, _like=None):
-        self.L = _lib.load()
-        self.device = int(device)
-        if _h is not None:
-            self.h = _h
-            self.batch, self.n, self.p, self.m, self.kkt_solver, self.lists, self.settings = (_like.batch, _like.n, _like.p, _like.m, _like.kkt_solver, _like.lists,
-                                                                                             _copy_settings(_like.settings))
-            return
-        if kkt_solver not in (DENSE_CHOLESKY, DENSE_LDLT_NO_PIVOT):
-            raise ValueError(f"kkt_solver {kkt_solver}: DENSE_CHOLESKY or DENSE_LDLT_NO_PIVOT")
-        shape = tuple(P.shape)
-        if len(shape) != 3 or shape[1] != shape[2]:
-            raise ValueError(f"P: shape {shape}, expected [batch, n, n]")
-        self.batch, self.n = int(shape[0]), int(shape[1])
-        self.p = 0 if A is None else int(A.shape[1]) if len(A.shape) == 3 else -1
-        self.m = 0 if G is None else int(G.shape[1]) if len(G.shape) == 3 else -1
-        if self.p < 0 or self.m < 0:
-            raise ValueError("A: [batch, p, n] and G: [batch, m, n] expected")
-        self.kkt_solver = int(kkt_solver)
+    def __init__(self, P, A=None, G=None, h_l_idx=None, h_u_idx=None, x_l_idx=None, x_u_idx=None, x_b_scaling=None, settings=None, kkt_solver=DENSE_CHOLESKY, device=0):
+        self._open(P, A, G, kkt_solver, device)
         self.settings = _copy_settings(settings if settings is not None else default_settings())
         self.settings.kkt_solver = self.kkt_solver
         if not 0 <= self.settings.iterative_refinement_max_iter <= MAX_REFINE_ITER:
@@ -89,8 +68,7 @@ class BatchKKTSystem(_Handle):
         return a
 
     def var_shapes(self):
-        b, n, p, m = self.batch, self.n, self.p, self.m
-        return dict(zip(VAR_NAMES, ((b, n), (b, p), (b, m), (b, m), (b, n), (b, n), (b, m), (b, m), (b, n), (b, n))))
+        return var_shapes(self.batch, self.n, self.p, self.m)
 
     def _used(self, name):
         if name in ("z_bl", "s_bl"):
@@ -101,6 +79,10 @@ class BatchKKTSystem(_Handle):
 
     def _vars(self, what, v, names=VAR_NAMES):
         """(MEM_*, dict name -> array or None) for a batch of variables: every vector with a meaningful part must be there"""
+        if self.lists is None:
+            raise RuntimeError("this BatchKKTSystem is borrowed from a BatchDenseSolver, which does not hand out its bound lists: calls that take variables "
+                               "(update_scalings_and_factor, solve, mul) are not available; the read-only hooks are (x_reg, z_reg, rhs_x_bar, rhs_z_bar, solve_ok, "
+                               "refine_steps, backend_solves, refine_error, rhs_norm, last_ms, backend)")
         shapes = self.var_shapes()
         for name in names:
             if self._used(name) and v.get(name) is None:
@@ -124,13 +106,11 @@ class BatchKKTSystem(_Handle):
     def clone(self):
         h = C.c_void_p()
         check(self.L.pq_kktsys_batch_clone(self.h, C.byref(h)), "pq_kktsys_batch_clone")
-        return BatchKKTSystem(None, device=self.device, _h=h, _like=self)
+        return self._adopt(h, self.device, self.kkt_solver, lists=self.lists, settings=_copy_settings(self.settings))
 
     def backend(self):
         """the BatchDenseKKT this system owns (borrowed: it lives as long as this object)"""
-        k = BatchDenseKKT(None, device=self.device, _h=C.c_void_p(self.L.pq_kktsys_batch_backend(self.h)), _dims=(self.batch, self.n, self.p, self.m, self.kkt_solver))
-        k._owned, k._parent = False, self
-        return k
+        return BatchDenseKKT._adopt(self.L.pq_kktsys_batch_backend(self.h), self.device, self.kkt_solver, owner=self)
 
     def update_data(self, P=None, A=None, G=None, x_b_scaling=None):
         """re-reads what is given (layouts as in the constructor); a new A recomputes A' A"""

@@ -236,35 +236,24 @@ void kb_compute_ata(pq_kkt_batch* k)
     if (k->p > 0) kb_launch_assemble(k, k->batch, k->p, k->AT.p, nullptr, nullptr, nullptr, nullptr, nullptr, k->ATA.p);
 }
 
-// an input of `count` doubles: the caller's device pointer, or its copy in the input staging at `off` (advanced)
-const double* kb_in(pq_kkt_batch* k, const double* src, size_t count, int mem, size_t& off)
-{
-    if (mem == PQ_MEM_DEVICE || count == 0) return mem == PQ_MEM_DEVICE ? src : k->stage_in.p;
-    double* dst = k->stage_in.p + off;
-    PQ_HIP(hipMemcpyAsync(dst, src, sizeof(double) * count, hipMemcpyHostToDevice, k->st));
-    off += count;
-    return dst;
-}
-
-// an output of `count` doubles: the caller's device pointer, or a place in the output staging (preload: the host's present values go there first, for the blocks
-// a kernel leaves alone)
-double* kb_out(pq_kkt_batch* k, double* dst, size_t count, int mem, size_t& off, bool preload)
-{
-    if (mem == PQ_MEM_DEVICE || count == 0) return mem == PQ_MEM_DEVICE ? dst : k->stage_out.p;
-    double* d = k->stage_out.p + off;
-    if (preload) PQ_HIP(hipMemcpyAsync(d, dst, sizeof(double) * count, hipMemcpyHostToDevice, k->st));
-    off += count;
-    return d;
-}
-
-void kb_back(pq_kkt_batch* k, double* host, const double* dev, size_t count, int mem)
-{
-    if (mem != PQ_MEM_DEVICE && count) PQ_HIP(hipMemcpyAsync(host, dev, sizeof(double) * count, hipMemcpyDeviceToHost, k->st));
-}
-
-bool kb_bad_mem(int mem) { return mem != PQ_MEM_HOST && mem != PQ_MEM_DEVICE; }
-
 }  // namespace
+
+int pq::kb_factor_done(pq_kkt_batch* k, const std::chrono::steady_clock::time_point* w0, const KbReadback* more, int n_more)
+{
+    hipStream_t st = k->st;
+    PQ_HIP(hipMemcpyAsync(k->status_h.p, k->status.p, sizeof(int) * 2 * k->batch, hipMemcpyDeviceToHost, st));
+    for (int i = 0; i < n_more; ++i) PQ_HIP(hipMemcpyAsync(more[i].host, more[i].dev, more[i].bytes, hipMemcpyDeviceToHost, st));
+    stream_wait(st);
+    if (w0) {
+        k->timed[0] = true;
+        k->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - *w0).count();
+    }
+    int good = 0;
+    for (int b = 0; b < k->batch; ++b) good += k->status_h.p[b] == 0;
+    k->n_ok = good;
+    k->computed = true;
+    return good;
+}
 
 extern "C" {
 
@@ -354,9 +343,9 @@ int pq_kkt_batch_update_scalings_and_factor(pq_kkt_batch* k, const double* delta
         KbFactorArgs a;
         a.n = n; a.p = k->p; a.m = k->m; a.ld = dfb_ld(n); a.width = n < 32 ? n : dfb_block_size_rule(n); a.batch = batch;
         a.Pu = k->Pu.p; a.ATA = k->p > 0 ? k->ATA.p : nullptr; a.GT = k->GT.p;
-        a.delta = kb_in(k, delta, (size_t)batch, mem, off);
-        a.x_reg = kb_in(k, x_reg, (size_t)batch * n, mem, off);
-        a.z_reg = kb_in(k, z_reg, (size_t)batch * k->m, mem, off);
+        a.delta = kb_in(k->stage_in, k->st, delta, (size_t)batch, mem, off);
+        a.x_reg = kb_in(k->stage_in, k->st, x_reg, (size_t)batch * n, mem, off);
+        a.z_reg = kb_in(k->stage_in, k->st, z_reg, (size_t)batch * k->m, mem, off);
         a.delta_s = k->delta_s.p; a.x_reg_s = k->x_reg_s.p; a.zinv_s = k->zinv_s.p;
         a.F = k->fac.p; a.info = k->status.p; a.badcol = k->status.p + batch;
         const size_t lds = kb_factor_lds_bytes(n);
@@ -371,13 +360,7 @@ int pq_kkt_batch_update_scalings_and_factor(pq_kkt_batch* k, const double* delta
         }
         PQ_HIP(hipGetLastError());
         PQ_HIP(hipEventRecord(k->ev[1], st));
-        PQ_HIP(hipMemcpyAsync(k->status_h.p, k->status.p, sizeof(int) * 2 * batch, hipMemcpyDeviceToHost, st));
-        stream_wait(st);
-        k->timed[0] = true;
-        k->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
-        for (int b = 0; b < batch; ++b) good += k->status_h.p[b] == 0;
-        k->n_ok = good;
-        k->computed = true;
+        good = kb_factor_done(k, &w0);
         return (int)PQ_OK;
     });
     return rc == PQ_OK ? good : rc;
@@ -408,21 +391,21 @@ int pq_kkt_batch_solve(pq_kkt_batch* k, const double* rhs_x, const double* rhs_y
         KbSolveArgs a;
         a.n = k->n; a.p = k->p; a.m = k->m; a.ld = dfb_ld(k->n);
         a.AT = k->AT.p; a.GT = k->GT.p; a.F = k->fac.p; a.delta_s = k->delta_s.p; a.zinv_s = k->zinv_s.p; a.info = k->status.p;
-        a.rhs_x = kb_in(k, rhs_x, b * n, mem, off);
-        a.rhs_y = kb_in(k, rhs_y, b * p, mem, off);
-        a.rhs_z = kb_in(k, rhs_z, b * m, mem, off);
-        a.lhs_x = kb_out(k, lhs_x, b * n, mem, ooff, preload);
-        a.lhs_y = kb_out(k, lhs_y, b * p, mem, ooff, preload);
-        a.lhs_z = kb_out(k, lhs_z, b * m, mem, ooff, preload);
+        a.rhs_x = kb_in(k->stage_in, k->st, rhs_x, b * n, mem, off);
+        a.rhs_y = kb_in(k->stage_in, k->st, rhs_y, b * p, mem, off);
+        a.rhs_z = kb_in(k->stage_in, k->st, rhs_z, b * m, mem, off);
+        a.lhs_x = kb_out(k->stage_out, k->st, lhs_x, b * n, mem, ooff, preload);
+        a.lhs_y = kb_out(k->stage_out, k->st, lhs_y, b * p, mem, ooff, preload);
+        a.lhs_z = kb_out(k->stage_out, k->st, lhs_z, b * m, mem, ooff, preload);
         const int threads = k->n <= 64 ? 64 : KB_SOLVE_THREADS;
         PQ_HIP(hipEventRecord(k->ev[2], st));
         if (k->kind == PQ_DENSE_CHOLESKY) k_kb_solve<0><<<k->batch, threads, kb_solve_lds_bytes(k->n), st>>>(a);
         else k_kb_solve<1><<<k->batch, threads, kb_solve_lds_bytes(k->n), st>>>(a);
         PQ_HIP(hipGetLastError());
         PQ_HIP(hipEventRecord(k->ev[3], st));
-        kb_back(k, lhs_x, a.lhs_x, b * n, mem);
-        kb_back(k, lhs_y, a.lhs_y, b * p, mem);
-        kb_back(k, lhs_z, a.lhs_z, b * m, mem);
+        kb_back(k->st, lhs_x, a.lhs_x, b * n, mem);
+        kb_back(k->st, lhs_y, a.lhs_y, b * p, mem);
+        kb_back(k->st, lhs_z, a.lhs_z, b * m, mem);
         stream_wait(st);
         k->timed[1] = true;
         return (int)PQ_OK;
@@ -437,12 +420,12 @@ int pq_kkt_batch_eval_P_x(pq_kkt_batch* k, const double* alpha, const double* x,
         PQ_HIP(hipSetDevice(k->device));
         const size_t b = (size_t)k->batch, n = (size_t)k->n;
         size_t off = 0, ooff = 0;
-        const double* da = kb_in(k, alpha, b, mem, off);
-        const double* dx = kb_in(k, x, b * n, mem, off);
-        double* dz = kb_out(k, z, b * n, mem, ooff, false);
+        const double* da = kb_in(k->stage_in, k->st, alpha, b, mem, off);
+        const double* dx = kb_in(k->stage_in, k->st, x, b * n, mem, off);
+        double* dz = kb_out(k->stage_out, k->st, z, b * n, mem, ooff, false);
         k_kb_eval_P<<<dim3(div_up(k->n, KB_EVAL_THREADS), k->batch), KB_EVAL_THREADS, 0, k->st>>>(k->n, k->Pu.p, da, dx, dz);
         PQ_HIP(hipGetLastError());
-        kb_back(k, z, dz, b * n, mem);
+        kb_back(k->st, z, dz, b * n, mem);
         stream_wait(k->st);
         return (int)PQ_OK;
     });
@@ -458,16 +441,16 @@ int kb_eval_nt(pq_kkt_batch* k, int cols, const DBuf<double>& M, const double* a
         PQ_HIP(hipSetDevice(k->device));
         const size_t b = (size_t)k->batch, n = (size_t)k->n, c = (size_t)cols;
         size_t off = 0, ooff = 0;
-        const double* dan = kb_in(k, alpha_n, b, mem, off);
-        const double* dat = kb_in(k, alpha_t, b, mem, off);
-        const double* dxn = kb_in(k, xn, b * n, mem, off);
-        const double* dxt = kb_in(k, xt, b * c, mem, off);
-        double* dzn = kb_out(k, zn, b * c, mem, ooff, false);
-        double* dzt = kb_out(k, zt, b * n, mem, ooff, false);
+        const double* dan = kb_in(k->stage_in, k->st, alpha_n, b, mem, off);
+        const double* dat = kb_in(k->stage_in, k->st, alpha_t, b, mem, off);
+        const double* dxn = kb_in(k->stage_in, k->st, xn, b * n, mem, off);
+        const double* dxt = kb_in(k->stage_in, k->st, xt, b * c, mem, off);
+        double* dzn = kb_out(k->stage_out, k->st, zn, b * c, mem, ooff, false);
+        double* dzt = kb_out(k->stage_out, k->st, zt, b * n, mem, ooff, false);
         k_kb_eval_NT<<<dim3(div_up(k->n + cols, KB_EVAL_THREADS), k->batch), KB_EVAL_THREADS, 0, k->st>>>(k->n, cols, M.p, dan, dat, dxn, dxt, dzn, dzt);
         PQ_HIP(hipGetLastError());
-        kb_back(k, zn, dzn, b * c, mem);
-        kb_back(k, zt, dzt, b * n, mem);
+        kb_back(k->st, zn, dzn, b * c, mem);
+        kb_back(k->st, zt, dzt, b * n, mem);
         stream_wait(k->st);
         return (int)PQ_OK;
     });

@@ -95,9 +95,13 @@ __device__ __forceinline__ double kb_dot(const double* __restrict__ a, const dou
     return s;
 }
 
+// The VECTOR arguments of the helpers below (rhs_*, lhs_*, x) may have been written by the calling launch itself (the refinement loop of dense_kktsys_batch.hip, the
+// residuals of dense_solver_batch.hip), so they are plain pointers and must not regain __restrict__: the compiler may serve a const __restrict__ read of a
+// workgroup-uniform address from the scalar cache, which does not see vector stores.  The matrices and zinv are never written by a launch that reads them here.
+
 // row i of dense_solve's right-hand side
 __device__ __forceinline__ double kb_rhs_row(int i, int n, int p, int m, const double* __restrict__ GT, const double* __restrict__ AT, const double* __restrict__ zinv,
-                                             double dinv, const double* __restrict__ rhs_x, const double* __restrict__ rhs_y, const double* __restrict__ rhs_z)
+                                             double dinv, const double* rhs_x, const double* rhs_y, const double* rhs_z)
 {
     double c = rhs_x[i];
     for (int j = 0; j < m; ++j) c = fma(GT[i + (size_t)j * n], zinv[j] * rhs_z[j], c);
@@ -142,8 +146,7 @@ __device__ __forceinline__ void kb_sweeps(const double* a, int n, int ld, double
 
 // lhs_y and lhs_z of dense_solve from the finished lhs_x (x, LDS or global): outputs strided over the `nthreads` threads of the caller
 __device__ __forceinline__ void kb_epilogues(int n, int p, int m, const double* __restrict__ GT, const double* __restrict__ AT, const double* __restrict__ zinv,
-                                             double dinv, const double* x, const double* __restrict__ rhs_y, const double* __restrict__ rhs_z,
-                                             double* __restrict__ lhs_y, double* __restrict__ lhs_z, int t, int nthreads)
+                                             double dinv, const double* x, const double* rhs_y, const double* rhs_z, double* lhs_y, double* lhs_z, int t, int nthreads)
 {
     for (int j = t; j < p; j += nthreads) {
         const double s = kb_dot(AT + (size_t)j * n, x, n);
@@ -163,7 +166,7 @@ __device__ __forceinline__ void kb_epilogues(int n, int p, int m, const double* 
 // ---- evaluators
 // dense_eval_P_x (k_ex_eval_P): z[t] is touched first by column t:  z[t] = 0 + fma(P_tt, alpha x_t, alpha * s_t),  s_t the dot product over the part of column t above
 // the diagonal;  after that by every column j > t:  z[t] = fma(P_tj, alpha x_j, z[t])
-__device__ __forceinline__ double kb_eval_P_row(int t, int n, const double* __restrict__ Pu, double alpha, const double* __restrict__ x)
+__device__ __forceinline__ double kb_eval_P_row(int t, int n, const double* __restrict__ Pu, double alpha, const double* x)
 {
     const double* col = Pu + (size_t)t * n;
     const double s = kb_dot(col, x, t);
@@ -172,12 +175,12 @@ __device__ __forceinline__ double kb_eval_P_row(int t, int n, const double* __re
     return v;
 }
 // gemv_t (k_ex_gemv_t mode 0): alpha * dot(column j, x)
-__device__ __forceinline__ double kb_gemv_t_col(int j, int rows, const double* __restrict__ M, const double* __restrict__ x, double alpha)
+__device__ __forceinline__ double kb_gemv_t_col(int j, int rows, const double* __restrict__ M, const double* x, double alpha)
 {
     return alpha * kb_dot(M + (size_t)j * rows, x, rows);
 }
 // gemv_n into a zeroed vector (k_ex_gemv_n): the chain over ascending j of fma(M[i][j], alpha * x[j], .)
-__device__ __forceinline__ double kb_gemv_n_row(int i, int rows, int cols, const double* __restrict__ M, const double* __restrict__ x, double alpha)
+__device__ __forceinline__ double kb_gemv_n_row(int i, int rows, int cols, const double* __restrict__ M, const double* x, double alpha)
 {
     double c = 0.0;
     for (int j = 0; j < cols; ++j) c = fma(M[i + (size_t)j * rows], alpha * x[j], c);

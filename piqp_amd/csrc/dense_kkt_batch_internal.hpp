@@ -1,7 +1,11 @@
-// piqp_amd/csrc/dense_kkt_batch_internal.hpp -- what stands behind a pq_kkt_batch handle (dense_kkt_batch.hip), for the one other file that writes it:
-// dense_kktsys_batch.hip, whose factorisation launch leaves the factor store, the stored scalings and the status exactly as pq_kkt_batch_update_scalings_and_factor
-// does.  The launch-shape helpers (kb_factor_lds_bytes, kb_solve_lds_bytes) are in dense_kkt_batch_device.hpp.
+// piqp_amd/csrc/dense_kkt_batch_internal.hpp -- what stands behind a pq_kkt_batch handle (dense_kkt_batch.hip), and what the layers above it
+// (dense_kktsys_batch.hip, dense_solver_batch.hip) share with it on the host: the host-mode staging, the length table of pq_vars and the refinement cap.  Only
+// dense_kkt_batch.hip writes the handle's fields; dense_kktsys_batch.hip, whose factorisation launch leaves the factor store, the stored scalings and the status
+// exactly as pq_kkt_batch_update_scalings_and_factor does, reads them and ends with kb_factor_done.  The launch-shape helpers (kb_factor_lds_bytes,
+// kb_solve_lds_bytes) are in dense_kkt_batch_device.hpp.
 #pragma once
+
+#include <chrono>
 
 #include "common.hpp"
 #include "dense_kkt_batch_device.hpp"
@@ -21,10 +25,61 @@ struct pq_kkt_batch {
     pq::Stream st;
 };
 
+namespace pq {
+
+constexpr int KB_MAX_REFINE_ITER = 64;  // safety cap on the in-kernel refinement loop (the reference's default is 10)
+
+// the lengths of the ten vectors of a pq_vars, in the header's order
+static_assert(sizeof(pq_vars) == 10 * sizeof(double*), "pq_vars is ten pointers");
+inline void vars_lens(size_t n, size_t p, size_t m, size_t len[10])
+{
+    const size_t l[10] = {n, p, m, m, n, n, m, m, n, n};
+    for (int i = 0; i < 10; ++i) len[i] = l[i];
+}
+
+// ---- host-mode staging: `stage` is device memory of the handle, `off` the next free place in it (advanced)
+inline bool kb_bad_mem(int mem) { return mem != PQ_MEM_HOST && mem != PQ_MEM_DEVICE; }
+
+// an input of `count` elements: the caller's device pointer, or its copy in the input staging (nothing to copy: the staging's base)
+template <class T>
+const T* kb_in(const DBuf<T>& stage, hipStream_t st, const T* src, size_t count, int mem, size_t& off)
+{
+    if (mem == PQ_MEM_DEVICE || count == 0) return mem == PQ_MEM_DEVICE ? src : stage.p;
+    T* dst = stage.p + off;
+    PQ_HIP(hipMemcpyAsync(dst, src, sizeof(T) * count, hipMemcpyHostToDevice, st));
+    off += count;
+    return dst;
+}
+
+// an output of `count` doubles: the caller's device pointer, or a place in the output staging (preload: the host's present values go there first, for the blocks
+// a kernel leaves alone)
+inline double* kb_out(const DBuf<double>& stage, hipStream_t st, double* dst, size_t count, int mem, size_t& off, bool preload)
+{
+    if (mem == PQ_MEM_DEVICE || count == 0) return mem == PQ_MEM_DEVICE ? dst : stage.p;
+    double* d = stage.p + off;
+    if (preload) PQ_HIP(hipMemcpyAsync(d, dst, sizeof(double) * count, hipMemcpyHostToDevice, st));
+    off += count;
+    return d;
+}
+
+inline void kb_back(hipStream_t st, double* host, const double* dev, size_t count, int mem)
+{
+    if (mem != PQ_MEM_DEVICE && count) PQ_HIP(hipMemcpyAsync(host, dev, sizeof(double) * count, hipMemcpyDeviceToHost, st));
+}
+
+// ---- the end of every factorisation launch on k->st (dense_kkt_batch.hip): the status is read back, then `n_more` further read-backs of the caller ride on the same
+// wait, the stream is WAITED for, and the host side of the handle is left factored (computed, n_ok).  w0: when the call that the handle's events ev[0], ev[1] time
+// began (timed[0], wall_ms), or null for a launch they do not time.  Returns the number of instances that factored.
+struct KbReadback {
+    void* host;
+    const void* dev;
+    size_t bytes;
+};
+int kb_factor_done(pq_kkt_batch* k, const std::chrono::steady_clock::time_point* w0, const KbReadback* more = nullptr, int n_more = 0);
+
 // The two heavy launches of a pq_kktsys_batch (dense_kktsys_batch.hip) on their own, for dense_solver_batch.hip, which clocks them in rounds: every pointer is
 // device memory, the launch goes on the handle's stream, nothing is read back and nothing waits.  active: null = every instance; else int [batch], an instance
 // whose word is 0 is left out (it reads nothing, writes nothing, and in the n < 32 variant its wave still reaches every barrier of its workgroup).
-namespace pq {
 void ksb_launch_factor(pq_kktsys_batch* k, const int* flags, const double* rho, const double* delta, const pq_vars& v, const int* active);
 void ksb_launch_solve(pq_kktsys_batch* k, const pq_vars& rhs, const pq_vars& lhs, const int* active);
 hipStream_t ksb_stream(pq_kktsys_batch* k);

@@ -21,10 +21,9 @@
 //
 // Memory of the solve kernel: beside the factor and the sweeps' scratch four n-vectors in LDS (lhs_x, ref_lhs_x, err_x, rhs_x_bar): n (n | 1) + 7 n + 2 doubles, 137.0 KiB
 // at n = 128.  The p- and m-length vectors (lhs, ref_lhs, err) live in a per-instance workspace in global memory, rhs_z_bar in the handle's state.  What a launch writes
-// to global memory and reads again is reached through plain pointers only, never through a const __restrict__ one (the compiler may serve such a read of a
-// workgroup-uniform address from the scalar cache, which does not see vector stores): the ksb_* twins of kb_rhs_row, kb_epilogues and kb_gemv_n_row below take the
-// launch-written vectors that way, and the phases are separated by __syncthreads().  The one exception is the weight vector of kb_assemble (1 / z_reg_iter_ref, written
-// by the factor launch a barrier earlier): its address is per lane, a vector load.
+// to global memory and reads again is reached through plain pointers only (the rule above the helpers of dense_kkt_batch_device.hpp), and the phases are separated by
+// __syncthreads().  The one exception is the weight vector of kb_assemble (1 / z_reg_iter_ref, written by the factor launch a barrier earlier): its address is per
+// lane, a vector load.
 #include <chrono>
 #include <cmath>
 #include <memory>
@@ -35,8 +34,6 @@
 namespace pq {
 
 namespace {
-
-constexpr int KSB_MAX_REFINE_ITER = 64;  // safety cap on the in-kernel loop (the reference's default is 10)
 
 inline size_t ksb_factor_lds_doubles(int n) { return kb_lds_doubles(n) + (size_t)n; }  // the backend's, and x_reg
 inline size_t ksb_factor_lds_bytes(int n) { return sizeof(double) * ksb_factor_lds_doubles(n) * (n < 32 ? DFB_THREADS / 64 : 1); }
@@ -176,39 +173,6 @@ __global__ __launch_bounds__(DFB_THREADS) void k_ksb_factor(const KsbFactorArgs 
 }
 
 // ---- solve
-// kb_rhs_row, kb_epilogues and kb_gemv_n_row with the vectors this launch wrote itself (rhs_z_bar, the refinement's err and lhs blocks) behind plain pointers
-__device__ __forceinline__ double ksb_rhs_row(int i, int n, int p, int m, const double* __restrict__ GT, const double* __restrict__ AT, const double* __restrict__ zinv,
-                                              double dinv, const double* rhs_x, const double* rhs_y, const double* rhs_z)
-{
-    double c = rhs_x[i];
-    for (int j = 0; j < m; ++j) c = fma(GT[i + (size_t)j * n], zinv[j] * rhs_z[j], c);
-    for (int j = 0; j < p; ++j) c = fma(AT[i + (size_t)j * n], dinv * rhs_y[j], c);
-    return c;
-}
-__device__ __forceinline__ void ksb_epilogues(int n, int p, int m, const double* __restrict__ GT, const double* __restrict__ AT, const double* __restrict__ zinv, double dinv,
-                                              const double* x, const double* rhs_y, const double* rhs_z, double* lhs_y, double* lhs_z, int t, int nthreads)
-{
-    for (int j = t; j < p; j += nthreads) {
-        const double s = kb_dot(AT + (size_t)j * n, x, n);
-        double v = dinv * s;
-        v = fma(-dinv, rhs_y[j], v);
-        lhs_y[j] = v;
-    }
-    for (int j = t; j < m; j += nthreads) {
-        const double s = kb_dot(GT + (size_t)j * n, x, n);
-        double v = 1.0 * s;
-        v = v - rhs_z[j];
-        v = v * zinv[j];
-        lhs_z[j] = v;
-    }
-}
-__device__ __forceinline__ double ksb_gemv_n_row(int i, int rows, int cols, const double* __restrict__ M, const double* x, double alpha)
-{
-    double c = 0.0;
-    for (int j = 0; j < cols; ++j) c = fma(M[i + (size_t)j * rows], alpha * x[j], c);
-    return c;
-}
-
 // NaN-sticky maximum over the workgroup; red: one double per wave (LDS).  Called by the whole workgroup; every thread gets the result.
 __device__ __forceinline__ double ksb_block_max_nan(double v, double* red)
 {
@@ -252,10 +216,10 @@ __device__ __forceinline__ void ksb_backend_solve(const KsbInst& I, const double
 {
     __syncthreads();
     double c = 0.0;
-    if (I.t < I.n) c = ksb_rhs_row(I.t, I.n, I.p, I.m, I.GT, I.AT, I.zinv, I.dinv, rx, ry, rz);
+    if (I.t < I.n) c = kb_rhs_row(I.t, I.n, I.p, I.m, I.GT, I.AT, I.zinv, I.dinv, rx, ry, rz);
     kb_sweeps<KIND>(I.a, I.n, I.ld, c, I.xs, I.pr, I.xb, I.t);
     if (I.t < I.n) ox[I.t] = I.xs[I.t];
-    ksb_epilogues(I.n, I.p, I.m, I.GT, I.AT, I.zinv, I.dinv, I.xs, ry, rz, oy, oz, I.t, I.T);
+    kb_epilogues(I.n, I.p, I.m, I.GT, I.AT, I.zinv, I.dinv, I.xs, ry, rz, oy, oz, I.t, I.T);
     __syncthreads();
 }
 
@@ -268,8 +232,8 @@ __device__ __forceinline__ double ksb_refine_error(const KsbInst& I, const doubl
     if (t < n) {
         double v = kb_eval_P_row(t, n, I.Pu, 1.0, lx);
         v = v + I.x_reg[t] * lx[t];
-        v = v + ksb_gemv_n_row(t, n, I.p, I.AT, ly, 1.0);
-        v = v + ksb_gemv_n_row(t, n, I.m, I.GT, lz, 1.0);
+        v = v + kb_gemv_n_row(t, n, I.p, I.AT, ly, 1.0);
+        v = v + kb_gemv_n_row(t, n, I.m, I.GT, lz, 1.0);
         const double e = I.rxb[t] - v;
         ex[t] = e;
         nrm = ksb_max_nan(nrm, fabs(e));
@@ -472,7 +436,7 @@ __global__ __launch_bounds__(KB_SOLVE_THREADS) void k_ksb_mul(const KsbMulArgs A
         double v = kb_eval_P_row(i, n, Pu, 1.0, lx);
         v = v + rho * lx[i];
         v = v + kb_gemv_n_row(i, n, p, AT, ly, 1.0);
-        v = v + ksb_gemv_n_row(i, n, m, GT, d, 1.0);
+        v = v + kb_gemv_n_row(i, n, m, GT, d, 1.0);
         if (A.pos_l[i] >= 0) v = v - xbs[i] * z_bl[A.pos_l[i]];
         if (A.pos_u[i] >= 0) v = v + xbs[i] * z_bu[A.pos_u[i]];
         A.rhs.x[on + i] = v;
@@ -539,80 +503,54 @@ size_t ksb_state_len(const pq_kktsys_batch* k, int s)
     }
 }
 
-// the length of the ten vectors of a pq_vars and whether this handle reads / writes them at all
-void ksb_var_lens(const pq_kktsys_batch* k, size_t len[10], bool used[10])
+// the doubles of the ten vectors of a pq_vars that this handle reads / writes (batch x length; 0: the vector has no meaningful part).  first: the positions
+// before it count as unused (x and y are not part of a state)
+void ksb_var_counts(const pq_kktsys_batch* k, int first, size_t count[10])
 {
-    const size_t n = (size_t)k->n, p = (size_t)k->p, m = (size_t)k->m;
-    const size_t l[10] = {n, p, m, m, n, n, m, m, n, n};
-    for (int i = 0; i < 10; ++i) { len[i] = l[i]; used[i] = l[i] > 0; }
-    used[4] = used[8] = k->cnt[2] > 0;  // z_bl, s_bl
-    used[5] = used[9] = k->cnt[3] > 0;  // z_bu, s_bu
+    vars_lens((size_t)k->n, (size_t)k->p, (size_t)k->m, count);
+    for (int i = 0; i < 10; ++i) count[i] = i < first ? 0 : count[i] * (size_t)k->batch;
+    if (k->cnt[2] == 0) count[4] = count[8] = 0;  // z_bl, s_bl
+    if (k->cnt[3] == 0) count[5] = count[9] = 0;  // z_bu, s_bu
 }
-static_assert(sizeof(pq_vars) == 10 * sizeof(double*), "pq_vars is ten pointers");
 double** ksb_fields(pq_vars* v) { return &v->x; }  // (ten pointers in the header's order)
 double* const* ksb_fields(const pq_vars* v) { return &v->x; }
 
-bool ksb_bad_mem(int mem) { return mem != PQ_MEM_HOST && mem != PQ_MEM_DEVICE; }
-
-// first: the positions 0 .. 9 to look at (x and y are not part of a state)
 int ksb_check_vars(const pq_kktsys_batch* k, const pq_vars* v, int first, const char* what)
 {
-    size_t len[10];
-    bool used[10];
-    ksb_var_lens(k, len, used);
+    size_t count[10];
+    ksb_var_counts(k, first, count);
     for (int i = first; i < 10; ++i)
-        if (used[i] && !ksb_fields(v)[i]) return fail(PQ_ERR_INVALID, "dense KKT system batch: %s: null vector (position %d of pq_vars)", what, i);
+        if (count[i] && !ksb_fields(v)[i]) return fail(PQ_ERR_INVALID, "dense KKT system batch: %s: null vector (position %d of pq_vars)", what, i);
     return PQ_OK;
 }
 
 // inputs of a call in device memory: the caller's pointers, or copies in the input staging
 pq_vars ksb_vars_in(pq_kktsys_batch* k, const pq_vars* v, int first, int mem, size_t& off)
 {
-    size_t len[10];
-    bool used[10];
-    ksb_var_lens(k, len, used);
-    pq_vars d = *v;
-    if (mem == PQ_MEM_DEVICE) return d;
-    for (int i = 0; i < 10; ++i) {
-        ksb_fields(&d)[i] = k->stage_in.p;
-        if (i < first || !used[i]) continue;
-        const size_t count = (size_t)k->batch * len[i];
-        double* dst = k->stage_in.p + off;
-        PQ_HIP(hipMemcpyAsync(dst, ksb_fields(v)[i], sizeof(double) * count, hipMemcpyHostToDevice, k->kb->st));
-        ksb_fields(&d)[i] = dst;
-        off += count;
-    }
+    size_t count[10];
+    ksb_var_counts(k, first, count);
+    pq_vars d;
+    for (int i = 0; i < 10; ++i) ksb_fields(&d)[i] = const_cast<double*>(kb_in(k->stage_in, k->kb->st, ksb_fields(v)[i], count[i], mem, off));
     return d;
 }
 // outputs: the caller's pointers, or places in the output staging.  Host mode: a block the launch may leave alone (an instance that failed; the unused tail of a box
 // row) goes there with the host's present values first
 pq_vars ksb_vars_out(pq_kktsys_batch* k, pq_vars* v, int mem, bool preload_all)
 {
-    size_t len[10], off = 0;
-    bool used[10];
-    ksb_var_lens(k, len, used);
-    pq_vars d = *v;
-    if (mem == PQ_MEM_DEVICE) return d;
+    size_t count[10], off = 0;
+    ksb_var_counts(k, 0, count);
+    pq_vars d;
     for (int i = 0; i < 10; ++i) {
-        ksb_fields(&d)[i] = k->stage_out.p;
-        if (!used[i]) continue;
-        const size_t count = (size_t)k->batch * len[i];
-        double* dst = k->stage_out.p + off;
         const bool box_tail = ((i == 4 || i == 8) && k->cnt[2] < k->n) || ((i == 5 || i == 9) && k->cnt[3] < k->n);
-        if (preload_all || box_tail) PQ_HIP(hipMemcpyAsync(dst, ksb_fields(v)[i], sizeof(double) * count, hipMemcpyHostToDevice, k->kb->st));
-        ksb_fields(&d)[i] = dst;
-        off += count;
+        ksb_fields(&d)[i] = kb_out(k->stage_out, k->kb->st, ksb_fields(v)[i], count[i], mem, off, preload_all || box_tail);
     }
     return d;
 }
 void ksb_vars_back(pq_kktsys_batch* k, pq_vars* host, const pq_vars& dev, int mem)
 {
-    if (mem == PQ_MEM_DEVICE) return;
-    size_t len[10];
-    bool used[10];
-    ksb_var_lens(k, len, used);
-    for (int i = 0; i < 10; ++i)
-        if (used[i]) PQ_HIP(hipMemcpyAsync(ksb_fields(host)[i], ksb_fields(&dev)[i], sizeof(double) * (size_t)k->batch * len[i], hipMemcpyDeviceToHost, k->kb->st));
+    size_t count[10];
+    ksb_var_counts(k, 0, count);
+    for (int i = 0; i < 10; ++i) kb_back(k->kb->st, ksb_fields(host)[i], ksb_fields(&dev)[i], count[i], mem);
 }
 
 void ksb_raise_lds()
@@ -669,9 +607,9 @@ const int* ksb_xu_idx(const pq_kktsys_batch* k) { return ksb_xl_idx(k) + k->cnt[
 int ksb_check_settings(const pq_settings* s)
 {
     if (!s) return fail(PQ_ERR_INVALID, "dense KKT system batch: null settings");
-    if (s->iterative_refinement_max_iter < 0 || s->iterative_refinement_max_iter > KSB_MAX_REFINE_ITER)
+    if (s->iterative_refinement_max_iter < 0 || s->iterative_refinement_max_iter > KB_MAX_REFINE_ITER)
         return fail(PQ_ERR_INVALID, "dense KKT system batch: iterative_refinement_max_iter = %d, [0, %d] wanted (the loop runs inside a kernel)", s->iterative_refinement_max_iter,
-                    KSB_MAX_REFINE_ITER);
+                    KB_MAX_REFINE_ITER);
     return PQ_OK;
 }
 
@@ -753,16 +691,11 @@ const int* ksb_solve_info(const pq_kktsys_batch* k) { return k->sinfo.p; }
 // after launches of the two functions above: the host side of both handles as the public calls leave it (status, counts and diagnostics read back; waits)
 void ksb_refresh_host(pq_kktsys_batch* k)
 {
-    pq_kkt_batch* kb = k->kb.get();
     const int batch = k->batch;
-    hipStream_t st = kb->st;
-    PQ_HIP(hipMemcpyAsync(kb->status_h.p, kb->status.p, sizeof(int) * 2 * batch, hipMemcpyDeviceToHost, st));
-    PQ_HIP(hipMemcpyAsync(k->sinfo_h.p, k->sinfo.p, sizeof(int) * 3 * batch, hipMemcpyDeviceToHost, st));
-    PQ_HIP(hipMemcpyAsync(k->dinfo_h.p, k->dinfo.p, sizeof(double) * 2 * batch, hipMemcpyDeviceToHost, st));
-    stream_wait(st);
-    int good = 0, solved = 0;
-    for (int b = 0; b < batch; ++b) { good += kb->status_h.p[b] == 0; solved += k->sinfo_h.p[b] != 0; }
-    kb->n_ok = good; kb->computed = true;
+    const KbReadback more[2] = {{k->sinfo_h.p, k->sinfo.p, sizeof(int) * 3 * batch}, {k->dinfo_h.p, k->dinfo.p, sizeof(double) * 2 * batch}};
+    kb_factor_done(k->kb.get(), nullptr, more, 2);  // (the rounds' launches are not timed by the backend's events)
+    int solved = 0;
+    for (int b = 0; b < batch; ++b) solved += k->sinfo_h.p[b] != 0;
     k->n_solved = solved; k->solved = true;
 }
 
@@ -889,7 +822,7 @@ int pq_kktsys_batch_set_settings(pq_kktsys_batch* k, const pq_settings* settings
 int pq_kktsys_batch_update_scalings_and_factor(pq_kktsys_batch* k, const int* iterative_refinement, const double* rho, const double* delta, const pq_vars* vars, int mem)
 {
     if (!k || !rho || !delta || !vars) return fail(PQ_ERR_INVALID, "null argument");
-    if (ksb_bad_mem(mem)) return fail(PQ_ERR_INVALID, "dense KKT system batch: bad mem");
+    if (kb_bad_mem(mem)) return fail(PQ_ERR_INVALID, "dense KKT system batch: bad mem");
     if (int rc = ksb_check_vars(k, vars, 2, "update_scalings_and_factor")) return rc;
     int good = 0;
     const int rc = guarded([&] {
@@ -898,29 +831,15 @@ int pq_kktsys_batch_update_scalings_and_factor(pq_kktsys_batch* k, const int* it
         const int batch = k->batch;
         const auto w0 = std::chrono::steady_clock::now();
         hipStream_t st = kb->st;
-        const int* flags = iterative_refinement;
-        const double *rho_d = rho, *delta_d = delta;
-        size_t off = 0;
-        if (mem != PQ_MEM_DEVICE) {
-            flags = iterative_refinement ? k->flags_d.p : nullptr;
-            if (iterative_refinement) PQ_HIP(hipMemcpyAsync(k->flags_d.p, iterative_refinement, sizeof(int) * batch, hipMemcpyHostToDevice, st));
-            PQ_HIP(hipMemcpyAsync(k->stage_in.p, rho, sizeof(double) * batch, hipMemcpyHostToDevice, st));
-            PQ_HIP(hipMemcpyAsync(k->stage_in.p + batch, delta, sizeof(double) * batch, hipMemcpyHostToDevice, st));
-            rho_d = k->stage_in.p; delta_d = k->stage_in.p + batch;
-            off = 2 * (size_t)batch;
-        }
+        size_t off = 0, foff = 0;
+        const int* flags = iterative_refinement ? kb_in(k->flags_d, st, iterative_refinement, (size_t)batch, mem, foff) : nullptr;
+        const double* rho_d = kb_in(k->stage_in, st, rho, (size_t)batch, mem, off);
+        const double* delta_d = kb_in(k->stage_in, st, delta, (size_t)batch, mem, off);
         const pq_vars v = ksb_vars_in(k, vars, 2, mem, off);
         PQ_HIP(hipEventRecord(kb->ev[0], st));
         ksb_launch_factor(k, flags, rho_d, delta_d, v, nullptr);
         PQ_HIP(hipEventRecord(kb->ev[1], st));
-        PQ_HIP(hipMemcpyAsync(kb->status_h.p, kb->status.p, sizeof(int) * 2 * batch, hipMemcpyDeviceToHost, st));
-        stream_wait(st);
-        // the backend handle: as its own update_scalings_and_factor leaves it
-        kb->timed[0] = true;
-        kb->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
-        for (int b = 0; b < batch; ++b) good += kb->status_h.p[b] == 0;
-        kb->n_ok = good;
-        kb->computed = true;
+        good = kb_factor_done(kb, &w0);  // the backend handle: as its own update_scalings_and_factor leaves it
         return (int)PQ_OK;
     });
     return rc == PQ_OK ? good : rc;
@@ -930,7 +849,7 @@ int pq_kktsys_batch_solve(pq_kktsys_batch* k, const pq_vars* rhs, pq_vars* lhs, 
 {
     if (!k || !rhs || !lhs) return fail(PQ_ERR_INVALID, "null argument");
     if (!k->kb->computed) return fail(PQ_ERR_INVALID, "dense KKT system batch: solve before update_scalings_and_factor");
-    if (ksb_bad_mem(mem)) return fail(PQ_ERR_INVALID, "dense KKT system batch: bad mem");
+    if (kb_bad_mem(mem)) return fail(PQ_ERR_INVALID, "dense KKT system batch: bad mem");
     if (int rc = ksb_check_vars(k, rhs, 0, "solve: rhs")) return rc;
     if (int rc = ksb_check_vars(k, lhs, 0, "solve: lhs")) return rc;
     if (int rc = ksb_check_settings(&k->settings)) return rc;
@@ -963,7 +882,7 @@ int pq_kktsys_batch_mul(pq_kktsys_batch* k, const pq_vars* lhs, pq_vars* rhs, in
 {
     if (!k || !lhs || !rhs) return fail(PQ_ERR_INVALID, "null argument");
     if (!k->kb->computed) return fail(PQ_ERR_INVALID, "dense KKT system batch: mul before update_scalings_and_factor");
-    if (ksb_bad_mem(mem)) return fail(PQ_ERR_INVALID, "dense KKT system batch: bad mem");
+    if (kb_bad_mem(mem)) return fail(PQ_ERR_INVALID, "dense KKT system batch: bad mem");
     if (int rc = ksb_check_vars(k, lhs, 0, "mul: lhs")) return rc;
     if (int rc = ksb_check_vars(k, rhs, 0, "mul: rhs")) return rc;
     return guarded([&] {

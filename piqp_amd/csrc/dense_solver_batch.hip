@@ -1,8 +1,8 @@
 // piqp_amd/csrc/dense_solver_batch.hip -- pq_solver_batch_*: piqp::DenseSolver::setup() / solve() (solver.hpp:69-216, 379-1259) for a BATCH of small dense QPs
 // (n <= 128) over the batched KKTSystem (dense_kktsys_batch.hip).  Per instance every number is the CPU oracle's (oracle/orc_solver.c) bit for bit.  This file is
 // compiled with -ffp-contract=off (piqp_amd/build.py, NO_CONTRACT) like orc_solver.c: every product and every sum is rounded on its own; the three mat-vec evaluators
-// inside update_residuals_nr are the contracted orc_dense.c and are written with explicit fma() (the formulas of kb_eval_P_row, kb_gemv_t_col, kb_gemv_n_row of
-// dense_kkt_batch_device.hpp, restated here with the vector behind a plain pointer -- see "memory" below).
+// inside update_residuals_nr are the contracted orc_dense.c and are written with explicit fma(): kb_eval_P_row, kb_gemv_t_col, kb_gemv_n_row of
+// dense_kkt_batch_device.hpp.
 //
 // The solve runs in ROUNDS clocked by the host.  The interior-point state of every instance (result, res_nr, res, step, prox, the pq_info fields, the refinement
 // flag and a stage word) lives in device memory.  orc_solver.c:664-953 is cut at its calls into KKTSystem:
@@ -30,8 +30,8 @@
 // Arithmetic: every dot product and every sigma sum is ONE sequential chain in index order, each chain on a lane of its own (the lanes pick their operands, then run
 // the same loop); maxima and minima are order-independent and are wave / workgroup reductions (the maximum of :581-615 is SIGNED; inf_scaled is NaN-sticky).  The
 // scalar logic runs on lane 0 on the instance's state in LDS.
-// Memory: the vectors a launch writes and reads again are reached through plain pointers only, never const __restrict__ ones (the header of dense_kktsys_batch.hip
-// says why), with __syncthreads() between the phases.
+// Memory: the vectors a launch writes and reads again are reached through plain pointers only (dense_kkt_batch_device.hpp says why), with __syncthreads() between
+// the phases.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -100,27 +100,12 @@ __device__ __forceinline__ void dsb_reduce(double (&v)[K], const int (&op)[K], d
 }
 constexpr int DSB_RED = 8 * (DSB_RUIZ_T / 64);  // doubles of `red`
 
-// ---- the sequential chains (orc_solver.c:439) and the mat-vec pieces of the contracted orc_dense.c with the vector behind a plain pointer
+// ---- the sequential chains (orc_solver.c:439)
 __device__ __forceinline__ double dsb_dot(const double* a, const double* b, int len)
 {
     double s = 0.0;
     for (int i = 0; i < len; ++i) s = s + a[i] * b[i];
     return s;
-}
-__device__ __forceinline__ double dsb_eval_P_row(int t, int n, const double* __restrict__ Pu, double alpha, const double* x)
-{
-    const double* col = Pu + (size_t)t * n;
-    const double s = kb_dot(col, x, t);
-    double v = 0.0 + fma(col[t], alpha * x[t], alpha * s);
-    for (int j = t + 1; j < n; ++j) v = fma(Pu[t + (size_t)j * n], alpha * x[j], v);
-    return v;
-}
-__device__ __forceinline__ double dsb_gemv_t_col(int j, int rows, const double* __restrict__ M, const double* x, double alpha) { return alpha * kb_dot(M + (size_t)j * rows, x, rows); }
-__device__ __forceinline__ double dsb_gemv_n_row(int i, int rows, int cols, const double* __restrict__ M, const double* x, double alpha)
-{
-    double c = 0.0;
-    for (int j = 0; j < cols; ++j) c = fma(M[i + (size_t)j * rows], alpha * x[j], c);
-    return c;
 }
 
 // ---- the interior-point state machine
@@ -191,20 +176,20 @@ __device__ __forceinline__ void dsb_update_nr(const DsbCtx& C)
     double* wx = C.st.x;    // work_x
     double* wz = C.st.z_l;  // work_z
     __syncthreads();
-    for (int j = t; j < p; j += DSB_T) nr.y[j] = dsb_gemv_t_col(j, n, C.AT, r.x, -1.0);
-    for (int i = t; i < n; i += DSB_T) wx[i] = dsb_gemv_n_row(i, n, p, C.AT, r.y, 1.0);
+    for (int j = t; j < p; j += DSB_T) nr.y[j] = kb_gemv_t_col(j, n, C.AT, r.x, -1.0);
+    for (int i = t; i < n; i += DSB_T) wx[i] = kb_gemv_n_row(i, n, p, C.AT, r.y, 1.0);
     for (int j = t; j < m; j += DSB_T) {
         wz[j] = r.z_u[j] - r.z_l[j];
-        const double g = dsb_gemv_t_col(j, n, C.GT, r.x, 1.0);
+        const double g = kb_gemv_t_col(j, n, C.GT, r.x, 1.0);
         nr.z_l[j] = g;
         nr.z_u[j] = -g;
     }
     __syncthreads();
     double a[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // dual_rel_norm: three parts; primal_rel_norm: two parts and the signed one
     for (int i = t; i < n; i += DSB_T) {
-        const double w2 = dsb_gemv_n_row(i, n, m, C.GT, wz, 1.0);
+        const double w2 = kb_gemv_n_row(i, n, m, C.GT, wz, 1.0);
         wx[i] = wx[i] + w2;
-        const double v = dsb_eval_P_row(i, n, C.Pu, -1.0, r.x);
+        const double v = kb_eval_P_row(i, n, C.Pu, -1.0, r.x);
         nr.x[i] = v;
         a[0] = dsb_comb(a[0], fabs(v * C.ci * C.pdi[i]), R_MAXNAN);
     }
@@ -960,7 +945,8 @@ struct VarSet {
     pq_vars v;
     void alloc(size_t b, size_t n, size_t p, size_t m, hipStream_t st)
     {
-        const size_t len[10] = {n, p, m, m, n, n, m, m, n, n};
+        size_t len[10];
+        vars_lens(n, p, m, len);
         buf.alloc(b * (5 * n + p + 4 * m));
         buf.zero(st);
         double** f = &v.x;
@@ -1009,8 +995,17 @@ namespace {
 
 size_t dsb_field_len(const DsbProblem* q, int field)
 {
-    const size_t len[10] = {(size_t)q->n, (size_t)q->p, (size_t)q->m, (size_t)q->m, (size_t)q->n, (size_t)q->n, (size_t)q->m, (size_t)q->m, (size_t)q->n, (size_t)q->n};
+    size_t len[10];
+    vars_lens((size_t)q->n, (size_t)q->p, (size_t)q->m, len);
     return len[field];
+}
+
+int dsb_check_refine_cap(const pq_settings& s)
+{
+    if (s.iterative_refinement_max_iter < 0 || s.iterative_refinement_max_iter > KB_MAX_REFINE_ITER)
+        return fail(PQ_ERR_INVALID, "dense solver batch: iterative_refinement_max_iter = %d, [0, %d] wanted (the loop runs inside a kernel)", s.iterative_refinement_max_iter,
+                    KB_MAX_REFINE_ITER);
+    return PQ_OK;
 }
 
 void dsb_ingest(hipStream_t st, const double* src, double* dst, int batch, int n, int cols, int mode, const int* dead)
@@ -1021,16 +1016,14 @@ void dsb_ingest(hipStream_t st, const double* src, double* dst, int batch, int n
     PQ_HIP(hipGetLastError());
 }
 
-void dsb_reset_state(pq_solver_batch* s, int status_only)
+void dsb_reset_state(pq_solver_batch* s)
 {
     DsbProblem* q = s->pr.get();
     for (int i = 0; i < q->batch; ++i) {
         DsbState& S = q->state_h.p[i];
-        if (!status_only) {
-            std::memset(&S, 0, sizeof(S));
-            S.info.rho = s->settings.rho_init;
-            S.info.delta = s->settings.delta_init;
-        }
+        std::memset(&S, 0, sizeof(S));
+        S.info.rho = s->settings.rho_init;
+        S.info.delta = s->settings.delta_init;
     }
 }
 
@@ -1082,7 +1075,7 @@ int pq_solver_batch_setup_dense(pq_solver_batch* s, int batch, int n, int p, int
     if (!s) return fail(PQ_ERR_INVALID, "null argument");
     if (batch < 1 || n < 1 || p < 0 || m < 0)
         return fail(PQ_ERR_INVALID, "dense solver batch: batch = %d, n = %d, p = %d, m = %d: batch, n >= 1 and p, m >= 0 wanted", batch, n, p, m);
-    if (mem != PQ_MEM_HOST && mem != PQ_MEM_DEVICE) return fail(PQ_ERR_INVALID, "dense solver batch: bad mem %d", mem);
+    if (kb_bad_mem(mem)) return fail(PQ_ERR_INVALID, "dense solver batch: bad mem %d", mem);
     if (order != PQ_COL_MAJOR && order != PQ_ROW_MAJOR) return fail(PQ_ERR_INVALID, "dense solver batch: bad order %d", order);
     const int kind = s->settings.kkt_solver;
     if (kind != PQ_DENSE_CHOLESKY && kind != PQ_DENSE_LDLT_NO_PIVOT)
@@ -1090,8 +1083,7 @@ int pq_solver_batch_setup_dense(pq_solver_batch* s, int batch, int n, int p, int
     if (!P || !c) return fail(PQ_ERR_INVALID, "dense solver batch: P and c must be given");
     if (p > 0 && !A) return fail(PQ_ERR_INVALID, "dense solver batch: A is null, p = %d", p);
     if (m > 0 && !G) return fail(PQ_ERR_INVALID, "dense solver batch: G is null, m = %d", m);
-    if (s->settings.iterative_refinement_max_iter < 0 || s->settings.iterative_refinement_max_iter > 64)
-        return fail(PQ_ERR_INVALID, "dense solver batch: iterative_refinement_max_iter = %d, [0, 64] wanted (the loop runs inside a kernel)", s->settings.iterative_refinement_max_iter);
+    if (int rc = dsb_check_refine_cap(s->settings)) return rc;
     if (n > PQ_KKT_BATCH_DENSE_MAX_N) return fail(PQ_ERR_UNSUPPORTED, "dense solver batch: n = %d, the limit is n <= %d", n, (int)PQ_KKT_BATCH_DENSE_MAX_N);
     return guarded([&] {
         PQ_HIP(hipSetDevice(s->device));
@@ -1192,7 +1184,7 @@ int pq_solver_batch_setup_dense(pq_solver_batch* s, int batch, int n, int p, int
         q->state.alloc(B); q->state_h.alloc(B);
         for (Event& e : q->ev) e = Event(0);
         s->pr = std::move(q);
-        dsb_reset_state(s, 0);  // init_workspace :361-377
+        dsb_reset_state(s);  // init_workspace :361-377
         PQ_HIP(hipMemcpyAsync(s->pr->state.p, s->pr->state_h.p, sizeof(DsbState) * B, hipMemcpyHostToDevice, kst));
         stream_wait(kst);
         s->solved = false;
@@ -1208,8 +1200,7 @@ int pq_solver_batch_solve(pq_solver_batch* s)
         s->invalid_info.status = PQ_UNSOLVED;
         return fail(PQ_ERR_INVALID, "dense solver batch: solve before setup");
     }
-    if (s->settings.iterative_refinement_max_iter < 0 || s->settings.iterative_refinement_max_iter > 64)
-        return fail(PQ_ERR_INVALID, "dense solver batch: iterative_refinement_max_iter = %d, [0, 64] wanted (the loop runs inside a kernel)", s->settings.iterative_refinement_max_iter);
+    if (int rc = dsb_check_refine_cap(s->settings)) return rc;
     if (!dsb_verify_settings(s->settings)) {  // solver.hpp:75-79: no launch
         for (int i = 0; i < q->batch; ++i) q->state_h.p[i].info.status = PQ_INVALID_SETTINGS;
         return fail(PQ_ERR_INVALID, "dense solver batch: invalid settings");
@@ -1324,7 +1315,7 @@ int pq_solver_batch_get_result_mem(pq_solver_batch* s, int field, double* out, i
 {
     if (!s || !out) return fail(PQ_ERR_INVALID, "null argument");
     if (field < 0 || field > 9) return fail(PQ_ERR_INVALID, "dense solver batch: field %d: 0 .. 9 wanted", field);
-    if (mem != PQ_MEM_HOST && mem != PQ_MEM_DEVICE) return fail(PQ_ERR_INVALID, "dense solver batch: bad mem %d", mem);
+    if (kb_bad_mem(mem)) return fail(PQ_ERR_INVALID, "dense solver batch: bad mem %d", mem);
     if (!s->pr || !s->solved) return fail(PQ_ERR_INVALID, "dense solver batch: no solve yet");
     return guarded([&] {
         PQ_HIP(hipSetDevice(s->device));

@@ -269,6 +269,10 @@ def test_the_borrowed_kkt_system_holds_each_instances_last_factorisation(orc, hi
     s = device(hip, qs, LLT)
     assert s.solve() == batch
     ks = s.kktsys()
+    if (n, p, m, batch) == (4, 2, 3, 67):  # the borrowed system knows its dimensions but not the bound lists: calls that take variables say so, before any launch
+        assert ks.batch == batch
+        with pytest.raises(RuntimeError):
+            ks.solve({})
     x_reg, z_reg = ks.x_reg(), ks.z_reg()
     for i, o in enumerate(ref):
         last = [st for st in o["states"] if st["kind"] == 0][-1]
