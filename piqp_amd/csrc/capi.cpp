@@ -18,27 +18,13 @@ using namespace pq;
 
 namespace {
 
-struct VarSizes {
-    int n, p, m;
-    int size(int k) const
-    {
-        switch (k) { case 0: return n; case 1: return p; case 2: case 3: return m; case 4: case 5: return n; case 6: case 7: return m; default: return n; }
-    }
-};
-inline double** var_field(pq_vars& v, int k)
-{
-    switch (k) { case 0: return &v.x; case 1: return &v.y; case 2: return &v.z_l; case 3: return &v.z_u; case 4: return &v.z_bl; case 5: return &v.z_bu;
-                 case 6: return &v.s_l; case 7: return &v.s_u; case 8: return &v.s_bl; default: return &v.s_bu; }
-}
-inline double* const* var_field(const pq_vars& v, int k) { return var_field(const_cast<pq_vars&>(v), k); }
-
 // device staging for one Variables set
 struct VarStage {
     DBuf<double> buf[10];
     pq_vars v{};
-    void alloc(VarSizes s)
+    void alloc(const size_t len[10])
     {
-        for (int k = 0; k < 10; ++k) { buf[k].alloc(s.size(k) > 0 ? s.size(k) : 1); *var_field(v, k) = buf[k].p; }
+        for (int k = 0; k < 10; ++k) { buf[k].alloc(len[k] > 0 ? len[k] : 1); vars_field(v, k) = buf[k].p; }
     }
     void zero(hipStream_t st) { for (int k = 0; k < 10; ++k) buf[k].zero(st); }
 };
@@ -74,8 +60,9 @@ struct pq_kktsys {
     void ensure_staging()
     {
         if (staged) return;
-        VarSizes s{impl->n(), impl->p(), impl->m()};
-        in.alloc(s); out.alloc(s); mul_in.alloc(s); mul_out.alloc(s);
+        size_t len[10];
+        vars_lens(impl->n(), impl->p(), impl->m(), len);
+        in.alloc(len); out.alloc(len); mul_in.alloc(len); mul_out.alloc(len);
         in.zero(impl->stream()); out.zero(impl->stream());
         staged = true;
     }
@@ -758,20 +745,18 @@ int pq_kktsys_update_data_sparse(pq_kktsys* k, const pq_sparse_data* data, int o
 static void stage_in(pq_kktsys* k, const pq_vars* src, VarStage& dst)
 {
     hipStream_t st = k->impl->stream();
-    VarSizes s{k->impl->n(), k->impl->p(), k->impl->m()};
-    for (int f = 0; f < 10; ++f) {
-        const double* hp = *var_field(*src, f);
-        if (hp) h2d(dst.buf[f].p, hp, s.size(f), st);
-    }
+    size_t len[10];
+    vars_lens(k->impl->n(), k->impl->p(), k->impl->m(), len);
+    for (int f = 0; f < 10; ++f)
+        if (vars_field(*src, f)) h2d(dst.buf[f].p, vars_field(*src, f), (int)len[f], st);
 }
 static void stage_out(pq_kktsys* k, VarStage& src, pq_vars* dst)
 {
     hipStream_t st = k->impl->stream();
-    VarSizes s{k->impl->n(), k->impl->p(), k->impl->m()};
-    for (int f = 0; f < 10; ++f) {
-        double* hp = *var_field(*dst, f);
-        if (hp) d2h(hp, src.buf[f].p, s.size(f), st);
-    }
+    size_t len[10];
+    vars_lens(k->impl->n(), k->impl->p(), k->impl->m(), len);
+    for (int f = 0; f < 10; ++f)
+        if (vars_field(*dst, f)) d2h(vars_field(*dst, f), src.buf[f].p, (int)len[f], st);
     stream_wait(st);
 }
 

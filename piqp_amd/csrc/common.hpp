@@ -258,6 +258,16 @@ inline void copy_in(void* dst_dev, const void* src, size_t bytes, int src_mem, h
 
 inline int div_up(int a, int b) { return (a + b - 1) / b; }
 
+// A pq_vars is ten pointers in the header's order (x, y, z_l, z_u, z_bl, z_bu, s_l, s_u, s_bl, s_bu): the lengths of its ten vectors, and field k
+static_assert(sizeof(pq_vars) == 10 * sizeof(double*), "pq_vars is ten pointers");
+inline void vars_lens(size_t n, size_t p, size_t m, size_t len[10])
+{
+    const size_t l[10] = {n, p, m, m, n, n, m, m, n, n};
+    for (int i = 0; i < 10; ++i) len[i] = l[i];
+}
+inline double*& vars_field(pq_vars& v, int k) { return (&v.x)[k]; }
+inline double* vars_field(const pq_vars& v, int k) { return (&v.x)[k]; }
+
 // ONE debugging variable for the whole library: PIQP_AMD_DEBUG="token[=value],token,...".  Returns nullptr when the token is
 // absent, "" when it is present without a value, its value otherwise.  Parsed once per process.  Tokens select measured-equivalent device
 // schedules for the bitwise-consistency tests (tests/test_sparse_variants_gpu.py) or switch diagnostics on; none is needed for normal use.

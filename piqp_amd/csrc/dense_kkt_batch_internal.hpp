@@ -1,5 +1,5 @@
 // piqp_amd/csrc/dense_kkt_batch_internal.hpp -- what stands behind a pq_kkt_batch handle (dense_kkt_batch.hip), and what the layers above it
-// (dense_kktsys_batch.hip, dense_solver_batch.hip) share with it on the host: the host-mode staging, the length table of pq_vars and the refinement cap.  Only
+// (dense_kktsys_batch.hip, dense_solver_batch.hip) share with it on the host: the host-mode staging and the refinement cap (the length table of pq_vars, vars_lens, is common.hpp's).  Only
 // dense_kkt_batch.hip writes the handle's fields; dense_kktsys_batch.hip, whose factorisation launch leaves the factor store, the stored scalings and the status
 // exactly as pq_kkt_batch_update_scalings_and_factor does, reads them and ends with kb_factor_done.  The launch-shape helpers (kb_factor_lds_bytes,
 // kb_solve_lds_bytes) are in dense_kkt_batch_device.hpp.
@@ -28,14 +28,6 @@ struct pq_kkt_batch {
 namespace pq {
 
 constexpr int KB_MAX_REFINE_ITER = 64;  // safety cap on the in-kernel refinement loop (the reference's default is 10)
-
-// the lengths of the ten vectors of a pq_vars, in the header's order
-static_assert(sizeof(pq_vars) == 10 * sizeof(double*), "pq_vars is ten pointers");
-inline void vars_lens(size_t n, size_t p, size_t m, size_t len[10])
-{
-    const size_t l[10] = {n, p, m, m, n, n, m, m, n, n};
-    for (int i = 0; i < 10; ++i) len[i] = l[i];
-}
 
 // ---- host-mode staging: `stage` is device memory of the handle, `off` the next free place in it (advanced)
 inline bool kb_bad_mem(int mem) { return mem != PQ_MEM_HOST && mem != PQ_MEM_DEVICE; }

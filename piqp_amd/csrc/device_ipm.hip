@@ -489,9 +489,7 @@ void DeviceIpm::refresh_data(const HostData& d, const Ruiz& rz)
 void DeviceIpm::download_result(HostVars& out)
 {
     Impl& s = *I;
-    const pq_vars& o = s.OUT;
-    const double* src[10] = {o.x, o.y, o.z_l, o.z_u, o.z_bl, o.z_bu, o.s_l, o.s_u, o.s_bl, o.s_bu};
-    for (int k = 0; k < 10; ++k) { Vec& v = out.field(k); if (!v.empty()) PQ_HIP(hipMemcpyAsync(v.data(), src[k], v.size() * sizeof(double), hipMemcpyDeviceToHost, s.st)); }
+    for (int k = 0; k < 10; ++k) { Vec& v = out.field(k); if (!v.empty()) PQ_HIP(hipMemcpyAsync(v.data(), vars_field(s.OUT, k), v.size() * sizeof(double), hipMemcpyDeviceToHost, s.st)); }
     stream_wait(s.st);
 }
 

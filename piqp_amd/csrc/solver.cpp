@@ -116,11 +116,19 @@ pq_sparse_data HostData::sparse_descriptor() const
     return d;
 }
 
-static void finish_data(HostData& d, const double* c, const double* b, const double* h_l, const double* h_u, const double* x_l, const double* x_u, IVec* zeroed_rows = nullptr)
+// The six vectors of a setup (all = true: a null bound means "none") or of an update (a null vector is left as it is) go into d.  The order is stated HERE and
+// nowhere else: c, b, then the bounds of G, then disable_inf_constraints -- between the h and the x bounds --, then the bounds of x.  Returns whether a row of G lost
+// its last finite bound and was zeroed (in d where the values are on the host; the rows are appended to *zeroed_rows for the copies that are not).
+static bool assign_vectors(HostData& d, bool all, const double* c, const double* b, const double* h_l, const double* h_u, const double* x_l, const double* x_u, IVec* zeroed_rows)
 {
-    std::copy(c, c + d.n, d.c.begin());
+    if (c) std::copy(c, c + d.n, d.c.begin());
     if (b && d.p) std::copy(b, b + d.p, d.b.begin());
-    d.set_h_l(h_l); d.set_h_u(h_u); d.disable_inf_constraints(zeroed_rows); d.set_x_l(x_l); d.set_x_u(x_u);
+    if (all || h_l) d.set_h_l(h_l);
+    if (all || h_u) d.set_h_u(h_u);
+    const bool row_zeroed = (all || h_l || h_u) && d.disable_inf_constraints(zeroed_rows);
+    if (all || x_l) d.set_x_l(x_l);
+    if (all || x_u) d.set_x_u(x_u);
+    return row_zeroed;
 }
 
 // MT(i, k) = M(k, i) for a rows x n column-major M: 32 x 32 tiles keep both sides of the transpose in cache
@@ -155,60 +163,56 @@ static void transposed_into(int n, const double* M, int rows, int layout, Vec& M
     else transpose_into(n, M, rows, MT);
 }
 
-// solver.hpp:169-192 (DenseSolver): P_utri = upper(P), AT = A^T, GT = G^T.  matrices_on_device: P, A, G only say which matrices exist; the three stay empty
-// (DeviceRuiz::ingest_dense fills the device copies) and the rows of G without a finite bound come back in *zeroed_rows
-std::unique_ptr<HostData> make_dense_host_data(int n, int p, int m, const double* P, const double* c, const double* A, const double* b, const double* G, const double* h_l,
-                                               const double* h_u, const double* x_l, const double* x_u, int layout, bool matrices_on_device, IVec* zeroed_rows)
+// solver.hpp:169-192 (DenseSolver): P_utri = upper(P), AT = A^T, GT = G^T; they stay empty where the matrices are in device memory (DeviceRuiz::ingest_dense fills the
+// device copies)
+std::unique_ptr<HostData> make_dense_host_data(const ProblemArgs& a, IVec* zeroed_rows)
 {
     auto d = std::make_unique<HostData>();
-    d->sparse = false; d->n = n; d->p = A ? p : 0; d->m = G ? m : 0;
-    p = d->p; m = d->m;
-    if (!matrices_on_device) {
-        upper_into(n, P, layout, d->P_utri);
-        if (p > 0) transposed_into(n, A, p, layout, d->AT); else d->AT.clear();
-        if (m > 0) transposed_into(n, G, m, layout, d->GT); else d->GT.clear();
+    const int n = a.n, p = a.A ? a.p : 0, m = a.G ? a.m : 0;
+    d->sparse = false; d->n = n; d->p = p; d->m = m;
+    if (a.mem != PQ_MEM_DEVICE) {
+        upper_into(n, a.P, a.layout, d->P_utri);
+        if (p > 0) transposed_into(n, a.A, p, a.layout, d->AT);
+        if (m > 0) transposed_into(n, a.G, m, a.layout, d->GT);
     }
     d->resize_vectors();
-    finish_data(*d, c, b, h_l, h_u, x_l, x_u, zeroed_rows);
+    assign_vectors(*d, true, a.c, a.b, a.h_l, a.h_u, a.x_l, a.x_u, zeroed_rows);
     return d;
 }
 
-static void csc_transpose(int rows, int cols, const int* Ap, const int* Ai, const double* Ax, Csc& T)
-{
-    const int nnz = Ap ? Ap[cols] : 0;
-    T.rows = cols; T.cols = rows;
-    T.colptr.assign(rows + 1, 0); T.rowind.assign(nnz, 0); T.val.assign(Ax ? nnz : 0, 0.0);  // (Ax null: pattern only, the values live on the device)
-    for (int k = 0; k < nnz; ++k) T.colptr[Ai[k] + 1]++;
-    for (int i = 0; i < rows; ++i) T.colptr[i + 1] += T.colptr[i];
-    IVec next(T.colptr.begin(), T.colptr.end() - 1);
-    for (int j = 0; j < cols; ++j) for (int k = Ap[j]; k < Ap[j + 1]; ++k) { const int q = next[Ai[k]]++; T.rowind[q] = j; if (Ax) T.val[q] = Ax[k]; }
-}
-
-void build_sparse_ingest_maps(int n, int p, int m, const int* Pp, const int* Pi, const int* Ap, const int* Ai, const int* Gp, const int* Gi, IVec& srcP, IVec& srcA, IVec& srcG)
+void build_sparse_ingest_maps(int n, int p, int m, const int* Pp, const int* Pi, const int* Ap, const int* Ai, const int* Gp, const int* Gi, Csc& U, Csc& AT, Csc& GT,
+                              IVec& srcP, IVec& srcA, IVec& srcG)
 {
     srcP.clear();
+    U.rows = U.cols = n; U.colptr.assign(n + 1, 0);
     std::vector<std::pair<int, int>> col;
     for (int j = 0; j < n; ++j) {
         col.clear();
         for (int k = Pp[j]; k < Pp[j + 1]; ++k) if (Pi[k] <= j) col.emplace_back(Pi[k], k);
-        std::sort(col.begin(), col.end(), [](const auto& a, const auto& b2) { return a.first < b2.first; });  // (the comparison make_sparse_host_data sorts the values with)
+        std::sort(col.begin(), col.end(), [](const auto& a, const auto& b2) { return a.first < b2.first; });
         for (auto& e : col) srcP.push_back(e.second);
+        U.colptr[j + 1] = (int)srcP.size();
     }
-    auto transposed = [&](int rows, const int* Mp, const int* Mi, IVec& src) {
+    U.rowind.resize(srcP.size());
+    for (size_t t = 0; t < srcP.size(); ++t) U.rowind[t] = Pi[srcP[t]];
+    auto transposed = [&](int rows, const int* Mp, const int* Mi, Csc& T, IVec& src) {
         src.clear();
-        if (!Mp || rows <= 0) return;
-        const int nnz = Mp[n];
-        IVec next(rows + 1, 0);
-        for (int k = 0; k < nnz; ++k) next[Mi[k] + 1]++;
-        for (int i = 0; i < rows; ++i) next[i + 1] += next[i];
+        if (!Mp || rows <= 0) rows = 0;
+        const int nnz = rows ? Mp[n] : 0;
+        T.rows = n; T.cols = rows;
+        T.colptr.assign(rows + 1, 0); T.rowind.assign(nnz, 0);
+        for (int k = 0; k < nnz; ++k) T.colptr[Mi[k] + 1]++;
+        for (int i = 0; i < rows; ++i) T.colptr[i + 1] += T.colptr[i];
+        IVec next(T.colptr.begin(), T.colptr.end() - 1);
         src.assign(nnz, 0);
-        for (int j = 0; j < n; ++j) for (int k = Mp[j]; k < Mp[j + 1]; ++k) src[next[Mi[k]]++] = k;
+        for (int j = 0; rows && j < n; ++j) for (int k = Mp[j]; k < Mp[j + 1]; ++k) { const int q = next[Mi[k]]++; T.rowind[q] = j; src[q] = k; }
     };
-    transposed(p, Ap, Ai, srcA);
-    transposed(m, Gp, Gi, srcG);
+    transposed(p, Ap, Ai, AT, srcA);
+    transposed(m, Gp, Gi, GT, srcG);
 }
 
-// solver.hpp:169-192 (SparseSolver)
+// solver.hpp:169-192 (SparseSolver): the stored matrices are the patterns above with the caller's values gathered through the maps -- here, or
+// (values_on_device: Px / Ax / Gx are not read) on the device by DeviceRuiz::ingest_sparse
 std::unique_ptr<HostData> make_sparse_host_data(int n, int p, int m, const int* Pp, const int* Pi, const double* Px, const double* c, const int* Ap, const int* Ai,
                                                 const double* Ax, const double* b, const int* Gp, const int* Gi, const double* Gx, const double* h_l, const double* h_u,
                                                 const double* x_l, const double* x_u, bool values_on_device, IVec* zeroed_rows)
@@ -217,28 +221,16 @@ std::unique_ptr<HostData> make_sparse_host_data(int n, int p, int m, const int* 
     d->sparse = true; d->n = n; d->p = Ap ? p : 0; d->m = Gp ? m : 0;
     p = d->p; m = d->m;
     d->values_on_device = values_on_device;
-    build_sparse_ingest_maps(n, p, m, Pp, Pi, p > 0 ? Ap : nullptr, Ai, m > 0 ? Gp : nullptr, Gi, d->srcP, d->srcA, d->srcG);
+    build_sparse_ingest_maps(n, p, m, Pp, Pi, p > 0 ? Ap : nullptr, Ai, m > 0 ? Gp : nullptr, Gi, d->sP_utri, d->sAT, d->sGT, d->srcP, d->srcA, d->srcG);
     d->nnz_in[0] = Pp[n]; d->nnz_in[1] = p > 0 ? Ap[n] : 0; d->nnz_in[2] = m > 0 ? Gp[n] : 0;
-    Csc& U = d->sP_utri;
-    U.rows = U.cols = n; U.colptr.assign(n + 1, 0);
-    if (values_on_device) {
-        // patterns only: Px / Ax / Gx are device pointers, the stored values are gathered on the device through the maps (DeviceRuiz::ingest_sparse)
-        Px = Ax = Gx = nullptr;
-        U.rowind.resize(d->srcP.size());
-        for (size_t t = 0; t < d->srcP.size(); ++t) U.rowind[t] = Pi[d->srcP[t]];
-        for (int j = 0; j < n; ++j) { int cnt = 0; for (int k = Pp[j]; k < Pp[j + 1]; ++k) cnt += Pi[k] <= j; U.colptr[j + 1] = U.colptr[j] + cnt; }
-    }
-    for (int j = 0; !values_on_device && j < n; ++j) {
-        std::vector<std::pair<int, double>> col;
-        for (int k = Pp[j]; k < Pp[j + 1]; ++k) if (Pi[k] <= j) col.emplace_back(Pi[k], Px[k]);
-        std::sort(col.begin(), col.end(), [](const auto& a, const auto& b2) { return a.first < b2.first; });
-        for (auto& e : col) { U.rowind.push_back(e.first); U.val.push_back(e.second); }
-        U.colptr[j + 1] = (int)U.rowind.size();
-    }
-    if (p > 0) csc_transpose(p, n, Ap, Ai, Ax, d->sAT); else { d->sAT.rows = n; d->sAT.cols = 0; d->sAT.colptr.assign(1, 0); }
-    if (m > 0) csc_transpose(m, n, Gp, Gi, Gx, d->sGT); else { d->sGT.rows = n; d->sGT.cols = 0; d->sGT.colptr.assign(1, 0); }
+    auto gather = [&](const double* x, const IVec& src, Vec& val) {
+        if (values_on_device || !x) return;
+        val.resize(src.size());
+        for (size_t t = 0; t < src.size(); ++t) val[t] = x[src[t]];
+    };
+    gather(Px, d->srcP, d->sP_utri.val); gather(Ax, d->srcA, d->sAT.val); gather(Gx, d->srcG, d->sGT.val);
     d->resize_vectors();
-    finish_data(*d, c, b, h_l, h_u, x_l, x_u, zeroed_rows);
+    assign_vectors(*d, true, c, b, h_l, h_u, x_l, x_u, zeroed_rows);
     return d;
 }
 
@@ -455,18 +447,14 @@ void Ruiz::scale_vectors(HostData& d) const
 // ------------------------------------------------------------------ HostVars
 void HostVars::resize(int n, int p, int m)
 {
-    x.assign(n, 0.0); y.assign(p, 0.0); z_l.assign(m, 0.0); z_u.assign(m, 0.0); z_bl.assign(n, 0.0); z_bu.assign(n, 0.0);
-    s_l.assign(m, 0.0); s_u.assign(m, 0.0); s_bl.assign(n, 0.0); s_bu.assign(n, 0.0);
+    size_t len[10];
+    vars_lens(n, p, m, len);
+    for (int k = 0; k < 10; ++k) field(k).assign(len[k], 0.0);
 }
 Vec& HostVars::field(int k)
 {
     switch (k) { case 0: return x; case 1: return y; case 2: return z_l; case 3: return z_u; case 4: return z_bl; case 5: return z_bu;
                  case 6: return s_l; case 7: return s_u; case 8: return s_bl; default: return s_bu; }
-}
-static double** vars_field(pq_vars& v, int k)
-{
-    switch (k) { case 0: return &v.x; case 1: return &v.y; case 2: return &v.z_l; case 3: return &v.z_u; case 4: return &v.z_bl; case 5: return &v.z_bu;
-                 case 6: return &v.s_l; case 7: return &v.s_u; case 8: return &v.s_bl; default: return &v.s_bu; }
 }
 
 // ------------------------------------------------------------------ Solver
@@ -479,13 +467,14 @@ void Solver::stage_alloc()
     PQ_HIP(hipSetDevice(device_));
     dev_in_.clear(); dev_out_.clear();
     dev_in_.resize(10); dev_out_.resize(10);
-    HostVars tmp; tmp.resize(n, p, m);
+    size_t len[10];
+    vars_lens(n, p, m, len);
     for (int k = 0; k < 10; ++k) {
-        const size_t sz = std::max<size_t>(tmp.field(k).size(), 1);
+        const size_t sz = std::max<size_t>(len[k], 1);
         dev_in_[k].alloc(sz); dev_out_[k].alloc(sz);
         dev_in_[k].zero(m_kkt_system->stream()); dev_out_[k].zero(m_kkt_system->stream());
-        *vars_field(din_, k) = dev_in_[k].p;
-        *vars_field(dout_, k) = dev_out_[k].p;
+        vars_field(din_, k) = dev_in_[k].p;
+        vars_field(dout_, k) = dev_out_[k].p;
     }
     dxa_.alloc(std::max(n, 1)); dxb_.alloc(std::max(n, 1)); dxc_.alloc(std::max(n, 1));
     dya_.alloc(std::max(p, 1)); dyb_.alloc(std::max(p, 1)); dza_.alloc(std::max(m, 1)); dzb_.alloc(std::max(m, 1));
@@ -500,7 +489,7 @@ void Solver::to_device(const HostVars& h, pq_vars& d)
         size_t cnt = v.size();
         if (k == 4 || k == 8) cnt = nxl;  // box vectors: only the compressed head is meaningful
         if (k == 5 || k == 9) cnt = nxu;
-        if (cnt) PQ_HIP(hipMemcpyAsync(*vars_field(d, k), v.data(), cnt * sizeof(double), hipMemcpyHostToDevice, st));
+        if (cnt) PQ_HIP(hipMemcpyAsync(vars_field(d, k), v.data(), cnt * sizeof(double), hipMemcpyHostToDevice, st));
     }
 }
 void Solver::from_device(const pq_vars& d, HostVars& h)
@@ -512,7 +501,7 @@ void Solver::from_device(const pq_vars& d, HostVars& h)
         size_t cnt = v.size();
         if (k == 4 || k == 8) cnt = nxl;
         if (k == 5 || k == 9) cnt = nxu;
-        if (cnt) PQ_HIP(hipMemcpyAsync(v.data(), *vars_field(const_cast<pq_vars&>(d), k), cnt * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (cnt) PQ_HIP(hipMemcpyAsync(v.data(), vars_field(d, k), cnt * sizeof(double), hipMemcpyDeviceToHost, st));
     }
     stream_wait(st);
 }
@@ -540,13 +529,51 @@ void Solver::make_kkt()
 // solver.hpp:151-216
 bool Solver::device_ingest() { return debug_token("host_ruiz") == nullptr; }
 
-bool Solver::setup(std::unique_ptr<HostData> data, const DenseDeviceSource* dev, const IVec* zeroed_rows, const SparseDeviceSource* sdev)
+// host staging of a device-mode call: the six vectors, and under PIQP_AMD_DEBUG=host_ruiz the three matrices
+struct Solver::FetchedVectors {
+    Vec buf[9];
+    const double* fetch(int k, const double* dev, size_t len)
+    {
+        buf[k].resize(len);
+        PQ_HIP(hipMemcpy(buf[k].data(), dev, sizeof(double) * len, hipMemcpyDeviceToHost));
+        return buf[k].data();
+    }
+};
+
+// How the data of every setup / update arrives, and where its byte count (ingest_) starts.  A device-mode call: the O(n + p + m) vectors (n, p, m: of the problem as
+// stored) are fetched into host staging and go through the host logic (bound lists, disabled rows of G) unchanged.  Without device_ingest() the matrices, mat_len[k]
+// doubles each, come to the host too, count as link bytes, and the call goes on as a host-fed one.  Returns the call as the rest of setup / update reads it.
+ProblemArgs Solver::arrive(const ProblemArgs& in, size_t n, size_t p, size_t m, const size_t mat_len[3], FetchedVectors& stage)
 {
-    if (data->sparse ? (dev != nullptr || data->values_on_device != (sdev != nullptr)) : sdev != nullptr) throw std::runtime_error("Solver::setup: device source of the wrong kind");
+    ingest_[0] = ingest_[1] = 0;
+    ProblemArgs a = in;
+    if (a.mem != PQ_MEM_DEVICE) return a;
+    PQ_HIP(hipSetDevice(device_));
+    const double** arr[9] = {&a.c, &a.b, &a.h_l, &a.h_u, &a.x_l, &a.x_u, &a.P, &a.A, &a.G};
+    const size_t len[9] = {n, p, m, m, n, n, mat_len[0], mat_len[1], mat_len[2]};
+    for (int k = 0; k < (device_ingest() ? 6 : 9); ++k) {
+        if (!*arr[k] || !len[k]) continue;
+        *arr[k] = stage.fetch(k, *arr[k], len[k]);
+        if (k >= 6) ingest_[0] += (long long)(sizeof(double) * len[k]);
+    }
+    if (!device_ingest()) a.mem = PQ_MEM_HOST;
+    return a;
+}
+
+bool Solver::setup(const ProblemArgs& in)
+{
+    const bool has_A = in.sparse ? in.Ap != nullptr : in.A != nullptr, has_G = in.sparse ? in.Gp != nullptr : in.G != nullptr;
+    const int n = in.n, p = has_A ? in.p : 0, m = has_G ? in.m : 0;
+    size_t mat_len[3] = {(size_t)n * n, (size_t)n * p, (size_t)n * m};
+    if (in.sparse) { mat_len[0] = in.Pp[n]; mat_len[1] = p ? in.Ap[n] : 0; mat_len[2] = m ? in.Gp[n] : 0; }
+    FetchedVectors stage;
+    const ProblemArgs a = arrive(in, n, p, m, mat_len, stage);
+    const bool on_device = a.mem == PQ_MEM_DEVICE;
+    IVec zeroed;
+    auto data = a.sparse ? make_sparse_host_data(n, a.p, a.m, a.Pp, a.Pi, a.P, a.c, a.Ap, a.Ai, a.A, a.b, a.Gp, a.Gi, a.G, a.h_l, a.h_u, a.x_l, a.x_u, on_device, &zeroed)
+                         : make_dense_host_data(a, &zeroed);
     const double t0 = now_s();
     m_data = std::move(data);
-    const int n = m_data->n, p = m_data->p, m = m_data->m;
-    ingest_[0] = ingest_[1] = 0;
     // init_workspace :361-377
     m_result.resize(n, p, m); res_nr.resize(n, p, m); res.resize(n, p, m); step.resize(n, p, m); prox_vars.resize(n, p, m);
     m_info = pq_info{};
@@ -554,19 +581,16 @@ bool Solver::setup(std::unique_ptr<HostData> data, const DenseDeviceSource* dev,
     m_preconditioner.init(*m_data);
     // dense/preconditioner.hpp:62-222 on the device (ruiz_kernels.hip); the host routine stays reachable for the bitwise comparison test
     druiz_.reset();
-    if (!debug_token("host_ruiz")) {
+    const int all = PQ_KKT_UPDATE_P | PQ_KKT_UPDATE_A | PQ_KKT_UPDATE_G;
+    if (device_ingest()) {
         druiz_ = std::make_unique<DeviceRuiz>(device_, *m_data);
-        if (!m_data->sparse && dev) {
-            ingest_[1] = druiz_->ingest_dense(dev->P, dev->A, dev->G, dev->layout, PQ_KKT_UPDATE_P | PQ_KKT_UPDATE_A | PQ_KKT_UPDATE_G);
-            if (zeroed_rows) druiz_->zero_G_rows(*zeroed_rows);
-        } else if (!m_data->sparse) { druiz_->upload_dense(*m_data, PQ_KKT_UPDATE_P | PQ_KKT_UPDATE_A | PQ_KKT_UPDATE_G); release_dense_staging(); }
-        else if (sdev) {
-            ingest_[1] = druiz_->ingest_sparse(*m_data, sdev->Px, sdev->Ax, sdev->Gx, PQ_KKT_UPDATE_P | PQ_KKT_UPDATE_A | PQ_KKT_UPDATE_G);
-            if (zeroed_rows) druiz_->zero_G_rows(*zeroed_rows);
-        }
-    } else if (dev || sdev) throw std::runtime_error("device matrices need the device preconditioner");
-    if (!m_data->sparse && !dev) ingest_[0] = 8LL * n * ((long long)n + p + m);  // P, A^T, G^T go up once (here, or in the KKT backend under host_ruiz)
-    if (m_data->sparse && !sdev) ingest_[0] = 8LL * ((long long)m_data->sP_utri.nnz() + m_data->sAT.nnz() + m_data->sGT.nnz());  // upper(P), A^T, G^T values go up
+        if (on_device) {
+            ingest_[1] = a.sparse ? druiz_->ingest_sparse(*m_data, a.P, p ? a.A : nullptr, m ? a.G : nullptr, all) : druiz_->ingest_dense(a.P, a.A, a.G, a.layout, all);
+            druiz_->zero_G_rows(zeroed);
+        } else if (!a.sparse) { druiz_->upload_dense(*m_data, all); release_dense_staging(); }
+    }
+    // host-fed: P, A^T, G^T (sparse: their values) go up once (here, or in the KKT backend under host_ruiz)
+    if (!on_device) ingest_[0] += a.sparse ? 8LL * ((long long)m_data->sP_utri.nnz() + m_data->sAT.nnz() + m_data->sGT.nnz()) : 8LL * n * ((long long)n + p + m);
     scale_problem(false);
     make_kkt();
     if (!m_kkt_system) { m_setup_done = false; return false; }
@@ -632,23 +656,45 @@ static void refresh_kkt(const DeviceRuiz* dr, KKTSystem& k, const HostData& d, i
     k.set_bounds(d.n_h_l, d.n_h_u, d.n_x_l, d.n_x_u, d.h_l_idx.data(), d.h_u_idx.data(), d.x_l_idx.data(), d.x_u_idx.data(), d.x_b_scaling.data(), PQ_MEM_HOST);
 }
 
+// solver.hpp:218-308
+bool Solver::update(const ProblemArgs& in)
+{
+    if (!m_setup_done || m_data->sparse != in.sparse) { std::fprintf(stderr, "Solver not setup yet\n"); return false; }
+    const HostData& d = *m_data;
+    const size_t n = d.n, p = d.p, m = d.m;
+    size_t mat_len[3] = {n * n, n * p, n * m};
+    if (in.sparse) std::copy(d.nnz_in, d.nnz_in + 3, mat_len);
+    // the host path of a sparse update walks the index arrays: they must be given where it is taken
+    if (in.sparse && in.mem == PQ_MEM_DEVICE && !device_ingest() && ((in.P && (!in.Pp || !in.Pi)) || (in.A && p > 0 && (!in.Ap || !in.Ai)) || (in.G && m > 0 && (!in.Gp || !in.Gi))))
+        throw std::runtime_error("PIQP_AMD_DEBUG=host_ruiz: a device-mode update needs the index arrays");
+    FetchedVectors stage;
+    const ProblemArgs a = arrive(in, n, p, m, mat_len, stage);
+    const double t0 = now_s();
+    if (!a.P && !a.A && !a.G) return update_vectors_only(a, t0);
+    return a.sparse ? update_sparse(a, t0) : update_dense(a, t0);
+}
+
+// The end of every update that has unscaled the problem: the scaling is computed afresh unless the settings -- or an update that changed no matrix -- keep the old one
+bool Solver::finish_update(int options, double t0)
+{
+    const bool reuse = m_settings.preconditioner_reuse_on_update != 0 || options == PQ_KKT_UPDATE_NONE;
+    scale_problem(reuse);
+    refresh_kkt(druiz_.get(), *m_kkt_system, *m_data, options);
+    if (dipm_) dipm_->refresh_data(*m_data, m_preconditioner);
+    m_info.update_time = now_s() - t0;
+    return true;
+}
+
 // update() without a matrix argument (solver.hpp:218-308 with every optional matrix empty): the reference still unscales and rescales
 // P, A, G with the unchanged scaling (reuse_prev_scaling is forced, :283-285) -- the identity up to rounding, O(n (n + p + m)) host work
 // and a full re-upload here.  Only the vectors go through unscale -> assign -> scale; the matrices stay as they are on host and device.
-bool Solver::update_vectors_only(const double* c, const double* b, const double* h_l, const double* h_u, const double* x_l, const double* x_u, double t0)
+bool Solver::update_vectors_only(const ProblemArgs& a, double t0)
 {
     HostData& d = *m_data;
-    ingest_[0] = ingest_[1] = 0;
     m_preconditioner.unscale_vectors(d);
-    if (c) std::copy(c, c + d.n, d.c.begin());
-    if (b) std::copy(b, b + d.p, d.b.begin());
-    if (h_l) d.set_h_l(h_l);
-    if (h_u) d.set_h_u(h_u);
     IVec zeroed;
-    const bool row_zeroed = (h_l || h_u) && d.disable_inf_constraints(&zeroed);  // a row of G without any finite bound is zeroed: that IS a matrix change
+    const bool row_zeroed = assign_vectors(d, false, a.c, a.b, a.h_l, a.h_u, a.x_l, a.x_u, &zeroed);  // a row of G without any finite bound is zeroed: that IS a matrix change
     if (row_zeroed && druiz_ && (!d.sparse || d.values_on_device)) druiz_->zero_G_rows(zeroed);
-    if (x_l) d.set_x_l(x_l);
-    if (x_u) d.set_x_u(x_u);
     m_preconditioner.scale_vectors(d);
     if (row_zeroed) { refresh_kkt(druiz_.get(), *m_kkt_system, d, PQ_KKT_UPDATE_G); }
     else m_kkt_system->set_bounds(d.n_h_l, d.n_h_u, d.n_x_l, d.n_x_u, d.h_l_idx.data(), d.h_u_idx.data(), d.x_l_idx.data(), d.x_u_idx.data(), d.x_b_scaling.data(), PQ_MEM_HOST);
@@ -657,144 +703,79 @@ bool Solver::update_vectors_only(const double* c, const double* b, const double*
     return true;
 }
 
-// solver.hpp:218-308 with the dense update_P/A/G of :311-351
-bool Solver::update_dense(const double* P, const double* c, const double* A, const double* b, const double* G, const double* h_l, const double* h_u, const double* x_l,
-                          const double* x_u, int mat_mem, int layout)
+// the dense update_P/A/G of solver.hpp:311-351
+bool Solver::update_dense(const ProblemArgs& a, double t0)
 {
-    if (!m_setup_done) { std::fprintf(stderr, "Solver not setup yet\n"); return false; }
-    const double t0 = now_s();
     HostData& d = *m_data;
     const int n = d.n, p = d.p, m = d.m;
-    if (!P && !A && !G) return update_vectors_only(c, b, h_l, h_u, x_l, x_u, t0);
-    const bool on_device = mat_mem == PQ_MEM_DEVICE;
-    if (on_device && !druiz_) throw std::runtime_error("device matrices need the device preconditioner");
+    const bool on_device = a.mem == PQ_MEM_DEVICE;
     unscale_problem();
     int opt = PQ_KKT_UPDATE_NONE;
-    if (P) { if (!on_device) upper_into(n, P, layout, d.P_utri); opt |= PQ_KKT_UPDATE_P; }
-    if (A) { if (!on_device) transposed_into(n, A, p, layout, d.AT); opt |= PQ_KKT_UPDATE_A; }
-    if (G) { if (!on_device) transposed_into(n, G, m, layout, d.GT); opt |= PQ_KKT_UPDATE_G; }
-    ingest_[0] = ingest_[1] = 0;
-    if (!on_device) ingest_[0] = 8LL * n * ((P ? (long long)n : 0) + (A ? p : 0) + (G ? m : 0));
-    if (c) std::copy(c, c + n, d.c.begin());
-    if (b) std::copy(b, b + p, d.b.begin());
-    if (h_l) d.set_h_l(h_l);
-    if (h_u) d.set_h_u(h_u);
+    if (a.P) { if (!on_device) upper_into(n, a.P, a.layout, d.P_utri); opt |= PQ_KKT_UPDATE_P; }
+    if (a.A) { if (!on_device) transposed_into(n, a.A, p, a.layout, d.AT); opt |= PQ_KKT_UPDATE_A; }
+    if (a.G) { if (!on_device) transposed_into(n, a.G, m, a.layout, d.GT); opt |= PQ_KKT_UPDATE_G; }
+    if (!on_device) ingest_[0] += 8LL * n * ((a.P ? (long long)n : 0) + (a.A ? p : 0) + (a.G ? m : 0));
     IVec zeroed;
-    if (h_l || h_u) d.disable_inf_constraints(&zeroed);
-    if (x_l) d.set_x_l(x_l);
-    if (x_u) d.set_x_u(x_u);
-    if (druiz_ && on_device) { ingest_[1] = druiz_->ingest_dense(P, A, G, layout, opt); druiz_->zero_G_rows(zeroed); }
+    assign_vectors(d, false, a.c, a.b, a.h_l, a.h_u, a.x_l, a.x_u, &zeroed);
+    if (druiz_ && on_device) { ingest_[1] = druiz_->ingest_dense(a.P, a.A, a.G, a.layout, opt); druiz_->zero_G_rows(zeroed); }
     else if (druiz_) { druiz_->upload_dense(d, opt); druiz_->zero_G_rows(zeroed); release_dense_staging(); }
-    bool reuse = m_settings.preconditioner_reuse_on_update != 0;
-    if (opt == PQ_KKT_UPDATE_NONE) reuse = true;
-    scale_problem(reuse);
-    refresh_kkt(druiz_.get(), *m_kkt_system, d, opt);
-    if (dipm_) dipm_->refresh_data(d, m_preconditioner);
-    m_info.update_time = now_s() - t0;
-    return true;
+    return finish_update(opt, t0);
 }
 
-// solver.hpp:218-308 with the sparse update_P/A/G of :317-358 (identical sparsity required)
-bool Solver::update_sparse(const int* Pp, const int* Pi, const double* Px, const double* c, const int* Ap, const int* Ai, const double* Ax, const double* b, const int* Gp,
-                           const int* Gi, const double* Gx, const double* h_l, const double* h_u, const double* x_l, const double* x_u, int mat_mem)
+// The sparse update_P/A/G of solver.hpp:317-358 (identical sparsity required).  The two ways differ only in how the matrix values get into place.
+//   * Into the host mirror (a host-fed solver, host values): the reference's rule, which reads the pattern given in THIS call -- of every column of P its leading
+//     entries, as many as upper(P) stores; A and G retransposed from the given indices.  A solver set up with a full symmetric P may be updated with its upper triangle.
+//   * Into DeviceRuiz's arrays (a device-fed solver, or from the first device-mode update of a host-fed one on): the values, device arrays or host arrays staged in HBM
+//     first, are in the CSC order given at setup and go through the maps of the setup; the index arrays may be null and only their lengths are checked.  unscale_data
+//     -> assign -> scale_data run on the device, the KKT system is refreshed from a device-mode descriptor; no matrix value comes to the host or goes back.
+bool Solver::update_sparse(const ProblemArgs& a, double t0)
 {
-    if (!m_setup_done) { std::fprintf(stderr, "Solver not setup yet\n"); return false; }
-    const double t0 = now_s();
     HostData& d = *m_data;
     const int n = d.n, p = d.p, m = d.m;
-    if (!d.sparse) { std::fprintf(stderr, "Solver not setup yet\n"); return false; }
-    if (!Px && !Ax && !Gx) return update_vectors_only(c, b, h_l, h_u, x_l, x_u, t0);
-    if (mat_mem == PQ_MEM_DEVICE || d.values_on_device) return update_sparse_on_device(Pp, Px, c, Ap, Ax, b, Gp, Gx, h_l, h_u, x_l, x_u, mat_mem, t0);
-    ingest_[0] = 8LL * ((Px ? (long long)d.sP_utri.nnz() : 0) + (Ax ? d.sAT.nnz() : 0) + (Gx ? d.sGT.nnz() : 0));
-    ingest_[1] = 0;
-    unscale_problem();
     int opt = PQ_KKT_UPDATE_NONE;
-    (void)Pi;
-    if (Px) {
-        for (int j = 0; j < n; ++j) {
-            const int have = Pp[j + 1] - Pp[j], need = d.sP_utri.colptr[j + 1] - d.sP_utri.colptr[j];
-            if (have < need) { std::fprintf(stderr, "P nonzeros missmatch\n"); return false; }
-            std::copy(Px + Pp[j], Px + Pp[j] + need, d.sP_utri.val.begin() + d.sP_utri.colptr[j]);
-        }
-        opt |= PQ_KKT_UPDATE_P;
-    }
-    auto retranspose = [&](const int* Mp, const int* Mi, const double* Mx, Csc& T, int rows) {
-        IVec next(T.colptr.begin(), T.colptr.end() - 1);
-        for (int j = 0; j < n; ++j) for (int q = Mp[j]; q < Mp[j + 1]; ++q) { const int t = next[Mi[q]]++; T.rowind[t] = j; T.val[t] = Mx[q]; }
-        (void)rows;
-    };
-    if (Ax) { if (Ap[n] != d.sAT.nnz()) { std::fprintf(stderr, "A nonzeros missmatch\n"); return false; } retranspose(Ap, Ai, Ax, d.sAT, p); opt |= PQ_KKT_UPDATE_A; }
-    if (Gx) { if (Gp[n] != d.sGT.nnz()) { std::fprintf(stderr, "G nonzeros missmatch\n"); return false; } retranspose(Gp, Gi, Gx, d.sGT, m); opt |= PQ_KKT_UPDATE_G; }
-    if (c) std::copy(c, c + n, d.c.begin());
-    if (b) std::copy(b, b + p, d.b.begin());
-    if (h_l) d.set_h_l(h_l);
-    if (h_u) d.set_h_u(h_u);
-    if (h_l || h_u) d.disable_inf_constraints();
-    if (x_l) d.set_x_l(x_l);
-    if (x_u) d.set_x_u(x_u);
-    bool reuse = m_settings.preconditioner_reuse_on_update != 0;
-    if (opt == PQ_KKT_UPDATE_NONE) reuse = true;
-    scale_problem(reuse);
-    refresh_kkt(druiz_.get(), *m_kkt_system, d, opt);
-    if (dipm_) dipm_->refresh_data(d, m_preconditioner);
-    m_info.update_time = now_s() - t0;
-    return true;
-}
-
-// The same with the matrix values in DeviceRuiz's arrays (a device-fed solver, or the first device-mode update of a host-fed one): unscale_data -> assign ->
-// scale_data on the device, the KKT system refreshed from a device-mode descriptor; no matrix value comes to the host or goes back.  Px / Ax / Gx: device arrays
-// (mat_mem = PQ_MEM_DEVICE) or host arrays (a host-fed update of a device-fed solver: staged in HBM first) in the CSC order given at setup; the index arrays may be
-// null (identical sparsity is the precondition, the maps of the setup are used) and are only checked for their length.
-bool Solver::update_sparse_on_device(const int* Pp, const double* Px, const double* c, const int* Ap, const double* Ax, const double* b, const int* Gp, const double* Gx,
-                                     const double* h_l, const double* h_u, const double* x_l, const double* x_u, int mat_mem, double t0)
-{
-    HostData& d = *m_data;
-    const int n = d.n, p = d.p, m = d.m;
-    if (!druiz_) throw std::runtime_error("device matrices need the device preconditioner");
-    if (Pp && Px && Pp[n] != d.nnz_in[0]) { std::fprintf(stderr, "P nonzeros missmatch\n"); return false; }
-    if (Ap && Ax && Ap[n] != d.nnz_in[1]) { std::fprintf(stderr, "A nonzeros missmatch\n"); return false; }
-    if (Gp && Gx && Gp[n] != d.nnz_in[2]) { std::fprintf(stderr, "G nonzeros missmatch\n"); return false; }
-    if (p == 0) Ax = nullptr;
-    if (m == 0) Gx = nullptr;
-    PQ_HIP(hipSetDevice(device_));
-    unscale_problem();  // (host-fed so far: the mirror goes up, is unscaled, and comes back for the last time -- the device arrays keep the same values)
-    if (!d.values_on_device) {
-        Vec().swap(d.sP_utri.val); Vec().swap(d.sAT.val); Vec().swap(d.sGT.val);
-        d.values_on_device = true;
-    }
-    ingest_[0] = ingest_[1] = 0;
     DBuf<double> stage[3];
-    if (mat_mem != PQ_MEM_DEVICE) {
-        const double** src[3] = {&Px, &Ax, &Gx};
-        for (int k = 0; k < 3; ++k) {
-            if (!*src[k] || d.nnz_in[k] <= 0) continue;
-            stage[k].alloc((size_t)d.nnz_in[k]);
-            PQ_HIP(hipMemcpy(stage[k].p, *src[k], sizeof(double) * (size_t)d.nnz_in[k], hipMemcpyHostToDevice));
-            ingest_[0] += 8LL * d.nnz_in[k];
-            *src[k] = stage[k].p;
+    if (a.mem != PQ_MEM_DEVICE && !d.values_on_device) {
+        ingest_[0] += 8LL * ((a.P ? (long long)d.sP_utri.nnz() : 0) + (a.A ? d.sAT.nnz() : 0) + (a.G ? d.sGT.nnz() : 0));
+        unscale_problem();
+        if (a.P) {
+            for (int j = 0; j < n; ++j) {
+                const int have = a.Pp[j + 1] - a.Pp[j], need = d.sP_utri.colptr[j + 1] - d.sP_utri.colptr[j];
+                if (have < need) { std::fprintf(stderr, "P nonzeros missmatch\n"); return false; }
+                std::copy(a.P + a.Pp[j], a.P + a.Pp[j] + need, d.sP_utri.val.begin() + d.sP_utri.colptr[j]);
+            }
+            opt |= PQ_KKT_UPDATE_P;
         }
+        auto retranspose = [&](const int* Mp, const int* Mi, const double* Mx, Csc& T) {
+            IVec next(T.colptr.begin(), T.colptr.end() - 1);
+            for (int j = 0; j < n; ++j) for (int q = Mp[j]; q < Mp[j + 1]; ++q) { const int t = next[Mi[q]]++; T.rowind[t] = j; T.val[t] = Mx[q]; }
+        };
+        if (a.A) { if (a.Ap[n] != d.sAT.nnz()) { std::fprintf(stderr, "A nonzeros missmatch\n"); return false; } retranspose(a.Ap, a.Ai, a.A, d.sAT); opt |= PQ_KKT_UPDATE_A; }
+        if (a.G) { if (a.Gp[n] != d.sGT.nnz()) { std::fprintf(stderr, "G nonzeros missmatch\n"); return false; } retranspose(a.Gp, a.Gi, a.G, d.sGT); opt |= PQ_KKT_UPDATE_G; }
+    } else {
+        if (a.Pp && a.P && a.Pp[n] != d.nnz_in[0]) { std::fprintf(stderr, "P nonzeros missmatch\n"); return false; }
+        if (a.Ap && a.A && a.Ap[n] != d.nnz_in[1]) { std::fprintf(stderr, "A nonzeros missmatch\n"); return false; }
+        if (a.Gp && a.G && a.Gp[n] != d.nnz_in[2]) { std::fprintf(stderr, "G nonzeros missmatch\n"); return false; }
+        const double* val[3] = {a.P, p ? a.A : nullptr, m ? a.G : nullptr};
+        PQ_HIP(hipSetDevice(device_));
+        unscale_problem();  // (host-fed so far: the mirror goes up, is unscaled, and comes back for the last time -- the device arrays keep the same values)
+        if (!d.values_on_device) {
+            Vec().swap(d.sP_utri.val); Vec().swap(d.sAT.val); Vec().swap(d.sGT.val);
+            d.values_on_device = true;
+        }
+        for (int k = 0; k < 3; ++k) {
+            if (val[k]) opt |= PQ_KKT_UPDATE_P << k;  // (the flags of P, A, G are bits 0, 1, 2)
+            if (a.mem == PQ_MEM_DEVICE || !val[k] || d.nnz_in[k] <= 0) continue;
+            stage[k].alloc((size_t)d.nnz_in[k]);
+            PQ_HIP(hipMemcpy(stage[k].p, val[k], sizeof(double) * (size_t)d.nnz_in[k], hipMemcpyHostToDevice));
+            ingest_[0] += 8LL * d.nnz_in[k];
+            val[k] = stage[k].p;
+        }
+        ingest_[1] = druiz_->ingest_sparse(d, val[0], val[1], val[2], opt);
     }
-    int opt = PQ_KKT_UPDATE_NONE;
-    if (Px) opt |= PQ_KKT_UPDATE_P;
-    if (Ax) opt |= PQ_KKT_UPDATE_A;
-    if (Gx) opt |= PQ_KKT_UPDATE_G;
-    ingest_[1] = druiz_->ingest_sparse(d, Px, Ax, Gx, opt);
-    if (c) std::copy(c, c + n, d.c.begin());
-    if (b) std::copy(b, b + p, d.b.begin());
-    if (h_l) d.set_h_l(h_l);
-    if (h_u) d.set_h_u(h_u);
     IVec zeroed;
-    if (h_l || h_u) d.disable_inf_constraints(&zeroed);
-    druiz_->zero_G_rows(zeroed);
-    if (x_l) d.set_x_l(x_l);
-    if (x_u) d.set_x_u(x_u);
-    bool reuse = m_settings.preconditioner_reuse_on_update != 0;
-    if (opt == PQ_KKT_UPDATE_NONE) reuse = true;
-    scale_problem(reuse);
-    refresh_kkt(druiz_.get(), *m_kkt_system, d, opt);
-    if (dipm_) dipm_->refresh_data(d, m_preconditioner);
-    m_info.update_time = now_s() - t0;
-    return true;
+    assign_vectors(d, false, a.c, a.b, a.h_l, a.h_u, a.x_l, a.x_u, &zeroed);
+    if (d.values_on_device) druiz_->zero_G_rows(zeroed);
+    return finish_update(opt, t0);
 }
 
 // ---- calls into the device KKTSystem ------------------------------------------------------------
@@ -1352,6 +1333,27 @@ struct pq_solver {
     std::unique_ptr<Solver> impl;
 };
 
+namespace {
+bool bad_mem_or_layout(int mem, int layout) { return (mem != PQ_MEM_HOST && mem != PQ_MEM_DEVICE) || (layout != PQ_COL_MAJOR && layout != PQ_ROW_MAJOR); }
+ProblemArgs dense_args(int n, int p, int m, const double* P, const double* c, const double* A, const double* b, const double* G, const double* h_l, const double* h_u,
+                       const double* x_l, const double* x_u, int mem, int layout)
+{
+    ProblemArgs a;
+    a.n = n; a.p = p; a.m = m; a.mem = mem; a.layout = layout;
+    a.P = P; a.A = A; a.G = G;
+    a.c = c; a.b = b; a.h_l = h_l; a.h_u = h_u; a.x_l = x_l; a.x_u = x_u;
+    return a;
+}
+ProblemArgs sparse_args(int n, int p, int m, const int* Pp, const int* Pi, const double* Px, const double* c, const int* Ap, const int* Ai, const double* Ax, const double* b,
+                        const int* Gp, const int* Gi, const double* Gx, const double* h_l, const double* h_u, const double* x_l, const double* x_u, int mem)
+{
+    ProblemArgs a = dense_args(n, p, m, Px, c, Ax, b, Gx, h_l, h_u, x_l, x_u, mem, PQ_COL_MAJOR);
+    a.sparse = true;
+    a.Pp = Pp; a.Pi = Pi; a.Ap = Ap; a.Ai = Ai; a.Gp = Gp; a.Gi = Gi;
+    return a;
+}
+}  // namespace
+
 extern "C" {
 
 int pq_solver_create(pq_solver** out, int device)
@@ -1371,30 +1373,6 @@ int pq_solver_clone(const pq_solver* s, pq_solver** out)
 }
 pq_settings* pq_solver_settings(pq_solver* s) { return s ? &s->impl->settings() : nullptr; }
 
-namespace {
-bool bad_mem_or_layout(int mem, int layout) { return (mem != PQ_MEM_HOST && mem != PQ_MEM_DEVICE) || (layout != PQ_COL_MAJOR && layout != PQ_ROW_MAJOR); }
-// device-mode calls: the O(n + p + m) vectors are fetched into host staging and go through the host logic (bound lists, disabled rows of G) unchanged
-struct FetchedVectors {
-    Vec buf[6];
-    const double* fetch(int k, const double* dev, int len)
-    {
-        if (!dev || len <= 0) return dev;
-        buf[k].resize((size_t)len);
-        PQ_HIP(hipMemcpy(buf[k].data(), dev, sizeof(double) * (size_t)len, hipMemcpyDeviceToHost));
-        return buf[k].data();
-    }
-};
-// PIQP_AMD_DEBUG=host_ruiz only: a device matrix comes to the host
-const double* fetch_matrix(Vec& buf, const double* dev, size_t count, long long& bytes)
-{
-    if (!dev || !count) return dev;
-    buf.resize(count);
-    PQ_HIP(hipMemcpy(buf.data(), dev, sizeof(double) * count, hipMemcpyDeviceToHost));
-    bytes += (long long)(sizeof(double) * count);
-    return buf.data();
-}
-}  // namespace
-
 int pq_solver_setup_dense_mem(pq_solver* s, int n, int p, int m, const double* P, const double* c, const double* A, const double* b, const double* G, const double* h_l,
                               const double* h_u, const double* x_l, const double* x_u, int mem, int layout)
 {
@@ -1402,26 +1380,7 @@ int pq_solver_setup_dense_mem(pq_solver* s, int n, int p, int m, const double* P
     if (bad_mem_or_layout(mem, layout)) return fail(PQ_ERR_INVALID, "mem must be PQ_MEM_HOST or PQ_MEM_DEVICE, layout PQ_COL_MAJOR or PQ_ROW_MAJOR");
     // solver.hpp:175-178 argument checks
     if ((A && !b && p > 0) || (!h_l && !h_u && G && m > 0)) return fail(PQ_ERR_INVALID, "b / h_l or h_u must be provided");
-    if (mem == PQ_MEM_HOST) return guarded([&] { return s->impl->setup(make_dense_host_data(n, p, m, P, c, A, b, G, h_l, h_u, x_l, x_u, layout)) ? 1 : 0; });
-    return guarded([&] {
-        PQ_HIP(hipSetDevice(s->impl->device()));
-        const int pp = A ? p : 0, mm = G ? m : 0;
-        FetchedVectors v;
-        c = v.fetch(0, c, n); b = v.fetch(1, b, pp); h_l = v.fetch(2, h_l, mm); h_u = v.fetch(3, h_u, mm); x_l = v.fetch(4, x_l, n); x_u = v.fetch(5, x_u, n);
-        if (!Solver::device_ingest()) {
-            Vec hP, hA, hG;
-            long long bytes = 0;
-            P = fetch_matrix(hP, P, (size_t)n * n, bytes); A = fetch_matrix(hA, A, (size_t)n * pp, bytes); G = fetch_matrix(hG, G, (size_t)n * mm, bytes);
-            const bool ok = s->impl->setup(make_dense_host_data(n, p, m, P, c, A, b, G, h_l, h_u, x_l, x_u, layout));
-            s->impl->add_link_bytes(bytes);
-            return ok ? 1 : 0;
-        }
-        IVec zeroed;
-        auto data = make_dense_host_data(n, p, m, P, c, A, b, G, h_l, h_u, x_l, x_u, layout, true, &zeroed);
-        DenseDeviceSource src;
-        src.P = P; src.A = A; src.G = G; src.layout = layout;
-        return s->impl->setup(std::move(data), &src, &zeroed) ? 1 : 0;
-    });
+    return guarded([&] { return s->impl->setup(dense_args(n, p, m, P, c, A, b, G, h_l, h_u, x_l, x_u, mem, layout)) ? 1 : 0; });
 }
 int pq_solver_setup_dense(pq_solver* s, int n, int p, int m, const double* P, const double* c, const double* A, const double* b, const double* G, const double* h_l,
                           const double* h_u, const double* x_l, const double* x_u)
@@ -1435,27 +1394,9 @@ int pq_solver_setup_sparse_mem(pq_solver* s, int n, int p, int m, const int* Pp,
     if (!s || !Pp || !c || n <= 0) return fail(PQ_ERR_INVALID, "bad argument");
     if (mem != PQ_MEM_HOST && mem != PQ_MEM_DEVICE) return fail(PQ_ERR_INVALID, "mem must be PQ_MEM_HOST or PQ_MEM_DEVICE");
     if ((Ap && !b && p > 0) || (!h_l && !h_u && Gp && m > 0)) return fail(PQ_ERR_INVALID, "b / h_l or h_u must be provided");
-    if (mem == PQ_MEM_HOST) return guarded([&] { return s->impl->setup(make_sparse_host_data(n, p, m, Pp, Pi, Px, c, Ap, Ai, Ax, b, Gp, Gi, Gx, h_l, h_u, x_l, x_u)) ? 1 : 0; });
-    if (!Pi || (Pp[n] > 0 && !Px) || (Ap && p > 0 && (!Ai || (Ap[n] > 0 && !Ax))) || (Gp && m > 0 && (!Gi || (Gp[n] > 0 && !Gx)))) return fail(PQ_ERR_INVALID, "bad argument");
-    return guarded([&] {
-        PQ_HIP(hipSetDevice(s->impl->device()));
-        const int pp = Ap ? p : 0, mm = Gp ? m : 0;
-        FetchedVectors v;
-        c = v.fetch(0, c, n); b = v.fetch(1, b, pp); h_l = v.fetch(2, h_l, mm); h_u = v.fetch(3, h_u, mm); x_l = v.fetch(4, x_l, n); x_u = v.fetch(5, x_u, n);
-        if (!Solver::device_ingest()) {
-            Vec hP, hA, hG;
-            long long bytes = 0;
-            Px = fetch_matrix(hP, Px, (size_t)Pp[n], bytes); Ax = fetch_matrix(hA, Ax, pp ? (size_t)Ap[n] : 0, bytes); Gx = fetch_matrix(hG, Gx, mm ? (size_t)Gp[n] : 0, bytes);
-            const bool ok = s->impl->setup(make_sparse_host_data(n, p, m, Pp, Pi, Px, c, Ap, Ai, Ax, b, Gp, Gi, Gx, h_l, h_u, x_l, x_u));
-            s->impl->add_link_bytes(bytes);
-            return ok ? 1 : 0;
-        }
-        IVec zeroed;
-        auto data = make_sparse_host_data(n, p, m, Pp, Pi, nullptr, c, Ap, Ai, nullptr, b, Gp, Gi, nullptr, h_l, h_u, x_l, x_u, true, &zeroed);
-        SparseDeviceSource src;
-        src.Px = Px; src.Ax = pp ? Ax : nullptr; src.Gx = mm ? Gx : nullptr;
-        return s->impl->setup(std::move(data), nullptr, &zeroed, &src) ? 1 : 0;
-    });
+    if (mem == PQ_MEM_DEVICE && (!Pi || (Pp[n] > 0 && !Px) || (Ap && p > 0 && (!Ai || (Ap[n] > 0 && !Ax))) || (Gp && m > 0 && (!Gi || (Gp[n] > 0 && !Gx)))))
+        return fail(PQ_ERR_INVALID, "bad argument");
+    return guarded([&] { return s->impl->setup(sparse_args(n, p, m, Pp, Pi, Px, c, Ap, Ai, Ax, b, Gp, Gi, Gx, h_l, h_u, x_l, x_u, mem)) ? 1 : 0; });
 }
 int pq_solver_setup_sparse(pq_solver* s, int n, int p, int m, const int* Pp, const int* Pi, const double* Px, const double* c, const int* Ap, const int* Ai, const double* Ax,
                            const double* b, const int* Gp, const int* Gi, const double* Gx, const double* h_l, const double* h_u, const double* x_l, const double* x_u)
@@ -1467,24 +1408,7 @@ int pq_solver_update_dense_mem(pq_solver* s, const double* P, const double* c, c
 {
     if (!s) return fail(PQ_ERR_INVALID, "null argument");
     if (bad_mem_or_layout(mem, layout)) return fail(PQ_ERR_INVALID, "mem must be PQ_MEM_HOST or PQ_MEM_DEVICE, layout PQ_COL_MAJOR or PQ_ROW_MAJOR");
-    if (mem == PQ_MEM_HOST) return guarded([&] { return s->impl->update_dense(P, c, A, b, G, h_l, h_u, x_l, x_u, PQ_MEM_HOST, layout) ? 1 : 0; });
-    return guarded([&] {
-        const HostData* d = s->impl->data();
-        if (!d || d->sparse) { std::fprintf(stderr, "Solver not setup yet\n"); return 0; }
-        PQ_HIP(hipSetDevice(s->impl->device()));
-        const int n = d->n, p = d->p, m = d->m;
-        FetchedVectors v;
-        c = v.fetch(0, c, n); b = v.fetch(1, b, p); h_l = v.fetch(2, h_l, m); h_u = v.fetch(3, h_u, m); x_l = v.fetch(4, x_l, n); x_u = v.fetch(5, x_u, n);
-        if (!Solver::device_ingest()) {
-            Vec hP, hA, hG;
-            long long bytes = 0;
-            P = fetch_matrix(hP, P, (size_t)n * n, bytes); A = fetch_matrix(hA, A, (size_t)n * p, bytes); G = fetch_matrix(hG, G, (size_t)n * m, bytes);
-            const bool ok = s->impl->update_dense(P, c, A, b, G, h_l, h_u, x_l, x_u, PQ_MEM_HOST, layout);
-            s->impl->add_link_bytes(bytes);
-            return ok ? 1 : 0;
-        }
-        return s->impl->update_dense(P, c, A, b, G, h_l, h_u, x_l, x_u, PQ_MEM_DEVICE, layout) ? 1 : 0;
-    });
+    return guarded([&] { return s->impl->update(dense_args(0, 0, 0, P, c, A, b, G, h_l, h_u, x_l, x_u, mem, layout)) ? 1 : 0; });
 }
 int pq_solver_update_dense(pq_solver* s, const double* P, const double* c, const double* A, const double* b, const double* G, const double* h_l, const double* h_u,
                            const double* x_l, const double* x_u)
@@ -1502,26 +1426,7 @@ int pq_solver_update_sparse_mem(pq_solver* s, const int* Pp, const int* Pi, cons
 {
     if (!s) return fail(PQ_ERR_INVALID, "null argument");
     if (mem != PQ_MEM_HOST && mem != PQ_MEM_DEVICE) return fail(PQ_ERR_INVALID, "mem must be PQ_MEM_HOST or PQ_MEM_DEVICE");
-    if (mem == PQ_MEM_HOST) return guarded([&] { return s->impl->update_sparse(Pp, Pi, Px, c, Ap, Ai, Ax, b, Gp, Gi, Gx, h_l, h_u, x_l, x_u) ? 1 : 0; });
-    return guarded([&] {
-        const HostData* d = s->impl->data();
-        if (!d || !d->sparse) { std::fprintf(stderr, "Solver not setup yet\n"); return 0; }
-        PQ_HIP(hipSetDevice(s->impl->device()));
-        const int n = d->n, p = d->p, m = d->m;
-        FetchedVectors v;
-        c = v.fetch(0, c, n); b = v.fetch(1, b, p); h_l = v.fetch(2, h_l, m); h_u = v.fetch(3, h_u, m); x_l = v.fetch(4, x_l, n); x_u = v.fetch(5, x_u, n);
-        if (!Solver::device_ingest()) {
-            // the host path walks the index arrays: they must be given here
-            if ((Px && (!Pp || !Pi)) || (Ax && p > 0 && (!Ap || !Ai)) || (Gx && m > 0 && (!Gp || !Gi))) throw std::runtime_error("PIQP_AMD_DEBUG=host_ruiz: a device-mode update needs the index arrays");
-            Vec hP, hA, hG;
-            long long bytes = 0;
-            Px = fetch_matrix(hP, Px, (size_t)d->nnz_in[0], bytes); Ax = fetch_matrix(hA, Ax, (size_t)d->nnz_in[1], bytes); Gx = fetch_matrix(hG, Gx, (size_t)d->nnz_in[2], bytes);
-            const bool ok = s->impl->update_sparse(Pp, Pi, Px, c, Ap, Ai, Ax, b, Gp, Gi, Gx, h_l, h_u, x_l, x_u);
-            s->impl->add_link_bytes(bytes);
-            return ok ? 1 : 0;
-        }
-        return s->impl->update_sparse(Pp, Pi, Px, c, Ap, Ai, Ax, b, Gp, Gi, Gx, h_l, h_u, x_l, x_u, PQ_MEM_DEVICE) ? 1 : 0;
-    });
+    return guarded([&] { return s->impl->update(sparse_args(0, 0, 0, Pp, Pi, Px, c, Ap, Ai, Ax, b, Gp, Gi, Gx, h_l, h_u, x_l, x_u, mem)) ? 1 : 0; });
 }
 int pq_solver_update_sparse(pq_solver* s, const int* Pp, const int* Pi, const double* Px, const double* c, const int* Ap, const int* Ai, const double* Ax, const double* b,
                             const int* Gp, const int* Gi, const double* Gx, const double* h_l, const double* h_u, const double* x_l, const double* x_u)
@@ -1535,8 +1440,9 @@ int pq_debug_sparse_ingest_maps(int n, int p, int m, const int* Pp, const int* P
     if (n <= 0 || !Pp || (Pp[n] > 0 && !Pi) || p < 0 || m < 0) return fail(PQ_ERR_INVALID, "bad argument");
     if ((Ap && p > 0 && Ap[n] > 0 && !Ai) || (Gp && m > 0 && Gp[n] > 0 && !Gi)) return fail(PQ_ERR_INVALID, "bad argument");
     return guarded([&] {
+        Csc U, AT, GT;
         IVec sP, sA, sG;
-        build_sparse_ingest_maps(n, Ap ? p : 0, Gp ? m : 0, Pp, Pi, Ap, Ai, Gp, Gi, sP, sA, sG);
+        build_sparse_ingest_maps(n, Ap ? p : 0, Gp ? m : 0, Pp, Pi, Ap, Ai, Gp, Gi, U, AT, GT, sP, sA, sG);
         auto scatter = [](const IVec& src, int cnt, int* map) {
             if (!map) return;
             std::fill(map, map + cnt, -1);
@@ -1562,15 +1468,15 @@ int pq_solver_get_result_mem(const pq_solver* s, pq_vars* out, int mem)
     if (!s || !out) return fail(PQ_ERR_INVALID, "null argument");
     if (mem != PQ_MEM_HOST && mem != PQ_MEM_DEVICE) return fail(PQ_ERR_INVALID, "mem must be PQ_MEM_HOST or PQ_MEM_DEVICE");
     const HostVars& r = s->impl->result();
-    double* dst[10] = {out->x, out->y, out->z_l, out->z_u, out->z_bl, out->z_bu, out->s_l, out->s_u, out->s_bl, out->s_bu};
     if (mem == PQ_MEM_HOST) {
-        for (int k = 0; k < 10; ++k) if (dst[k]) std::copy(r.field(k).begin(), r.field(k).end(), dst[k]);
+        for (int k = 0; k < 10; ++k) if (vars_field(*out, k)) std::copy(r.field(k).begin(), r.field(k).end(), vars_field(*out, k));
         return PQ_OK;
     }
     // the solution the solve left in result() (unscaled, boxes expanded), O(n + p + m); blocking copies: the outputs are written when this returns
     return guarded([&] {
         PQ_HIP(hipSetDevice(s->impl->device()));
-        for (int k = 0; k < 10; ++k) if (dst[k] && !r.field(k).empty()) PQ_HIP(hipMemcpy(dst[k], r.field(k).data(), sizeof(double) * r.field(k).size(), hipMemcpyHostToDevice));
+        for (int k = 0; k < 10; ++k)
+            if (vars_field(*out, k) && !r.field(k).empty()) PQ_HIP(hipMemcpy(vars_field(*out, k), r.field(k).data(), sizeof(double) * r.field(k).size(), hipMemcpyHostToDevice));
         return (int)PQ_OK;
     });
 }

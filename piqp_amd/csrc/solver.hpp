@@ -86,16 +86,15 @@ private:
     std::unique_ptr<Impl> I;
 };
 
-// the dense matrices of a setup / update that already live in HBM on the solver's device: P n x n, A p x n, G m x n in storage order `layout`
-// (PQ_COL_MAJOR / PQ_ROW_MAJOR); nullptr = absent (setup) / unchanged (update).  They go to DeviceRuiz by kernel (ingest_kernels.hip), never through HostData.
-struct DenseDeviceSource {
-    const double *P = nullptr, *A = nullptr, *G = nullptr;
-    int layout = PQ_COL_MAJOR;
-};
-
-// the CSC value arrays of a sparse setup that already live in HBM on the solver's device, in the order of the (host) index arrays of the same call; nullptr = absent
-struct SparseDeviceSource {
-    const double *Px = nullptr, *Ax = nullptr, *Gx = nullptr;
+// The problem data of ONE setup() / update() call, as the C entry points receive it.  `mem` says where the value arrays live -- the matrices and the six vectors;
+// index arrays are host memory always.  nullptr = absent (setup) / unchanged (update); n, p, m are read at setup only.
+struct ProblemArgs {
+    bool sparse = false;
+    int n = 0, p = 0, m = 0;
+    int mem = PQ_MEM_HOST, layout = PQ_COL_MAJOR;             // layout: storage order of the dense P (n x n), A (p x n), G (m x n)
+    const double *P = nullptr, *A = nullptr, *G = nullptr;    // dense: the matrices; sparse: the values of the three CSC triples, beside
+    const int *Pp = nullptr, *Pi = nullptr, *Ap = nullptr, *Ai = nullptr, *Gp = nullptr, *Gi = nullptr;  // their column pointers and row indices
+    const double *c = nullptr, *b = nullptr, *h_l = nullptr, *h_u = nullptr, *x_l = nullptr, *x_u = nullptr;
 };
 
 class Solver {
@@ -105,19 +104,12 @@ public:
     std::unique_ptr<Solver> clone() const;
 
     pq_settings& settings() { return m_settings; }
-    // solver.hpp:151-216.  dev: the matrices of a dense problem come from device memory (data then carries vectors and bound lists only, and
-    // zeroed_rows the rows of G that data.hpp:144-169 disables); requires device_ingest()
-    // sdev: the same for a sparse problem (data built with values_on_device: patterns, gather maps, vectors and bound lists)
-    bool setup(std::unique_ptr<HostData> data, const DenseDeviceSource* dev = nullptr, const IVec* zeroed_rows = nullptr, const SparseDeviceSource* sdev = nullptr);
-    // solver.hpp:218-308.  The vectors are host arrays; P, A, G are host arrays (mat_mem = PQ_MEM_HOST) or device arrays (PQ_MEM_DEVICE, requires device_ingest())
-    // in storage order `layout`
-    bool update_dense(const double* P, const double* c, const double* A, const double* b, const double* G, const double* h_l, const double* h_u, const double* x_l,
-                      const double* x_u, int mat_mem = PQ_MEM_HOST, int layout = PQ_COL_MAJOR);
-    static bool device_ingest();                                  // false under PIQP_AMD_DEBUG=host_ruiz: the matrices are scaled on the host there
-    const long long* last_ingest() const { return ingest_; }      // pq_solver_last_ingest
-    void add_link_bytes(long long bytes) { ingest_[0] += bytes; }  // matrix bytes the C-ABI layer itself moved across the link for the last setup / update
-    bool update_sparse(const int* Pp, const int* Pi, const double* Px, const double* c, const int* Ap, const int* Ai, const double* Ax, const double* b, const int* Gp,
-                       const int* Gi, const double* Gx, const double* h_l, const double* h_u, const double* x_l, const double* x_u, int mat_mem = PQ_MEM_HOST);
+    // solver.hpp:151-216 and :218-308.  Device memory (a.mem = PQ_MEM_DEVICE) goes to DeviceRuiz by kernel (ingest_kernels.hip), never through HostData -- or, where
+    // device_ingest() is false, comes to the host first.  update() before a setup() of the same kind prints "Solver not setup yet" and returns false.
+    bool setup(const ProblemArgs& a);
+    bool update(const ProblemArgs& a);
+    static bool device_ingest();                              // false under PIQP_AMD_DEBUG=host_ruiz: the matrices are scaled on the host there
+    const long long* last_ingest() const { return ingest_; }  // pq_solver_last_ingest
     int solve();  // solver.hpp:69-148
     const pq_info& info() const { return m_info; }
     const HostVars& result() const { return m_result; }
@@ -129,9 +121,12 @@ public:
 
 private:
     int solve_impl();
-    bool update_sparse_on_device(const int* Pp, const double* Px, const double* c, const int* Ap, const double* Ax, const double* b, const int* Gp, const double* Gx,
-                                 const double* h_l, const double* h_u, const double* x_l, const double* x_u, int mat_mem, double t0);
-    bool update_vectors_only(const double* c, const double* b, const double* h_l, const double* h_u, const double* x_l, const double* x_u, double t0);
+    struct FetchedVectors;
+    ProblemArgs arrive(const ProblemArgs& in, size_t n, size_t p, size_t m, const size_t mat_len[3], FetchedVectors& stage);
+    bool update_vectors_only(const ProblemArgs& a, double t0);
+    bool update_dense(const ProblemArgs& a, double t0);
+    bool update_sparse(const ProblemArgs& a, double t0);
+    bool finish_update(int options, double t0);
     bool kkt_factor();
     void kkt_solve(const HostVars& rhs, HostVars& lhs);
     void eval_P_x(double alpha, const Vec& x, Vec& z);
@@ -177,15 +172,16 @@ private:
 
 bool verify_settings(const pq_settings& s);  // settings.hpp:84-106
 
-std::unique_ptr<HostData> make_dense_host_data(int n, int p, int m, const double* P, const double* c, const double* A, const double* b, const double* G, const double* h_l,
-                                               const double* h_u, const double* x_l, const double* x_u, int layout = PQ_COL_MAJOR, bool matrices_on_device = false,
-                                               IVec* zeroed_rows = nullptr);
+// HostData of a setup.  on_device (a.mem = PQ_MEM_DEVICE / values_on_device): the matrix values stay where they are -- the dense matrices only say which exist,
+// the sparse patterns and gather maps are built as ever -- and the rows of G without a finite bound, which DeviceRuiz then has to zero, are appended to *zeroed_rows.
+std::unique_ptr<HostData> make_dense_host_data(const ProblemArgs& a, IVec* zeroed_rows = nullptr);
 std::unique_ptr<HostData> make_sparse_host_data(int n, int p, int m, const int* Pp, const int* Pi, const double* Px, const double* c, const int* Ap, const int* Ai,
                                                 const double* Ax, const double* b, const int* Gp, const int* Gi, const double* Gx, const double* h_l, const double* h_u,
                                                 const double* x_l, const double* x_u, bool values_on_device = false, IVec* zeroed_rows = nullptr);
-// Gather maps of a sparse setup, from the patterns alone (host-only; pq_debug_sparse_ingest_maps): srcP[t] = position in the caller's P arrays of the t-th stored
-// entry of upper(P) -- per column the entries on or above the diagonal, rows ascending --, srcA[t] / srcG[t] = position in the caller's A / G arrays of the t-th
-// stored entry of A^T / G^T (the order csc_transpose and the retranspose of Solver::update_sparse produce).  Absent matrix: null pattern, empty map.
-void build_sparse_ingest_maps(int n, int p, int m, const int* Pp, const int* Pi, const int* Ap, const int* Ai, const int* Gp, const int* Gi, IVec& srcP, IVec& srcA, IVec& srcG);
+// The stored order of a sparse problem, from the patterns alone (host-only; pq_debug_sparse_ingest_maps): the patterns of U = upper(P) -- per column the entries on
+// or above the diagonal, rows ascending --, AT = A^T and GT = G^T -- in transposition order, the one the retranspose of Solver::update_sparse produces -- and the
+// gather maps to them: stored entry t = the caller's entry srcP[t] / srcA[t] / srcG[t].  Absent matrix: null pattern, n x 0 transpose, empty map.
+void build_sparse_ingest_maps(int n, int p, int m, const int* Pp, const int* Pi, const int* Ap, const int* Ai, const int* Gp, const int* Gi, Csc& U, Csc& AT, Csc& GT,
+                              IVec& srcP, IVec& srcA, IVec& srcG);
 
 }  // namespace pq

@@ -206,3 +206,23 @@ def test_clone_bitwise(hip):
     s2 = s1.clone()
     assert s1.solve() == 1 and s2.solve() == 1
     assert np.array_equal(s1.result()["x"], s2.result()["x"])
+
+
+def test_sparse_update_reads_the_upper_triangle_of_the_pattern_it_is_given(hip):
+    """a host-fed SparseSolver set up with the full symmetric P: update(P2) reads the pattern of THAT call -- of every column its leading entries, as many
+    as upper(P) keeps -- so the full P2 and triu(P2) are the same update (solver.hpp:317-331 update_P; tests/c/c_interface_kat.c relies on it through the C layer)"""
+    import scipy.sparse as sp
+    n, p, m = 7, 2, 3
+    q = dense_strongly_convex_qp(n, p, m, seed=5)
+    sym = lambda U: U + np.triu(U, 1).T
+    P2 = dense_strongly_convex_qp(n, p, m, seed=6)["P"]  # dense upper triangle: the same pattern as q["P"]
+    s0 = hip.SparseSolver()
+    s0.settings.kkt_solver = 1  # sparse_ldlt
+    assert s0.setup(sp.csc_matrix(sym(q["P"])), q["c"], sp.csc_matrix(q["A"]), q["b"], sp.csc_matrix(q["G"]), q["h_l"], q["h_u"], q["x_l"], q["x_u"])
+    s_full, s_triu = s0.clone(), s0.clone()
+    assert s_full.update(P=sp.csc_matrix(sym(P2))) and s_triu.update(P=sp.csc_matrix(np.triu(P2)))
+    assert s_full.solve() == s_triu.solve() == hip.kkt.PIQP_SOLVED
+    assert s_full.info.iter == s_triu.info.iter
+    r_full, r_triu = s_full.result(), s_triu.result()
+    for k in ("x", "y", "z_l", "z_u", "z_bl", "z_bu", "s_l", "s_u", "s_bl", "s_bu"):
+        assert np.array_equal(r_full[k], r_triu[k]), k
