@@ -670,8 +670,13 @@ int pq_kktsys_batch_last_ms(const pq_kktsys_batch *k, double out3[3]);
  * one pq_settings and the set of finite bounds.  The solve runs in rounds clocked by the host: a small kernel advances every instance to its next KKTSystem call, then
  * the factor launch and the solve launch of pq_kktsys_batch_* run on the instances that asked for them; the host reads three counters per round.  The instances need
  * not run in lock step; an instance that has ended is not touched again.
- * There is no update() and no clone() yet: a changed problem goes through pq_solver_batch_setup_dense again (the reference's update un-scales and re-scales all
- * three matrices even when only vectors change, and its dense backend then does not recompute A'A; reproducing that bit for bit is left to a later change).
+ * There is no clone() yet.  pq_solver_batch_update_dense is DenseSolver::update (solver.hpp:218-308): per instance it un-scales everything stored, assigns what is
+ * given, and scales again -- with the stored scalings when preconditioner_reuse_on_update is set or no matrix is given, else by a new equilibration -- so an update of
+ * c alone moves P, A' and G' by roundings, as in the reference.  ONE RULE IS NOT THE REFERENCE'S: its dense backend recomputes A'A only when A is given
+ * (dense/kkt.hpp:62-71); when P or G comes without A and the scalings are recomputed, A' is rescaled and A'A stays that of the old scalings, which turns solvable
+ * problems into MAX_ITER_REACHED or PRIMAL_INFEASIBLE.  Here A'A is recomputed from the rescaled A' when A is given, or when any matrix is given and
+ * preconditioner_reuse_on_update is 0; in every other case it is left alone, as the reference leaves it (the staleness is rounding only).  The state after such a call
+ * is the reference's after update(..., A = its own unscaled A), bit for bit.
  * Every argument is checked before the device is touched: PQ_ERR_UNSUPPORTED for n > 128; PQ_ERR_INVALID for batch < 1, n < 1, negative p or m, another kkt_solver,
  * a NULL P or c, a NULL matrix with a positive count, iterative_refinement_max_iter outside [0, 64], a bad mem or order, a solve before a setup (status PQ_UNSOLVED)
  * and settings that verify_settings refuses (every instance PQ_INVALID_SETTINGS, no launch). */
@@ -686,10 +691,24 @@ pq_settings *pq_solver_batch_settings(pq_solver_batch *s); /* shared by all inst
  * called again on the same handle; it is the only call besides create and destroy that may allocate.  Returns 1. */
 int pq_solver_batch_setup_dense(pq_solver_batch *s, int batch, int n, int p, int m, const double *P, const double *c, const double *A, const double *b,
                                 const double *G, const double *h_l, const double *h_u, const double *x_l, const double *x_u, int mem, int order);
+/* DenseSolver::update per instance, on the device, where the data stand.  Any pointer may be NULL (unchanged); all NULL is an unscale and a rescale, as in the
+ * reference.  Shapes, layouts, mem and order as in pq_solver_batch_setup_dense.  settings.preconditioner_reuse_on_update, preconditioner_iter and
+ * preconditioner_scale_cost are read at the call.  The set of finite bounds stays the setup's: the lists the reference would hold after the call (set_h_l / set_h_u
+ * with the given vector for a given side and the stored finiteness for the other, a row dropped at setup being stored finite on both sides as -1 / 1; then
+ * disable_inf_constraints, set_x_l, set_x_u) are worked out on the host, and if those of any instance differ from the setup's the call returns PQ_ERR_INVALID and the
+ * handle is as it was.  As in the reference, a row whose two bounds are both given infinite has its column of G' zeroed and its bounds set to -1 / 1, and the columns of
+ * a new G' of rows dropped earlier are zeroed only in a call that also gives h_l or h_u.  PQ_ERR_INVALID before the device is touched: a NULL handle, a call before a
+ * setup, a bad mem or order, A or b with p = 0, G, h_l or h_u with m = 0.  The call allocates nothing.  The next solve starts every instance from INIT (no warm start);
+ * statuses, results and traces of the previous solve stay readable until then.  info.update_time is the wall time of the call (the batch's), and a solve after an
+ * update reports run_time = update_time + solve_time.  Returns 1. */
+int pq_solver_batch_update_dense(pq_solver_batch *s, const double *P, const double *c, const double *A, const double *b, const double *G, const double *h_l,
+                                 const double *h_u, const double *x_l, const double *x_u, int mem, int order);
+/* of the last update: out2 = { wall ms, device ms (hipEvents around its kernels and copies) } */
+int pq_solver_batch_last_update_ms(const pq_solver_batch *s, double out2[2]);
 /* solve() of every instance; returns the number of instances that ended PQ_SOLVED (>= 0).  The number of rounds is bounded before the loop starts by
  * (max_iter + 1) (max_factor_retires + 4); a loop that reaches the bound returns PQ_ERR_INTERNAL and leaves every unfinished instance PQ_UNSOLVED. */
 int pq_solver_batch_solve(pq_solver_batch *s);
-/* result().info of one instance, n_factor and n_solve included; solve_time and run_time are the batch's, the other time fields are 0 */
+/* result().info of one instance, n_factor and n_solve included; update_time, solve_time and run_time are the batch's, the other time fields are 0 */
 const pq_info *pq_solver_batch_info(const pq_solver_batch *s, int instance);
 /* field 0..9 of Variables of ALL instances into a host or device array [batch][len], len as in the single solver's result (the box vectors at full length n,
  * restore_dual applied).  Device mode makes no allocation. */

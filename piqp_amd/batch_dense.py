@@ -31,8 +31,9 @@ class BatchDenseSolver(_BatchHandle):
 
     s.settings: the pq_settings shared by the batch.  s.setup(P, c, A=None, b=None, G=None, h_l=None, h_u=None, x_l=None, x_u=None): P [batch, n, n], A [batch, p, n],
     G [batch, m, n], vectors [batch, len]; NumPy arrays, or torch CUDA float64 tensors (with any CUDA tensor among the arguments the data stays on the GPU and NumPy
-    arguments beside it are moved there).  The instances share the set of finite bounds.  s.solve() returns the number of instances that ended SOLVED.  There is no
-    update(): a changed problem goes through setup() again."""
+    arguments beside it are moved there).  The instances share the set of finite bounds.  s.solve() returns the number of instances that ended SOLVED.
+    s.update(P=None, c=None, A=None, b=None, G=None, h_l=None, h_u=None, x_l=None, x_u=None): DenseSolver::update on the device, without a new setup; any subset of
+    the arguments, under the rules of setup; the set of finite bounds must stay the setup's (RuntimeError otherwise, the handle is as it was).  There is no clone()."""
     _destroy = "pq_solver_batch_destroy"
 
     def __init__(self, device=0, kkt_solver=DENSE_CHOLESKY):
@@ -68,14 +69,25 @@ class BatchDenseSolver(_BatchHandle):
         m = 0 if G is None else int(G.shape[1])
         return (b, n, p, m), dict(P=(b, n, n), c=(b, n), A=(b, p, n), b=(b, p), G=(b, m, n), h_l=(b, m), h_u=(b, m), x_l=(b, n), x_u=(b, n))
 
-    def _prepare(self, args):
-        """(dims, mem, order, the arrays to pass in the order of _NAMES); raises before any library call"""
+    def _prepare(self, args, dims=None):
+        """(dims, mem, order, the arrays to pass in the order of _NAMES); raises before any library call.  dims: None for a setup, which takes them from P, A and G;
+        the (batch, n, p, m) of the setup for an update, where every argument is optional"""
         a = dict(zip(_NAMES, args))
-        if a["P"] is None or a["c"] is None:
-            raise ValueError("P and c must be given")
-        dims, shapes = self.shapes(a["P"], a["A"], a["G"])
-        if a["A"] is None and a["b"] is not None or a["G"] is None and (a["h_l"] is not None or a["h_u"] is not None):
-            raise ValueError("b without A, or h_l / h_u without G")
+        if dims is None:
+            if a["P"] is None or a["c"] is None:
+                raise ValueError("P and c must be given")
+            dims, shapes = self.shapes(a["P"], a["A"], a["G"])
+            if a["A"] is None and a["b"] is not None or a["G"] is None and (a["h_l"] is not None or a["h_u"] is not None):
+                raise ValueError("b without A, or h_l / h_u without G")
+        else:
+            b, n, p, m = dims
+            shapes = dict(P=(b, n, n), c=(b, n), A=(b, p, n), b=(b, p), G=(b, m, n), h_l=(b, m), h_u=(b, m), x_l=(b, n), x_u=(b, n))
+            for k in ("A", "b") if p == 0 else ():
+                if a[k] is not None:
+                    raise ValueError(f"{k} given, the setup has p = 0")
+            for k in ("G", "h_l", "h_u") if m == 0 else ():
+                if a[k] is not None:
+                    raise ValueError(f"{k} given, the setup has m = 0")
         if device_call(args):
             mats = {}
             for k in ("P", "A", "G"):
@@ -109,6 +121,20 @@ class BatchDenseSolver(_BatchHandle):
             sync_current_stream(self.device)
         check(self.L.pq_solver_batch_setup_dense(self.h, *dims, *[self._p(v) for v in arrs], mem, order), "pq_solver_batch_setup_dense")
         self.batch, self.n, self.p, self.m = dims
+
+    def update(self, P=None, c=None, A=None, b=None, G=None, h_l=None, h_u=None, x_l=None, x_u=None):
+        if self.batch is None:
+            raise RuntimeError("update before setup")
+        _, mem, order, arrs = self._prepare((P, c, A, b, G, h_l, h_u, x_l, x_u), (self.batch, self.n, self.p, self.m))
+        if mem == MEM_DEVICE:
+            sync_current_stream(self.device)
+        return check(self.L.pq_solver_batch_update_dense(self.h, *[self._p(v) for v in arrs], mem, order), "pq_solver_batch_update_dense") == 1
+
+    def last_update_ms(self):
+        """of the last update: dict(wall_ms, device_ms)"""
+        o = np.zeros(2)
+        check(self.L.pq_solver_batch_last_update_ms(self.h, o.ctypes.data), "pq_solver_batch_last_update_ms")
+        return dict(wall_ms=float(o[0]), device_ms=float(o[1]))
 
     def solve(self):
         return check(self.L.pq_solver_batch_solve(self.h), "pq_solver_batch_solve")

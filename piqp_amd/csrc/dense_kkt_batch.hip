@@ -238,6 +238,8 @@ void kb_compute_ata(pq_kkt_batch* k)
 
 }  // namespace
 
+void pq::kb_refresh_ata(pq_kkt_batch* k) { kb_compute_ata(k); }
+
 int pq::kb_factor_done(pq_kkt_batch* k, const std::chrono::steady_clock::time_point* w0, const KbReadback* more, int n_more)
 {
     hipStream_t st = k->st;

@@ -1,6 +1,7 @@
 // piqp_amd/csrc/dense_kkt_batch_internal.hpp -- what stands behind a pq_kkt_batch handle (dense_kkt_batch.hip), and what the layers above it
 // (dense_kktsys_batch.hip, dense_solver_batch.hip) share with it on the host: the host-mode staging and the refinement cap (the length table of pq_vars, vars_lens, is common.hpp's).  Only
-// dense_kkt_batch.hip writes the handle's fields; dense_kktsys_batch.hip, whose factorisation launch leaves the factor store, the stored scalings and the status
+// dense_kkt_batch.hip writes the handle's fields, with one exception named at ksb_data_rewritten below (the solver's update rewrites Pu, AT, GT in place);
+// dense_kktsys_batch.hip, whose factorisation launch leaves the factor store, the stored scalings and the status
 // exactly as pq_kkt_batch_update_scalings_and_factor does, reads them and ends with kb_factor_done.  The launch-shape helpers (kb_factor_lds_bytes,
 // kb_solve_lds_bytes) are in dense_kkt_batch_device.hpp.
 #pragma once
@@ -74,6 +75,12 @@ int kb_factor_done(pq_kkt_batch* k, const std::chrono::steady_clock::time_point*
 // whose word is 0 is left out (it reads nothing, writes nothing, and in the n < 32 variant its wave still reaches every barrier of its workgroup).
 void ksb_launch_factor(pq_kktsys_batch* k, const int* flags, const double* rho, const double* delta, const pq_vars& v, const int* active);
 void ksb_launch_solve(pq_kktsys_batch* k, const pq_vars& rhs, const pq_vars& lhs, const int* active);
+// The one writer of the backend's data outside dense_kkt_batch.hip: pq_solver_batch_update_dense (dense_solver_batch.hip) unscales, assigns and rescales Pu, AT and
+// GT where they stand, by kernels on the handle's stream, and then says so here.  options: the PQ_KKT_UPDATE_* flags of the matrices its caller gave (P: the
+// system's P_diag is taken again, as KKTSystem::update_data does); refresh_ata: A'A is computed again from AT (kb_refresh_ata, dense_kkt_batch.hip);
+// x_b_scaling: device, [batch][n], copied into the system's own.  Everything goes on the stream, nothing waits.
+void ksb_data_rewritten(pq_kktsys_batch* k, int options, bool refresh_ata, const double* x_b_scaling);
+void kb_refresh_ata(pq_kkt_batch* k);
 hipStream_t ksb_stream(pq_kktsys_batch* k);
 const int* ksb_factor_status(const pq_kktsys_batch* k);  // device, [batch]: 0 = the instance's last factorisation succeeded
 const int* ksb_solve_info(const pq_kktsys_batch* k);     // device, [3][batch]: solve_ok, refine steps, backend solves of the instance's last solve

@@ -58,6 +58,16 @@ __device__ __forceinline__ double ksb_wave_max(double a)
     return a;
 }
 
+// ---- extract_P_diag (kkt_system.hpp:430-453): the diagonal the refinement's max_diag reads is the one of the last update_data that carried P, not the live one
+__global__ void k_ksb_pdiag(const double* __restrict__ Pu, double* __restrict__ out, int n, long long total)
+{
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= total) return;
+    const long long inst = e / n;
+    const int i = (int)(e % n);
+    out[e] = Pu[inst * (size_t)n * n + i + (size_t)i * n];
+}
+
 // ---- update_scalings_and_factor
 struct KsbFactorArgs {
     int n, p, m, ld, width, batch, nxl, nxu;
@@ -68,6 +78,7 @@ struct KsbFactorArgs {
     const double *v_s_l, *v_z_l, *v_s_u, *v_z_u, *v_s_bl, *v_z_bl, *v_s_bu, *v_z_bu;  // the caller's state, [batch][m] resp. [batch][n]
     const int *has_l, *has_u, *pos_l, *pos_u;  // row i has a lower / upper bound (>= 0); variable i is entry pos of the lower / upper box list (or -1)
     const double* xbs;                         // [batch][n]
+    const double* pdiag;                       // [batch][n]: the diagonal of P as of the last update_data that carried P (kkt_system.hpp:134-141)
     double reg_eps, reg_rel;
     double *s_l, *zinv_l, *s_u, *zinv_u, *s_bl, *zinv_bl, *s_bu, *zinv_bu, *z_reg, *rho_s, *mdelta_s;  // the handle's state
     int* use_ref;
@@ -118,7 +129,7 @@ __global__ __launch_bounds__(DFB_THREADS) void k_ksb_factor(const KsbFactorArgs 
             if (il >= 0) v += sc * sc / ((1.0 / A.v_z_bl[on + il]) * A.v_s_bl[on + il] + delta);
             if (iu >= 0) v += sc * sc / ((1.0 / A.v_z_bu[on + iu]) * A.v_s_bu[on + iu] + delta);
             xr[i] = v;
-            const double d = fabs(A.Pu[inst * nn + i + (size_t)i * n] + v);
+            const double d = fabs(A.pdiag[on + i] + v);
             if (d > md) md = d;  // (a NaN is ignored)
         }
     }
@@ -469,7 +480,7 @@ using namespace pq;
 
 namespace {
 // the state vectors of a handle, [batch][len] each
-enum { S_SL, S_ZIL, S_SU, S_ZIU, S_SBL, S_ZIBL, S_SBU, S_ZIBU, S_ZREG, S_RHO, S_MDELTA, S_RXB, S_RZB, S_XBS, S_COUNT };
+enum { S_SL, S_ZIL, S_SU, S_ZIU, S_SBL, S_ZIBL, S_SBU, S_ZIBU, S_ZREG, S_RHO, S_MDELTA, S_RXB, S_RZB, S_XBS, S_PDIAG, S_COUNT };
 struct KbDeleter {
     void operator()(pq_kkt_batch* b) const { pq_kkt_batch_destroy(b); }
 };
@@ -597,6 +608,13 @@ void ksb_upload_tables(pq_kktsys_batch* k)
     PQ_HIP(hipMemcpyAsync(k->tab.p, t.data(), sizeof(int) * t.size(), hipMemcpyHostToDevice, k->kb->st));
     stream_wait(k->kb->st);
 }
+// P_diag of every instance from the backend's P, on the handle's stream (nothing waits)
+void ksb_extract_pdiag(pq_kktsys_batch* k)
+{
+    const long long total = (long long)k->batch * k->n;
+    k_ksb_pdiag<<<(unsigned)((total + 255) / 256), 256, 0, k->kb->st>>>(k->kb->Pu.p, k->state[S_PDIAG].p, k->n, total);
+    PQ_HIP(hipGetLastError());
+}
 const int* ksb_has_l(const pq_kktsys_batch* k) { return k->tab.p; }
 const int* ksb_has_u(const pq_kktsys_batch* k) { return k->tab.p + k->m; }
 const int* ksb_pos_l(const pq_kktsys_batch* k) { return k->tab.p + 2 * (size_t)k->m; }
@@ -643,7 +661,7 @@ void ksb_launch_factor(pq_kktsys_batch* k, const int* flags, const double* rho, 
     a.flags = flags; a.active = active; a.rho = rho; a.delta = delta;
     a.v_s_l = v.s_l; a.v_z_l = v.z_l; a.v_s_u = v.s_u; a.v_z_u = v.z_u; a.v_s_bl = v.s_bl; a.v_z_bl = v.z_bl; a.v_s_bu = v.s_bu; a.v_z_bu = v.z_bu;
     a.has_l = ksb_has_l(k); a.has_u = ksb_has_u(k); a.pos_l = ksb_pos_l(k); a.pos_u = ksb_pos_u(k);
-    a.xbs = k->state[S_XBS].p;
+    a.xbs = k->state[S_XBS].p; a.pdiag = k->state[S_PDIAG].p;
     a.reg_eps = k->settings.iterative_refinement_static_regularization_eps; a.reg_rel = k->settings.iterative_refinement_static_regularization_rel;
     a.s_l = k->state[S_SL].p; a.zinv_l = k->state[S_ZIL].p; a.s_u = k->state[S_SU].p; a.zinv_u = k->state[S_ZIU].p;
     a.s_bl = k->state[S_SBL].p; a.zinv_bl = k->state[S_ZIBL].p; a.s_bu = k->state[S_SBU].p; a.zinv_bu = k->state[S_ZIBU].p;
@@ -682,6 +700,13 @@ void ksb_launch_solve(pq_kktsys_batch* k, const pq_vars& rhs, const pq_vars& lhs
     if (kb->kind == PQ_DENSE_CHOLESKY) k_ksb_solve<0><<<batch, threads, ksb_solve_lds_bytes(n), st>>>(a);
     else k_ksb_solve<1><<<batch, threads, ksb_solve_lds_bytes(n), st>>>(a);
     PQ_HIP(hipGetLastError());
+}
+
+void ksb_data_rewritten(pq_kktsys_batch* k, int options, bool refresh_ata, const double* x_b_scaling)
+{
+    if (options & PQ_KKT_UPDATE_P) ksb_extract_pdiag(k);
+    if (refresh_ata) kb_refresh_ata(k->kb.get());
+    copy_in(k->state[S_XBS].p, x_b_scaling, k->state[S_XBS].bytes(), PQ_MEM_DEVICE, k->kb->st);
 }
 
 hipStream_t ksb_stream(pq_kktsys_batch* k) { return k->kb->st; }
@@ -743,6 +768,7 @@ int pq_kktsys_batch_create_dense(pq_kktsys_batch** out, int device, int batch, i
             PQ_HIP(hipMemcpyAsync(k->state[S_XBS].p, ones.data(), sizeof(double) * ones.size(), hipMemcpyHostToDevice, st));
             stream_wait(st);
         }
+        ksb_extract_pdiag(k.get());
         stream_wait(st);
         *out = k.release();
         return (int)PQ_OK;
@@ -800,10 +826,11 @@ int pq_kktsys_batch_update_data_dense(pq_kktsys_batch* k, const double* P_utri, 
 {
     if (!k) return fail(PQ_ERR_INVALID, "null argument");
     if (int rc = pq_kkt_batch_update_data_dense(k->kb.get(), P_utri, AT, GT, options, mem)) return rc;
-    if (!x_b_scaling) return PQ_OK;
+    if (!x_b_scaling && !(options & PQ_KKT_UPDATE_P)) return PQ_OK;
     return guarded([&] {
         PQ_HIP(hipSetDevice(k->device));
-        copy_in(k->state[S_XBS].p, x_b_scaling, k->state[S_XBS].bytes(), mem, k->kb->st);
+        if (options & PQ_KKT_UPDATE_P) ksb_extract_pdiag(k);
+        if (x_b_scaling) copy_in(k->state[S_XBS].p, x_b_scaling, k->state[S_XBS].bytes(), mem, k->kb->st);
         stream_wait(k->kb->st);
         return (int)PQ_OK;
     });

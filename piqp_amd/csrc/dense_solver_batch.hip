@@ -27,6 +27,17 @@
 // number of rounds is bounded before it starts ((max_iter + 1) (max_factor_retires + 4)), a loop that reaches the bound returns PQ_ERR_INTERNAL.  No kernel here polls
 // memory, waits for another workgroup or loops on a condition computed from floating-point data (the Ruiz loop is counted, with the oracle's early exit).
 //
+// update() (solver.hpp:218-308, orc_solver.c:357-384) runs where the data stand, on the backend's own Pu, AT, GT and the vectors here: k_dsb_unscale, the assignment
+// (k_dsb_ingest for a given matrix, copies for c and b, the bound vectors through the host logic of the lists), then k_dsb_ruiz -- with the stored scalings when
+// preconditioner_reuse_on_update is set or no matrix was given, else the equilibration from delta = 1 on the unscaled data.  Unscaling and rescaling do not give the
+// stored bits back: an update of c alone moves P, A' and G' by roundings, and the kernels run the oracle's multiplications in the oracle's order.  The finite-bound set
+// stays the setup's (it is baked into the KKT system and into `tab`); a call whose lists would differ is refused before anything is written.
+// ONE RULE IS NOT THE REFERENCE'S.  dense/kkt.hpp:62-71 (orc_dense.c:609-613) recomputes A'A only when A is given.  When P or G comes without A and the scalings are
+// recomputed, A' is rescaled with the new scalings and A'A stays that of the old ones: on the oracle this turns solvable problems into MAX_ITER_REACHED or
+// PRIMAL_INFEASIBLE.  Here A'A is recomputed from the rescaled A' when A is given, or when any matrix is given and preconditioner_reuse_on_update == 0; in every other
+// case (vectors only; matrices without A under reuse) it is left alone as the reference leaves it, where the staleness is rounding only.  The single dense backends
+// refresh A'A at every update for the same reason (dense_exact.hip, dense_kkt.cpp).  The oracle reaches the same state with update(..., A = its own unscaled A).
+//
 // Arithmetic: every dot product and every sigma sum is ONE sequential chain in index order, each chain on a lane of its own (the lanes pick their operands, then run
 // the same loop); maxima and minima are order-independent and are wave / workgroup reductions (the maximum of :581-615 is SIGNED; inf_scaled is NaN-sticky).  The
 // scalar logic runs on lane 0 on the instance's state in LDS.
@@ -46,7 +57,7 @@ namespace pq {
 namespace {
 
 constexpr int DSB_T = 128;       // threads of k_dsb_advance, k_dsb_finish
-constexpr int DSB_RUIZ_T = 256;  // threads of k_dsb_ruiz
+constexpr int DSB_RUIZ_T = 256;  // threads of k_dsb_ruiz, k_dsb_unscale
 constexpr double DSB_INF = 1e30;  // fwd.hpp:54 PIQP_INF
 
 enum { ST_INIT = 0, ST_FACTOR0, ST_SOLVE0, ST_FACTOR, ST_PRED, ST_CORR, ST_NOINEQ, ST_DONE };
@@ -800,8 +811,10 @@ __global__ __launch_bounds__(DSB_T) void k_dsb_finish(const DsbFinishArgs A)
 
 // ---- the data of a setup: upper(P), A' and G' column-major from the caller's stacks
 // mode 0: dst = src (a row-major A is the column-major A'); 1: transpose of a column-major rows x n matrix; 2: upper triangle of a column-major P; 3: of a row-major P.
-// dead: columns of the result that are zeroed (rows of G without a finite bound)
-__global__ void k_dsb_ingest(const double* __restrict__ src, double* __restrict__ dst, int n, int cols, long long total, int mode, const int* __restrict__ dead)
+// dead: columns of the result that are zeroed (rows of G without a finite bound); instance `inst` reads dead[inst * dead_stride + column]: stride 0 at setup, where
+// the batch shares the mask, `cols` at an update, where an instance may give both bounds of a row infinite and another not
+__global__ void k_dsb_ingest(const double* __restrict__ src, double* __restrict__ dst, int n, int cols, long long total, int mode, const int* __restrict__ dead,
+                             int dead_stride)
 {
     const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= total) return;
@@ -813,13 +826,51 @@ __global__ void k_dsb_ingest(const double* __restrict__ src, double* __restrict_
     else if (mode == 1) v = s[j + (size_t)i * cols];
     else if (mode == 2) v = i <= j ? s[q] : 0.0;
     else v = i <= j ? s[j + (size_t)i * n] : 0.0;
-    if (dead && dead[j]) v = 0.0;
+    if (dead && dead[inst * dead_stride + j]) v = 0.0;
     dst[e] = v;
 }
 
-// ---- RuizEquilibration::scale_data, dense, first run (orc_solver.c:136-240), one workgroup per instance, in place
+// ---- RuizEquilibration::unscale_data, dense (orc_solver.c:243-256), one workgroup per instance, in place: the first step of an update
+// dead: null, or [batch][m]: the columns of G' that disable_inf_constraints zeroes in this update (a row whose two bounds are both given infinite)
+struct DsbUnscaleArgs {
+    int n, p, m, nxl, nxu;
+    double *Pu, *AT, *GT, *c, *b, *h_l, *h_u, *x_l, *x_u, *xbs;
+    const double *pdi, *pdbi, *pc_inv;
+    const int *xl_idx, *xu_idx, *dead;
+};
+__global__ __launch_bounds__(DSB_RUIZ_T) void k_dsb_unscale(const DsbUnscaleArgs A)
+{
+    const long long inst = blockIdx.x;
+    const int t = threadIdx.x, T = DSB_RUIZ_T, n = A.n, p = A.p, m = A.m, N = n + p + m;
+    double* P = A.Pu + inst * (size_t)n * n;
+    double* AT = A.AT + inst * (size_t)n * p;
+    double* GT = A.GT + inst * (size_t)n * m;
+    double *c = A.c + inst * (size_t)n, *b = A.b + inst * (size_t)p, *h_l = A.h_l + inst * (size_t)m, *h_u = A.h_u + inst * (size_t)m;
+    double *x_l = A.x_l + inst * (size_t)n, *x_u = A.x_u + inst * (size_t)n, *xbs = A.xbs + inst * (size_t)n;
+    const double *di = A.pdi + inst * (size_t)N, *dib = A.pdbi + inst * (size_t)n;
+    const int* dead = A.dead ? A.dead + inst * (size_t)m : nullptr;
+    const double ci = A.pc_inv[inst];
+    for (int e = t; e < n * n; e += T) {  // scale_P_scalar, then scale_P: the column pass, the row pass (the lower triangle is zero and stays zero)
+        const int i = e % n, j = e / n;
+        if (i <= j) P[e] = ((P[e] * ci) * di[j]) * di[i];
+    }
+    for (int i = t; i < n; i += T) {
+        c[i] = c[i] * (ci * di[i]);
+        xbs[i] = xbs[i] * (dib[i] * di[i]);
+    }
+    for (int e = t; e < n * p; e += T) AT[e] = (di[e % n] * AT[e]) * di[n + e / n];
+    for (size_t e = t; e < (size_t)n * m; e += T) GT[e] = dead && dead[e / n] ? 0.0 : (di[e % n] * GT[e]) * di[n + p + e / n];
+    for (int i = t; i < p; i += T) b[i] = b[i] * di[n + i];
+    for (int i = t; i < m; i += T) { h_l[i] = h_l[i] * di[n + p + i]; h_u[i] = h_u[i] * di[n + p + i]; }
+    for (int i = t; i < A.nxl; i += T) x_l[i] = x_l[i] * dib[A.xl_idx[i]];
+    for (int i = t; i < A.nxu; i += T) x_u[i] = x_u[i] * dib[A.xu_idx[i]];
+}
+
+// ---- RuizEquilibration::scale_data, dense (orc_solver.c:136-240), one workgroup per instance, in place.  reuse = 0: the equilibration from delta = 1 (a setup; an
+// update that gave a matrix with preconditioner_reuse_on_update off: xbs is read as it stands).  reuse = 1: the stored scalings are applied (:229-235) and they, their
+// inverses and c stay untouched.  Both end in the one tail :236-239.
 struct DsbRuizArgs {
-    int n, p, m, nxl, nxu, max_iter, scale_cost;
+    int n, p, m, nxl, nxu, max_iter, scale_cost, reuse;
     double epsilon;
     double *Pu, *AT, *GT, *c, *b, *h_l, *h_u, *x_l, *x_u, *xbs;
     double *pd, *pdb, *pdi, *pdbi, *pc, *pc_inv;
@@ -841,10 +892,24 @@ __global__ __launch_bounds__(DSB_RUIZ_T) void k_dsb_ruiz(const DsbRuizArgs A)
     double *x_l = A.x_l + inst * (size_t)n, *x_u = A.x_u + inst * (size_t)n, *xbs = A.xbs + inst * (size_t)n;
     double *delta = A.pd + inst * (size_t)N, *di = A.pdi + inst * (size_t)N, *delta_b = A.pdb + inst * (size_t)n, *dib = A.pdbi + inst * (size_t)n;
     double rc = 1.0;
-    for (int i = t; i < N; i += T) { delta[i] = 1.0; di[i] = 0.0; }
-    for (int i = t; i < n; i += T) { delta_b[i] = 1.0; dib[i] = 0.0; }
+    if (A.reuse) {
+        rc = A.pc[inst];
+        for (int e = t; e < n * n; e += T) {  // scale_P_scalar, then scale_P
+            const int i = e % n, j = e / n;
+            if (i <= j) P[e] = ((P[e] * rc) * delta[j]) * delta[i];
+        }
+        for (int i = t; i < n; i += T) {
+            c[i] = c[i] * (rc * delta[i]);
+            xbs[i] = xbs[i] * (delta_b[i] * delta[i]);
+        }
+        for (int e = t; e < n * p; e += T) AT[e] = (delta[e % n] * AT[e]) * delta[n + e / n];
+        for (size_t e = t; e < (size_t)n * m; e += T) GT[e] = (delta[e % n] * GT[e]) * delta[n + p + e / n];
+    } else {
+        for (int i = t; i < N; i += T) { delta[i] = 1.0; di[i] = 0.0; }
+        for (int i = t; i < n; i += T) { delta_b[i] = 1.0; dib[i] = 0.0; }
+    }
     __syncthreads();
-    for (int it = 0; it < A.max_iter; ++it) {
+    for (int it = 0; it < (A.reuse ? 0 : A.max_iter); ++it) {
         double dev[1] = {0.0};
         for (int i = t; i < N; i += T) dev[0] = dsb_dmax(dev[0], fabs(1.0 - di[i]));
         for (int i = t; i < n; i += T) dev[0] = dsb_dmax(dev[0], fabs(1.0 - dib[i]));
@@ -916,9 +981,11 @@ __global__ __launch_bounds__(DSB_RUIZ_T) void k_dsb_ruiz(const DsbRuizArgs A)
         }
     }
     __syncthreads();
-    if (t == 0) { A.pc[inst] = rc; A.pc_inv[inst] = 1.0 / rc; }
-    for (int i = t; i < N; i += T) di[i] = 1.0 / delta[i];
-    for (int i = t; i < n; i += T) dib[i] = 1.0 / delta_b[i];
+    if (!A.reuse) {
+        if (t == 0) { A.pc[inst] = rc; A.pc_inv[inst] = 1.0 / rc; }
+        for (int i = t; i < N; i += T) di[i] = 1.0 / delta[i];
+        for (int i = t; i < n; i += T) dib[i] = 1.0 / delta_b[i];
+    }
     for (int i = t; i < p; i += T) b[i] = b[i] * delta[n + i];
     for (int i = t; i < m; i += T) { h_l[i] = h_l[i] * delta[n + p + i]; h_u[i] = h_u[i] * delta[n + p + i]; }
     for (int i = t; i < A.nxl; i += T) x_l[i] = x_l[i] * delta_b[A.xl_idx[i]];
@@ -963,6 +1030,11 @@ struct DsbProblem {
     VarSet sets[6];  // result, res_nr, res, step, prox, the results handed out
     DBuf<double> c, b, h_l, h_u, x_l, x_u, xbs, pd, pdb, pdi, pdbi, pc, pc_inv, rho, delta, trace;
     DBuf<int> tab, flags, act, counters;
+    // what an update needs and only a setup may allocate: the staging of a host-fed matrix, the mask of the rows an update drops ([batch][m]; a setup uses the
+    // first m), and pinned room for the four bound vectors as fetched and as packed (2 batch (2 m + 2 n) doubles)
+    DBuf<double> raw;
+    DBuf<int> dead_d;
+    HBuf<double> bnd_h;
     DBuf<DsbState> state;
     HBuf<DsbState> state_h;
     HBuf<int> counters_h;
@@ -984,7 +1056,8 @@ struct pq_solver_batch {
     int device = 0;
     pq_settings settings;
     int trace_max = 0;
-    bool solved = false;
+    bool solved = false, updated = false;
+    double update_wall_ms = 0.0, update_device_ms = 0.0;
     double wall_ms = 0.0, device_ms = 0.0, factor_ms = 0.0, solve_ms = 0.0;
     int rounds = 0, launches = 0;
     pq_info invalid_info;  // what pq_solver_batch_info answers before a setup
@@ -1008,11 +1081,37 @@ int dsb_check_refine_cap(const pq_settings& s)
     return PQ_OK;
 }
 
-void dsb_ingest(hipStream_t st, const double* src, double* dst, int batch, int n, int cols, int mode, const int* dead)
+void dsb_ingest(hipStream_t st, const double* src, double* dst, int batch, int n, int cols, int mode, const int* dead, int dead_stride)
 {
     const long long total = (long long)batch * n * cols;
     if (total == 0) return;
-    k_dsb_ingest<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(src, dst, n, cols, total, mode, dead);
+    k_dsb_ingest<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(src, dst, n, cols, total, mode, dead, dead_stride);
+    PQ_HIP(hipGetLastError());
+}
+
+// one of the caller's matrix stacks into upper(P), A' or G' at `dst` (device): a host stack goes through the problem's staging first
+void dsb_matrix(DsbProblem* q, hipStream_t st, const double* src, double* dst, int cols, int mode, const int* dead, int dead_stride, int mem)
+{
+    if (!cols) return;
+    const double* from = src;
+    if (mem == PQ_MEM_HOST) {
+        PQ_HIP(hipMemcpyAsync(q->raw.p, src, sizeof(double) * (size_t)q->batch * q->n * cols, hipMemcpyHostToDevice, st));
+        from = q->raw.p;
+    }
+    dsb_ingest(st, from, dst, q->batch, q->n, cols, mode, dead, dead_stride);
+}
+
+// scale_data of every instance on the matrices at Pu, AT, GT (device), with the settings as they stand
+void dsb_launch_ruiz(const pq_solver_batch* s, DsbProblem* q, hipStream_t st, double* Pu, double* AT, double* GT, int reuse)
+{
+    DsbRuizArgs r;
+    r.n = q->n; r.p = q->p; r.m = q->m; r.nxl = q->cnt[2]; r.nxu = q->cnt[3]; r.max_iter = s->settings.preconditioner_iter; r.scale_cost = s->settings.preconditioner_scale_cost;
+    r.reuse = reuse;
+    r.epsilon = 1e-3;
+    r.Pu = Pu; r.AT = AT; r.GT = GT; r.c = q->c.p; r.b = q->b.p; r.h_l = q->h_l.p; r.h_u = q->h_u.p; r.x_l = q->x_l.p; r.x_u = q->x_u.p; r.xbs = q->xbs.p;
+    r.pd = q->pd.p; r.pdb = q->pdb.p; r.pdi = q->pdi.p; r.pdbi = q->pdbi.p; r.pc = q->pc.p; r.pc_inv = q->pc_inv.p;
+    r.xl_idx = q->xl_idx(); r.xu_idx = q->xu_idx();
+    k_dsb_ruiz<<<q->batch, DSB_RUIZ_T, 0, st>>>(r);
     PQ_HIP(hipGetLastError());
 }
 
@@ -1136,24 +1235,14 @@ int pq_solver_batch_setup_dense(pq_solver_batch* s, int batch, int n, int p, int
         }
         // the matrices: upper(P), A', G' column-major in temporaries, equilibrated there, then handed to the KKT system (which keeps its own copies)
         Stream st(s->device);
-        DBuf<double> Pu(B * n * n), AT(B * n * p), GT(B * n * m), raw;
-        DBuf<int> dead_d((size_t)m);
+        DBuf<double> Pu(B * n * n), AT(B * n * p), GT(B * n * m);
         q->tab.alloc(tab.size());
+        q->dead_d.alloc(B * m); q->raw.alloc(B * n * (size_t)std::max(n, std::max(p, m))); q->bnd_h.alloc(2 * B * (2 * (size_t)m + 2 * (size_t)n));
         if (!tab.empty()) PQ_HIP(hipMemcpyAsync(q->tab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, st));
-        if (m > 0) PQ_HIP(hipMemcpyAsync(dead_d.p, dead.data(), sizeof(int) * m, hipMemcpyHostToDevice, st));
-        if (mem == PQ_MEM_HOST) raw.alloc(B * n * (size_t)std::max(n, std::max(p, m)));
-        auto matrix = [&](const double* src, double* dst, int cols, int mode, const int* dd) {
-            if (!cols) return;
-            const double* from = src;
-            if (mem == PQ_MEM_HOST) {
-                PQ_HIP(hipMemcpyAsync(raw.p, src, sizeof(double) * B * n * cols, hipMemcpyHostToDevice, st));
-                from = raw.p;
-            }
-            dsb_ingest(st, from, dst, batch, n, cols, mode, dd);
-        };
-        matrix(P, Pu.p, n, order == PQ_COL_MAJOR ? 2 : 3, nullptr);
-        matrix(A, AT.p, p, order == PQ_COL_MAJOR ? 1 : 0, nullptr);
-        matrix(G, GT.p, m, order == PQ_COL_MAJOR ? 1 : 0, dead_d.p);
+        if (m > 0) PQ_HIP(hipMemcpyAsync(q->dead_d.p, dead.data(), sizeof(int) * m, hipMemcpyHostToDevice, st));
+        dsb_matrix(q.get(), st, P, Pu.p, n, order == PQ_COL_MAJOR ? 2 : 3, nullptr, 0, mem);
+        dsb_matrix(q.get(), st, A, AT.p, p, order == PQ_COL_MAJOR ? 1 : 0, nullptr, 0, mem);
+        dsb_matrix(q.get(), st, G, GT.p, m, order == PQ_COL_MAJOR ? 1 : 0, q->dead_d.p, 0, mem);
         auto up = [&](DBuf<double>& d, const std::vector<double>& v, size_t count) {
             d.alloc(count);
             if (count) PQ_HIP(hipMemcpyAsync(d.p, v.data(), sizeof(double) * count, hipMemcpyHostToDevice, st));
@@ -1161,14 +1250,7 @@ int pq_solver_batch_setup_dense(pq_solver_batch* s, int batch, int n, int p, int
         const std::vector<double> ones(B * n, 1.0);
         up(q->c, hc, B * n); up(q->b, hb, B * p); up(q->h_l, vhl, B * m); up(q->h_u, vhu, B * m); up(q->x_l, vxl, B * n); up(q->x_u, vxu, B * n); up(q->xbs, ones, B * n);
         q->pd.alloc(B * N); q->pdi.alloc(B * N); q->pdb.alloc(B * n); q->pdbi.alloc(B * n); q->pc.alloc(B); q->pc_inv.alloc(B);
-        DsbRuizArgs r;
-        r.n = n; r.p = p; r.m = m; r.nxl = q->cnt[2]; r.nxu = q->cnt[3]; r.max_iter = s->settings.preconditioner_iter; r.scale_cost = s->settings.preconditioner_scale_cost;
-        r.epsilon = 1e-3;
-        r.Pu = Pu.p; r.AT = AT.p; r.GT = GT.p; r.c = q->c.p; r.b = q->b.p; r.h_l = q->h_l.p; r.h_u = q->h_u.p; r.x_l = q->x_l.p; r.x_u = q->x_u.p; r.xbs = q->xbs.p;
-        r.pd = q->pd.p; r.pdb = q->pdb.p; r.pdi = q->pdi.p; r.pdbi = q->pdbi.p; r.pc = q->pc.p; r.pc_inv = q->pc_inv.p;
-        r.xl_idx = q->xl_idx(); r.xu_idx = q->xu_idx();
-        k_dsb_ruiz<<<batch, DSB_RUIZ_T, 0, st>>>(r);
-        PQ_HIP(hipGetLastError());
+        dsb_launch_ruiz(s, q.get(), st, Pu.p, AT.p, GT.p, 0);
         stream_wait(st);
         pq_kktsys_batch* ks = nullptr;
         if (int rc = pq_kktsys_batch_create_dense(&ks, s->device, batch, n, p, m, Pu.p, AT.p, GT.p, q->cnt[0], q->cnt[1], q->cnt[2], q->cnt[3], q->idx[0].data(), q->idx[1].data(),
@@ -1188,8 +1270,117 @@ int pq_solver_batch_setup_dense(pq_solver_batch* s, int batch, int n, int p, int
         PQ_HIP(hipMemcpyAsync(s->pr->state.p, s->pr->state_h.p, sizeof(DsbState) * B, hipMemcpyHostToDevice, kst));
         stream_wait(kst);
         s->solved = false;
+        s->updated = false;
         return 1;
     });
+}
+
+int pq_solver_batch_update_dense(pq_solver_batch* s, const double* P, const double* c, const double* A, const double* b, const double* G, const double* h_l,
+                                 const double* h_u, const double* x_l, const double* x_u, int mem, int order)
+{
+    if (!s) return fail(PQ_ERR_INVALID, "null argument");
+    if (kb_bad_mem(mem)) return fail(PQ_ERR_INVALID, "dense solver batch: bad mem %d", mem);
+    if (order != PQ_COL_MAJOR && order != PQ_ROW_MAJOR) return fail(PQ_ERR_INVALID, "dense solver batch: bad order %d", order);
+    DsbProblem* q = s->pr.get();
+    if (!q) return fail(PQ_ERR_INVALID, "dense solver batch: update before setup");
+    if (q->p == 0 && (A || b)) return fail(PQ_ERR_INVALID, "dense solver batch: update: A or b given, p = 0");
+    if (q->m == 0 && (G || h_l || h_u)) return fail(PQ_ERR_INVALID, "dense solver batch: update: G, h_l or h_u given, m = 0");
+    return guarded([&] {
+        PQ_HIP(hipSetDevice(s->device));
+        const auto w0 = std::chrono::steady_clock::now();
+        const int batch = q->batch, n = q->n, p = q->p, m = q->m;
+        const size_t B = (size_t)batch, half = B * (2 * (size_t)m + 2 * (size_t)n);
+        pq_kktsys_batch* ks = q->ks.get();
+        pq_kkt_batch* kb = pq_kktsys_batch_backend(ks);
+        hipStream_t st = ksb_stream(ks);
+        // ---- the host: the lists the reference would hold after this call (dense/data.hpp:98-207) must be the setup's, which the KKT system and `tab` carry
+        const double* given[4] = {h_l, h_u, x_l, x_u};
+        const double* hv[4];
+        double* packed[4];
+        bool fetched = false;
+        for (int k = 0; k < 4; ++k) {
+            const size_t off = k == 0 ? 0 : k == 1 ? B * m : k == 2 ? 2 * B * m : 2 * B * m + B * n, count = B * (k < 2 ? m : n);
+            packed[k] = q->bnd_h.p + half + off;
+            hv[k] = given[k];
+            if (given[k] && mem == PQ_MEM_DEVICE && count) {
+                PQ_HIP(hipMemcpyAsync(q->bnd_h.p + off, given[k], sizeof(double) * count, hipMemcpyDeviceToHost, st));
+                hv[k] = q->bnd_h.p + off;
+                fetched = true;
+            }
+        }
+        if (fetched) stream_wait(st);
+        std::vector<char> in[4] = {std::vector<char>(m, 0), std::vector<char>(m, 0), std::vector<char>(n, 0), std::vector<char>(n, 0)};  // stored finite: in the list
+        for (int k = 0; k < 4; ++k)
+            for (int j : q->idx[k]) in[k][j] = 1;
+        const bool rows = h_l || h_u;
+        std::vector<int> dead;
+        bool any_dead = false;
+        if (rows) dead.assign(B * m, 0);
+        for (size_t i = 0; i < B; ++i) {
+            for (int j = 0; j < m && rows; ++j) {
+                const bool fl = h_l ? hv[0][i * m + j] > -DSB_INF : (bool)in[0][j], fu = h_u ? hv[1][i * m + j] < DSB_INF : (bool)in[1][j];
+                const bool dd = !fl && !fu;  // disable_inf_constraints: the row of G is zeroed, its bounds become -1 / 1
+                if ((fl || dd) != (bool)in[0][j] || (fu || dd) != (bool)in[1][j])
+                    return fail(PQ_ERR_INVALID, "dense solver batch: update: the set of finite bounds of row %d of G changes in instance %zu (it is fixed at setup)", j, i);
+                dead[i * m + j] = dd;
+                any_dead = any_dead || dd;
+                if (h_l) packed[0][i * m + j] = dd ? -1.0 : fl ? hv[0][i * m + j] : -DSB_INF;
+                if (h_u) packed[1][i * m + j] = dd ? 1.0 : fu ? hv[1][i * m + j] : DSB_INF;
+            }
+            for (int k = 2; k < 4; ++k) {
+                if (!given[k]) continue;
+                for (int j = 0; j < n; ++j) {
+                    const double v = hv[k][i * n + j];
+                    if ((k == 2 ? v > -DSB_INF : v < DSB_INF) != (bool)in[k][j])
+                        return fail(PQ_ERR_INVALID, "dense solver batch: update: the set of finite bounds of variable %d changes in instance %zu (it is fixed at setup)", j, i);
+                    packed[k][i * n + j] = 0.0;
+                }
+                for (int e = 0; e < q->cnt[k]; ++e) packed[k][i * n + e] = hv[k][i * n + q->idx[k][e]];
+            }
+        }
+        // ---- the device: unscale, assign, rescale, all where the data stand
+        PQ_HIP(hipEventRecord(q->ev[0], st));
+        const int* dd = nullptr;
+        if (any_dead) {
+            PQ_HIP(hipMemcpyAsync(q->dead_d.p, dead.data(), sizeof(int) * dead.size(), hipMemcpyHostToDevice, st));
+            dd = q->dead_d.p;
+        }
+        DsbUnscaleArgs u;
+        u.n = n; u.p = p; u.m = m; u.nxl = q->cnt[2]; u.nxu = q->cnt[3];
+        u.Pu = kb->Pu.p; u.AT = kb->AT.p; u.GT = kb->GT.p; u.c = q->c.p; u.b = q->b.p; u.h_l = q->h_l.p; u.h_u = q->h_u.p; u.x_l = q->x_l.p; u.x_u = q->x_u.p; u.xbs = q->xbs.p;
+        u.pdi = q->pdi.p; u.pdbi = q->pdbi.p; u.pc_inv = q->pc_inv.p; u.xl_idx = q->xl_idx(); u.xu_idx = q->xu_idx(); u.dead = dd;
+        k_dsb_unscale<<<batch, DSB_RUIZ_T, 0, st>>>(u);
+        PQ_HIP(hipGetLastError());
+        int opt = PQ_KKT_UPDATE_NONE;
+        if (P) { dsb_matrix(q, st, P, kb->Pu.p, n, order == PQ_COL_MAJOR ? 2 : 3, nullptr, 0, mem); opt |= PQ_KKT_UPDATE_P; }
+        if (A) { dsb_matrix(q, st, A, kb->AT.p, p, order == PQ_COL_MAJOR ? 1 : 0, nullptr, 0, mem); opt |= PQ_KKT_UPDATE_A; }
+        if (G) { dsb_matrix(q, st, G, kb->GT.p, m, order == PQ_COL_MAJOR ? 1 : 0, dd, m, mem); opt |= PQ_KKT_UPDATE_G; }
+        if (c) copy_in(q->c.p, c, sizeof(double) * B * n, mem, st);
+        if (b) copy_in(q->b.p, b, sizeof(double) * B * p, mem, st);
+        DBuf<double>* dst[4] = {&q->h_l, &q->h_u, &q->x_l, &q->x_u};
+        for (int k = 0; k < 4; ++k)
+            if (given[k]) copy_in(dst[k]->p, packed[k], dst[k]->bytes(), PQ_MEM_HOST, st);
+        const bool reuse = s->settings.preconditioner_reuse_on_update || opt == PQ_KKT_UPDATE_NONE;
+        dsb_launch_ruiz(s, q, st, kb->Pu.p, kb->AT.p, kb->GT.p, reuse);
+        // A'A: the reference takes it again only with A; with new scalings it has to follow A' (the header says why)
+        ksb_data_rewritten(ks, opt, A != nullptr || !reuse, q->xbs.p);
+        PQ_HIP(hipEventRecord(q->ev[1], st));
+        stream_wait(st);
+        float ms = 0.f;
+        PQ_HIP(hipEventElapsedTime(&ms, q->ev[0], q->ev[1]));
+        const double wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
+        for (int i = 0; i < batch; ++i) q->state_h.p[i].info.update_time = wall * 1e-3;  // (the batch's)
+        s->update_wall_ms = wall; s->update_device_ms = ms;
+        s->updated = true;
+        return 1;
+    });
+}
+
+int pq_solver_batch_last_update_ms(const pq_solver_batch* s, double out2[2])
+{
+    if (!s || !out2) return fail(PQ_ERR_INVALID, "null argument");
+    out2[0] = s->update_wall_ms; out2[1] = s->update_device_ms;
+    return PQ_OK;
 }
 
 int pq_solver_batch_solve(pq_solver_batch* s)
@@ -1292,7 +1483,7 @@ int pq_solver_batch_solve(pq_solver_batch* s)
             if (!done && q->state_h.p[i].stage != ST_DONE) I.status = PQ_UNSOLVED;
             solved += I.status == PQ_SOLVED;
             I.solve_time = wall * 1e-3;  // (the batch's)
-            I.run_time = I.setup_time + I.solve_time;
+            I.run_time = (s->updated ? I.update_time : I.setup_time) + I.solve_time;
         }
         s->wall_ms = wall; s->device_ms = dev_ms; s->factor_ms = f_ms; s->solve_ms = s_ms; s->rounds = (int)round; s->launches = launches;
         s->solved = true;
