@@ -762,6 +762,34 @@ int pq_microbench_potrf_block(int device, int ldlt, int reps, double *us_out, lo
  * (LDLT), the operand pack of the panel solve pack[36 * 256] (blocks j (j - 1) / 2 + k: -L(j, k), blocks 28 + k: the inverse of L_kk; column-major 16 x 16 each), info
  * (-1 or the first failing column), and the number of repetitions whose outputs differ from the first one's in any bit (0: the kernel is deterministic) */
 int pq_debug_potrf_block(int device, int ldlt, int nb, int reps, const double *A, double *L, double *rdiag, double *dvec, double *pack, int *info, int *differing_reps);
+/* testing aid: ONE operation of the CSC mat-vec layer under every sparse backend (csrc/sparse_ops.hip, CscOperators) on the caller's data, with no symbolic analysis and
+ * no factorisation: the operators are built from `data` (host arrays), the values are replaced through the update path when P_val2 / AT_val2 / GT_val2 are given (all
+ * three then, same patterns; an array of a matrix without entries may be NULL), the operation runs once on a stream of its own in the default or (ref_order != 0) the
+ * reference-order mode, and the results come back.  All vectors are HOST memory.  The three outputs out_x[n], out_y[p], out_z[m] are copied DOWN before the operation
+ * and back up after it whatever the operation writes, so an entry it leaves alone keeps the caller's value.  A NULL input vector is read as zeros.
+ *   PQ_CSC_EVAL_P_X:  out_x = alpha_n P in_x
+ *   PQ_CSC_EVAL_A:    out_y = alpha_n A in_x, out_x = alpha_t A' in_y         PQ_CSC_EVAL_G: out_z = alpha_n G in_x, out_x = alpha_t G' in_z
+ *   PQ_CSC_FOLD_RHS:  out_x = rhs_x + G' (zinv .* rhs_z) + delta_inv A' rhs_y  (with_A / with_G: 0 leaves the term out)
+ *   PQ_CSC_RECOVER_DUALS: out_y = delta_inv A in_x - delta_inv rhs_y, out_z = (G in_x - rhs_z) .* zinv  (with_A / with_G: 0 leaves the output alone)
+ *   PQ_CSC_FOLD_RHS_ROWS, PQ_CSC_RECOVER_DUALS_ROWS: the same two on the listed rows (rows_x[nx]; rows_y[ny], rows_z[nz])
+ *   PQ_CSC_RESIDUAL_ROWS: the refinement residual of (in_x, in_y, in_z) against rhs_* with x_reg, delta, z_reg on the listed rows into out_*; absmax_bits receives the
+ *                     bit pattern of max |err| over them (NaN-propagating, 0 for no rows) and result 1, or result 0 when a column is too long for this form
+ *   PQ_CSC_P_DIAG:    out_x = diag(P) */
+enum { PQ_CSC_EVAL_P_X = 0, PQ_CSC_EVAL_A, PQ_CSC_EVAL_G, PQ_CSC_FOLD_RHS, PQ_CSC_RECOVER_DUALS, PQ_CSC_FOLD_RHS_ROWS, PQ_CSC_RECOVER_DUALS_ROWS, PQ_CSC_RESIDUAL_ROWS,
+       PQ_CSC_P_DIAG };
+typedef struct {
+    double alpha_n, alpha_t, delta, delta_inv;
+    int with_A, with_G;
+    const double *P_val2, *AT_val2, *GT_val2;
+    const double *in_x, *in_y, *in_z;
+    const double *rhs_x, *rhs_y, *rhs_z, *zinv, *x_reg, *z_reg;
+    const int *rows_x, *rows_y, *rows_z;
+    int nx, ny, nz;
+    double *out_x, *out_y, *out_z;
+    unsigned long long absmax_bits;
+    int result;
+} pq_csc_op_io;
+int pq_debug_csc_ops(int device, const pq_sparse_data *data, int op, int ref_order, pq_csc_op_io *io);
 
 #ifdef __cplusplus
 }

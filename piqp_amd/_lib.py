@@ -35,6 +35,22 @@ class SparseData(C.Structure):
                 ("x_b_scaling", vp), ("mem", C.c_int)]
 
 
+class CscOpIO(C.Structure):
+    """pq_csc_op_io: arguments and results of pq_debug_csc_ops"""
+    _fields_ = [("alpha_n", C.c_double), ("alpha_t", C.c_double), ("delta", C.c_double), ("delta_inv", C.c_double),
+                ("with_A", C.c_int), ("with_G", C.c_int),
+                ("P_val2", vp), ("AT_val2", vp), ("GT_val2", vp),
+                ("in_x", vp), ("in_y", vp), ("in_z", vp),
+                ("rhs_x", vp), ("rhs_y", vp), ("rhs_z", vp), ("zinv", vp), ("x_reg", vp), ("z_reg", vp),
+                ("rows_x", vp), ("rows_y", vp), ("rows_z", vp),
+                ("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int),
+                ("out_x", vp), ("out_y", vp), ("out_z", vp),
+                ("absmax_bits", C.c_ulonglong), ("result", C.c_int)]
+
+
+CSC_OPS = ("eval_P_x", "eval_A", "eval_G", "fold_rhs", "recover_duals", "fold_rhs_rows", "recover_duals_rows", "residual_rows", "P_diag")  # PQ_CSC_*
+
+
 class Vars(C.Structure):
     _fields_ = [(k, vp) for k in VAR_NAMES]
 
@@ -96,7 +112,7 @@ SYMBOLS = [
     "pq_solver_batch_create", "pq_solver_batch_destroy", "pq_solver_batch_settings", "pq_solver_batch_setup_dense", "pq_solver_batch_solve", "pq_solver_batch_info",
     "pq_solver_batch_get_result_mem", "pq_solver_batch_set_trace", "pq_solver_batch_get_trace", "pq_solver_batch_dims", "pq_solver_batch_last_ms", "pq_solver_batch_scaled_data",
     "pq_solver_batch_kktsys", "pq_solver_batch_update_dense", "pq_solver_batch_last_update_ms",
-    "pq_debug_alloc_count", "pq_debug_chol_plan", "pq_debug_syrk_plan", "pq_debug_device_sqrt", "pq_kkt_set_exchange_norm", "pq_kkt_sharded_calls", "pq_kkt_sharded_solve_calls", "pq_solver_sharded_solve_calls", "pq_solver_set_exchange_norm", "pq_solver_sharded_calls", "pq_microbench_mfma_f64", "pq_microbench_hbm_copy", "pq_microbench_potrf_block", "pq_debug_potrf_block", "pq_rccl_unique_id", "pq_kkt_set_comm_rccl", "pq_solver_set_comm_rccl", "pq_kkt_native_exchange_calls", "pq_kkt_min_abs_pivot", "pq_solver_native_exchange_calls",
+    "pq_debug_alloc_count", "pq_debug_chol_plan", "pq_debug_syrk_plan", "pq_debug_device_sqrt", "pq_kkt_set_exchange_norm", "pq_kkt_sharded_calls", "pq_kkt_sharded_solve_calls", "pq_solver_sharded_solve_calls", "pq_solver_set_exchange_norm", "pq_solver_sharded_calls", "pq_microbench_mfma_f64", "pq_microbench_hbm_copy", "pq_microbench_potrf_block", "pq_debug_potrf_block", "pq_debug_csc_ops", "pq_rccl_unique_id", "pq_kkt_set_comm_rccl", "pq_solver_set_comm_rccl", "pq_kkt_native_exchange_calls", "pq_kkt_min_abs_pivot", "pq_solver_native_exchange_calls",
     "pq_solver_setup_sparse_mem", "pq_solver_update_sparse_mem", "pq_debug_sparse_ingest_maps",
     "pq_solver_setup_dense_mem", "pq_solver_update_dense_mem", "pq_solver_get_result_mem", "pq_solver_last_ingest", "pq_batch_update_mem", "pq_batch_update_data_mem",
     "pq_batch_get_result_mem", "pq_microbench_transpose",
@@ -317,6 +333,7 @@ def load():
     L.pq_microbench_hbm_copy.argtypes = [C.c_int, C.c_size_t, C.c_int, _dp]
     L.pq_microbench_potrf_block.argtypes = [C.c_int, C.c_int, C.c_int, _dp, C.c_void_p]
     L.pq_debug_potrf_block.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pq_debug_csc_ops.argtypes = [C.c_int, C.POINTER(SparseData), C.c_int, C.c_int, C.POINTER(CscOpIO)]
     _lib = L
     return L
 

@@ -875,6 +875,13 @@ int pq_debug_potrf_block(int device, int ldlt, int nb, int reps, const double* A
     if (rc < 0) return rc;
     return guarded([&] { PQ_HIP(hipSetDevice(device)); *differing_reps = dense::debug_potrf_block(ldlt != 0, nb, reps, A, L, rdiag, dvec, pack, info, nullptr); return (int)PQ_OK; });
 }
+int pq_debug_csc_ops(int device, const pq_sparse_data* data, int op, int ref_order, pq_csc_op_io* io)
+{
+    if (!data || !io || op < PQ_CSC_EVAL_P_X || op > PQ_CSC_P_DIAG) return fail(PQ_ERR_INVALID, "bad argument");
+    int rc = check_device(device);
+    if (rc < 0) return rc;
+    return guarded([&] { pq::debug_csc_ops(data, op, ref_order != 0, io, device); return (int)PQ_OK; });
+}
 int pq_microbench_hbm_copy(int device, size_t bytes, int iters, double* gbps_out)
 {
     int rc = check_device(device);

@@ -112,6 +112,7 @@ std::unique_ptr<KKTSolverBase> make_dense_exact_kkt(const pq_dense_data* data, i
 inline bool dense_kkt_kind(int k) { return k == PQ_DENSE_CHOLESKY || k == PQ_DENSE_LDLT_NO_PIVOT || k == PQ_DENSE_CHOLESKY_EXACT; }
 constexpr int DENSE_EXACT_MAX_N = 1024;
 void debug_device_sqrt(const double* in_host, double* out_host, long long count, int device);  // dense_exact.hip (pq_debug_device_sqrt)
+void debug_csc_ops(const pq_sparse_data* data, int op, bool ref_order, pq_csc_op_io* io, int device);  // sparse_ops.hip (pq_debug_csc_ops)
 std::unique_ptr<KKTSolverBase> make_sparse_kkt(const pq_sparse_data* data, int kkt_solver, int device);
 std::unique_ptr<KKTSolverBase> make_multistage_kkt(const pq_sparse_data* data, int device);
 // sparse_kkt.hip: the supernodal multifrontal engine, any KKTMode.  adopt: a stream the engine runs on and owns from the moment this returns (if it throws, the caller still owns it)

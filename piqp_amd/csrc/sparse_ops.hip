@@ -2,6 +2,9 @@
 #include "sparse_ops.hpp"
 
 #include <stdexcept>
+#include <string>
+
+#include "kkt_solver_base.hpp"
 
 namespace pq {
 
@@ -36,7 +39,7 @@ __global__ void k_gather_or_zero(int cnt, const int* __restrict__ src_idx, const
 // touches 64 cache lines (measured on the n = 500k chain: k_recover_duals 190 us and k_fold_rhs 110 us per call for 76 MB of matrix = 0.4 TB/s, a third of
 // a KKT step).  Here the wave owns 64 consecutive columns, i.e. ONE contiguous range of entries: it streams that range through LDS in chunks -- lane e
 // loads entries e, e + 64, ... (coalesced) together with the gathered operand -- and every lane then sums the part of ITS column that lies in the chunk,
-// left to right, with the same multiply-add expression as before: bitwise the results of the thread-per-column loops (tests/test_sparse_gpu.py), at
+// left to right, with the same multiply-add expression as before: bitwise the results of the thread-per-column loops (tests/test_csc_ops_gpu.py), at
 // streaming bandwidth.  OP(q, i) = the operand of entry q in row i (x[i], or zinv[i] * rhs_z[i] for the folds).
 constexpr int DOT_CHUNK = 512;               // entries per wave and chunk: 2 x 4 KB of LDS per wave
 constexpr int DOT_LDS_DOUBLES = 2 * DOT_CHUNK * 4;  // per 256-thread workgroup
@@ -73,13 +76,13 @@ __device__ __forceinline__ double wave_col_dot(int j, int ncols, const int* __re
     return s;
 }
 
-// y[j] = (ACC ? y[j] : 0) + alpha * sum_q val[q] * x[row[q]] over column j  (CSC column dot)
+// y[j] = alpha * sum_q val[q] * x[row[q]] over column j  (CSC column dot)
 constexpr int SPMV_LONG_COL = 2048;  // columns with more entries than this are summed by a whole workgroup (k_spmv_long_cols)
 // ALPHA_FIRST: every term is val * (alpha * x[row]) and the sum is stored as it is -- the form of the reference's scatter products (sparse/kkt.hpp:188,199:
 // z.noalias() += alpha * M * x walks the columns of M and adds val * (alpha x_j) to the target row, i.e. row by row a left-to-right sum of such terms);
 // otherwise alpha * (sum of val * x[row]), the form of its transposed (column-dot) products.  max_len: columns with more entries are left to k_spmv_long_cols
 // (0: none are -- the reference-order mode sums every column left to right).
-template <bool ACC, bool ALPHA_FIRST>
+template <bool ALPHA_FIRST>
 __global__ __launch_bounds__(256) void k_spmv_cols(int ncols, const int* __restrict__ colptr, const int* __restrict__ rowind, const double* __restrict__ val, const double* __restrict__ x,
                                                    double alpha, double* __restrict__ y, int max_len)
 {
@@ -90,8 +93,7 @@ __global__ __launch_bounds__(256) void k_spmv_cols(int ncols, const int* __restr
     else s = wave_col_dot(j, ncols, colptr, rowind, val, [&](int i) { return x[i]; }, sm, max_len);
     if (j >= ncols) return;
     if (max_len > 0 && colptr[j + 1] - colptr[j] > max_len) return;
-    const double t = ALPHA_FIRST ? s : alpha * s;
-    y[j] = ACC ? y[j] + t : t;
+    y[j] = ALPHA_FIRST ? s : alpha * s;
 }
 // eval_P_x in the reference's order (sparse/kkt.hpp:179-185: z = alpha * P_utri.selfadjointView<Upper>() * x as the CPU oracle restates it, oracle/orc_sparse.c
 // sparse_eval_P_x): row r first collects val * (alpha x_j) over the stored entries (r, j), j >= r ascending -- the scatter pass over the upper triangle --
@@ -113,7 +115,6 @@ __global__ __launch_bounds__(256) void k_sym_spmv_ref(int n, const int* __restri
 // A column with very many entries (a dense row of A seen from its transpose copy: MM BOYD1 has 18 of 93 261 entries each) costs a thread-per-
 // column kernel a serial loop -- 1.15 ms per mat-vec there.  One workgroup per such column: thread t sums the entries t, t + 256, ... in
 // order, the 256 partial sums are added pairwise in a fixed tree.  Reproducible; not the left-to-right sum of the short columns.
-template <bool ACC>
 __global__ __launch_bounds__(256) void k_spmv_long_cols(const int* __restrict__ cols, const int* __restrict__ colptr, const int* __restrict__ rowind,
                                                         const double* __restrict__ val, const double* __restrict__ x, double alpha, double* __restrict__ y)
 {
@@ -128,7 +129,7 @@ __global__ __launch_bounds__(256) void k_spmv_long_cols(const int* __restrict__ 
         if (t < w) part[t] += part[t + w];
         __syncthreads();
     }
-    if (t == 0) y[j] = ACC ? y[j] + alpha * part[0] : alpha * part[0];
+    if (t == 0) y[j] = alpha * part[0];
 }
 
 // out[j] = rhs_x[j] + sum_{G rows i of column j} G(i,j) zinv[i] rhs_z[i] + delta_inv * sum_{A rows i} A(i,j) rhs_y[i]
@@ -397,34 +398,33 @@ void CscOperators::clone_from(const CscOperators& o, hipStream_t st)
 }
 
 // scatter: the product the reference forms by walking columns and adding into the target (M * x for a column-major M); ref: reference-order mode
-template <bool ACC>
 static void spmv(int ncols, const DBuf<int>& cp, const DBuf<int>& ri, const DBuf<double>& v, const DBuf<int>& long_cols, int nlong, const double* x, double alpha, double* y,
                  hipStream_t st, bool ref = false, bool scatter = false)
 {
     if (ncols <= 0) return;
     if (ref) {
-        if (scatter) hipLaunchKernelGGL((k_spmv_cols<ACC, true>), g1(ncols), dim3(256), 0, st, ncols, cp.p, ri.p, v.p, x, alpha, y, 0);
-        else hipLaunchKernelGGL((k_spmv_cols<ACC, false>), g1(ncols), dim3(256), 0, st, ncols, cp.p, ri.p, v.p, x, alpha, y, 0);
+        if (scatter) hipLaunchKernelGGL(k_spmv_cols<true>, g1(ncols), dim3(256), 0, st, ncols, cp.p, ri.p, v.p, x, alpha, y, 0);
+        else hipLaunchKernelGGL(k_spmv_cols<false>, g1(ncols), dim3(256), 0, st, ncols, cp.p, ri.p, v.p, x, alpha, y, 0);
         return;
     }
-    hipLaunchKernelGGL((k_spmv_cols<ACC, false>), g1(ncols), dim3(256), 0, st, ncols, cp.p, ri.p, v.p, x, alpha, y, SPMV_LONG_COL);
-    if (nlong > 0) hipLaunchKernelGGL(k_spmv_long_cols<ACC>, dim3(nlong), dim3(256), 0, st, long_cols.p, cp.p, ri.p, v.p, x, alpha, y);
+    hipLaunchKernelGGL(k_spmv_cols<false>, g1(ncols), dim3(256), 0, st, ncols, cp.p, ri.p, v.p, x, alpha, y, SPMV_LONG_COL);
+    if (nlong > 0) hipLaunchKernelGGL(k_spmv_long_cols, dim3(nlong), dim3(256), 0, st, long_cols.p, cp.p, ri.p, v.p, x, alpha, y);
 }
 
 void CscOperators::eval_P_x(double alpha, const double* x, double* z, hipStream_t st) const
 {
     if (ref_order_) { if (n_ > 0) hipLaunchKernelGGL(k_sym_spmv_ref, g1(n_), dim3(256), 0, st, n_, Pf_p_.p, Pf_i_.p, Pf_x_.p, x, alpha, z); return; }
-    spmv<false>(n_, Pf_p_, Pf_i_, Pf_x_, long_Pf_, nlong_[0], x, alpha, z, st);
+    spmv(n_, Pf_p_, Pf_i_, Pf_x_, long_Pf_, nlong_[0], x, alpha, z, st);
 }
 void CscOperators::eval_A_xn_and_AT_xt(double an, double at, const double* xn, const double* xt, double* zn, double* zt, hipStream_t st) const
 {
-    spmv<false>(p_, AT_p_, AT_i_, AT_x_, long_AT_, nlong_[1], xn, an, zn, st, ref_order_, false);  // A x = (AT)^T x
-    spmv<false>(n_, A_p_, A_i_, A_x_, long_A_, nlong_[2], xt, at, zt, st, ref_order_, true);       // AT y = (A)^T y
+    spmv(p_, AT_p_, AT_i_, AT_x_, long_AT_, nlong_[1], xn, an, zn, st, ref_order_, false);  // A x = (AT)^T x
+    spmv(n_, A_p_, A_i_, A_x_, long_A_, nlong_[2], xt, at, zt, st, ref_order_, true);       // AT y = (A)^T y
 }
 void CscOperators::eval_G_xn_and_GT_xt(double an, double at, const double* xn, const double* xt, double* zn, double* zt, hipStream_t st) const
 {
-    spmv<false>(m_, GT_p_, GT_i_, GT_x_, long_GT_, nlong_[3], xn, an, zn, st, ref_order_, false);
-    spmv<false>(n_, G_p_, G_i_, G_x_, long_G_, nlong_[4], xt, at, zt, st, ref_order_, true);
+    spmv(m_, GT_p_, GT_i_, GT_x_, long_GT_, nlong_[3], xn, an, zn, st, ref_order_, false);
+    spmv(n_, G_p_, G_i_, G_x_, long_G_, nlong_[4], xt, at, zt, st, ref_order_, true);
 }
 bool CscOperators::residual_rows(const int* rows_x, int nx, const int* rows_y, int ny, const int* rows_z, int nz, const double* lhs_x, const double* lhs_y, const double* lhs_z,
                                  const double* rhs_x, const double* rhs_y, const double* rhs_z, const double* x_reg, double delta, const double* z_reg, double* err_x, double* err_y,
@@ -471,13 +471,88 @@ void CscOperators::recover_duals_rows(const int* rows_y, int ny, const int* rows
         hipLaunchKernelGGL(k_recover_duals_rows, g1(ny + nz), dim3(256), 0, st, rows_y, ny, rows_z, nz, AT_p_.p, AT_i_.p, AT_x_.p, GT_p_.p, GT_i_.p, GT_x_.p, x, rhs_y, rhs_z, zinv,
                            delta_inv, lhs_y, lhs_z);
 }
-void CscOperators::add_AT_y(double alpha, const double* y, double* z, hipStream_t st) const
+// test hook (pq_debug_csc_ops): one CscOperators operation on the caller's host data -- init, optionally new values through upload_values, the operation on a stream
+// of its own, the three outputs back.  Everything the kernels index with is checked first: a pattern or a row list out of range is an error, not a launch.
+void debug_csc_ops(const pq_sparse_data* d, int op, bool ref_order, pq_csc_op_io* io, int device)
 {
-    if (p_ > 0) spmv<true>(n_, A_p_, A_i_, A_x_, long_A_, nlong_[2], y, alpha, z, st);
-}
-void CscOperators::add_GT_y(double alpha, const double* y, double* z, hipStream_t st) const
-{
-    if (m_ > 0) spmv<true>(n_, G_p_, G_i_, G_x_, long_G_, nlong_[4], y, alpha, z, st);
+    const int n = d->n, p = d->p, m = d->m;
+    if (n < 0 || p < 0 || m < 0) throw std::runtime_error("debug_csc_ops: negative dimension");
+    if (d->mem != PQ_MEM_HOST) throw std::runtime_error("debug_csc_ops: host arrays only");
+    auto check_csc = [&](const char* nm, int cols, const int* cp, const int* ri, const double* v) {
+        if (!cp || cp[0] != 0) throw std::runtime_error(std::string("debug_csc_ops: bad colptr of ") + nm);  // (init reads colptr[0] of an absent matrix too)
+        for (int j = 0; j < cols; ++j) if (cp[j + 1] < cp[j]) throw std::runtime_error(std::string("debug_csc_ops: colptr of ") + nm + " decreases");
+        if (cp[cols] > 0 && (!ri || !v)) throw std::runtime_error(std::string("debug_csc_ops: null arrays of ") + nm);
+        for (int q = 0; q < cp[cols]; ++q) if (ri[q] < 0 || ri[q] >= n) throw std::runtime_error(std::string("debug_csc_ops: row index of ") + nm + " out of range");
+        return cp[cols];
+    };
+    const int nzP = check_csc("P_utri", n, d->P_colptr, d->P_rowind, d->P_val);
+    const int nzA = check_csc("AT", p, d->AT_colptr, d->AT_rowind, d->AT_val);
+    const int nzG = check_csc("GT", m, d->GT_colptr, d->GT_rowind, d->GT_val);
+    if (n == 0) throw std::runtime_error("debug_csc_ops: n = 0");
+    for (int j = 0; j < n; ++j) for (int q = d->P_colptr[j]; q < d->P_colptr[j + 1]; ++q) if (d->P_rowind[q] > j) throw std::runtime_error("debug_csc_ops: P_utri is not upper triangular");
+    auto check_rows = [&](const char* nm, const int* rows, int cnt, int dim) {
+        if (cnt < 0 || (cnt > 0 && !rows)) throw std::runtime_error(std::string("debug_csc_ops: bad row list ") + nm);
+        for (int t = 0; t < cnt; ++t) if (rows[t] < 0 || rows[t] >= dim) throw std::runtime_error(std::string("debug_csc_ops: row list ") + nm + " out of range");
+    };
+    const bool rows_op = op == PQ_CSC_FOLD_RHS_ROWS || op == PQ_CSC_RECOVER_DUALS_ROWS || op == PQ_CSC_RESIDUAL_ROWS;
+    const int nx = rows_op && op != PQ_CSC_RECOVER_DUALS_ROWS ? io->nx : 0, ny = rows_op && op != PQ_CSC_FOLD_RHS_ROWS ? io->ny : 0,
+              nz = rows_op && op != PQ_CSC_FOLD_RHS_ROWS ? io->nz : 0;
+    check_rows("rows_x", io->rows_x, nx, n); check_rows("rows_y", io->rows_y, ny, p); check_rows("rows_z", io->rows_z, nz, m);
+    if (!io->out_x || (p > 0 && !io->out_y) || (m > 0 && !io->out_z)) throw std::runtime_error("debug_csc_ops: null output");
+    const bool second = io->P_val2 || io->AT_val2 || io->GT_val2;
+    if (second && ((nzP > 0 && !io->P_val2) || (nzA > 0 && !io->AT_val2) || (nzG > 0 && !io->GT_val2))) throw std::runtime_error("debug_csc_ops: second values incomplete");
+
+    PQ_HIP(hipSetDevice(device));
+    // (buffers first, the stream last: it is drained and destroyed before anything it may still use is released)
+    CscOperators ops;
+    DBuf<double> in_x, in_y, in_z, rhs_x, rhs_y, rhs_z, zinv, x_reg, z_reg, out_x, out_y, out_z;
+    DBuf<int> rows_x, rows_y, rows_z;
+    DBuf<unsigned long long> bits(1);
+    Stream st(device);
+    ops.init(d, st);
+    if (second) {
+        pq_sparse_data d2 = *d;
+        d2.P_val = io->P_val2; d2.AT_val = io->AT_val2; d2.GT_val = io->GT_val2;
+        ops.upload_values(&d2, st);
+    }
+    ops.set_reference_order(ref_order);
+    auto put = [&](DBuf<double>& b, const double* h, int len) {
+        b.alloc(len > 0 ? len : 1);
+        if (h && len > 0) PQ_HIP(hipMemcpyAsync(b.p, h, sizeof(double) * len, hipMemcpyHostToDevice, st));
+        else b.zero(st);
+    };
+    auto put_rows = [&](DBuf<int>& b, const int* h, int len) {
+        b.alloc(len > 0 ? len : 1);
+        if (len > 0) PQ_HIP(hipMemcpyAsync(b.p, h, sizeof(int) * len, hipMemcpyHostToDevice, st));
+    };
+    put(in_x, io->in_x, n); put(in_y, io->in_y, p); put(in_z, io->in_z, m);
+    put(rhs_x, io->rhs_x, n); put(rhs_y, io->rhs_y, p); put(rhs_z, io->rhs_z, m);
+    put(zinv, io->zinv, m); put(x_reg, io->x_reg, n); put(z_reg, io->z_reg, m);
+    put(out_x, io->out_x, n); put(out_y, io->out_y, p); put(out_z, io->out_z, m);
+    put_rows(rows_x, io->rows_x, nx); put_rows(rows_y, io->rows_y, ny); put_rows(rows_z, io->rows_z, nz);
+    bits.zero(st);
+    io->result = 1;
+    switch (op) {
+    case PQ_CSC_EVAL_P_X: ops.eval_P_x(io->alpha_n, in_x.p, out_x.p, st); break;
+    case PQ_CSC_EVAL_A: ops.eval_A_xn_and_AT_xt(io->alpha_n, io->alpha_t, in_x.p, in_y.p, out_y.p, out_x.p, st); break;
+    case PQ_CSC_EVAL_G: ops.eval_G_xn_and_GT_xt(io->alpha_n, io->alpha_t, in_x.p, in_z.p, out_z.p, out_x.p, st); break;
+    case PQ_CSC_FOLD_RHS: ops.fold_rhs(rhs_x.p, rhs_y.p, rhs_z.p, zinv.p, io->delta_inv, out_x.p, st, io->with_A != 0, io->with_G != 0); break;
+    case PQ_CSC_RECOVER_DUALS: ops.recover_duals(in_x.p, rhs_y.p, rhs_z.p, zinv.p, io->delta_inv, out_y.p, out_z.p, st, io->with_A != 0, io->with_G != 0); break;
+    case PQ_CSC_FOLD_RHS_ROWS: ops.fold_rhs_rows(rows_x.p, nx, rhs_x.p, rhs_y.p, rhs_z.p, zinv.p, io->delta_inv, out_x.p, st, io->with_A != 0, io->with_G != 0); break;
+    case PQ_CSC_RECOVER_DUALS_ROWS: ops.recover_duals_rows(rows_y.p, ny, rows_z.p, nz, in_x.p, rhs_y.p, rhs_z.p, zinv.p, io->delta_inv, out_y.p, out_z.p, st); break;
+    case PQ_CSC_RESIDUAL_ROWS:
+        io->result = ops.residual_rows(rows_x.p, nx, rows_y.p, ny, rows_z.p, nz, in_x.p, in_y.p, in_z.p, rhs_x.p, rhs_y.p, rhs_z.p, x_reg.p, io->delta, z_reg.p, out_x.p, out_y.p,
+                                       out_z.p, bits.p, st) ? 1 : 0;
+        break;
+    case PQ_CSC_P_DIAG: PQ_HIP(hipMemcpyAsync(out_x.p, ops.P_diag(), sizeof(double) * n, hipMemcpyDeviceToDevice, st)); break;
+    default: throw std::runtime_error("debug_csc_ops: unknown operation");
+    }
+    PQ_HIP(hipGetLastError());
+    PQ_HIP(hipMemcpyAsync(io->out_x, out_x.p, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    if (p > 0) PQ_HIP(hipMemcpyAsync(io->out_y, out_y.p, sizeof(double) * p, hipMemcpyDeviceToHost, st));
+    if (m > 0) PQ_HIP(hipMemcpyAsync(io->out_z, out_z.p, sizeof(double) * m, hipMemcpyDeviceToHost, st));
+    PQ_HIP(hipMemcpyAsync(&io->absmax_bits, bits.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    stream_wait(st);
 }
 
 }  // namespace pq

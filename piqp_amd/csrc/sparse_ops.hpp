@@ -35,9 +35,6 @@ public:
     void eval_P_x(double alpha, const double* x, double* z, hipStream_t st) const;
     void eval_A_xn_and_AT_xt(double an, double at, const double* xn, const double* xt, double* zn, double* zt, hipStream_t st) const;
     void eval_G_xn_and_GT_xt(double an, double at, const double* xn, const double* xt, double* zn, double* zt, hipStream_t st) const;
-    // z += alpha * AT * y  /  z += alpha * GT * y  (n-vectors; used by the condensed right-hand sides)
-    void add_AT_y(double alpha, const double* y, double* z, hipStream_t st) const;
-    void add_GT_y(double alpha, const double* y, double* z, hipStream_t st) const;
 
     // out = rhs_x + GT * (zinv .* rhs_z) + delta_inv * AT * rhs_y   (condensed right-hand side, multistage_kkt.hpp:234-252)
     void fold_rhs(const double* rhs_x, const double* rhs_y, const double* rhs_z, const double* zinv, double delta_inv, double* out, hipStream_t st, bool with_A = true,
