@@ -790,6 +790,41 @@ typedef struct {
     int result;
 } pq_csc_op_io;
 int pq_debug_csc_ops(int device, const pq_sparse_data *data, int op, int ref_order, pq_csc_op_io *io);
+/* testing aid: the device Ruiz equilibration ALONE (csrc/ruiz_kernels.hip) on the caller's host arrays -- no solver, no KKT backend, no symbolic analysis.  Every array
+ * below is HOST memory, read before and written after the one run; production code runs unchanged in between.
+ *   path PQ_RUIZ_SOLVER_DENSE / PQ_RUIZ_SOLVER_SPARSE: what Solver::setup / update do -- a HostData and a Ruiz from the arrays, a DeviceRuiz (dense: upload_dense; sparse:
+ *     host-fed), then scale(reuse = mode == PQ_RUIZ_REUSE, scale_cost, max_iter) or unscale().  Dense: P (the n x n column-major P_utri; only i <= j is touched), AT
+ *     (n x p), GT (n x m).  Sparse: the three CSC triples, P / AT / GT their values.  batch, threads, stride, the tail and the guards are not used.
+ *   path PQ_RUIZ_KERNEL: what the batched solver does -- launch_ruiz_sparse without a grid workspace on `batch` instances of one pattern, `threads` per workgroup
+ *     (a multiple of 64, <= 1024), on an arena the hook lays out: per instance `stride` doubles holding, in this order and each between two runs of PQ_RUIZ_GUARD
+ *     sentinel doubles, P | AT | GT values, c, x_b_scaling, delta, delta_inv, delta_b, delta_b_inv, scratch (n) and the tail b (p), h_l, h_u (m), x_l (n_x_l), x_u
+ *     (n_x_u); what is left of the stride is sentinel too, and so are PQ_RUIZ_GUARD doubles before the first and after the last instance and around c_scale[batch].
+ *     Arrays are [batch][len], instance after instance.  A NULL tail pointer reaches the kernel as NULL.  stride must hold the layout.
+ * mode: PQ_RUIZ_COMPUTE reads the matrices, c and x_b_scaling; PQ_RUIZ_REUSE / PQ_RUIZ_UNSCALE also delta, delta_inv, delta_b, delta_b_inv and c_scale (the cost scaling
+ * c; its inverse is formed as the solver forms it).  Every one of these comes back as the device left it.  guards (PQ_RUIZ_KERNEL): every sentinel double of the
+ * arena in address order, then those around c_scale; guards_cap is the caller's capacity, guards_len the number written.  launch: what was launched last -- the
+ * kernel (PQ_RUIZ_LAUNCH_*), grid x, grid y (dense: the tile grid of P; 1 otherwise), threads per workgroup.
+ * Patterns, index lists, sizes and the stride are checked before anything is launched. */
+enum { PQ_RUIZ_SOLVER_DENSE = 0, PQ_RUIZ_SOLVER_SPARSE, PQ_RUIZ_KERNEL };
+enum { PQ_RUIZ_COMPUTE = 0, PQ_RUIZ_REUSE, PQ_RUIZ_UNSCALE };
+enum { PQ_RUIZ_LAUNCH_DENSE = 0, PQ_RUIZ_LAUNCH_ONE_WG, PQ_RUIZ_LAUNCH_GRID };
+#define PQ_RUIZ_GUARD 8
+#define PQ_RUIZ_SENTINEL_BITS 0x7FF8DEADBEEF5AFEull /* a quiet NaN of fixed payload */
+typedef struct {
+    int path, mode, n, p, m, scale_cost, max_iter;
+    int batch, threads;
+    long long stride;
+    const int *P_colptr, *P_rowind, *AT_colptr, *AT_rowind, *GT_colptr, *GT_rowind;
+    double *P, *AT, *GT, *c, *x_b_scaling;
+    double *delta, *delta_inv, *delta_b, *delta_b_inv, *c_scale;
+    double *b, *h_l, *h_u, *x_l, *x_u;
+    const int *x_l_idx, *x_u_idx;
+    int n_x_l, n_x_u;
+    double *guards;
+    long long guards_cap, guards_len;
+    int launch[4];
+} pq_ruiz_io;
+int pq_debug_ruiz(int device, pq_ruiz_io *io);
 
 #ifdef __cplusplus
 }

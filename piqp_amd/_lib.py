@@ -51,6 +51,21 @@ class CscOpIO(C.Structure):
 CSC_OPS = ("eval_P_x", "eval_A", "eval_G", "fold_rhs", "recover_duals", "fold_rhs_rows", "recover_duals_rows", "residual_rows", "P_diag")  # PQ_CSC_*
 
 
+class RuizIO(C.Structure):
+    """pq_ruiz_io: arguments and results of pq_debug_ruiz"""
+    _fields_ = [(k, C.c_int) for k in ("path", "mode", "n", "p", "m", "scale_cost", "max_iter", "batch", "threads")] + [("stride", C.c_longlong)] + [
+        (k, vp) for k in ("P_colptr", "P_rowind", "AT_colptr", "AT_rowind", "GT_colptr", "GT_rowind", "P", "AT", "GT", "c", "x_b_scaling",
+                          "delta", "delta_inv", "delta_b", "delta_b_inv", "c_scale", "b", "h_l", "h_u", "x_l", "x_u", "x_l_idx", "x_u_idx")] + [
+        ("n_x_l", C.c_int), ("n_x_u", C.c_int), ("guards", vp), ("guards_cap", C.c_longlong), ("guards_len", C.c_longlong), ("launch", C.c_int * 4)]
+
+
+RUIZ_PATHS = ("solver_dense", "solver_sparse", "kernel")  # PQ_RUIZ_SOLVER_DENSE, PQ_RUIZ_SOLVER_SPARSE, PQ_RUIZ_KERNEL
+RUIZ_MODES = ("compute", "reuse", "unscale")              # PQ_RUIZ_COMPUTE, PQ_RUIZ_REUSE, PQ_RUIZ_UNSCALE
+RUIZ_LAUNCHES = ("dense", "one_wg", "grid")               # PQ_RUIZ_LAUNCH_*
+RUIZ_GUARD = 8
+RUIZ_SENTINEL_BITS = 0x7FF8DEADBEEF5AFE
+
+
 class Vars(C.Structure):
     _fields_ = [(k, vp) for k in VAR_NAMES]
 
@@ -112,7 +127,7 @@ SYMBOLS = [
     "pq_solver_batch_create", "pq_solver_batch_destroy", "pq_solver_batch_settings", "pq_solver_batch_setup_dense", "pq_solver_batch_solve", "pq_solver_batch_info",
     "pq_solver_batch_get_result_mem", "pq_solver_batch_set_trace", "pq_solver_batch_get_trace", "pq_solver_batch_dims", "pq_solver_batch_last_ms", "pq_solver_batch_scaled_data",
     "pq_solver_batch_kktsys", "pq_solver_batch_update_dense", "pq_solver_batch_last_update_ms",
-    "pq_debug_alloc_count", "pq_debug_chol_plan", "pq_debug_syrk_plan", "pq_debug_device_sqrt", "pq_kkt_set_exchange_norm", "pq_kkt_sharded_calls", "pq_kkt_sharded_solve_calls", "pq_solver_sharded_solve_calls", "pq_solver_set_exchange_norm", "pq_solver_sharded_calls", "pq_microbench_mfma_f64", "pq_microbench_hbm_copy", "pq_microbench_potrf_block", "pq_debug_potrf_block", "pq_debug_csc_ops", "pq_rccl_unique_id", "pq_kkt_set_comm_rccl", "pq_solver_set_comm_rccl", "pq_kkt_native_exchange_calls", "pq_kkt_min_abs_pivot", "pq_solver_native_exchange_calls",
+    "pq_debug_alloc_count", "pq_debug_chol_plan", "pq_debug_syrk_plan", "pq_debug_device_sqrt", "pq_kkt_set_exchange_norm", "pq_kkt_sharded_calls", "pq_kkt_sharded_solve_calls", "pq_solver_sharded_solve_calls", "pq_solver_set_exchange_norm", "pq_solver_sharded_calls", "pq_microbench_mfma_f64", "pq_microbench_hbm_copy", "pq_microbench_potrf_block", "pq_debug_potrf_block", "pq_debug_csc_ops", "pq_debug_ruiz","pq_rccl_unique_id", "pq_kkt_set_comm_rccl", "pq_solver_set_comm_rccl", "pq_kkt_native_exchange_calls", "pq_kkt_min_abs_pivot", "pq_solver_native_exchange_calls",
     "pq_solver_setup_sparse_mem", "pq_solver_update_sparse_mem", "pq_debug_sparse_ingest_maps",
     "pq_solver_setup_dense_mem", "pq_solver_update_dense_mem", "pq_solver_get_result_mem", "pq_solver_last_ingest", "pq_batch_update_mem", "pq_batch_update_data_mem",
     "pq_batch_get_result_mem", "pq_microbench_transpose",
@@ -334,6 +349,7 @@ def load():
     L.pq_microbench_potrf_block.argtypes = [C.c_int, C.c_int, C.c_int, _dp, C.c_void_p]
     L.pq_debug_potrf_block.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pq_debug_csc_ops.argtypes = [C.c_int, C.POINTER(SparseData), C.c_int, C.c_int, C.POINTER(CscOpIO)]
+    L.pq_debug_ruiz.argtypes = [C.c_int, C.POINTER(RuizIO)]
     _lib = L
     return L
 

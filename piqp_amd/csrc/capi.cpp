@@ -882,6 +882,13 @@ int pq_debug_csc_ops(int device, const pq_sparse_data* data, int op, int ref_ord
     if (rc < 0) return rc;
     return guarded([&] { pq::debug_csc_ops(data, op, ref_order != 0, io, device); return (int)PQ_OK; });
 }
+int pq_debug_ruiz(int device, pq_ruiz_io* io)
+{
+    if (!io) return fail(PQ_ERR_INVALID, "bad argument");
+    int rc = check_device(device);
+    if (rc < 0) return rc;
+    return guarded([&] { pq::debug_ruiz(io, device); return (int)PQ_OK; });
+}
 int pq_microbench_hbm_copy(int device, size_t bytes, int iters, double* gbps_out)
 {
     int rc = check_device(device);

@@ -35,6 +35,9 @@ struct RuizSparseArgs {
 };
 void launch_ruiz_sparse(const RuizSparseArgs& a, int batch, int threads, hipStream_t s);
 size_t ruiz_grid_ws_words();
+struct RuizLaunch { int kernel = -1, gx = 0, gy = 0, threads = 0; };  // PQ_RUIZ_LAUNCH_*, grid, workgroup size
+RuizLaunch ruiz_last_launch();                                        // of this thread's last launch_ruiz_sparse / DeviceRuiz run (test hook)
+void debug_ruiz(pq_ruiz_io* io, int device);                          // pq_debug_ruiz
 
 struct HostData;
 struct Ruiz;

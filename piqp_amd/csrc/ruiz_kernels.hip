@@ -2,9 +2,13 @@
 #include "ruiz_device.hpp"
 #include "ingest_kernels.hpp"
 
+#include <algorithm>
 #include <climits>
+#include <cstring>
 #include <memory>
 #include <stdexcept>
+#include <string>
+#include <vector>
 
 #include "solver.hpp"
 
@@ -337,7 +341,11 @@ __global__ void k_rzd_vectors(int n, double* c, double* xbs, const double* s, co
     if (i < n) { c[i] *= *cs * s[i]; xbs[i] *= sb[i] * s[i]; }
 }
 
+thread_local RuizLaunch g_last_launch;  // what the test hook reports; written on the host beside each launch, read by nothing else
+
 }  // namespace
+
+RuizLaunch ruiz_last_launch() { return g_last_launch; }
 
 void launch_ruiz_sparse(const RuizSparseArgs& a, int batch, int threads, hipStream_t s)
 {
@@ -356,11 +364,13 @@ void launch_ruiz_sparse(const RuizSparseArgs& a, int batch, int threads, hipStre
             PQ_HIP(hipMemsetAsync(a.grid_ws, 0, sizeof(unsigned long long) * RUIZ_WS_WORDS, s));
             hipLaunchKernelGGL(k_ruiz_sparse<true>, dim3(g), dim3(256), 0, s, a);
             PQ_HIP(hipGetLastError());
+            g_last_launch = RuizLaunch{PQ_RUIZ_LAUNCH_GRID, g, 1, 256};
             return;
         }
     }
     hipLaunchKernelGGL(k_ruiz_sparse<false>, dim3(batch), dim3(threads), 0, s, a);
     PQ_HIP(hipGetLastError());
+    g_last_launch = RuizLaunch{PQ_RUIZ_LAUNCH_ONE_WG, batch, 1, threads};
 }
 size_t ruiz_grid_ws_words() { return RUIZ_WS_WORDS; }
 
@@ -611,6 +621,7 @@ void DeviceRuiz::run(HostData& d, Ruiz& rz, int mode, bool scale_cost, int max_i
             hipLaunchKernelGGL(k_rzd_vectors, dim3(div_up(n, eb)), dim3(eb), 0, st, n, s.c, s.xbs, sv, sb, cs);
         }
         PQ_HIP(hipGetLastError());
+        g_last_launch = RuizLaunch{PQ_RUIZ_LAUNCH_DENSE, (int)gP.x, (int)gP.y, TR};
     }
     // ---- device -> host: c, x_b_scaling and (after a fresh equilibration) the scalings
     PQ_HIP(hipMemcpyAsync(h, s.vec.p, (odbi + n) * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -625,6 +636,174 @@ void DeviceRuiz::run(HostData& d, Ruiz& rz, int mode, bool scale_cost, int max_i
         if (!s.sparse) rz.c = hs.c;
         rz.c_inv = 1.0 / rz.c;
     }
+}
+
+// ------------------------------------------------------------------------------------------------ test hook (pq_debug_ruiz)
+namespace {
+void check_csc(const char* nm, int rows, int cols, const int* cp, const int* ri, const double* v, bool upper)
+{
+    const std::string w = std::string("debug_ruiz: ") + nm;
+    if (cols == 0) return;
+    if (!cp || cp[0] != 0) throw std::runtime_error(w + ": bad colptr");
+    for (int j = 0; j < cols; ++j) if (cp[j + 1] < cp[j]) throw std::runtime_error(w + ": colptr decreases");
+    if (cp[cols] > 0 && (!ri || !v)) throw std::runtime_error(w + ": null arrays");
+    for (int j = 0; j < cols; ++j)
+        for (int q = cp[j]; q < cp[j + 1]; ++q)
+            if (ri[q] < 0 || ri[q] >= rows || (upper && ri[q] > j)) throw std::runtime_error(w + (upper && ri[q] > j ? ": not upper triangular" : ": row index out of range"));
+}
+double ruiz_sentinel()
+{
+    const unsigned long long b = PQ_RUIZ_SENTINEL_BITS;
+    double d;
+    std::memcpy(&d, &b, sizeof d);
+    return d;
+}
+}  // namespace
+
+void debug_ruiz(pq_ruiz_io* io, int device)
+{
+    const int n = io->n, p = io->p, m = io->m, mode = io->mode;
+    if (n < 1 || p < 0 || m < 0 || (long long)n + p + m > (1 << 22)) throw std::runtime_error("debug_ruiz: bad dimensions");
+    if (mode < RUIZ_COMPUTE || mode > RUIZ_UNSCALE || io->max_iter < 0 || io->max_iter > 1000) throw std::runtime_error("debug_ruiz: bad mode or max_iter");
+    if (io->path < PQ_RUIZ_SOLVER_DENSE || io->path > PQ_RUIZ_KERNEL) throw std::runtime_error("debug_ruiz: unknown path");
+    const size_t N = (size_t)n + p + m;
+    const bool sparse = io->path != PQ_RUIZ_SOLVER_DENSE, kernel = io->path == PQ_RUIZ_KERNEL;
+    const int batch = kernel ? io->batch : 1;
+    if (batch < 1 || batch > 1024) throw std::runtime_error("debug_ruiz: bad batch");
+    if (!io->c || !io->x_b_scaling || !io->delta || !io->delta_inv || !io->delta_b || !io->delta_b_inv || !io->c_scale) throw std::runtime_error("debug_ruiz: null vector");
+    size_t nz[3] = {(size_t)n * n, (size_t)n * p, (size_t)n * m};
+    if (sparse) {
+        if (!io->P_colptr) throw std::runtime_error("debug_ruiz: P: bad colptr");
+        nz[0] = io->P_colptr[n]; nz[1] = p ? io->AT_colptr ? io->AT_colptr[p] : 0 : 0; nz[2] = m ? io->GT_colptr ? io->GT_colptr[m] : 0 : 0;
+        check_csc("P", n, n, io->P_colptr, io->P_rowind, io->P, true);
+        check_csc("AT", n, p, io->AT_colptr, io->AT_rowind, io->AT, false);
+        check_csc("GT", n, m, io->GT_colptr, io->GT_rowind, io->GT, false);
+    } else if (n > 8192 || !io->P || (p && !io->AT) || (m && !io->GT)) {
+        throw std::runtime_error("debug_ruiz: dense: null matrix or n > 8192");
+    }
+    io->guards_len = 0;
+    PQ_HIP(hipSetDevice(device));
+
+    if (!kernel) {
+        // ---- what Solver::setup / update do
+        HostData d;
+        d.sparse = sparse; d.n = n; d.p = p; d.m = m;
+        auto csc = [&](Csc& M, int cols, const int* cp, const int* ri, const double* v, size_t cnt) {
+            M.rows = n; M.cols = cols;
+            if (cols) M.colptr.assign(cp, cp + cols + 1); else M.colptr.assign(1, 0);
+            if (cnt) { M.rowind.assign(ri, ri + cnt); M.val.assign(v, v + cnt); }
+        };
+        if (sparse) {
+            csc(d.sP_utri, n, io->P_colptr, io->P_rowind, io->P, nz[0]);
+            csc(d.sAT, p, io->AT_colptr, io->AT_rowind, io->AT, nz[1]);
+            csc(d.sGT, m, io->GT_colptr, io->GT_rowind, io->GT, nz[2]);
+        } else {
+            d.P_utri.assign(io->P, io->P + nz[0]);
+            if (nz[1]) d.AT.assign(io->AT, io->AT + nz[1]);
+            if (nz[2]) d.GT.assign(io->GT, io->GT + nz[2]);
+        }
+        d.c.assign(io->c, io->c + n);
+        d.x_b_scaling.assign(io->x_b_scaling, io->x_b_scaling + n);
+        Ruiz rz;
+        rz.init(d);
+        if (mode != RUIZ_COMPUTE) {
+            rz.delta.assign(io->delta, io->delta + N); rz.delta_inv.assign(io->delta_inv, io->delta_inv + N);
+            rz.delta_b.assign(io->delta_b, io->delta_b + n); rz.delta_b_inv.assign(io->delta_b_inv, io->delta_b_inv + n);
+            rz.c = io->c_scale[0]; rz.c_inv = 1.0 / rz.c;
+        }
+        DeviceRuiz dr(device, d);
+        if (!sparse) dr.upload_dense(d, PQ_KKT_UPDATE_P | PQ_KKT_UPDATE_A | PQ_KKT_UPDATE_G);
+        g_last_launch = RuizLaunch{};
+        if (mode == RUIZ_UNSCALE) dr.unscale(d, rz);
+        else dr.scale(d, rz, mode == RUIZ_REUSE, io->scale_cost != 0, io->max_iter);
+        if (sparse) {
+            std::copy(d.sP_utri.val.begin(), d.sP_utri.val.end(), io->P);
+            std::copy(d.sAT.val.begin(), d.sAT.val.end(), io->AT);
+            std::copy(d.sGT.val.begin(), d.sGT.val.end(), io->GT);
+        } else {
+            const pq_dense_data desc = dr.dense_descriptor(d);
+            PQ_HIP(hipMemcpy(io->P, desc.P_utri, nz[0] * sizeof(double), hipMemcpyDeviceToHost));
+            if (nz[1]) PQ_HIP(hipMemcpy(io->AT, desc.AT, nz[1] * sizeof(double), hipMemcpyDeviceToHost));
+            if (nz[2]) PQ_HIP(hipMemcpy(io->GT, desc.GT, nz[2] * sizeof(double), hipMemcpyDeviceToHost));
+        }
+        std::copy(d.c.begin(), d.c.end(), io->c);
+        std::copy(d.x_b_scaling.begin(), d.x_b_scaling.end(), io->x_b_scaling);
+        std::copy(rz.delta.begin(), rz.delta.end(), io->delta); std::copy(rz.delta_inv.begin(), rz.delta_inv.end(), io->delta_inv);
+        std::copy(rz.delta_b.begin(), rz.delta_b.end(), io->delta_b); std::copy(rz.delta_b_inv.begin(), rz.delta_b_inv.end(), io->delta_b_inv);
+        io->c_scale[0] = rz.c;
+    } else {
+        // ---- what the batched solver does: launch_ruiz_sparse on a strided arena, no grid workspace
+        const int G = PQ_RUIZ_GUARD;
+        if (io->threads < 64 || io->threads > 1024 || io->threads % 64) throw std::runtime_error("debug_ruiz: threads must be a multiple of 64 up to 1024");
+        const int nxl = io->n_x_l, nxu = io->n_x_u;
+        if (nxl < 0 || nxl > n || nxu < 0 || nxu > n || (io->x_l && nxl && !io->x_l_idx) || (io->x_u && nxu && !io->x_u_idx)) throw std::runtime_error("debug_ruiz: bad box index lists");
+        for (int k = 0; io->x_l && k < nxl; ++k) if (io->x_l_idx[k] < 0 || io->x_l_idx[k] >= n) throw std::runtime_error("debug_ruiz: x_l_idx out of range");
+        for (int k = 0; io->x_u && k < nxu; ++k) if (io->x_u_idx[k] < 0 || io->x_u_idx[k] >= n) throw std::runtime_error("debug_ruiz: x_u_idx out of range");
+        enum { F_PX, F_ATX, F_GTX, F_C, F_XBS, F_DL, F_DLI, F_DB, F_DBI, F_TMP, F_B, F_HL, F_HU, F_XL, F_XU, F_COUNT };
+        const size_t len[F_COUNT] = {nz[0], nz[1], nz[2], (size_t)n, (size_t)n, N, N, (size_t)n, (size_t)n, (size_t)n, (size_t)p, (size_t)m, (size_t)m, (size_t)nxl, (size_t)nxu};
+        double* host[F_COUNT] = {io->P, io->AT, io->GT, io->c, io->x_b_scaling, io->delta, io->delta_inv, io->delta_b, io->delta_b_inv, nullptr, io->b, io->h_l, io->h_u, io->x_l, io->x_u};
+        size_t off[F_COUNT], need = G;
+        for (int f = 0; f < F_COUNT; ++f) { off[f] = need; need += len[f] + G; }
+        if (io->stride < (long long)need || io->stride > (1LL << 26)) throw std::runtime_error("debug_ruiz: stride " + std::to_string(io->stride) + " does not hold the layout of " + std::to_string(need) + " doubles");
+        const size_t stride = (size_t)io->stride, total = (size_t)batch * stride + G;
+        const double S = ruiz_sentinel();
+        std::vector<double> arena(total, S), cs((size_t)batch + 2 * G, S);
+        std::vector<char> is_field(total, 0);
+        const bool reads_scalings = mode != RUIZ_COMPUTE;
+        for (int b = 0; b < batch; ++b)
+            for (int f = 0; f < F_COUNT; ++f) {
+                const bool present = f == F_TMP || host[f] != nullptr;
+                if (!present || !len[f]) continue;
+                double* dst = arena.data() + b * stride + off[f];
+                std::fill(is_field.begin() + (b * stride + off[f]), is_field.begin() + (b * stride + off[f] + len[f]), 1);
+                const bool scaling = f >= F_DL && f <= F_DBI;
+                if (f != F_TMP && (!scaling || reads_scalings)) std::copy(host[f] + b * len[f], host[f] + (b + 1) * len[f], dst);
+            }
+        if (reads_scalings) std::copy(io->c_scale, io->c_scale + batch, cs.begin() + G);
+        Stream st(device);
+        DBuf<double> dArena(total), dCs(cs.size());
+        DBuf<int> ip[8];
+        auto upi = [&](DBuf<int>& dst, const int* h, size_t cnt) -> const int* {
+            dst.alloc(std::max<size_t>(cnt, 1));
+            if (cnt) PQ_HIP(hipMemcpyAsync(dst.p, h, cnt * sizeof(int), hipMemcpyHostToDevice, st));
+            return dst.p;
+        };
+        RuizSparseArgs a;
+        a.n = n; a.p = p; a.m = m;
+        a.Pp = upi(ip[0], io->P_colptr, (size_t)n + 1); a.Pi = upi(ip[1], io->P_rowind, nz[0]);
+        a.ATp = upi(ip[2], io->AT_colptr, p ? (size_t)p + 1 : 0); a.ATi = upi(ip[3], io->AT_rowind, nz[1]);
+        a.GTp = upi(ip[4], io->GT_colptr, m ? (size_t)m + 1 : 0); a.GTi = upi(ip[5], io->GT_rowind, nz[2]);
+        a.x_l_idx = upi(ip[6], io->x_l_idx, io->x_l ? (size_t)nxl : 0); a.x_u_idx = upi(ip[7], io->x_u_idx, io->x_u ? (size_t)nxu : 0);
+        a.n_x_l = nxl; a.n_x_u = nxu;
+        a.stride = io->stride;
+        auto at = [&](int f) { return dArena.p + off[f]; };
+        a.Px = at(F_PX); a.ATx = at(F_ATX); a.GTx = at(F_GTX); a.c = at(F_C); a.xbs = at(F_XBS);
+        a.delta = at(F_DL); a.delta_inv = at(F_DLI); a.delta_b = at(F_DB); a.delta_b_inv = at(F_DBI); a.tmp = at(F_TMP);
+        a.b = io->b ? at(F_B) : nullptr; a.h_l = io->h_l ? at(F_HL) : nullptr; a.h_u = io->h_u ? at(F_HU) : nullptr;
+        a.x_l = io->x_l ? at(F_XL) : nullptr; a.x_u = io->x_u ? at(F_XU) : nullptr;
+        a.c_scale = dCs.p + G;
+        a.mode = mode; a.scale_cost = io->scale_cost != 0; a.max_iter = io->max_iter;
+        PQ_HIP(hipMemcpyAsync(dArena.p, arena.data(), total * sizeof(double), hipMemcpyHostToDevice, st));
+        PQ_HIP(hipMemcpyAsync(dCs.p, cs.data(), cs.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        g_last_launch = RuizLaunch{};
+        launch_ruiz_sparse(a, batch, io->threads, st);
+        PQ_HIP(hipMemcpyAsync(arena.data(), dArena.p, total * sizeof(double), hipMemcpyDeviceToHost, st));
+        PQ_HIP(hipMemcpyAsync(cs.data(), dCs.p, cs.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        stream_wait(st);
+        for (int b = 0; b < batch; ++b)
+            for (int f = 0; f < F_COUNT; ++f)
+                if (f != F_TMP && host[f] && len[f]) std::copy(arena.data() + b * stride + off[f], arena.data() + b * stride + off[f] + len[f], host[f] + b * len[f]);
+        std::copy(cs.begin() + G, cs.begin() + G + batch, io->c_scale);
+        long long g = 0;
+        auto guard = [&](double v) { if (io->guards && g < io->guards_cap) io->guards[g] = v; ++g; };
+        for (size_t i = 0; i < total; ++i) if (!is_field[i]) guard(arena[i]);
+        for (int i = 0; i < G; ++i) guard(cs[i]);
+        for (int i = 0; i < G; ++i) guard(cs[(size_t)G + batch + i]);
+        if (!io->guards || g > io->guards_cap) throw std::runtime_error("debug_ruiz: guards_cap too small: " + std::to_string(g) + " guard doubles");
+        io->guards_len = g;
+    }
+    const RuizLaunch l = ruiz_last_launch();
+    io->launch[0] = l.kernel; io->launch[1] = l.gx; io->launch[2] = l.gy; io->launch[3] = l.threads;
 }
 
 }  // namespace pq

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Worker of tests/test_ruiz_gpu.py: whole solves (setup, solve, update of matrices + bounds, solve, matrix-free update that disables a
 row of G, solve) of dense and sparse fixtures with the equilibration wherever the parent's PIQP_AMD_DEBUG puts it (device kernels by
-default, the host routine under `host_ruiz`).  Solutions, iteration counts and the scaled-back data land in an .npz for a bitwise comparison.
+default, the host routine under `host_ruiz`).  Status, iteration count, the solution (x, y, z_*, s_l, s_u) and the residuals and objectives of every solve land in
+an .npz for a bitwise comparison.  The scaled data and the scalings themselves are NOT recorded -- no solver exposes them; tests/test_ruiz_kernels_gpu.py reads them
+through pq_debug_ruiz.
 
   python tests/workers/ruiz_variant.py out.npz
 """
