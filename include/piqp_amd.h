@@ -634,8 +634,20 @@ typedef struct pq_kktsys_batch pq_kktsys_batch;
 int pq_kktsys_batch_create_dense(pq_kktsys_batch **out, int device, int batch, int n, int p, int m, const double *P_utri, const double *AT, const double *GT,
                                  int n_h_l, int n_h_u, int n_x_l, int n_x_u, const int *h_l_idx, const int *h_u_idx, const int *x_l_idx, const int *x_u_idx,
                                  const double *x_b_scaling, const pq_settings *settings, int mem);
+/* The same with finite-bound lists of its OWN for every instance.  counts: int [batch][4] = n_h_l, n_h_u, n_x_l, n_x_u per instance; the four list arrays are
+ * int [batch][m], [batch][m], [batch][n], [batch][n], row i meaningful in its first counts[i][k] entries; all HOST memory in either mode.  Every check of the
+ * creator above is made per instance before the device is touched, and the error text names the instance; a NULL counts is refused.  Of the box vectors of a
+ * pq_vars the first counts[i][2] / counts[i][3] entries of row i are meaningful; a box pointer may be NULL only when no instance uses that vector.  On the device
+ * the tables get one row of 2 m + 4 n ints per instance; a handle of the creator above keeps its one shared row and reads nothing per instance. */
+int pq_kktsys_batch_create_dense_lists(pq_kktsys_batch **out, int device, int batch, int n, int p, int m, const double *P_utri, const double *AT, const double *GT,
+                                       const int *counts, const int *h_l_idx, const int *h_u_idx, const int *x_l_idx, const int *x_u_idx,
+                                       const double *x_b_scaling, const pq_settings *settings, int mem);
+/* Replaces the lists of a handle of pq_kktsys_batch_create_dense_lists (arguments and checks as there; a failed check leaves the handle as it was).  Allocates
+ * nothing.  The factors and the stored scalings belong to the old lists: solve, mul and state return PQ_ERR_INVALID until the next update_scalings_and_factor, as
+ * before the first.  PQ_ERR_INVALID on a handle whose lists are shared. */
+int pq_kktsys_batch_set_lists(pq_kktsys_batch *k, const int *counts, const int *h_l_idx, const int *h_u_idx, const int *x_l_idx, const int *x_u_idx);
 void pq_kktsys_batch_destroy(pq_kktsys_batch *k);
-int pq_kktsys_batch_clone(const pq_kktsys_batch *k, pq_kktsys_batch **out); /* kkt_system.hpp:70-95: the scalings state is copied, the backend cloned */
+int pq_kktsys_batch_clone(const pq_kktsys_batch *k, pq_kktsys_batch **out); /* kkt_system.hpp:70-95: the scalings state is copied, the backend cloned; so are the kind of the lists and the tables */
 int pq_kktsys_batch_dims(const pq_kktsys_batch *k, int *batch, int *n, int *p, int *m);
 pq_kkt_batch *pq_kktsys_batch_backend(pq_kktsys_batch *k); /* borrowed; NULL for a NULL handle */
 /* kkt_system.hpp:134-141: pq_kkt_batch_update_data_dense on the backend; a non-NULL x_b_scaling is re-read */
@@ -667,7 +679,7 @@ int pq_kktsys_batch_last_ms(const pq_kktsys_batch *k, double out3[3]);
  *     for (i < batch) { DenseSolver s; s.settings() = settings; s.setup(P_i, c_i, A_i, b_i, G_i, h_l_i, h_u_i, x_l_i, x_u_i); s.solve(); }
  * (csrc/dense_solver_batch.hip): per instance status, iterations, trace, results and every non-time info field are those of the CPU oracle (oracle/orc_solver.c) bit
  * for bit.  n <= PQ_KKT_BATCH_DENSE_MAX_N; p and m are not limited; settings->kkt_solver is PQ_DENSE_CHOLESKY or PQ_DENSE_LDLT_NO_PIVOT.  The instances share n, p, m,
- * one pq_settings and the set of finite bounds.  The solve runs in rounds clocked by the host: a small kernel advances every instance to its next KKTSystem call, then
+ * one pq_settings and, unless pq_solver_batch_set_bound_sets says otherwise, the set of finite bounds.  The solve runs in rounds clocked by the host: a small kernel advances every instance to its next KKTSystem call, then
  * the factor launch and the solve launch of pq_kktsys_batch_* run on the instances that asked for them; the host reads three counters per round.  The instances need
  * not run in lock step; an instance that has ended is not touched again.
  * There is no clone() yet.  pq_solver_batch_update_dense is DenseSolver::update (solver.hpp:218-308): per instance it un-scales everything stored, assigns what is
@@ -684,9 +696,17 @@ typedef struct pq_solver_batch pq_solver_batch;
 int pq_solver_batch_create(pq_solver_batch **out, int device);
 void pq_solver_batch_destroy(pq_solver_batch *s);
 pq_settings *pq_solver_batch_settings(pq_solver_batch *s); /* shared by all instances; kkt_solver and the preconditioner fields are read by setup */
+/* Who owns the set of finite bounds.  PQ_BOUND_SETS_SHARED (the default): one set for the batch, a checked promise -- setup refuses an instance that differs from
+ * instance 0 and update refuses a bound that turns infinite or finite, as described at those calls.  PQ_BOUND_SETS_PER_INSTANCE: every instance has the lists
+ * DenseSolver would hold for its own vectors (dense/data.hpp:98-207), at setup and after every update, so constraints can be switched off per instance with
+ * -/+ infinity and come back later.  The mode is read by setup; a problem that is set up keeps the mode its setup read.  PQ_ERR_INVALID for any other value and
+ * for a NULL handle. */
+enum { PQ_BOUND_SETS_SHARED = 0, PQ_BOUND_SETS_PER_INSTANCE = 1 };
+int pq_solver_batch_set_bound_sets(pq_solver_batch *s, int mode);
 /* DenseSolver::setup per instance.  P [batch] n x n, A [batch] p x n, G [batch] m x n: stacks of matrices in the layout `order` (PQ_COL_MAJOR / PQ_ROW_MAJOR) and
  * under the ordering contract of pq_solver_setup_dense_mem; vectors [batch][len]; NULL optionals as in the single solver.  mem: where EVERY array lives.  The
- * finite-bound pattern is taken from instance 0; another instance that differs is refused (PQ_ERR_INVALID, as pq_batch_update does).  Rows of G without a finite bound
+ * finite-bound pattern is taken from instance 0; another instance that differs is refused (PQ_ERR_INVALID, as pq_batch_update does) -- with
+ * PQ_BOUND_SETS_PER_INSTANCE every instance gets its own lists, dropped rows and packed box vectors instead, and nothing is refused.  Rows of G without a finite bound
  * are zeroed (disable_inf_constraints), the Ruiz equilibration runs per instance (one kernel), and the internal pq_kktsys_batch is created on the scaled data.  May be
  * called again on the same handle; it is the only call besides create and destroy that may allocate.  Returns 1. */
 int pq_solver_batch_setup_dense(pq_solver_batch *s, int batch, int n, int p, int m, const double *P, const double *c, const double *A, const double *b,
@@ -700,7 +720,15 @@ int pq_solver_batch_setup_dense(pq_solver_batch *s, int batch, int n, int p, int
  * a new G' of rows dropped earlier are zeroed only in a call that also gives h_l or h_u.  PQ_ERR_INVALID before the device is touched: a NULL handle, a call before a
  * setup, a bad mem or order, A or b with p = 0, G, h_l or h_u with m = 0.  The call allocates nothing.  The next solve starts every instance from INIT (no warm start);
  * statuses, results and traces of the previous solve stay readable until then.  info.update_time is the wall time of the call (the batch's), and a solve after an
- * update reports run_time = update_time + solve_time.  Returns 1. */
+ * update reports run_time = update_time + solve_time.  Returns 1.
+ * With PQ_BOUND_SETS_PER_INSTANCE the call never refuses on finiteness: the lists of every instance are worked out in the same way and REPLACE its own, in the tables
+ * here and in the internal KKT system (pq_kktsys_batch_set_lists), and a given box vector is packed to its new list (a variable whose bound is no longer in the list
+ * has no entry).  A row that comes back keeps the zero column of G' until a G is given, as in the reference.  Everything else above holds unchanged, A'A, rows
+ * dropped earlier, no warm start and no allocation included.  A SECOND RULE IS NOT THE REFERENCE'S, and it can show in this mode only: a stored infinite bound is
+ * infinite.  The reference stores it as -/+ 1e30, scales it with its row and un-scales it at the next update, and (1e30 d) (1 / d) may round to the neighbour of
+ * 1e30, which disable_inf_constraints sees as finite.  So when h_l or h_u comes ALONE and is infinite on a row whose other side is stored infinite, the reference
+ * either drops the row or, by the rounding of that product, leaves it in neither list -- a row without a bound, whose solves turn into NaN.  Here the row is
+ * dropped.  With both vectors given, or with finite numbers on such rows, the lists are the reference's. */
 int pq_solver_batch_update_dense(pq_solver_batch *s, const double *P, const double *c, const double *A, const double *b, const double *G, const double *h_l,
                                  const double *h_u, const double *x_l, const double *x_u, int mem, int order);
 /* of the last update: out2 = { wall ms, device ms (hipEvents around its kernels and copies) } */
@@ -721,7 +749,7 @@ int pq_solver_batch_dims(const pq_solver_batch *s, int *batch, int *n, int *p, i
 /* of the last solve: out6 = { wall ms, device ms summed over its launches (hipEvents), rounds, launches, device ms of the factor launches, of the solve launches } */
 int pq_solver_batch_last_ms(const pq_solver_batch *s, double out6[6]);
 /* test hooks.  scaled_data: one item of one instance after setup, to HOST memory: the scaled P_utri (n x n), AT (n x p), GT (n x m), c, b, h_l, h_u, x_l, x_u (the box
- * bounds compressed to the lists), x_b_scaling, and delta (n + p + m), delta_b (n), c (1) of the preconditioner.  kktsys: the borrowed KKT system; after a solve it is
+ * bounds compressed to the lists of that instance: the entries past its count are unspecified), x_b_scaling, and delta (n + p + m), delta_b (n), c (1) of the preconditioner.  kktsys: the borrowed KKT system; after a solve it is
  * in the state the last factorisation and the last solve of each instance left. */
 enum { PQ_SOLVER_BATCH_P_UTRI = 0, PQ_SOLVER_BATCH_AT, PQ_SOLVER_BATCH_GT, PQ_SOLVER_BATCH_C, PQ_SOLVER_BATCH_B, PQ_SOLVER_BATCH_H_L, PQ_SOLVER_BATCH_H_U,
        PQ_SOLVER_BATCH_X_L, PQ_SOLVER_BATCH_X_U, PQ_SOLVER_BATCH_X_B_SCALING, PQ_SOLVER_BATCH_PRECOND_DELTA, PQ_SOLVER_BATCH_PRECOND_DELTA_B, PQ_SOLVER_BATCH_PRECOND_C };
@@ -738,6 +766,17 @@ long long pq_debug_alloc_count(void);
  * k_chol_persistent), five ints per task (kind, round, a, b, gate).
  * Returns the number of tasks (-1: T outside [3, 1024]).  tests/test_chol_plan.py replays the list on the CPU: every task only waits for EARLIER tickets. */
 int pq_debug_chol_plan(int T, int *out5, int capacity_tasks);
+/* host-only (no device needed): the host logic of dense/data.hpp:98-207 for ONE instance -- set_h_l, set_h_u, disable_inf_constraints, set_x_l, set_x_u -- the very
+ * function pq_solver_batch_setup_dense and pq_solver_batch_update_dense call for every instance in both modes of the bound sets (csrc/dense_solver_batch.hip
+ * dsb_bound_lists).  h_l, h_u [m], x_l, x_u [n]: any may be NULL.  fin_*: all NULL for a setup (a vector that is not given is infinite everywhere); for an update
+ * the finiteness flags (int, [m], [m], [n], [n]) of the four vectors as stored: 1 = in the list, a row dropped earlier being stored finite on both sides as
+ * -1 / 1; 0 = infinite; a vector that is not given keeps what is stored (a stored infinite bound IS infinite: the second rule at pq_solver_batch_update_dense).  Outputs, any but counts may be NULL: counts = n_h_l, n_h_u, n_x_l, n_x_u; the four ascending lists ([m], [m], [n], [n]); dead [m]:
+ * 1 on the rows dropped in this call (both bounds infinite; in both lists, bounds -1 / 1; an update without h_l and h_u drops nothing); the vectors as stored: a
+ * given h vector (every one in a setup) at full length, one that an update does not give on the rows dropped in this call only; a given box vector (every one in a
+ * setup) packed to its list and followed by zeros, one that an update does not give untouched.  Returns PQ_OK. */
+int pq_debug_bound_lists(int m, int n, const double *h_l, const double *h_u, const double *x_l, const double *x_u, const int *fin_h_l, const int *fin_h_u,
+                         const int *fin_x_l, const int *fin_x_u, int counts[4], int *h_l_idx, int *h_u_idx, int *x_l_idx, int *x_u_idx, int *dead, double *h_l_out,
+                         double *h_u_out, double *x_l_out, double *x_u_out);
 /* host-only (no device needed): the launch plan of the SYRK behind the dense KKT assembly and A^T A (csrc/dense_kernels.hip launch_syrk) for an n x n result with
  * inner dimension kdim, with (the G' W G assembly) or without (A^T A) the split-K workspace: out = { T = ceil(n / 128), tiles of the lower triangle, 1 if the 16-wave
  * low-latency shape runs (kdim <= 256), 1 if the launch asks for the XCD-aware tile-order table (if its allocation fails the launch falls back to the triangular

@@ -14,6 +14,7 @@ from .kkt import (COL_MAJOR, DENSE_CHOLESKY, DENSE_LDLT_NO_PIVOT, MEM_DEVICE, ME
 
 SCALED_ITEMS = ("P_utri", "AT", "GT", "c", "b", "h_l", "h_u", "x_l", "x_u", "x_b_scaling", "delta", "delta_b", "c_scale")  # PQ_SOLVER_BATCH_*
 _NAMES = ("P", "c", "A", "b", "G", "h_l", "h_u", "x_l", "x_u")
+BOUND_SETS = {"shared": 0, "per_instance": 1}  # PQ_BOUND_SETS_*
 
 
 def stack_layout(t):
@@ -27,18 +28,22 @@ def stack_layout(t):
 
 
 class BatchDenseSolver(_BatchHandle):
-    """BatchDenseSolver(device=0, kkt_solver=DENSE_CHOLESKY)
+    """BatchDenseSolver(device=0, kkt_solver=DENSE_CHOLESKY, bounds="shared")
 
     s.settings: the pq_settings shared by the batch.  s.setup(P, c, A=None, b=None, G=None, h_l=None, h_u=None, x_l=None, x_u=None): P [batch, n, n], A [batch, p, n],
     G [batch, m, n], vectors [batch, len]; NumPy arrays, or torch CUDA float64 tensors (with any CUDA tensor among the arguments the data stays on the GPU and NumPy
-    arguments beside it are moved there).  The instances share the set of finite bounds.  s.solve() returns the number of instances that ended SOLVED.
+    arguments beside it are moved there).  bounds="shared" (the default): the instances share the set of finite bounds, a checked promise; bounds="per_instance": every
+    instance has the finite-bound lists DenseSolver would hold for its own vectors, at setup and after every update (-/+ inf switches a bound off).  s.solve() returns the number of instances that ended SOLVED.
     s.update(P=None, c=None, A=None, b=None, G=None, h_l=None, h_u=None, x_l=None, x_u=None): DenseSolver::update on the device, without a new setup; any subset of
-    the arguments, under the rules of setup; the set of finite bounds must stay the setup's (RuntimeError otherwise, the handle is as it was).  There is no clone()."""
+    the arguments, under the rules of setup; with shared bounds the set of finite bounds must stay the setup's (RuntimeError otherwise, the handle is as it was).
+    There is no clone()."""
     _destroy = "pq_solver_batch_destroy"
 
-    def __init__(self, device=0, kkt_solver=DENSE_CHOLESKY):
+    def __init__(self, device=0, kkt_solver=DENSE_CHOLESKY, bounds="shared"):
         if kkt_solver not in (DENSE_CHOLESKY, DENSE_LDLT_NO_PIVOT):
             raise ValueError(f"kkt_solver {kkt_solver}: DENSE_CHOLESKY or DENSE_LDLT_NO_PIVOT")
+        if bounds not in BOUND_SETS:
+            raise ValueError(f"bounds {bounds!r}: 'shared' or 'per_instance'")
         self.L = _lib.load()
         self.device = int(device)
         self.kkt_solver = int(kkt_solver)
@@ -47,6 +52,9 @@ class BatchDenseSolver(_BatchHandle):
         check(self.L.pq_solver_batch_create(C.byref(h), self.device), "pq_solver_batch_create")
         self.h = h
         self.settings.kkt_solver = self.kkt_solver
+        self.bounds = bounds
+        if bounds != "shared":
+            check(self.L.pq_solver_batch_set_bound_sets(self.h, BOUND_SETS[bounds]), "pq_solver_batch_set_bound_sets")
 
     @property
     def settings(self):

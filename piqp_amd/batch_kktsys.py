@@ -28,17 +28,21 @@ class BatchKKTSystem(_BatchHandle):
     ones) lives where the matrices live.  settings: a piqp_amd.default_settings() structure shared by the batch (its kkt_solver field is replaced by `kkt_solver`).
     A batch of variables is a dict of [batch, len] arrays under the names of piqp_amd.Variables (x, y, z_l, z_u, z_bl, z_bu, s_l, s_u, s_bl, s_bu; len = n, p, m, m, n,
     n, m, m, n, n); of the box vectors the first len(x_l_idx) / len(x_u_idx) entries of a row are meaningful.  An entry whose vector has no meaningful part may be
-    missing.  numpy in, numpy out; torch CUDA tensors by pointer, torch out; every array of one call lives in the same memory; wrong dtype, shape, contiguity or device
+    missing.  BatchKKTSystem.per_instance(P, A, G, lists, ...) makes a system in which every instance has lists of its own.  numpy in, numpy out; torch CUDA tensors by pointer, torch out; every array of one call lives in the same memory; wrong dtype, shape, contiguity or device
     is refused before any library call."""
     _destroy = "pq_kktsys_batch_destroy"
     _dims_fn = "pq_kktsys_batch_dims"
+    per_inst = False  # True: self.lists is a list of `batch` 4-tuples, one per instance (BatchKKTSystem.per_instance)
 
-    def __init__(self, P, A=None, G=None, h_l_idx=None, h_u_idx=None, x_l_idx=None, x_u_idx=None, x_b_scaling=None, settings=None, kkt_solver=DENSE_CHOLESKY, device=0):
+    def _open_settings(self, P, A, G, settings, kkt_solver, device):
         self._open(P, A, G, kkt_solver, device)
         self.settings = _copy_settings(settings if settings is not None else default_settings())
         self.settings.kkt_solver = self.kkt_solver
         if not 0 <= self.settings.iterative_refinement_max_iter <= MAX_REFINE_ITER:
             raise ValueError(f"iterative_refinement_max_iter {self.settings.iterative_refinement_max_iter}: [0, {MAX_REFINE_ITER}] (the loop runs inside a kernel)")
+
+    def __init__(self, P, A=None, G=None, h_l_idx=None, h_u_idx=None, x_l_idx=None, x_u_idx=None, x_b_scaling=None, settings=None, kkt_solver=DENSE_CHOLESKY, device=0):
+        self._open_settings(P, A, G, settings, kkt_solver, device)
         every = np.arange(self.m, dtype=np.int32)
         self.lists = tuple(self._list(name, v, default, length) for name, v, default, length in (
             ("h_l_idx", h_l_idx, every, self.m), ("h_u_idx", h_u_idx, every, self.m), ("x_l_idx", x_l_idx, every[:0], self.n), ("x_u_idx", x_u_idx, every[:0], self.n)))
@@ -54,7 +58,59 @@ class BatchKKTSystem(_BatchHandle):
               "pq_kktsys_batch_create_dense")
         self.h = h
 
+    @classmethod
+    def per_instance(cls, P, A, G, lists, x_b_scaling=None, settings=None, kkt_solver=DENSE_CHOLESKY, device=0):
+        """the same system with finite-bound lists of its own for every instance: `lists` is a sequence of `batch` 4-tuples (h_l_idx, h_u_idx, x_l_idx, x_u_idx) of
+        ascending integer lists, each under the rules of the constructor (None: its default there).  Of the box vectors of a batch of variables the first
+        len(x_l_idx) / len(x_u_idx) entries of row i are meaningful for instance i; a box vector has to be passed when any instance uses it.  set_lists(lists)
+        replaces the lists later (a new update_scalings_and_factor has to follow)."""
+        k = cls.__new__(cls)
+        k._open_settings(P, A, G, settings, kkt_solver, device)
+        k.per_inst = True
+        k.lists, packed = k._pack_lists(lists)
+        mem, (Pm, Am, Gm, xbs) = k._args(("P", P, (k.batch, k.n, k.n), True), ("A", A, (k.batch, k.p, k.n)), ("G", G, (k.batch, k.m, k.n)),
+                                         ("x_b_scaling", x_b_scaling, (k.batch, k.n)))
+        h = C.c_void_p()
+        if mem == MEM_DEVICE:
+            sync_current_stream(k.device)
+        check(k.L.pq_kktsys_batch_create_dense_lists(C.byref(h), k.device, k.batch, k.n, k.p, k.m, k._p(Pm), k._p(Am), k._p(Gm), *[a.ctypes.data for a in packed], k._p(xbs),
+                                                     C.byref(k.settings), mem), "pq_kktsys_batch_create_dense_lists")
+        k.h = h
+        return k
+
+    def set_lists(self, lists):
+        """other lists for every instance of a per_instance system (validated as there, before the library call); allocates nothing on the device"""
+        if not self.per_inst or self.lists is None:
+            raise RuntimeError("set_lists: the lists of this BatchKKTSystem are shared by the batch (or it is borrowed)")
+        new, packed = self._pack_lists(lists)
+        check(self.L.pq_kktsys_batch_set_lists(self.h, *[a.ctypes.data for a in packed]), "pq_kktsys_batch_set_lists")
+        self.lists = new
+
     # ---- argument handling: no library call in here
+    def _pack_lists(self, lists):
+        """(the validated per-instance lists, [counts [batch, 4], h_l_idx [batch, m], h_u_idx [batch, m], x_l_idx [batch, n], x_u_idx [batch, n]] as int32)"""
+        try:
+            lists = [tuple(t) for t in lists]
+        except TypeError:
+            raise TypeError("lists: a sequence of `batch` 4-tuples of index lists expected") from None
+        if len(lists) != self.batch or any(len(t) != 4 for t in lists):
+            raise ValueError(f"lists: {self.batch} 4-tuples (h_l_idx, h_u_idx, x_l_idx, x_u_idx) expected")
+        every = np.arange(self.m, dtype=np.int32)
+        lens = (self.m, self.m, self.n, self.n)
+        counts = np.zeros((self.batch, 4), dtype=np.int32)
+        packed = [np.zeros((self.batch, max(l, 1)), dtype=np.int32) for l in lens]
+        out = []
+        for i, t in enumerate(lists):
+            one = tuple(self._list(f"lists[{i}].{name}", v, default, length) for name, v, default, length in (
+                ("h_l_idx", t[0], every, self.m), ("h_u_idx", t[1], every, self.m), ("x_l_idx", t[2], every[:0], self.n), ("x_u_idx", t[3], every[:0], self.n)))
+            if self.m and len(np.union1d(one[0], one[1])) != self.m:
+                raise ValueError(f"lists[{i}]: every row of G must be in h_l_idx or h_u_idx")
+            for k, a in enumerate(one):
+                counts[i, k] = len(a)
+                packed[k][i, :len(a)] = a
+            out.append(one)
+        return out, [counts] + packed
+
     @staticmethod
     def _list(name, v, default, length):
         if v is None:
@@ -71,10 +127,9 @@ class BatchKKTSystem(_BatchHandle):
         return var_shapes(self.batch, self.n, self.p, self.m)
 
     def _used(self, name):
-        if name in ("z_bl", "s_bl"):
-            return len(self.lists[2]) > 0
-        if name in ("z_bu", "s_bu"):
-            return len(self.lists[3]) > 0
+        if name in ("z_bl", "s_bl", "z_bu", "s_bu"):
+            k = 2 if name in ("z_bl", "s_bl") else 3
+            return any(len(t[k]) > 0 for t in self.lists) if self.per_inst else len(self.lists[k]) > 0
         return self.var_shapes()[name][1] > 0
 
     def _vars(self, what, v, names=VAR_NAMES):
@@ -106,7 +161,7 @@ class BatchKKTSystem(_BatchHandle):
     def clone(self):
         h = C.c_void_p()
         check(self.L.pq_kktsys_batch_clone(self.h, C.byref(h)), "pq_kktsys_batch_clone")
-        return self._adopt(h, self.device, self.kkt_solver, lists=self.lists, settings=_copy_settings(self.settings))
+        return self._adopt(h, self.device, self.kkt_solver, lists=self.lists, per_inst=self.per_inst, settings=_copy_settings(self.settings))
 
     def backend(self):
         """the BatchDenseKKT this system owns (borrowed: it lives as long as this object)"""

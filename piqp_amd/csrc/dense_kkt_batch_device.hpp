@@ -187,4 +187,28 @@ __device__ __forceinline__ double kb_gemv_n_row(int i, int rows, int cols, const
     return c;
 }
 
+// ---- the finite-bound tables of the layers above the backend (dense_kktsys_batch.hip, dense_solver_batch.hip).  A row of tables is
+//   has_l[m], has_u[m] (the position of row i of G in h_l_idx / h_u_idx, or -1), pos_l[n], pos_u[n] (the same for the box lists; the KKT system only), x_l_idx, x_u_idx.
+// Shared sets: ONE row for the whole batch; the six pointers and the four counts are what the kernels had as plain arguments before sets per instance existed, and a
+// kernel built with PER = false uses them as they are: nothing is computed and nothing is read per instance, the code is the one of before.
+// Sets per instance (PER = true): the six pointers are those of instance 0's row, row `inst` lies inst * stride ints further, and the instance's counts are
+// cnt[4 inst ..] = n_h_l, n_h_u, n_x_l, n_x_u.
+struct KbBounds {
+    const int *has_l, *has_u, *pos_l, *pos_u, *xl_idx, *xu_idx;
+    int nhl, nhu, nxl, nxu;
+    const int* cnt;
+    int stride;
+};
+template <bool PER>
+__device__ __forceinline__ KbBounds kb_bound_row(const KbBounds& B, long long inst)
+{
+    if (!PER) return B;
+    KbBounds r = B;
+    const size_t off = (size_t)inst * B.stride;
+    r.has_l += off; r.has_u += off; r.pos_l += off; r.pos_u += off; r.xl_idx += off; r.xu_idx += off;
+    const int* c = B.cnt + 4 * (size_t)inst;
+    r.nhl = c[0]; r.nhu = c[1]; r.nxl = c[2]; r.nxu = c[3];
+    return r;
+}
+
 }  // namespace pq

@@ -19,13 +19,22 @@
 //   inf_norm3 / amax :140-145,:202-208        NaN-sticky workgroup maximum (wave_max_nan of kkt_system.hip)
 //   mul :365-394                              k_ksb_mul, one launch, one workgroup per instance
 //
+// The finite-bound lists: one set for the batch (pq_kktsys_batch_create_dense), or one per instance (pq_kktsys_batch_create_dense_lists, replaced by
+// pq_kktsys_batch_set_lists).  The kernels get them as a KbBounds (dense_kkt_batch_device.hpp) and are built twice, template parameter PER: with shared lists the
+// six table pointers and the counts are used as they come, as plain arguments were before -- nothing is computed or read per instance, the code is the one of
+// before; with lists per instance kb_bound_row moves the pointers to row `inst` of 2 m + 4 n ints and reads cnt_d[4 inst ..].  In the n < 32 variant of k_ksb_factor,
+// four instances to a workgroup, row and counts are per wave.  Every loop over a box list runs to the instance's own count.
+//
 // Memory of the solve kernel: beside the factor and the sweeps' scratch four n-vectors in LDS (lhs_x, ref_lhs_x, err_x, rhs_x_bar): n (n | 1) + 7 n + 2 doubles, 137.0 KiB
 // at n = 128.  The p- and m-length vectors (lhs, ref_lhs, err) live in a per-instance workspace in global memory, rhs_z_bar in the handle's state.  What a launch writes
 // to global memory and reads again is reached through plain pointers only (the rule above the helpers of dense_kkt_batch_device.hpp), and the phases are separated by
 // __syncthreads().  The one exception is the weight vector of kb_assemble (1 / z_reg_iter_ref, written by the factor launch a barrier earlier): its address is per
 // lane, a vector load.
+#include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstdio>
+#include <cstring>
 #include <memory>
 #include <vector>
 
@@ -70,13 +79,13 @@ __global__ void k_ksb_pdiag(const double* __restrict__ Pu, double* __restrict__ 
 
 // ---- update_scalings_and_factor
 struct KsbFactorArgs {
-    int n, p, m, ld, width, batch, nxl, nxu;
+    int n, p, m, ld, width, batch;
+    KbBounds bd;                  // row i has a lower / upper bound (has_* >= 0); variable i is entry pos_* of the lower / upper box list (or -1)
     const double *Pu, *ATA, *GT;  // the backend's data
     const int* flags;             // [batch] or null (off everywhere)
     const int* active;            // [batch] or null (every instance): an instance whose word is 0 is left out -- nothing of it is read or written
     const double *rho, *delta;    // [batch]
     const double *v_s_l, *v_z_l, *v_s_u, *v_z_u, *v_s_bl, *v_z_bl, *v_s_bu, *v_z_bu;  // the caller's state, [batch][m] resp. [batch][n]
-    const int *has_l, *has_u, *pos_l, *pos_u;  // row i has a lower / upper bound (>= 0); variable i is entry pos of the lower / upper box list (or -1)
     const double* xbs;                         // [batch][n]
     const double* pdiag;                       // [batch][n]: the diagonal of P as of the last update_data that carried P (kkt_system.hpp:134-141)
     double reg_eps, reg_rel;
@@ -86,7 +95,7 @@ struct KsbFactorArgs {
     int *info, *badcol;
 };
 
-template <int KIND, int G>
+template <int KIND, int G, bool PER>
 __global__ __launch_bounds__(DFB_THREADS) void k_ksb_factor(const KsbFactorArgs A)
 {
     extern __shared__ double ksb_lds[];
@@ -107,6 +116,8 @@ __global__ __launch_bounds__(DFB_THREADS) void k_ksb_factor(const KsbFactorArgs 
     double* z_reg = A.z_reg + om;  // (written and read again below: a plain pointer)
     double rho = 0.0, delta = 1.0, md = 0.0, zm = 0.0;
     if (have) {
+        // (the instance is the same in every lane of a wave: with G == 64 the table row and the counts are per wave, not per workgroup)
+        const KbBounds R = kb_bound_row<PER>(A.bd, G == 64 ? (long long)__builtin_amdgcn_readfirstlane((int)inst) : inst);
         rho = A.rho[inst];
         delta = A.delta[inst];
         // kkt_system.hpp:150-193, the formulas of k_scalings_fused
@@ -114,18 +125,18 @@ __global__ __launch_bounds__(DFB_THREADS) void k_ksb_factor(const KsbFactorArgs 
             const double sl = A.v_s_l[om + i], zil = 1.0 / A.v_z_l[om + i], su = A.v_s_u[om + i], ziu = 1.0 / A.v_z_u[om + i];
             A.s_l[om + i] = sl; A.zinv_l[om + i] = zil; A.s_u[om + i] = su; A.zinv_u[om + i] = ziu;
             double v = 0.0;
-            if (A.has_l[i] >= 0) v += 1.0 / (zil * sl + delta);
-            if (A.has_u[i] >= 0) v += 1.0 / (ziu * su + delta);
+            if (R.has_l[i] >= 0) v += 1.0 / (zil * sl + delta);
+            if (R.has_u[i] >= 0) v += 1.0 / (ziu * su + delta);
             v = 1.0 / v;
             z_reg[i] = v;
             zm = ksb_max_nan(zm, fabs(v));
         }
-        for (int i = t; i < A.nxl; i += G) { A.s_bl[on + i] = A.v_s_bl[on + i]; A.zinv_bl[on + i] = 1.0 / A.v_z_bl[on + i]; }
-        for (int i = t; i < A.nxu; i += G) { A.s_bu[on + i] = A.v_s_bu[on + i]; A.zinv_bu[on + i] = 1.0 / A.v_z_bu[on + i]; }
+        for (int i = t; i < R.nxl; i += G) { A.s_bl[on + i] = A.v_s_bl[on + i]; A.zinv_bl[on + i] = 1.0 / A.v_z_bl[on + i]; }
+        for (int i = t; i < R.nxu; i += G) { A.s_bu[on + i] = A.v_s_bu[on + i]; A.zinv_bu[on + i] = 1.0 / A.v_z_bu[on + i]; }
         for (int i = t; i < n; i += G) {
             double v = rho;
             const double sc = A.xbs[on + i];
-            const int il = A.pos_l[i], iu = A.pos_u[i];
+            const int il = R.pos_l[i], iu = R.pos_u[i];
             if (il >= 0) v += sc * sc / ((1.0 / A.v_z_bl[on + il]) * A.v_s_bl[on + il] + delta);
             if (iu >= 0) v += sc * sc / ((1.0 / A.v_z_bu[on + iu]) * A.v_s_bu[on + iu] + delta);
             xr[i] = v;
@@ -197,13 +208,14 @@ __device__ __forceinline__ double ksb_block_max_nan(double v, double* red)
 }
 
 struct KsbSolveArgs {
-    int n, p, m, ld, nxl, nxu, max_iter, batch;
+    int n, p, m, ld, max_iter, batch;
+    KbBounds bd;
     double eps_abs, eps_rel, min_rate;
     const double *Pu, *AT, *GT, *F, *delta_s, *x_reg_s, *zinv_s;  // the backend's data, stored scalings and factors
     const int* info;
     const int* active;  // [batch] or null (every instance): the workgroup of an instance whose word is 0 returns at once
     const double *s_l, *zinv_l, *s_u, *zinv_u, *s_bl, *zinv_bl, *s_bu, *zinv_bu, *z_reg, *mdelta_s, *xbs;  // the state of the last update_scalings_and_factor
-    const int *use_ref, *has_l, *has_u, *pos_l, *pos_u, *xl_idx, *xu_idx;
+    const int* use_ref;
     pq_vars rhs, lhs;                // [batch][len] each; rhs is only read
     double *rhs_x_bar, *rhs_z_bar;   // state: [batch][n], [batch][m]
     double *wy, *wz;                 // workspace: [batch][3][p], [batch][3][m] (lhs, ref_lhs, err)
@@ -268,7 +280,7 @@ __device__ __forceinline__ double ksb_refine_error(const KsbInst& I, const doubl
 
 __device__ __forceinline__ void ksb_swap(double*& a, double*& b) { double* c = a; a = b; b = c; }
 
-template <int KIND>
+template <int KIND, bool PER>
 __global__ __launch_bounds__(KB_SOLVE_THREADS) void k_ksb_solve(const KsbSolveArgs A)
 {
     extern __shared__ double ksb_lds[];
@@ -297,6 +309,7 @@ __global__ __launch_bounds__(KB_SOLVE_THREADS) void k_ksb_solve(const KsbSolveAr
         if (i >= j) a[i + j * ld] = src[e];
     }
     const size_t om = (size_t)inst * m, on = (size_t)inst * n, op = (size_t)inst * p;
+    const KbBounds R = kb_bound_row<PER>(A.bd, inst);
     const double delta = A.mdelta_s[inst];
     double* rzb = A.rhs_z_bar + om;
     double *ly = A.wy + 3 * op, *rly = ly + p, *ey = rly + p;
@@ -307,15 +320,15 @@ __global__ __launch_bounds__(KB_SOLVE_THREADS) void k_ksb_solve(const KsbSolveAr
         const double *r_z_l = A.rhs.z_l + om, *r_s_l = A.rhs.s_l + om, *r_z_u = A.rhs.z_u + om, *r_s_u = A.rhs.s_u + om;
         for (int i = t; i < m; i += T) {
             double v = 0.0;
-            if (A.has_l[i] >= 0) v -= 1.0 / (zinv_l[i] * s_l[i] + delta) * (r_z_l[i] - zinv_l[i] * r_s_l[i]);
-            if (A.has_u[i] >= 0) v += 1.0 / (zinv_u[i] * s_u[i] + delta) * (r_z_u[i] - zinv_u[i] * r_s_u[i]);
+            if (R.has_l[i] >= 0) v -= 1.0 / (zinv_l[i] * s_l[i] + delta) * (r_z_l[i] - zinv_l[i] * r_s_l[i]);
+            if (R.has_u[i] >= 0) v += 1.0 / (zinv_u[i] * s_u[i] + delta) * (r_z_u[i] - zinv_u[i] * r_s_u[i]);
             rzb[i] = v * z_reg[i];
         }
         const double *s_bl = A.s_bl + on, *zinv_bl = A.zinv_bl + on, *s_bu = A.s_bu + on, *zinv_bu = A.zinv_bu + on, *xbs = A.xbs + on;
         const double *r_z_bl = A.rhs.z_bl + on, *r_s_bl = A.rhs.s_bl + on, *r_z_bu = A.rhs.z_bu + on, *r_s_bu = A.rhs.s_bu + on;
         for (int i = t; i < n; i += T) {
             double v = A.rhs.x[on + i];
-            const int il = A.pos_l[i], iu = A.pos_u[i];
+            const int il = R.pos_l[i], iu = R.pos_u[i];
             if (il >= 0) v -= xbs[i] * (r_z_bl[il] - zinv_bl[il] * r_s_bl[il]) / (s_bl[il] * zinv_bl[il] + delta);
             if (iu >= 0) v += xbs[i] * (r_z_bu[iu] - zinv_bu[iu] * r_s_bu[iu]) / (s_bu[iu] * zinv_bu[iu] + delta);
             rxb[i] = v;
@@ -376,7 +389,7 @@ __global__ __launch_bounds__(KB_SOLVE_THREADS) void k_ksb_solve(const KsbSolveAr
         const double *s_l = A.s_l + om, *zinv_l = A.zinv_l + om, *s_u = A.s_u + om, *zinv_u = A.zinv_u + om, *z_reg = A.z_reg + om;
         const double *r_z_l = A.rhs.z_l + om, *r_s_l = A.rhs.s_l + om, *r_z_u = A.rhs.z_u + om, *r_s_u = A.rhs.s_u + om;
         for (int i = t; i < m; i += T) {
-            const bool l = A.has_l[i] >= 0, u = A.has_u[i] >= 0;
+            const bool l = R.has_l[i] >= 0, u = R.has_u[i] >= 0;
             double zl = 0.0, zu = 0.0, sl = 0.0, su = 0.0;
             if (l && u) {
                 const double rz_l_bar = r_z_l[i] - zinv_l[i] * r_s_l[i];
@@ -401,15 +414,15 @@ __global__ __launch_bounds__(KB_SOLVE_THREADS) void k_ksb_solve(const KsbSolveAr
     // :347-366, k_box_recovery
     {
         const double* xbs = A.xbs + on;
-        for (int i = t; i < A.nxl; i += T) {
-            const int idx = A.xl_idx[i];
+        for (int i = t; i < R.nxl; i += T) {
+            const int idx = R.xl_idx[i];
             const double zinv = A.zinv_bl[on + i], s = A.s_bl[on + i], r_s = A.rhs.s_bl[on + i];
             const double zb = (-1.0 * xbs[idx] * lx[idx] - A.rhs.z_bl[on + i] + zinv * r_s) / (s * zinv + delta);
             A.lhs.z_bl[on + i] = zb;
             A.lhs.s_bl[on + i] = zinv * (r_s - s * zb);
         }
-        for (int i = t; i < A.nxu; i += T) {
-            const int idx = A.xu_idx[i];
+        for (int i = t; i < R.nxu; i += T) {
+            const int idx = R.xu_idx[i];
             const double zinv = A.zinv_bu[on + i], s = A.s_bu[on + i], r_s = A.rhs.s_bu[on + i];
             const double zb = (1.0 * xbs[idx] * lx[idx] - A.rhs.z_bu[on + i] + zinv * r_s) / (s * zinv + delta);
             A.lhs.z_bu[on + i] = zb;
@@ -422,21 +435,23 @@ __global__ __launch_bounds__(KB_SOLVE_THREADS) void k_ksb_solve(const KsbSolveAr
 
 // ---- mul
 struct KsbMulArgs {
-    int n, p, m, nxl, nxu;
+    int n, p, m;
+    KbBounds bd;
     const double *Pu, *AT, *GT;
     const double *s_l, *zinv_l, *s_u, *zinv_u, *s_bl, *zinv_bl, *s_bu, *zinv_bu, *rho_s, *mdelta_s, *xbs;
-    const int *pos_l, *pos_u, *xl_idx, *xu_idx;
     pq_vars lhs, rhs;  // lhs is only read
     double* wz;        // [batch][3][m]: the first m of an instance hold z_u - z_l
 };
 
 // kkt_system.hpp:392-425 (k_mul_x, k_mul_y, k_mul_z, k_mul_box): blockIdx.x = instance
+template <bool PER>
 __global__ __launch_bounds__(KB_SOLVE_THREADS) void k_ksb_mul(const KsbMulArgs A)
 {
     const long long inst = blockIdx.x;
     const int n = A.n, p = A.p, m = A.m, t = threadIdx.x, T = blockDim.x;
     const size_t om = (size_t)inst * m, on = (size_t)inst * n, op = (size_t)inst * p;
     const double rho = A.rho_s[inst], delta = A.mdelta_s[inst];
+    const KbBounds R = kb_bound_row<PER>(A.bd, inst);
     const double *Pu = A.Pu + inst * (size_t)n * n, *AT = A.AT + inst * (size_t)n * p, *GT = A.GT + inst * (size_t)n * m, *xbs = A.xbs + on;
     const double *lx = A.lhs.x + on, *ly = A.lhs.y + op, *z_l = A.lhs.z_l + om, *z_u = A.lhs.z_u + om, *s_l = A.lhs.s_l + om, *s_u = A.lhs.s_u + om;
     const double *z_bl = A.lhs.z_bl + on, *z_bu = A.lhs.z_bu + on, *s_bl = A.lhs.s_bl + on, *s_bu = A.lhs.s_bu + on;
@@ -448,8 +463,8 @@ __global__ __launch_bounds__(KB_SOLVE_THREADS) void k_ksb_mul(const KsbMulArgs A
         v = v + rho * lx[i];
         v = v + kb_gemv_n_row(i, n, p, AT, ly, 1.0);
         v = v + kb_gemv_n_row(i, n, m, GT, d, 1.0);
-        if (A.pos_l[i] >= 0) v = v - xbs[i] * z_bl[A.pos_l[i]];
-        if (A.pos_u[i] >= 0) v = v + xbs[i] * z_bu[A.pos_u[i]];
+        if (R.pos_l[i] >= 0) v = v - xbs[i] * z_bl[R.pos_l[i]];
+        if (R.pos_u[i] >= 0) v = v + xbs[i] * z_bu[R.pos_u[i]];
         A.rhs.x[on + i] = v;
     }
     for (int j = t; j < p; j += T) A.rhs.y[op + j] = kb_gemv_t_col(j, n, AT, lx, 1.0) - delta * ly[j];
@@ -460,13 +475,13 @@ __global__ __launch_bounds__(KB_SOLVE_THREADS) void k_ksb_mul(const KsbMulArgs A
         A.rhs.s_l[om + j] = A.s_l[om + j] * z_l[j] + s_l[j] / A.zinv_l[om + j];
         A.rhs.s_u[om + j] = A.s_u[om + j] * z_u[j] + s_u[j] / A.zinv_u[om + j];
     }
-    for (int i = t; i < A.nxl; i += T) {
-        const int idx = A.xl_idx[i];
+    for (int i = t; i < R.nxl; i += T) {
+        const int idx = R.xl_idx[i];
         A.rhs.z_bl[on + i] = -1.0 * xbs[idx] * lx[idx] - delta * z_bl[i] + s_bl[i];
         A.rhs.s_bl[on + i] = A.s_bl[on + i] * z_bl[i] + s_bl[i] / A.zinv_bl[on + i];
     }
-    for (int i = t; i < A.nxu; i += T) {
-        const int idx = A.xu_idx[i];
+    for (int i = t; i < R.nxu; i += T) {
+        const int idx = R.xu_idx[i];
         A.rhs.z_bu[on + i] = 1.0 * xbs[idx] * lx[idx] - delta * z_bu[i] + s_bu[i];
         A.rhs.s_bu[on + i] = A.s_bu[on + i] * z_bu[i] + s_bu[i] / A.zinv_bu[on + i];
     }
@@ -488,13 +503,19 @@ struct KbDeleter {
 
 struct pq_kktsys_batch {
     int device = 0, batch = 0, n = 0, p = 0, m = 0;
-    int cnt[4] = {0, 0, 0, 0};       // n_h_l, n_h_u, n_x_l, n_x_u
-    std::vector<int> idx[4];         // the four lists (host)
+    bool per_inst = false;           // every instance has lists of its own (pq_kktsys_batch_create_dense_lists)
+    int cnt[4] = {0, 0, 0, 0};       // n_h_l, n_h_u, n_x_l, n_x_u; per instance: the largest of the batch (is a box vector used at all)
+    int box_min[2] = {0, 0};         // the smallest n_x_l, n_x_u of the batch (has a box row an unused tail)
+    std::vector<int> idx[4];         // shared: the four lists (host)
+    std::vector<int> tab_h, cnt_h;   // per instance: the host images of tab and cnt_d, sized at creation (pq_kktsys_batch_set_lists allocates nothing)
+    std::vector<char> seen;          // [m]: scratch of the checks
     pq_settings settings;
     int n_solved = 0;
     bool solved = false, timed[2] = {false, false};
+    bool stale = false;              // the lists were replaced after the last factorisation (pq_kktsys_batch_set_lists): as before the first one
     DBuf<double> state[S_COUNT];
-    DBuf<int> tab;                   // has_l[m], has_u[m], pos_l[n], pos_u[n], x_l_idx[n_x_l], x_u_idx[n_x_u]
+    DBuf<int> tab;                   // shared: has_l[m], has_u[m], pos_l[n], pos_u[n], x_l_idx[n_x_l], x_u_idx[n_x_u]; per instance: [batch] rows of 2 m + 4 n (KbBounds)
+    DBuf<int> cnt_d;                 // per instance: [batch][4]
     DBuf<int> use_ref, flags_d, sinfo;
     DBuf<double> dinfo, wy, wz, stage_in, stage_out;
     HBuf<int> sinfo_h;
@@ -552,7 +573,7 @@ pq_vars ksb_vars_out(pq_kktsys_batch* k, pq_vars* v, int mem, bool preload_all)
     ksb_var_counts(k, 0, count);
     pq_vars d;
     for (int i = 0; i < 10; ++i) {
-        const bool box_tail = ((i == 4 || i == 8) && k->cnt[2] < k->n) || ((i == 5 || i == 9) && k->cnt[3] < k->n);
+        const bool box_tail = ((i == 4 || i == 8) && k->box_min[0] < k->n) || ((i == 5 || i == 9) && k->box_min[1] < k->n);
         ksb_fields(&d)[i] = kb_out(k->stage_out, k->kb->st, ksb_fields(v)[i], count[i], mem, off, preload_all || box_tail);
     }
     return d;
@@ -569,10 +590,11 @@ void ksb_raise_lds()
     static PerDeviceOnce once;
     once([&] {
         const int fb = (int)ksb_factor_lds_bytes(PQ_KKT_BATCH_DENSE_MAX_N), sb = (int)ksb_solve_lds_bytes(PQ_KKT_BATCH_DENSE_MAX_N);
-        PQ_HIP(hipFuncSetAttribute((const void*)k_ksb_factor<0, DFB_THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, fb));
-        PQ_HIP(hipFuncSetAttribute((const void*)k_ksb_factor<1, DFB_THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, fb));
-        PQ_HIP(hipFuncSetAttribute((const void*)k_ksb_solve<0>, hipFuncAttributeMaxDynamicSharedMemorySize, sb));
-        PQ_HIP(hipFuncSetAttribute((const void*)k_ksb_solve<1>, hipFuncAttributeMaxDynamicSharedMemorySize, sb));
+        const void* const factor[4] = {(const void*)k_ksb_factor<0, DFB_THREADS, false>, (const void*)k_ksb_factor<1, DFB_THREADS, false>,
+                                       (const void*)k_ksb_factor<0, DFB_THREADS, true>, (const void*)k_ksb_factor<1, DFB_THREADS, true>};
+        const void* const solve[4] = {(const void*)k_ksb_solve<0, false>, (const void*)k_ksb_solve<1, false>, (const void*)k_ksb_solve<0, true>, (const void*)k_ksb_solve<1, true>};
+        for (const void* fn : factor) PQ_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, fb));
+        for (const void* fn : solve) PQ_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, sb));
     });
 }
 
@@ -582,7 +604,8 @@ void ksb_alloc(pq_kktsys_batch* k)
     const size_t b = (size_t)k->batch, n = (size_t)k->n, p = (size_t)k->p, m = (size_t)k->m;
     hipStream_t st = k->kb->st;
     for (int s = 0; s < S_COUNT; ++s) { k->state[s].alloc(b * ksb_state_len(k, s)); k->state[s].zero(st); }
-    k->tab.alloc(2 * m + 2 * n + (size_t)k->cnt[2] + (size_t)k->cnt[3]);
+    if (k->per_inst) { k->tab.alloc(b * (2 * m + 4 * n)); k->cnt_d.alloc(4 * b); }
+    else k->tab.alloc(2 * m + 2 * n + (size_t)k->cnt[2] + (size_t)k->cnt[3]);
     k->use_ref.alloc(b); k->use_ref.zero(st);
     k->flags_d.alloc(b);
     k->sinfo.alloc(3 * b); k->sinfo.zero(st);
@@ -600,6 +623,12 @@ void ksb_alloc(pq_kktsys_batch* k)
 void ksb_upload_tables(pq_kktsys_batch* k)
 {
     const int n = k->n, m = k->m;
+    if (k->per_inst) {  // (the images were filled by ksb_take_lists)
+        PQ_HIP(hipMemcpyAsync(k->tab.p, k->tab_h.data(), sizeof(int) * k->tab_h.size(), hipMemcpyHostToDevice, k->kb->st));
+        PQ_HIP(hipMemcpyAsync(k->cnt_d.p, k->cnt_h.data(), sizeof(int) * k->cnt_h.size(), hipMemcpyHostToDevice, k->kb->st));
+        stream_wait(k->kb->st);
+        return;
+    }
     std::vector<int> t((size_t)2 * m + 2 * n + k->cnt[2] + k->cnt[3], -1);
     for (int i = 0; i < k->cnt[0]; ++i) t[k->idx[0][i]] = i;
     for (int i = 0; i < k->cnt[1]; ++i) t[(size_t)m + k->idx[1][i]] = i;
@@ -615,12 +644,17 @@ void ksb_extract_pdiag(pq_kktsys_batch* k)
     k_ksb_pdiag<<<(unsigned)((total + 255) / 256), 256, 0, k->kb->st>>>(k->kb->Pu.p, k->state[S_PDIAG].p, k->n, total);
     PQ_HIP(hipGetLastError());
 }
-const int* ksb_has_l(const pq_kktsys_batch* k) { return k->tab.p; }
-const int* ksb_has_u(const pq_kktsys_batch* k) { return k->tab.p + k->m; }
-const int* ksb_pos_l(const pq_kktsys_batch* k) { return k->tab.p + 2 * (size_t)k->m; }
-const int* ksb_pos_u(const pq_kktsys_batch* k) { return k->tab.p + 2 * (size_t)k->m + k->n; }
-const int* ksb_xl_idx(const pq_kktsys_batch* k) { return k->tab.p + 2 * (size_t)k->m + 2 * (size_t)k->n; }
-const int* ksb_xu_idx(const pq_kktsys_batch* k) { return ksb_xl_idx(k) + k->cnt[2]; }
+KbBounds ksb_bounds(const pq_kktsys_batch* k)
+{
+    const size_t m = (size_t)k->m, n = (size_t)k->n;
+    KbBounds b;
+    b.has_l = k->tab.p; b.has_u = b.has_l + m; b.pos_l = b.has_u + m; b.pos_u = b.pos_l + n; b.xl_idx = b.pos_u + n;
+    b.xu_idx = b.xl_idx + (k->per_inst ? n : (size_t)k->cnt[2]);
+    b.nhl = k->cnt[0]; b.nhu = k->cnt[1]; b.nxl = k->cnt[2]; b.nxu = k->cnt[3];
+    b.cnt = k->per_inst ? k->cnt_d.p : nullptr;
+    b.stride = k->per_inst ? (int)(2 * m + 4 * n) : 0;
+    return b;
+}
 
 int ksb_check_settings(const pq_settings* s)
 {
@@ -631,16 +665,68 @@ int ksb_check_settings(const pq_settings* s)
     return PQ_OK;
 }
 
-int ksb_check_list(const char* name, int cnt, const int* idx, int len)
+// who: "" for the lists a batch shares, "instance 12: " for those of one instance
+int ksb_check_list(const char* who, const char* name, int cnt, const int* idx, int len)
 {
-    if (cnt < 0) return fail(PQ_ERR_INVALID, "dense KKT system batch: n_%s = %d is negative", name, cnt);
-    if (cnt > len) return fail(PQ_ERR_INVALID, "dense KKT system batch: n_%s = %d, its vector has %d entries", name, cnt, len);
-    if (cnt > 0 && !idx) return fail(PQ_ERR_INVALID, "dense KKT system batch: %s_idx is null, n_%s = %d", name, name, cnt);
+    if (cnt < 0) return fail(PQ_ERR_INVALID, "dense KKT system batch: %sn_%s = %d is negative", who, name, cnt);
+    if (cnt > len) return fail(PQ_ERR_INVALID, "dense KKT system batch: %sn_%s = %d, its vector has %d entries", who, name, cnt, len);
+    if (cnt > 0 && !idx) return fail(PQ_ERR_INVALID, "dense KKT system batch: %s%s_idx is null, n_%s = %d", who, name, name, cnt);
     for (int i = 0; i < cnt; ++i) {
-        if (idx[i] < 0 || idx[i] >= len) return fail(PQ_ERR_INVALID, "dense KKT system batch: %s_idx[%d] = %d outside [0, %d)", name, i, idx[i], len);
-        if (i > 0 && idx[i] <= idx[i - 1]) return fail(PQ_ERR_INVALID, "dense KKT system batch: %s_idx is not strictly ascending at %d", name, i);
+        if (idx[i] < 0 || idx[i] >= len) return fail(PQ_ERR_INVALID, "dense KKT system batch: %s%s_idx[%d] = %d outside [0, %d)", who, name, i, idx[i], len);
+        if (i > 0 && idx[i] <= idx[i - 1]) return fail(PQ_ERR_INVALID, "dense KKT system batch: %s%s_idx is not strictly ascending at %d", who, name, i);
     }
     return PQ_OK;
+}
+
+// the four lists of the batch (inst < 0) or of one instance: counts, order, range, and every row of G in h_l_idx or h_u_idx.  seen: m chars of scratch
+int ksb_check_lists(int inst, int n, int m, const int cnt[4], const int* const lists[4], char* seen)
+{
+    static const char* const names[4] = {"h_l", "h_u", "x_l", "x_u"};
+    char who[32] = "";
+    if (inst >= 0) std::snprintf(who, sizeof(who), "instance %d: ", inst);
+    for (int q = 0; q < 4; ++q)
+        if (int rc = ksb_check_list(who, names[q], cnt[q], lists[q], q < 2 ? m : n)) return rc;
+    std::memset(seen, 0, (size_t)m);
+    for (int i = 0; i < cnt[0]; ++i) seen[lists[0][i]] = 1;
+    for (int i = 0; i < cnt[1]; ++i) seen[lists[1][i]] = 1;
+    for (int i = 0; i < m; ++i)
+        if (!seen[i])
+            return fail(PQ_ERR_INVALID, "dense KKT system batch: %srow %d of G is in neither h_l_idx nor h_u_idx (a row without a finite bound takes no part in a QP)", who, i);
+    return PQ_OK;
+}
+
+// per-instance lists: counts [batch][4], the four list arrays [batch][m], [batch][m], [batch][n], [batch][n].  Every instance is checked, nothing is written
+int ksb_check_all_lists(int batch, int n, int m, const int* counts, const int* h_l_idx, const int* h_u_idx, const int* x_l_idx, const int* x_u_idx, char* seen)
+{
+    if (!counts) return fail(PQ_ERR_INVALID, "dense KKT system batch: counts is null");
+    for (int i = 0; i < batch; ++i) {
+        const int* lists[4] = {h_l_idx ? h_l_idx + (size_t)i * m : nullptr, h_u_idx ? h_u_idx + (size_t)i * m : nullptr, x_l_idx ? x_l_idx + (size_t)i * n : nullptr,
+                               x_u_idx ? x_u_idx + (size_t)i * n : nullptr};
+        if (int rc = ksb_check_lists(i, n, m, counts + 4 * (size_t)i, lists, seen)) return rc;
+    }
+    return PQ_OK;
+}
+
+// checked per-instance lists into the host images of the tables (sized already) and the handle's summary counts
+void ksb_take_lists(pq_kktsys_batch* k, const int* counts, const int* h_l_idx, const int* h_u_idx, const int* x_l_idx, const int* x_u_idx)
+{
+    const int n = k->n, m = k->m;
+    const size_t stride = 2 * (size_t)m + 4 * (size_t)n;
+    std::fill(k->tab_h.begin(), k->tab_h.end(), -1);
+    std::copy(counts, counts + 4 * (size_t)k->batch, k->cnt_h.begin());
+    for (int q = 0; q < 4; ++q) k->cnt[q] = 0;
+    k->box_min[0] = k->box_min[1] = n;
+    for (int i = 0; i < k->batch; ++i) {
+        const int* c = counts + 4 * (size_t)i;
+        int* t = k->tab_h.data() + i * stride;
+        for (int e = 0; e < c[0]; ++e) t[h_l_idx[(size_t)i * m + e]] = e;
+        for (int e = 0; e < c[1]; ++e) t[(size_t)m + h_u_idx[(size_t)i * m + e]] = e;
+        for (int e = 0; e < c[2]; ++e) { const int j = x_l_idx[(size_t)i * n + e]; t[(size_t)2 * m + j] = e; t[(size_t)2 * m + 2 * n + e] = j; }
+        for (int e = 0; e < c[3]; ++e) { const int j = x_u_idx[(size_t)i * n + e]; t[(size_t)2 * m + n + j] = e; t[(size_t)2 * m + 3 * n + e] = j; }
+        for (int q = 0; q < 4; ++q) k->cnt[q] = std::max(k->cnt[q], c[q]);
+        k->box_min[0] = std::min(k->box_min[0], c[2]);
+        k->box_min[1] = std::min(k->box_min[1], c[3]);
+    }
 }
 
 }  // namespace
@@ -656,11 +742,11 @@ void ksb_launch_factor(pq_kktsys_batch* k, const int* flags, const double* rho, 
     const int n = k->n, batch = k->batch;
     hipStream_t st = kb->st;
     KsbFactorArgs a;
-    a.n = n; a.p = k->p; a.m = k->m; a.ld = dfb_ld(n); a.width = n < 32 ? n : dfb_block_size_rule(n); a.batch = batch; a.nxl = k->cnt[2]; a.nxu = k->cnt[3];
+    k->stale = false;  // (also for a launch masked by `active`: the one caller that masks, the solver's rounds, factors every instance in its first round)
+    a.n = n; a.p = k->p; a.m = k->m; a.ld = dfb_ld(n); a.width = n < 32 ? n : dfb_block_size_rule(n); a.batch = batch; a.bd = ksb_bounds(k);
     a.Pu = kb->Pu.p; a.ATA = k->p > 0 ? kb->ATA.p : nullptr; a.GT = kb->GT.p;
     a.flags = flags; a.active = active; a.rho = rho; a.delta = delta;
     a.v_s_l = v.s_l; a.v_z_l = v.z_l; a.v_s_u = v.s_u; a.v_z_u = v.z_u; a.v_s_bl = v.s_bl; a.v_z_bl = v.z_bl; a.v_s_bu = v.s_bu; a.v_z_bu = v.z_bu;
-    a.has_l = ksb_has_l(k); a.has_u = ksb_has_u(k); a.pos_l = ksb_pos_l(k); a.pos_u = ksb_pos_u(k);
     a.xbs = k->state[S_XBS].p; a.pdiag = k->state[S_PDIAG].p;
     a.reg_eps = k->settings.iterative_refinement_static_regularization_eps; a.reg_rel = k->settings.iterative_refinement_static_regularization_rel;
     a.s_l = k->state[S_SL].p; a.zinv_l = k->state[S_ZIL].p; a.s_u = k->state[S_SU].p; a.zinv_u = k->state[S_ZIU].p;
@@ -670,11 +756,17 @@ void ksb_launch_factor(pq_kktsys_batch* k, const int* flags, const double* rho, 
     const size_t lds = ksb_factor_lds_bytes(n);
     if (n < 32) {
         const int grid = div_up(batch, DFB_THREADS / 64);
-        if (kb->kind == PQ_DENSE_CHOLESKY) k_ksb_factor<0, 64><<<grid, DFB_THREADS, lds, st>>>(a);
-        else k_ksb_factor<1, 64><<<grid, DFB_THREADS, lds, st>>>(a);
+        if (k->per_inst) {
+            if (kb->kind == PQ_DENSE_CHOLESKY) k_ksb_factor<0, 64, true><<<grid, DFB_THREADS, lds, st>>>(a);
+            else k_ksb_factor<1, 64, true><<<grid, DFB_THREADS, lds, st>>>(a);
+        } else if (kb->kind == PQ_DENSE_CHOLESKY) k_ksb_factor<0, 64, false><<<grid, DFB_THREADS, lds, st>>>(a);
+        else k_ksb_factor<1, 64, false><<<grid, DFB_THREADS, lds, st>>>(a);
     } else {
-        if (kb->kind == PQ_DENSE_CHOLESKY) k_ksb_factor<0, DFB_THREADS><<<batch, DFB_THREADS, lds, st>>>(a);
-        else k_ksb_factor<1, DFB_THREADS><<<batch, DFB_THREADS, lds, st>>>(a);
+        if (k->per_inst) {
+            if (kb->kind == PQ_DENSE_CHOLESKY) k_ksb_factor<0, DFB_THREADS, true><<<batch, DFB_THREADS, lds, st>>>(a);
+            else k_ksb_factor<1, DFB_THREADS, true><<<batch, DFB_THREADS, lds, st>>>(a);
+        } else if (kb->kind == PQ_DENSE_CHOLESKY) k_ksb_factor<0, DFB_THREADS, false><<<batch, DFB_THREADS, lds, st>>>(a);
+        else k_ksb_factor<1, DFB_THREADS, false><<<batch, DFB_THREADS, lds, st>>>(a);
     }
     PQ_HIP(hipGetLastError());
 }
@@ -685,7 +777,7 @@ void ksb_launch_solve(pq_kktsys_batch* k, const pq_vars& rhs, const pq_vars& lhs
     const int n = k->n, batch = k->batch;
     hipStream_t st = kb->st;
     KsbSolveArgs a;
-    a.n = n; a.p = k->p; a.m = k->m; a.ld = dfb_ld(n); a.nxl = k->cnt[2]; a.nxu = k->cnt[3]; a.max_iter = k->settings.iterative_refinement_max_iter; a.batch = batch;
+    a.n = n; a.p = k->p; a.m = k->m; a.ld = dfb_ld(n); a.bd = ksb_bounds(k); a.max_iter = k->settings.iterative_refinement_max_iter; a.batch = batch;
     a.eps_abs = k->settings.iterative_refinement_eps_abs; a.eps_rel = k->settings.iterative_refinement_eps_rel;
     a.min_rate = k->settings.iterative_refinement_min_improvement_rate;
     a.Pu = kb->Pu.p; a.AT = kb->AT.p; a.GT = kb->GT.p; a.F = kb->fac.p; a.delta_s = kb->delta_s.p; a.x_reg_s = kb->x_reg_s.p; a.zinv_s = kb->zinv_s.p; a.info = kb->status.p;
@@ -693,12 +785,16 @@ void ksb_launch_solve(pq_kktsys_batch* k, const pq_vars& rhs, const pq_vars& lhs
     a.s_l = k->state[S_SL].p; a.zinv_l = k->state[S_ZIL].p; a.s_u = k->state[S_SU].p; a.zinv_u = k->state[S_ZIU].p;
     a.s_bl = k->state[S_SBL].p; a.zinv_bl = k->state[S_ZIBL].p; a.s_bu = k->state[S_SBU].p; a.zinv_bu = k->state[S_ZIBU].p;
     a.z_reg = k->state[S_ZREG].p; a.mdelta_s = k->state[S_MDELTA].p; a.xbs = k->state[S_XBS].p;
-    a.use_ref = k->use_ref.p; a.has_l = ksb_has_l(k); a.has_u = ksb_has_u(k); a.pos_l = ksb_pos_l(k); a.pos_u = ksb_pos_u(k); a.xl_idx = ksb_xl_idx(k); a.xu_idx = ksb_xu_idx(k);
+    a.use_ref = k->use_ref.p;
     a.rhs = rhs; a.lhs = lhs;
     a.rhs_x_bar = k->state[S_RXB].p; a.rhs_z_bar = k->state[S_RZB].p; a.wy = k->wy.p; a.wz = k->wz.p; a.sinfo = k->sinfo.p; a.dinfo = k->dinfo.p;
     const int threads = n <= 64 ? 64 : KB_SOLVE_THREADS;
-    if (kb->kind == PQ_DENSE_CHOLESKY) k_ksb_solve<0><<<batch, threads, ksb_solve_lds_bytes(n), st>>>(a);
-    else k_ksb_solve<1><<<batch, threads, ksb_solve_lds_bytes(n), st>>>(a);
+    const size_t lds = ksb_solve_lds_bytes(n);
+    if (k->per_inst) {
+        if (kb->kind == PQ_DENSE_CHOLESKY) k_ksb_solve<0, true><<<batch, threads, lds, st>>>(a);
+        else k_ksb_solve<1, true><<<batch, threads, lds, st>>>(a);
+    } else if (kb->kind == PQ_DENSE_CHOLESKY) k_ksb_solve<0, false><<<batch, threads, lds, st>>>(a);
+    else k_ksb_solve<1, false><<<batch, threads, lds, st>>>(a);
     PQ_HIP(hipGetLastError());
 }
 
@@ -728,26 +824,11 @@ void ksb_refresh_host(pq_kktsys_batch* k)
 
 extern "C" {
 
-int pq_kktsys_batch_create_dense(pq_kktsys_batch** out, int device, int batch, int n, int p, int m, const double* P_utri, const double* AT, const double* GT, int n_h_l,
-                                 int n_h_u, int n_x_l, int n_x_u, const int* h_l_idx, const int* h_u_idx, const int* x_l_idx, const int* x_u_idx, const double* x_b_scaling,
-                                 const pq_settings* settings, int mem)
+// what the two creators share once the lists are checked: the backend, the allocations, the tables, x_b_scaling and P_diag.  counts / lists: the four counts and lists
+// of the batch, or with per_inst [batch][4] and four arrays of `batch` rows
+static int ksb_create(pq_kktsys_batch** out, int device, int batch, int n, int p, int m, const double* P_utri, const double* AT, const double* GT, bool per_inst,
+                      const int* counts, const int* const lists[4], const double* x_b_scaling, const pq_settings* settings, int mem)
 {
-    if (!out) return fail(PQ_ERR_INVALID, "null argument");
-    if (batch < 1 || n < 1 || p < 0 || m < 0)
-        return fail(PQ_ERR_INVALID, "dense KKT system batch: batch = %d, n = %d, p = %d, m = %d: batch, n >= 1 and p, m >= 0 wanted", batch, n, p, m);
-    if (int rc = ksb_check_settings(settings)) return rc;
-    const int cnt[4] = {n_h_l, n_h_u, n_x_l, n_x_u};
-    const int* lists[4] = {h_l_idx, h_u_idx, x_l_idx, x_u_idx};
-    const char* names[4] = {"h_l", "h_u", "x_l", "x_u"};
-    for (int q = 0; q < 4; ++q)
-        if (int rc = ksb_check_list(names[q], cnt[q], lists[q], q < 2 ? m : n)) return rc;
-    {
-        std::vector<char> seen((size_t)m, 0);
-        for (int i = 0; i < n_h_l; ++i) seen[h_l_idx[i]] = 1;
-        for (int i = 0; i < n_h_u; ++i) seen[h_u_idx[i]] = 1;
-        for (int i = 0; i < m; ++i)
-            if (!seen[i]) return fail(PQ_ERR_INVALID, "dense KKT system batch: row %d of G is in neither h_l_idx nor h_u_idx (a row without a finite bound takes no part in a QP)", i);
-    }
     // (the backend's create checks its arguments before it touches the device, too)
     pq_kkt_batch* kb = nullptr;
     if (int rc = pq_kkt_batch_create_dense(&kb, device, batch, n, p, m, settings->kkt_solver, P_utri, AT, GT, mem)) return rc;
@@ -757,7 +838,16 @@ int pq_kktsys_batch_create_dense(pq_kktsys_batch** out, int device, int batch, i
         std::unique_ptr<pq_kktsys_batch> k(new pq_kktsys_batch);
         k->device = device; k->batch = batch; k->n = n; k->p = p; k->m = m;
         k->settings = *settings;
-        for (int q = 0; q < 4; ++q) { k->cnt[q] = cnt[q]; k->idx[q].assign(lists[q], lists[q] + cnt[q]); }
+        k->per_inst = per_inst;
+        k->seen.assign((size_t)m, 0);
+        if (per_inst) {
+            k->tab_h.assign((size_t)batch * (2 * (size_t)m + 4 * (size_t)n), -1);
+            k->cnt_h.assign(4 * (size_t)batch, 0);
+            ksb_take_lists(k.get(), counts, lists[0], lists[1], lists[2], lists[3]);
+        } else {
+            for (int q = 0; q < 4; ++q) { k->cnt[q] = counts[q]; k->idx[q].assign(lists[q], lists[q] + counts[q]); }
+            k->box_min[0] = counts[2]; k->box_min[1] = counts[3];
+        }
         k->kb = std::move(own);
         ksb_alloc(k.get());
         ksb_upload_tables(k.get());
@@ -771,6 +861,53 @@ int pq_kktsys_batch_create_dense(pq_kktsys_batch** out, int device, int batch, i
         ksb_extract_pdiag(k.get());
         stream_wait(st);
         *out = k.release();
+        return (int)PQ_OK;
+    });
+}
+
+static int ksb_check_create(pq_kktsys_batch** out, int batch, int n, int p, int m, const pq_settings* settings)
+{
+    if (!out) return fail(PQ_ERR_INVALID, "null argument");
+    if (batch < 1 || n < 1 || p < 0 || m < 0)
+        return fail(PQ_ERR_INVALID, "dense KKT system batch: batch = %d, n = %d, p = %d, m = %d: batch, n >= 1 and p, m >= 0 wanted", batch, n, p, m);
+    return ksb_check_settings(settings);
+}
+
+int pq_kktsys_batch_create_dense(pq_kktsys_batch** out, int device, int batch, int n, int p, int m, const double* P_utri, const double* AT, const double* GT, int n_h_l,
+                                 int n_h_u, int n_x_l, int n_x_u, const int* h_l_idx, const int* h_u_idx, const int* x_l_idx, const int* x_u_idx, const double* x_b_scaling,
+                                 const pq_settings* settings, int mem)
+{
+    if (int rc = ksb_check_create(out, batch, n, p, m, settings)) return rc;
+    const int cnt[4] = {n_h_l, n_h_u, n_x_l, n_x_u};
+    const int* lists[4] = {h_l_idx, h_u_idx, x_l_idx, x_u_idx};
+    std::vector<char> seen((size_t)m, 0);
+    if (int rc = ksb_check_lists(-1, n, m, cnt, lists, seen.data())) return rc;
+    return ksb_create(out, device, batch, n, p, m, P_utri, AT, GT, false, cnt, lists, x_b_scaling, settings, mem);
+}
+
+int pq_kktsys_batch_create_dense_lists(pq_kktsys_batch** out, int device, int batch, int n, int p, int m, const double* P_utri, const double* AT, const double* GT,
+                                       const int* counts, const int* h_l_idx, const int* h_u_idx, const int* x_l_idx, const int* x_u_idx, const double* x_b_scaling,
+                                       const pq_settings* settings, int mem)
+{
+    if (int rc = ksb_check_create(out, batch, n, p, m, settings)) return rc;
+    std::vector<char> seen((size_t)m, 0);
+    if (int rc = ksb_check_all_lists(batch, n, m, counts, h_l_idx, h_u_idx, x_l_idx, x_u_idx, seen.data())) return rc;
+    const int* lists[4] = {h_l_idx, h_u_idx, x_l_idx, x_u_idx};
+    return ksb_create(out, device, batch, n, p, m, P_utri, AT, GT, true, counts, lists, x_b_scaling, settings, mem);
+}
+
+int pq_kktsys_batch_set_lists(pq_kktsys_batch* k, const int* counts, const int* h_l_idx, const int* h_u_idx, const int* x_l_idx, const int* x_u_idx)
+{
+    if (!k) return fail(PQ_ERR_INVALID, "null argument");
+    if (!k->per_inst) return fail(PQ_ERR_INVALID, "dense KKT system batch: set_lists: the handle's lists are shared by the batch (pq_kktsys_batch_create_dense_lists makes the other kind)");
+    if (int rc = ksb_check_all_lists(k->batch, k->n, k->m, counts, h_l_idx, h_u_idx, x_l_idx, x_u_idx, k->seen.data())) return rc;
+    return guarded([&] {
+        PQ_HIP(hipSetDevice(k->device));
+        stream_wait(k->kb->st);  // (a launch that still reads the tables; the host images are pageable)
+        ksb_take_lists(k, counts, h_l_idx, h_u_idx, x_l_idx, x_u_idx);
+        ksb_upload_tables(k);
+        k->stale = true;  // the factors and the stored scalings belong to the old lists
+        k->solved = false;
         return (int)PQ_OK;
     });
 }
@@ -790,6 +927,8 @@ int pq_kktsys_batch_clone(const pq_kktsys_batch* k, pq_kktsys_batch** out)
         c->device = k->device; c->batch = k->batch; c->n = k->n; c->p = k->p; c->m = k->m;
         c->settings = k->settings;
         for (int q = 0; q < 4; ++q) { c->cnt[q] = k->cnt[q]; c->idx[q] = k->idx[q]; }
+        c->per_inst = k->per_inst; c->stale = k->stale; c->box_min[0] = k->box_min[0]; c->box_min[1] = k->box_min[1];
+        c->tab_h = k->tab_h; c->cnt_h = k->cnt_h; c->seen = k->seen;
         c->n_solved = k->n_solved; c->solved = k->solved;
         c->kb = std::move(own);
         ksb_alloc(c.get());
@@ -875,7 +1014,7 @@ int pq_kktsys_batch_update_scalings_and_factor(pq_kktsys_batch* k, const int* it
 int pq_kktsys_batch_solve(pq_kktsys_batch* k, const pq_vars* rhs, pq_vars* lhs, int mem)
 {
     if (!k || !rhs || !lhs) return fail(PQ_ERR_INVALID, "null argument");
-    if (!k->kb->computed) return fail(PQ_ERR_INVALID, "dense KKT system batch: solve before update_scalings_and_factor");
+    if (!k->kb->computed || k->stale) return fail(PQ_ERR_INVALID, "dense KKT system batch: solve before update_scalings_and_factor");
     if (kb_bad_mem(mem)) return fail(PQ_ERR_INVALID, "dense KKT system batch: bad mem");
     if (int rc = ksb_check_vars(k, rhs, 0, "solve: rhs")) return rc;
     if (int rc = ksb_check_vars(k, lhs, 0, "solve: lhs")) return rc;
@@ -908,7 +1047,7 @@ int pq_kktsys_batch_solve(pq_kktsys_batch* k, const pq_vars* rhs, pq_vars* lhs, 
 int pq_kktsys_batch_mul(pq_kktsys_batch* k, const pq_vars* lhs, pq_vars* rhs, int mem)
 {
     if (!k || !lhs || !rhs) return fail(PQ_ERR_INVALID, "null argument");
-    if (!k->kb->computed) return fail(PQ_ERR_INVALID, "dense KKT system batch: mul before update_scalings_and_factor");
+    if (!k->kb->computed || k->stale) return fail(PQ_ERR_INVALID, "dense KKT system batch: mul before update_scalings_and_factor");
     if (kb_bad_mem(mem)) return fail(PQ_ERR_INVALID, "dense KKT system batch: bad mem");
     if (int rc = ksb_check_vars(k, lhs, 0, "mul: lhs")) return rc;
     if (int rc = ksb_check_vars(k, rhs, 0, "mul: rhs")) return rc;
@@ -918,17 +1057,17 @@ int pq_kktsys_batch_mul(pq_kktsys_batch* k, const pq_vars* lhs, pq_vars* rhs, in
         hipStream_t st = kb->st;
         size_t off = 0;
         KsbMulArgs a;
-        a.n = k->n; a.p = k->p; a.m = k->m; a.nxl = k->cnt[2]; a.nxu = k->cnt[3];
+        a.n = k->n; a.p = k->p; a.m = k->m; a.bd = ksb_bounds(k);
         a.Pu = kb->Pu.p; a.AT = kb->AT.p; a.GT = kb->GT.p;
         a.s_l = k->state[S_SL].p; a.zinv_l = k->state[S_ZIL].p; a.s_u = k->state[S_SU].p; a.zinv_u = k->state[S_ZIU].p;
         a.s_bl = k->state[S_SBL].p; a.zinv_bl = k->state[S_ZIBL].p; a.s_bu = k->state[S_SBU].p; a.zinv_bu = k->state[S_ZIBU].p;
         a.rho_s = k->state[S_RHO].p; a.mdelta_s = k->state[S_MDELTA].p; a.xbs = k->state[S_XBS].p;
-        a.pos_l = ksb_pos_l(k); a.pos_u = ksb_pos_u(k); a.xl_idx = ksb_xl_idx(k); a.xu_idx = ksb_xu_idx(k);
         a.lhs = ksb_vars_in(k, lhs, 0, mem, off);
         a.rhs = ksb_vars_out(k, rhs, mem, false);
         a.wz = k->wz.p;
         PQ_HIP(hipEventRecord(k->ev[2], st));
-        k_ksb_mul<<<k->batch, KB_SOLVE_THREADS, 0, st>>>(a);
+        if (k->per_inst) k_ksb_mul<true><<<k->batch, KB_SOLVE_THREADS, 0, st>>>(a);
+        else k_ksb_mul<false><<<k->batch, KB_SOLVE_THREADS, 0, st>>>(a);
         PQ_HIP(hipGetLastError());
         PQ_HIP(hipEventRecord(k->ev[3], st));
         ksb_vars_back(k, rhs, a.rhs, mem);
@@ -957,7 +1096,7 @@ int pq_kktsys_batch_state(pq_kktsys_batch* k, int what, double* out_host)
 {
     if (!k || !out_host) return fail(PQ_ERR_INVALID, "null argument");
     if (what < PQ_KKTSYS_BATCH_X_REG || what > PQ_KKTSYS_BATCH_RHS_Z_BAR) return fail(PQ_ERR_INVALID, "dense KKT system batch: state %d: 0 .. 3 wanted", what);
-    if (!k->kb->computed) return fail(PQ_ERR_INVALID, "dense KKT system batch: no factorisation yet");
+    if (!k->kb->computed || k->stale) return fail(PQ_ERR_INVALID, "dense KKT system batch: no factorisation yet");
     if (what >= PQ_KKTSYS_BATCH_RHS_X_BAR && !k->solved) return fail(PQ_ERR_INVALID, "dense KKT system batch: no solve yet");
     return guarded([&] {
         PQ_HIP(hipSetDevice(k->device));

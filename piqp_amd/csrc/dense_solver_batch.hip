@@ -30,8 +30,12 @@
 // update() (solver.hpp:218-308, orc_solver.c:357-384) runs where the data stand, on the backend's own Pu, AT, GT and the vectors here: k_dsb_unscale, the assignment
 // (k_dsb_ingest for a given matrix, copies for c and b, the bound vectors through the host logic of the lists), then k_dsb_ruiz -- with the stored scalings when
 // preconditioner_reuse_on_update is set or no matrix was given, else the equilibration from delta = 1 on the unscaled data.  Unscaling and rescaling do not give the
-// stored bits back: an update of c alone moves P, A' and G' by roundings, and the kernels run the oracle's multiplications in the oracle's order.  The finite-bound set
-// stays the setup's (it is baked into the KKT system and into `tab`); a call whose lists would differ is refused before anything is written.
+// stored bits back: an update of c alone moves P, A' and G' by roundings, and the kernels run the oracle's multiplications in the oracle's order.  With shared bound
+// sets (the default) the finite-bound set stays the setup's (it is baked into the KKT system and into `tab`); a call whose lists would differ is refused before
+// anything is written.  With PQ_BOUND_SETS_PER_INSTANCE (pq_solver_batch_set_bound_sets) every instance has lists of its own: `tab` has a row and `cnt_d` four counts
+// per instance (KbBounds; the kernels below are built twice, PER = false being the code of before, PER = true taking row and counts from the instance), and an update replaces the lists -- the unscaling still runs
+// on the old tables, everything after it on the new ones -- here and in the KKT system (pq_kktsys_batch_set_lists).  The host logic of the lists is ONE function for
+// both modes, setup and update: dsb_bound_lists.
 // ONE RULE IS NOT THE REFERENCE'S.  dense/kkt.hpp:62-71 (orc_dense.c:609-613) recomputes A'A only when A is given.  When P or G comes without A and the scalings are
 // recomputed, A' is rescaled with the new scalings and A'A stays that of the old ones: on the oracle this turns solvable problems into MAX_ITER_REACHED or
 // PRIMAL_INFEASIBLE.  Here A'A is recomputed from the rescaled A' when A is given, or when any matrix is given and preconditioner_reuse_on_update == 0; in every other
@@ -121,12 +125,12 @@ __device__ __forceinline__ double dsb_dot(const double* a, const double* b, int 
 
 // ---- the interior-point state machine
 struct DsbArgs {
-    int n, p, m, nhl, nhu, nxl, nxu, batch, trace_max, slot;
+    int n, p, m, batch, trace_max, slot;
+    KbBounds bd;                                          // the finite-bound tables: of the batch, or one row and four counts per instance
     pq_settings set;
     const double *Pu, *AT, *GT;                           // the backend's (scaled) data
     const double *c, *b, *h_l, *h_u, *x_l, *x_u, *xbs;    // scaled, [batch][len]
     const double *pd, *pdb, *pdi, *pdbi, *pc_inv;         // the preconditioner: delta [n + p + m], delta_b [n], their inverses, 1 / c
-    const int *has_l, *has_u, *xl_idx, *xu_idx;
     pq_vars r, nr, res, st, px;                           // result, res_nr, res, step, prox
     DsbState* state;
     double *rho, *delta;                                  // [batch]: what the factor launch reads
@@ -501,6 +505,7 @@ __device__ __forceinline__ int dsb_loop_head(const DsbCtx& C, const DsbArgs& A, 
     return WANT_FACTOR;
 }
 
+template <bool PER>
 __global__ __launch_bounds__(DSB_T) void k_dsb_advance(const DsbArgs A)
 {
     __shared__ DsbState S;
@@ -524,18 +529,19 @@ __global__ __launch_bounds__(DSB_T) void k_dsb_advance(const DsbArgs A)
     }
     const size_t on = (size_t)inst * n, op = (size_t)inst * p, om = (size_t)inst * m;
     const pq_settings& set = A.set;
+    const KbBounds R = kb_bound_row<PER>(A.bd, inst);
     DsbCtx C;
-    C.n = n; C.p = p; C.m = m; C.nxl = A.nxl; C.nxu = A.nxu; C.t = t;
-    C.cnt = (double)(A.nhl + A.nhu + A.nxl + A.nxu);
+    C.n = n; C.p = p; C.m = m; C.nxl = R.nxl; C.nxu = R.nxu; C.t = t;
+    C.cnt = (double)(R.nhl + R.nhu + R.nxl + R.nxu);
     C.ci = A.pc_inv[inst];
     C.Pu = A.Pu + inst * (size_t)n * n; C.AT = A.AT + inst * (size_t)n * p; C.GT = A.GT + inst * (size_t)n * m;
     C.c = A.c + on; C.b = A.b + op; C.h_l = A.h_l + om; C.h_u = A.h_u + om; C.x_l = A.x_l + on; C.x_u = A.x_u + on; C.xbs = A.xbs + on;
     C.pd = A.pd + (size_t)inst * (n + p + m); C.pdi = A.pdi + (size_t)inst * (n + p + m); C.pdb = A.pdb + on; C.pdbi = A.pdbi + on;
-    C.has_l = A.has_l; C.has_u = A.has_u; C.xl_idx = A.xl_idx; C.xu_idx = A.xu_idx;
+    C.has_l = R.has_l; C.has_u = R.has_u; C.xl_idx = R.xl_idx; C.xu_idx = R.xu_idx;
     C.r = dsb_at(A.r, on, op, om); C.nr = dsb_at(A.nr, on, op, om); C.res = dsb_at(A.res, on, op, om); C.st = dsb_at(A.st, on, op, om); C.px = dsb_at(A.px, on, op, om);
     C.S = &S; C.sc = sc; C.red = red;
     const DsbVars &r = C.r, &res = C.res, &st = C.st, &px = C.px;
-    const bool ineq = m + A.nxl + A.nxu > 0;
+    const bool ineq = m + R.nxl + R.nxu > 0;
     int want = WANT_DONE;
     bool to_loop = false;
     __syncthreads();
@@ -558,11 +564,11 @@ __global__ __launch_bounds__(DSB_T) void k_dsb_advance(const DsbArgs A)
             dsb_want_factor(&S);
         }
         for (int j = t; j < m; j += DSB_T) {
-            const double l = A.has_l[j] >= 0 ? 1.0 : 0.0, u = A.has_u[j] >= 0 ? 1.0 : 0.0;
+            const double l = R.has_l[j] >= 0 ? 1.0 : 0.0, u = R.has_u[j] >= 0 ? 1.0 : 0.0;
             r.s_l[j] = l; r.z_l[j] = l; r.s_u[j] = u; r.z_u[j] = u;
         }
-        for (int i = t; i < A.nxl; i += DSB_T) { r.s_bl[i] = 1.0; r.z_bl[i] = 1.0; }
-        for (int i = t; i < A.nxu; i += DSB_T) { r.s_bu[i] = 1.0; r.z_bu[i] = 1.0; }
+        for (int i = t; i < R.nxl; i += DSB_T) { r.s_bl[i] = 1.0; r.z_bl[i] = 1.0; }
+        for (int i = t; i < R.nxu; i += DSB_T) { r.s_bu[i] = 1.0; r.z_bu[i] = 1.0; }
         want = WANT_FACTOR;
     } else if (stage == ST_FACTOR0 || stage == ST_FACTOR) {
         const bool ok = A.fstatus[inst] == 0;
@@ -587,8 +593,8 @@ __global__ __launch_bounds__(DSB_T) void k_dsb_advance(const DsbArgs A)
             if (changed) dsb_update_r(C);
             if (ineq) {
                 for (int j = t; j < m; j += DSB_T) { res.s_l[j] = -r.s_l[j] * r.z_l[j]; res.s_u[j] = -r.s_u[j] * r.z_u[j]; }
-                for (int i = t; i < A.nxl; i += DSB_T) res.s_bl[i] = -r.s_bl[i] * r.z_bl[i];
-                for (int i = t; i < A.nxu; i += DSB_T) res.s_bu[i] = -r.s_bu[i] * r.z_bu[i];
+                for (int i = t; i < R.nxl; i += DSB_T) res.s_bl[i] = -r.s_bl[i] * r.z_bl[i];
+                for (int i = t; i < R.nxu; i += DSB_T) res.s_bu[i] = -r.s_bu[i] * r.z_bu[i];
             }
             if (t == 0) { S.stage = ineq ? ST_PRED : ST_NOINEQ; dsb_want_solve(&S); }
             want = WANT_SOLVE;
@@ -601,8 +607,8 @@ __global__ __launch_bounds__(DSB_T) void k_dsb_advance(const DsbArgs A)
                 for (int i = t; i < n; i += DSB_T) r.x[i] = st.x[i];
                 for (int j = t; j < p; j += DSB_T) r.y[j] = st.y[j];
                 for (int j = t; j < m; j += DSB_T) { r.z_l[j] = st.z_l[j]; r.z_u[j] = st.z_u[j]; r.s_l[j] = st.s_l[j]; r.s_u[j] = st.s_u[j]; }
-                for (int i = t; i < A.nxl; i += DSB_T) { r.z_bl[i] = st.z_bl[i]; r.s_bl[i] = st.s_bl[i]; }
-                for (int i = t; i < A.nxu; i += DSB_T) { r.z_bu[i] = st.z_bu[i]; r.s_bu[i] = st.s_bu[i]; }
+                for (int i = t; i < R.nxl; i += DSB_T) { r.z_bl[i] = st.z_bl[i]; r.s_bl[i] = st.s_bl[i]; }
+                for (int i = t; i < R.nxu; i += DSB_T) { r.z_bu[i] = st.z_bu[i]; r.s_bu[i] = st.s_bu[i]; }
             }
             __syncthreads();
             if (ineq) {
@@ -612,42 +618,42 @@ __global__ __launch_bounds__(DSB_T) void k_dsb_advance(const DsbArgs A)
                     mn[0] = dsb_dmin(mn[0], r.s_l[j]); mn[1] = dsb_dmin(mn[1], r.s_u[j]);
                     mn[4] = dsb_dmin(mn[4], r.z_l[j]); mn[5] = dsb_dmin(mn[5], r.z_u[j]);
                 }
-                for (int i = t; i < A.nxl; i += DSB_T) { mn[2] = dsb_dmin(mn[2], r.s_bl[i]); mn[6] = dsb_dmin(mn[6], r.z_bl[i]); }
-                for (int i = t; i < A.nxu; i += DSB_T) { mn[3] = dsb_dmin(mn[3], r.s_bu[i]); mn[7] = dsb_dmin(mn[7], r.z_bu[i]); }
+                for (int i = t; i < R.nxl; i += DSB_T) { mn[2] = dsb_dmin(mn[2], r.s_bl[i]); mn[6] = dsb_dmin(mn[6], r.z_bl[i]); }
+                for (int i = t; i < R.nxu; i += DSB_T) { mn[3] = dsb_dmin(mn[3], r.s_bu[i]); mn[7] = dsb_dmin(mn[7], r.z_bu[i]); }
                 const int opm[8] = {R_MIN, R_MIN, R_MIN, R_MIN, R_MIN, R_MIN, R_MIN, R_MIN};
                 dsb_reduce<8>(mn, opm, red);
                 double delta_s = 0.0, delta_z = 0.0;
                 if (m > 0) { delta_s = dsb_dmax(delta_s, -mn[0]); delta_s = dsb_dmax(delta_s, -mn[1]); }
-                if (A.nxl > 0) delta_s = dsb_dmax(delta_s, -mn[2]);
-                if (A.nxu > 0) delta_s = dsb_dmax(delta_s, -mn[3]);
+                if (R.nxl > 0) delta_s = dsb_dmax(delta_s, -mn[2]);
+                if (R.nxu > 0) delta_s = dsb_dmax(delta_s, -mn[3]);
                 if (m > 0) { delta_z = dsb_dmax(delta_z, -mn[4]); delta_z = dsb_dmax(delta_z, -mn[5]); }
-                if (A.nxl > 0) delta_z = dsb_dmax(delta_z, -mn[6]);
-                if (A.nxu > 0) delta_z = dsb_dmax(delta_z, -mn[7]);
+                if (R.nxl > 0) delta_z = dsb_dmax(delta_z, -mn[6]);
+                if (R.nxu > 0) delta_z = dsb_dmax(delta_z, -mn[7]);
                 for (int j = t; j < m; j += DSB_T) {
-                    if (A.has_l[j] >= 0) { r.s_l[j] += delta_s; r.z_l[j] += delta_z; }
-                    if (A.has_u[j] >= 0) { r.s_u[j] += delta_s; r.z_u[j] += delta_z; }
+                    if (R.has_l[j] >= 0) { r.s_l[j] += delta_s; r.z_l[j] += delta_z; }
+                    if (R.has_u[j] >= 0) { r.s_u[j] += delta_s; r.z_u[j] += delta_z; }
                 }
-                for (int i = t; i < A.nxl; i += DSB_T) { r.s_bl[i] += delta_s; r.z_bl[i] += delta_z; }
-                for (int i = t; i < A.nxu; i += DSB_T) { r.s_bu[i] += delta_s; r.z_bu[i] += delta_z; }
+                for (int i = t; i < R.nxl; i += DSB_T) { r.s_bl[i] += delta_s; r.z_bl[i] += delta_z; }
+                for (int i = t; i < R.nxu; i += DSB_T) { r.s_bu[i] += delta_s; r.z_bu[i] += delta_z; }
                 double mu = dsb_dmax(dsb_mu(C), 1e-10);
                 for (int j = t; j < m; j += DSB_T) {
-                    if (A.has_l[j] >= 0) {
+                    if (R.has_l[j] >= 0) {
                         const double c = r.z_l[j] - delta_z;
                         r.z_l[j] = (c + sqrt(c * c + 4 * mu)) / 2;
                         r.s_l[j] = r.z_l[j] - c;
                     }
-                    if (A.has_u[j] >= 0) {
+                    if (R.has_u[j] >= 0) {
                         const double c = r.z_u[j] - delta_z;
                         r.z_u[j] = (c + sqrt(c * c + 4 * mu)) / 2;
                         r.s_u[j] = r.z_u[j] - c;
                     }
                 }
-                for (int i = t; i < A.nxl; i += DSB_T) {
+                for (int i = t; i < R.nxl; i += DSB_T) {
                     const double c = r.z_bl[i] - delta_z;
                     r.z_bl[i] = (c + sqrt(c * c + 4 * mu)) / 2;
                     r.s_bl[i] = r.z_bl[i] - c;
                 }
-                for (int i = t; i < A.nxu; i += DSB_T) {
+                for (int i = t; i < R.nxu; i += DSB_T) {
                     const double c = r.z_bu[i] - delta_z;
                     r.z_bu[i] = (c + sqrt(c * c + 4 * mu)) / 2;
                     r.s_bu[i] = r.z_bu[i] - c;
@@ -658,8 +664,8 @@ __global__ __launch_bounds__(DSB_T) void k_dsb_advance(const DsbArgs A)
             for (int i = t; i < n; i += DSB_T) px.x[i] = r.x[i];
             for (int j = t; j < p; j += DSB_T) px.y[j] = r.y[j];
             for (int j = t; j < m; j += DSB_T) { px.z_l[j] = r.z_l[j]; px.z_u[j] = r.z_u[j]; }
-            for (int i = t; i < A.nxl; i += DSB_T) px.z_bl[i] = r.z_bl[i];
-            for (int i = t; i < A.nxu; i += DSB_T) px.z_bu[i] = r.z_bu[i];
+            for (int i = t; i < R.nxl; i += DSB_T) px.z_bl[i] = r.z_bl[i];
+            for (int i = t; i < R.nxu; i += DSB_T) px.z_bu[i] = r.z_bu[i];
             to_loop = true;
         } else if (stage == ST_PRED) {  // :854-879
             double alpha_s, alpha_z;
@@ -671,7 +677,7 @@ __global__ __launch_bounds__(DSB_T) void k_dsb_advance(const DsbArgs A)
                 const double* s1 = t == 0 ? st.s_l : t == 1 ? st.s_u : t == 2 ? st.s_bl : st.s_bu;
                 const double* z0 = t == 0 ? r.z_l : t == 1 ? r.z_u : t == 2 ? r.z_bl : r.z_bu;
                 const double* z1 = t == 0 ? st.z_l : t == 1 ? st.z_u : t == 2 ? st.z_bl : st.z_bu;
-                const int len = t < 2 ? m : t == 2 ? A.nxl : t == 3 ? A.nxu : 0;
+                const int len = t < 2 ? m : t == 2 ? R.nxl : t == 3 ? R.nxu : 0;
                 double acc = 0.0;
                 for (int i = 0; i < len; ++i) acc += (s0[i] + alpha_s * s1[i]) * (z0[i] + alpha_z * z1[i]);
                 if (t < 4) sc[t] = acc;
@@ -689,8 +695,8 @@ __global__ __launch_bounds__(DSB_T) void k_dsb_advance(const DsbArgs A)
             __syncthreads();
             if (t == 0) { S.info.sigma = sigma; S.stage = ST_CORR; dsb_want_solve(&S); }
             for (int j = t; j < m; j += DSB_T) { res.s_l[j] += -st.s_l[j] * st.z_l[j] + sm; res.s_u[j] += -st.s_u[j] * st.z_u[j] + sm; }
-            for (int i = t; i < A.nxl; i += DSB_T) res.s_bl[i] += -st.s_bl[i] * st.z_bl[i] + sm;
-            for (int i = t; i < A.nxu; i += DSB_T) res.s_bu[i] += -st.s_bu[i] * st.z_bu[i] + sm;
+            for (int i = t; i < R.nxl; i += DSB_T) res.s_bl[i] += -st.s_bl[i] * st.z_bl[i] + sm;
+            for (int i = t; i < R.nxu; i += DSB_T) res.s_bu[i] += -st.s_bu[i] * st.z_bu[i] + sm;
             want = WANT_SOLVE;
         } else {  // ST_CORR :882-924, ST_NOINEQ :929-948
             double ps = 1.0, ds = 1.0;
@@ -707,8 +713,8 @@ __global__ __launch_bounds__(DSB_T) void k_dsb_advance(const DsbArgs A)
             double mu_rate = 0.0;
             if (stage == ST_CORR) {
                 for (int j = t; j < m; j += DSB_T) { r.z_l[j] += ds * st.z_l[j]; r.z_u[j] += ds * st.z_u[j]; r.s_l[j] += ps * st.s_l[j]; r.s_u[j] += ps * st.s_u[j]; }
-                for (int i = t; i < A.nxl; i += DSB_T) { r.z_bl[i] += ds * st.z_bl[i]; r.s_bl[i] += ps * st.s_bl[i]; }
-                for (int i = t; i < A.nxu; i += DSB_T) { r.z_bu[i] += ds * st.z_bu[i]; r.s_bu[i] += ps * st.s_bu[i]; }
+                for (int i = t; i < R.nxl; i += DSB_T) { r.z_bl[i] += ds * st.z_bl[i]; r.s_bl[i] += ps * st.s_bl[i]; }
+                for (int i = t; i < R.nxu; i += DSB_T) { r.z_bu[i] += ds * st.z_bu[i]; r.s_bu[i] += ps * st.s_bu[i]; }
                 __syncthreads();
                 const double mu_prev = S.info.mu;
                 const double mu = dsb_mu(C);
@@ -746,8 +752,8 @@ __global__ __launch_bounds__(DSB_T) void k_dsb_advance(const DsbArgs A)
                 for (int j = t; j < p; j += DSB_T) px.y[j] = r.y[j];
                 if (stage == ST_CORR) {
                     for (int j = t; j < m; j += DSB_T) { px.z_l[j] = r.z_l[j]; px.z_u[j] = r.z_u[j]; }
-                    for (int i = t; i < A.nxl; i += DSB_T) px.z_bl[i] = r.z_bl[i];
-                    for (int i = t; i < A.nxu; i += DSB_T) px.z_bu[i] = r.z_bu[i];
+                    for (int i = t; i < R.nxl; i += DSB_T) px.z_bl[i] = r.z_bl[i];
+                    for (int i = t; i < R.nxu; i += DSB_T) px.z_bu[i] = r.z_bu[i];
                 }
             }
             to_loop = true;
@@ -770,17 +776,19 @@ __global__ __launch_bounds__(DSB_T) void k_dsb_advance(const DsbArgs A)
 
 // ---- unscale_results and restore_dual :956-986, into the result arrays (full length, boxes expanded)
 struct DsbFinishArgs {
-    int n, p, m, nxl, nxu;
+    int n, p, m;
+    KbBounds bd;
     const double *pd, *pdb, *pdi, *pdbi, *pc_inv;
-    const int *xl_idx, *xu_idx;
     pq_vars r, out;
 };
+template <bool PER>
 __global__ __launch_bounds__(DSB_T) void k_dsb_finish(const DsbFinishArgs A)
 {
     const long long inst = blockIdx.x;
     const int t = threadIdx.x, n = A.n, p = A.p, m = A.m;
     const size_t on = (size_t)inst * n, op = (size_t)inst * p, om = (size_t)inst * m;
     const DsbVars r = dsb_at(A.r, on, op, om), o = dsb_at(A.out, on, op, om);
+    const KbBounds R = kb_bound_row<PER>(A.bd, inst);
     const double* pd = A.pd + (size_t)inst * (n + p + m);
     const double* pdi = A.pdi + (size_t)inst * (n + p + m);
     const double ci = A.pc_inv[inst];
@@ -797,13 +805,13 @@ __global__ __launch_bounds__(DSB_T) void k_dsb_finish(const DsbFinishArgs A)
         o.s_u[j] = zu == 0 ? DSB_INF : r.s_u[j] * pdi[n + p + j];
     }
     __syncthreads();
-    for (int i = t; i < A.nxl; i += DSB_T) {
-        const int idx = A.xl_idx[i];
+    for (int i = t; i < R.nxl; i += DSB_T) {
+        const int idx = R.xl_idx[i];
         o.z_bl[idx] = r.z_bl[i] * ci * A.pdb[on + idx];
         o.s_bl[idx] = r.s_bl[i] * A.pdbi[on + idx];
     }
-    for (int i = t; i < A.nxu; i += DSB_T) {
-        const int idx = A.xu_idx[i];
+    for (int i = t; i < R.nxu; i += DSB_T) {
+        const int idx = R.xu_idx[i];
         o.z_bu[idx] = r.z_bu[i] * ci * A.pdb[on + idx];
         o.s_bu[idx] = r.s_bu[i] * A.pdbi[on + idx];
     }
@@ -833,11 +841,13 @@ __global__ void k_dsb_ingest(const double* __restrict__ src, double* __restrict_
 // ---- RuizEquilibration::unscale_data, dense (orc_solver.c:243-256), one workgroup per instance, in place: the first step of an update
 // dead: null, or [batch][m]: the columns of G' that disable_inf_constraints zeroes in this update (a row whose two bounds are both given infinite)
 struct DsbUnscaleArgs {
-    int n, p, m, nxl, nxu;
+    int n, p, m;
+    KbBounds bd;  // the tables as they stood BEFORE this update: the stored box vectors are packed to them
     double *Pu, *AT, *GT, *c, *b, *h_l, *h_u, *x_l, *x_u, *xbs;
     const double *pdi, *pdbi, *pc_inv;
-    const int *xl_idx, *xu_idx, *dead;
+    const int* dead;
 };
+template <bool PER>
 __global__ __launch_bounds__(DSB_RUIZ_T) void k_dsb_unscale(const DsbUnscaleArgs A)
 {
     const long long inst = blockIdx.x;
@@ -850,6 +860,7 @@ __global__ __launch_bounds__(DSB_RUIZ_T) void k_dsb_unscale(const DsbUnscaleArgs
     const double *di = A.pdi + inst * (size_t)N, *dib = A.pdbi + inst * (size_t)n;
     const int* dead = A.dead ? A.dead + inst * (size_t)m : nullptr;
     const double ci = A.pc_inv[inst];
+    const KbBounds R = kb_bound_row<PER>(A.bd, inst);
     for (int e = t; e < n * n; e += T) {  // scale_P_scalar, then scale_P: the column pass, the row pass (the lower triangle is zero and stays zero)
         const int i = e % n, j = e / n;
         if (i <= j) P[e] = ((P[e] * ci) * di[j]) * di[i];
@@ -861,23 +872,28 @@ __global__ __launch_bounds__(DSB_RUIZ_T) void k_dsb_unscale(const DsbUnscaleArgs
     for (int e = t; e < n * p; e += T) AT[e] = (di[e % n] * AT[e]) * di[n + e / n];
     for (size_t e = t; e < (size_t)n * m; e += T) GT[e] = dead && dead[e / n] ? 0.0 : (di[e % n] * GT[e]) * di[n + p + e / n];
     for (int i = t; i < p; i += T) b[i] = b[i] * di[n + i];
-    for (int i = t; i < m; i += T) { h_l[i] = h_l[i] * di[n + p + i]; h_u[i] = h_u[i] * di[n + p + i]; }
-    for (int i = t; i < A.nxl; i += T) x_l[i] = x_l[i] * dib[A.xl_idx[i]];
-    for (int i = t; i < A.nxu; i += T) x_u[i] = x_u[i] * dib[A.xu_idx[i]];
+    for (int i = t; i < m; i += T) {  // (a row dropped in this update: -1 / 1 on both sides, also on the side the caller did not give)
+        const bool dd = dead && dead[i];
+        h_l[i] = dd ? -1.0 : h_l[i] * di[n + p + i];
+        h_u[i] = dd ? 1.0 : h_u[i] * di[n + p + i];
+    }
+    for (int i = t; i < R.nxl; i += T) x_l[i] = x_l[i] * dib[R.xl_idx[i]];
+    for (int i = t; i < R.nxu; i += T) x_u[i] = x_u[i] * dib[R.xu_idx[i]];
 }
 
 // ---- RuizEquilibration::scale_data, dense (orc_solver.c:136-240), one workgroup per instance, in place.  reuse = 0: the equilibration from delta = 1 (a setup; an
 // update that gave a matrix with preconditioner_reuse_on_update off: xbs is read as it stands).  reuse = 1: the stored scalings are applied (:229-235) and they, their
 // inverses and c stay untouched.  Both end in the one tail :236-239.
 struct DsbRuizArgs {
-    int n, p, m, nxl, nxu, max_iter, scale_cost, reuse;
+    int n, p, m, max_iter, scale_cost, reuse;
+    KbBounds bd;
     double epsilon;
     double *Pu, *AT, *GT, *c, *b, *h_l, *h_u, *x_l, *x_u, *xbs;
     double *pd, *pdb, *pdi, *pdbi, *pc, *pc_inv;
-    const int *xl_idx, *xu_idx;
 };
 __device__ __forceinline__ double dsb_limit_scaling(double d) { return d < 1e-4 ? 1.0 : (d > 1e4 ? 1e4 : d); }
 
+template <bool PER>
 __global__ __launch_bounds__(DSB_RUIZ_T) void k_dsb_ruiz(const DsbRuizArgs A)
 {
     __shared__ double red[DSB_RED];
@@ -891,6 +907,7 @@ __global__ __launch_bounds__(DSB_RUIZ_T) void k_dsb_ruiz(const DsbRuizArgs A)
     double *c = A.c + inst * (size_t)n, *b = A.b + inst * (size_t)p, *h_l = A.h_l + inst * (size_t)m, *h_u = A.h_u + inst * (size_t)m;
     double *x_l = A.x_l + inst * (size_t)n, *x_u = A.x_u + inst * (size_t)n, *xbs = A.xbs + inst * (size_t)n;
     double *delta = A.pd + inst * (size_t)N, *di = A.pdi + inst * (size_t)N, *delta_b = A.pdb + inst * (size_t)n, *dib = A.pdbi + inst * (size_t)n;
+    const KbBounds R = kb_bound_row<PER>(A.bd, inst);
     double rc = 1.0;
     if (A.reuse) {
         rc = A.pc[inst];
@@ -988,8 +1005,8 @@ __global__ __launch_bounds__(DSB_RUIZ_T) void k_dsb_ruiz(const DsbRuizArgs A)
     }
     for (int i = t; i < p; i += T) b[i] = b[i] * delta[n + i];
     for (int i = t; i < m; i += T) { h_l[i] = h_l[i] * delta[n + p + i]; h_u[i] = h_u[i] * delta[n + p + i]; }
-    for (int i = t; i < A.nxl; i += T) x_l[i] = x_l[i] * delta_b[A.xl_idx[i]];
-    for (int i = t; i < A.nxu; i += T) x_u[i] = x_u[i] * delta_b[A.xu_idx[i]];
+    for (int i = t; i < R.nxl; i += T) x_l[i] = x_l[i] * delta_b[R.xl_idx[i]];
+    for (int i = t; i < R.nxu; i += T) x_u[i] = x_u[i] * delta_b[R.xu_idx[i]];
 }
 
 // settings.hpp:84-106 verify_settings
@@ -1025,13 +1042,21 @@ struct VarSet {
 // everything a setup creates
 struct DsbProblem {
     int batch = 0, n = 0, p = 0, m = 0, trace_max = 0;
-    int cnt[4] = {0, 0, 0, 0};
-    std::vector<int> idx[4];
+    // the finite-bound sets (dense/data.hpp:98-207, dsb_bound_lists): `rows` = 1 set shared by the batch, or one per instance.  Host images, sized by the setup:
+    bool per_inst = false;
+    int rows = 1;
+    std::vector<int> cnt_h;      // [rows][4]: n_h_l, n_h_u, n_x_l, n_x_u
+    std::vector<int> lists_h;    // four arrays [rows][m], [rows][m], [rows][n], [rows][n] one after the other: the lists, meaningful in their first cnt entries
+    std::vector<int> fin_h;      // the same four arrays as flags: the stored vector is finite at this place (a dropped row: on both sides)
+    std::vector<int> tab_h;      // [rows] rows of `tab`
+    std::vector<int> try_h;      // 2 m + 2 n + 4: the lists and counts of one instance while they are compared with the shared ones
+    std::vector<int> dead_h;     // [batch][m]
+    std::vector<int> keep_h;     // per instance only: cnt_h and lists_h as they stood before an update, put back if the update fails on its way
     VarSet sets[6];  // result, res_nr, res, step, prox, the results handed out
     DBuf<double> c, b, h_l, h_u, x_l, x_u, xbs, pd, pdb, pdi, pdbi, pc, pc_inv, rho, delta, trace;
-    DBuf<int> tab, flags, act, counters;
-    // what an update needs and only a setup may allocate: the staging of a host-fed matrix, the mask of the rows an update drops ([batch][m]; a setup uses the
-    // first m), and pinned room for the four bound vectors as fetched and as packed (2 batch (2 m + 2 n) doubles)
+    DBuf<int> tab, cnt_d, flags, act, counters;  // tab: has_l[m], has_u[m], x_l_idx, x_u_idx (KbBounds without pos_*); cnt_d: [batch][4], per instance only
+    // what an update needs and only a setup may allocate: the staging of a host-fed matrix, the mask of the rows an update drops ([batch][m]; a setup with shared
+    // sets uses the first m), and pinned room for the four bound vectors as fetched and as packed (2 batch (2 m + 2 n) doubles)
     DBuf<double> raw;
     DBuf<int> dead_d;
     HBuf<double> bnd_h;
@@ -1040,10 +1065,41 @@ struct DsbProblem {
     HBuf<int> counters_h;
     Event ev[8];  // advance, factor, solve, finish: begin / end
     std::unique_ptr<pq_kktsys_batch, KsDeleter> ks;  // last: destroyed first, which drains the one stream everything here runs on
-    const int* has_l() const { return tab.p; }
-    const int* has_u() const { return tab.p + m; }
-    const int* xl_idx() const { return tab.p + 2 * (size_t)m; }
-    const int* xu_idx() const { return tab.p + 2 * (size_t)m + cnt[2]; }
+    size_t tab_stride() const { return 2 * (size_t)m + (per_inst ? 2 * (size_t)n : (size_t)cnt_h[2] + (size_t)cnt_h[3]); }
+    int* list(int k, size_t row) { return lists_h.data() + (k == 0 ? 0 : k == 1 ? (size_t)rows * m : k == 2 ? 2 * (size_t)rows * m : 2 * (size_t)rows * m + (size_t)rows * n) + row * (k < 2 ? m : n); }
+    int* fin(int k, size_t row) { return fin_h.data() + (list(k, row) - lists_h.data()); }
+    KbBounds bounds() const
+    {
+        KbBounds b;
+        b.has_l = tab.p; b.has_u = b.has_l + m; b.pos_l = b.pos_u = tab.p;  // (never read: the solver's kernels do not ask where a variable stands in a box list)
+        b.xl_idx = b.has_u + m; b.xu_idx = b.xl_idx + (per_inst ? n : cnt_h[2]);
+        b.nhl = cnt_h[0]; b.nhu = cnt_h[1]; b.nxl = cnt_h[2]; b.nxu = cnt_h[3];  // (used with shared sets only)
+        b.cnt = per_inst ? cnt_d.p : nullptr;
+        b.stride = per_inst ? (int)tab_stride() : 0;
+        return b;
+    }
+    // has_l, has_u and the two box lists of every row of tab_h from lists_h and cnt_h
+    void fill_tab()
+    {
+        const size_t stride = tab_stride();
+        std::fill(tab_h.begin(), tab_h.end(), -1);
+        for (int r = 0; r < rows; ++r) {
+            const int* c = cnt_h.data() + 4 * (size_t)r;
+            int* t = tab_h.data() + r * stride;
+            for (int e = 0; e < c[0]; ++e) t[list(0, r)[e]] = e;
+            for (int e = 0; e < c[1]; ++e) t[(size_t)m + list(1, r)[e]] = e;
+            std::copy(list(2, r), list(2, r) + c[2], t + 2 * (size_t)m);
+            std::copy(list(3, r), list(3, r) + c[3], t + 2 * (size_t)m + (per_inst ? n : c[2]));
+        }
+    }
+    // the lists as flags
+    void fill_fin()
+    {
+        std::fill(fin_h.begin(), fin_h.end(), 0);
+        for (int r = 0; r < rows; ++r)
+            for (int k = 0; k < 4; ++k)
+                for (int e = 0; e < cnt_h[4 * (size_t)r + k]; ++e) fin(k, r)[list(k, r)[e]] = 1;
+    }
 };
 
 }  // namespace
@@ -1056,6 +1112,7 @@ struct pq_solver_batch {
     int device = 0;
     pq_settings settings;
     int trace_max = 0;
+    int bound_sets = PQ_BOUND_SETS_SHARED;  // read by the next setup
     bool solved = false, updated = false;
     double update_wall_ms = 0.0, update_device_ms = 0.0;
     double wall_ms = 0.0, device_ms = 0.0, factor_ms = 0.0, solve_ms = 0.0;
@@ -1105,14 +1162,60 @@ void dsb_matrix(DsbProblem* q, hipStream_t st, const double* src, double* dst, i
 void dsb_launch_ruiz(const pq_solver_batch* s, DsbProblem* q, hipStream_t st, double* Pu, double* AT, double* GT, int reuse)
 {
     DsbRuizArgs r;
-    r.n = q->n; r.p = q->p; r.m = q->m; r.nxl = q->cnt[2]; r.nxu = q->cnt[3]; r.max_iter = s->settings.preconditioner_iter; r.scale_cost = s->settings.preconditioner_scale_cost;
+    r.n = q->n; r.p = q->p; r.m = q->m; r.bd = q->bounds(); r.max_iter = s->settings.preconditioner_iter; r.scale_cost = s->settings.preconditioner_scale_cost;
     r.reuse = reuse;
     r.epsilon = 1e-3;
     r.Pu = Pu; r.AT = AT; r.GT = GT; r.c = q->c.p; r.b = q->b.p; r.h_l = q->h_l.p; r.h_u = q->h_u.p; r.x_l = q->x_l.p; r.x_u = q->x_u.p; r.xbs = q->xbs.p;
     r.pd = q->pd.p; r.pdb = q->pdb.p; r.pdi = q->pdi.p; r.pdbi = q->pdbi.p; r.pc = q->pc.p; r.pc_inv = q->pc_inv.p;
-    r.xl_idx = q->xl_idx(); r.xu_idx = q->xu_idx();
-    k_dsb_ruiz<<<q->batch, DSB_RUIZ_T, 0, st>>>(r);
+    if (q->per_inst) k_dsb_ruiz<true><<<q->batch, DSB_RUIZ_T, 0, st>>>(r);
+    else k_dsb_ruiz<false><<<q->batch, DSB_RUIZ_T, 0, st>>>(r);
     PQ_HIP(hipGetLastError());
+}
+
+// ---- the host logic of dense/data.hpp:98-207 for ONE instance: set_h_l, set_h_u, disable_inf_constraints, set_x_l, set_x_u.  The one copy: setup and update call it
+// in both modes of the bound sets, pq_debug_bound_lists hands it out.
+//   h_l, h_u [m], x_l, x_u [n]: what the caller gave, any may be null.
+//   fin: null for a setup, where a vector that is not given is infinite everywhere.  For an update the four flag vectors of the data as stored ([m], [m], [n], [n]):
+//        1 = in the list (a row dropped earlier is stored as -1 / 1, in both lists), 0 = infinite.  A vector that is not given keeps what is stored.
+//        ONE RULE IS NOT THE REFERENCE'S: a stored infinite bound IS infinite here.  The reference stores it as -/+ 1e30, scales it with its row and un-scales it at
+//        the next update, and (1e30 d) (1 / d) may round to the neighbour of 1e30; disable_inf_constraints compares that NUMBER, so when h_l or h_u comes alone and
+//        is infinite on a row whose other side is stored infinite, the reference drops the row or -- by the rounding of that product -- leaves it in neither
+//        list, a row without a bound that turns its solves into NaN.  Here the row is dropped.
+//   cnt[4], idx[4] ([m], [m], [n], [n]): the counts and the ascending lists.  dead [m]: the rows disable_inf_constraints drops in this call -- both bounds infinite, a
+//        given one or a stored one; the row of G is zeroed and the bounds become -1 / 1, so the row is in both lists.  Without h_l and h_u an update does not look at
+//        the rows: nothing is dropped.
+//   packed[4] ([m], [m], [n], [n]): the vectors as the reference stores them.  A given h vector (every one in a setup) is written at full length: the value, -1 / 1 on a
+//        dropped row, -/+ 1e30 where infinite.  An h vector an update does not give is written on the rows dropped in this call only.  A given box vector (every one in a
+//        setup) is written at full length: the finite values in list order, then zeros; one an update does not give is not touched.
+// idx, dead, packed and their entries may be null: that output is not wanted.
+void dsb_bound_lists(int m, int n, const double* h_l, const double* h_u, const double* x_l, const double* x_u, const int* const* fin, int cnt[4], int* const* idx, int* dead,
+                     double* const* packed)
+{
+    const bool setup = !fin, rows = setup || h_l || h_u;
+    cnt[0] = cnt[1] = cnt[2] = cnt[3] = 0;
+    for (int j = 0; j < m; ++j) {
+        const bool fl = h_l ? h_l[j] > -DSB_INF : (!setup && fin[0][j] != 0), fu = h_u ? h_u[j] < DSB_INF : (!setup && fin[1][j] != 0);
+        const bool dd = rows && !fl && !fu;
+        const bool in_l = fl || dd, in_u = fu || dd;
+        if (dead) dead[j] = dd;
+        if (in_l) { if (idx && idx[0]) idx[0][cnt[0]] = j; ++cnt[0]; }
+        if (in_u) { if (idx && idx[1]) idx[1][cnt[1]] = j; ++cnt[1]; }
+        if (packed && packed[0] && (setup || h_l || dd)) packed[0][j] = dd ? -1.0 : fl ? h_l[j] : -DSB_INF;
+        if (packed && packed[1] && (setup || h_u || dd)) packed[1][j] = dd ? 1.0 : fu ? h_u[j] : DSB_INF;
+    }
+    for (int k = 2; k < 4; ++k) {
+        const double* v = k == 2 ? x_l : x_u;
+        double* out = packed ? packed[k] : nullptr;
+        for (int j = 0; j < n; ++j) {
+            const bool f = v ? (k == 2 ? v[j] > -DSB_INF : v[j] < DSB_INF) : (!setup && fin[k][j] != 0);
+            if (!f) continue;
+            if (idx && idx[k]) idx[k][cnt[k]] = j;
+            if (out && v) out[cnt[k]] = v[j];
+            ++cnt[k];
+        }
+        if (out && (setup || v))
+            for (int j = cnt[k]; j < n; ++j) out[j] = 0.0;
+    }
 }
 
 void dsb_reset_state(pq_solver_batch* s)
@@ -1168,6 +1271,30 @@ int pq_solver_batch_set_trace(pq_solver_batch* s, int max_rows)
     return PQ_OK;
 }
 
+int pq_solver_batch_set_bound_sets(pq_solver_batch* s, int mode)
+{
+    if (!s) return fail(PQ_ERR_INVALID, "null argument");
+    if (mode != PQ_BOUND_SETS_SHARED && mode != PQ_BOUND_SETS_PER_INSTANCE)
+        return fail(PQ_ERR_INVALID, "dense solver batch: bound sets %d: PQ_BOUND_SETS_SHARED or PQ_BOUND_SETS_PER_INSTANCE wanted", mode);
+    s->bound_sets = mode;  // (a problem that is set up keeps the mode its setup read)
+    return PQ_OK;
+}
+
+int pq_debug_bound_lists(int m, int n, const double* h_l, const double* h_u, const double* x_l, const double* x_u, const int* fin_h_l, const int* fin_h_u, const int* fin_x_l,
+                         const int* fin_x_u, int counts[4], int* h_l_idx, int* h_u_idx, int* x_l_idx, int* x_u_idx, int* dead, double* h_l_out, double* h_u_out, double* x_l_out,
+                         double* x_u_out)
+{
+    if (m < 0 || n < 1 || !counts) return fail(PQ_ERR_INVALID, "bound lists: m = %d, n = %d, counts %s: m >= 0, n >= 1 and counts wanted", m, n, counts ? "given" : "null");
+    const bool any = fin_h_l || fin_h_u || fin_x_l || fin_x_u;
+    if (any && ((m > 0 && (!fin_h_l || !fin_h_u)) || !fin_x_l || !fin_x_u))
+        return fail(PQ_ERR_INVALID, "bound lists: the stored flags of an update are four vectors, or none for a setup");
+    const int* fin[4] = {fin_h_l, fin_h_u, fin_x_l, fin_x_u};
+    int* idx[4] = {h_l_idx, h_u_idx, x_l_idx, x_u_idx};
+    double* packed[4] = {h_l_out, h_u_out, x_l_out, x_u_out};
+    dsb_bound_lists(m, n, h_l, h_u, x_l, x_u, any ? fin : nullptr, counts, idx, dead, packed);
+    return PQ_OK;
+}
+
 int pq_solver_batch_setup_dense(pq_solver_batch* s, int batch, int n, int p, int m, const double* P, const double* c, const double* A, const double* b, const double* G,
                                 const double* h_l, const double* h_u, const double* x_l, const double* x_u, int mem, int order)
 {
@@ -1187,7 +1314,7 @@ int pq_solver_batch_setup_dense(pq_solver_batch* s, int batch, int n, int p, int
     return guarded([&] {
         PQ_HIP(hipSetDevice(s->device));
         const size_t B = (size_t)batch, N = (size_t)n + p + m;
-        // the vectors on the host: the finite-bound lists are host logic (dense/data.hpp:98-207), shared by the batch
+        // the vectors on the host: the finite-bound lists are host logic (dsb_bound_lists), one set for the batch or one per instance
         auto fetch = [&](const double* src, size_t len) {
             std::vector<double> v;
             if (!src || !len) return v;
@@ -1197,52 +1324,44 @@ int pq_solver_batch_setup_dense(pq_solver_batch* s, int batch, int n, int p, int
         };
         std::vector<double> hc = fetch(c, n), hb = fetch(b, p), hhl = fetch(h_l, m), hhu = fetch(h_u, m), hxl = fetch(x_l, n), hxu = fetch(x_u, n);
         if (hb.empty()) hb.assign(B * p, 0.0);
-        std::vector<char> fl(m, 0), fu(m, 0), bl(n, 0), bu(n, 0);
-        for (size_t i = 0; i < B; ++i)
-            for (int q = 0; q < 4; ++q) {
-                const std::vector<double>& v = q == 0 ? hhl : q == 1 ? hhu : q == 2 ? hxl : hxu;
-                std::vector<char>& f = q == 0 ? fl : q == 1 ? fu : q == 2 ? bl : bu;
-                const size_t len = q < 2 ? m : n;
-                for (size_t j = 0; j < len; ++j) {
-                    const bool finite = !v.empty() && ((q & 1) ? v[i * len + j] < DSB_INF : v[i * len + j] > -DSB_INF);
-                    if (i == 0) f[j] = finite;
-                    else if ((bool)f[j] != finite) throw std::runtime_error("dense solver batch: the set of finite bounds differs from the one of instance 0 (it is shared by the batch)");
-                }
-            }
         std::unique_ptr<DsbProblem> q(new DsbProblem);
         q->batch = batch; q->n = n; q->p = p; q->m = m; q->trace_max = s->trace_max;
-        std::vector<int> dead(m, 0), tab((size_t)2 * m, -1);
-        for (int j = 0; j < m; ++j) {
-            dead[j] = !fl[j] && !fu[j];  // disable_inf_constraints: the row of G is zeroed, its bounds become -1 / 1
-            if (fl[j] || dead[j]) { tab[j] = (int)q->idx[0].size(); q->idx[0].push_back(j); }
-            if (fu[j] || dead[j]) { tab[(size_t)m + j] = (int)q->idx[1].size(); q->idx[1].push_back(j); }
-        }
-        for (int j = 0; j < n; ++j) {
-            if (bl[j]) q->idx[2].push_back(j);
-            if (bu[j]) q->idx[3].push_back(j);
-        }
-        for (int k = 0; k < 4; ++k) q->cnt[k] = (int)q->idx[k].size();
-        tab.insert(tab.end(), q->idx[2].begin(), q->idx[2].end());
-        tab.insert(tab.end(), q->idx[3].begin(), q->idx[3].end());
+        q->per_inst = s->bound_sets == PQ_BOUND_SETS_PER_INSTANCE;
+        const int R = q->rows = q->per_inst ? batch : 1;
+        q->cnt_h.assign(4 * (size_t)R, 0); q->lists_h.assign((size_t)R * (2 * (size_t)m + 2 * (size_t)n), 0); q->fin_h.assign(q->lists_h.size(), 0);
+        q->try_h.assign(2 * (size_t)m + 2 * (size_t)n + 4, 0); q->dead_h.assign(B * m, 0);
+        if (q->per_inst) q->keep_h.assign(q->cnt_h.size() + q->lists_h.size(), 0);
         std::vector<double> vhl(B * m), vhu(B * m), vxl(B * n, 0.0), vxu(B * n, 0.0);
         for (size_t i = 0; i < B; ++i) {
-            for (int j = 0; j < m; ++j) {
-                vhl[i * m + j] = dead[j] ? -1.0 : fl[j] ? hhl[i * m + j] : -DSB_INF;
-                vhu[i * m + j] = dead[j] ? 1.0 : fu[j] ? hhu[i * m + j] : DSB_INF;
-            }
-            for (int k = 0; k < q->cnt[2]; ++k) vxl[i * n + k] = hxl[i * n + q->idx[2][k]];
-            for (int k = 0; k < q->cnt[3]; ++k) vxu[i * n + k] = hxu[i * n + q->idx[3][k]];
+            // the lists of instance i: its own row, or with shared sets those of instance 0, which every other instance must reproduce (with the rows it drops)
+            const bool own = q->per_inst || i == 0;
+            int* t = q->try_h.data();
+            int* idx[4] = {own ? q->list(0, i) : t, own ? q->list(1, i) : t + m, own ? q->list(2, i) : t + 2 * (size_t)m, own ? q->list(3, i) : t + 2 * (size_t)m + n};
+            int* cnt = own ? q->cnt_h.data() + 4 * i : t + 2 * (size_t)m + 2 * (size_t)n;
+            double* packed[4] = {vhl.data() + i * m, vhu.data() + i * m, vxl.data() + i * n, vxu.data() + i * n};
+            dsb_bound_lists(m, n, hhl.empty() ? nullptr : hhl.data() + i * m, hhu.empty() ? nullptr : hhu.data() + i * m, hxl.empty() ? nullptr : hxl.data() + i * n,
+                            hxu.empty() ? nullptr : hxu.data() + i * n, nullptr, cnt, idx, q->dead_h.data() + i * m, packed);
+            if (own) continue;
+            bool same = std::equal(cnt, cnt + 4, q->cnt_h.data()) && std::equal(q->dead_h.begin(), q->dead_h.begin() + m, q->dead_h.begin() + i * m);
+            for (int k = 0; k < 4 && same; ++k) same = std::equal(idx[k], idx[k] + cnt[k], q->list(k, 0));
+            if (!same) throw std::runtime_error("dense solver batch: the set of finite bounds differs from the one of instance 0 (it is shared by the batch)");
         }
+        q->tab_h.assign((size_t)R * q->tab_stride(), -1);
+        q->fill_tab();
+        q->fill_fin();
         // the matrices: upper(P), A', G' column-major in temporaries, equilibrated there, then handed to the KKT system (which keeps its own copies)
         Stream st(s->device);
         DBuf<double> Pu(B * n * n), AT(B * n * p), GT(B * n * m);
-        q->tab.alloc(tab.size());
+        q->tab.alloc(q->tab_h.size());
+        if (q->per_inst) q->cnt_d.alloc(4 * B);
         q->dead_d.alloc(B * m); q->raw.alloc(B * n * (size_t)std::max(n, std::max(p, m))); q->bnd_h.alloc(2 * B * (2 * (size_t)m + 2 * (size_t)n));
-        if (!tab.empty()) PQ_HIP(hipMemcpyAsync(q->tab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, st));
-        if (m > 0) PQ_HIP(hipMemcpyAsync(q->dead_d.p, dead.data(), sizeof(int) * m, hipMemcpyHostToDevice, st));
+        if (!q->tab_h.empty()) PQ_HIP(hipMemcpyAsync(q->tab.p, q->tab_h.data(), sizeof(int) * q->tab_h.size(), hipMemcpyHostToDevice, st));
+        if (q->per_inst) PQ_HIP(hipMemcpyAsync(q->cnt_d.p, q->cnt_h.data(), sizeof(int) * 4 * B, hipMemcpyHostToDevice, st));
+        const int dead_stride = q->per_inst ? m : 0;  // (shared sets: every instance drops the rows instance 0 drops)
+        if (m > 0) PQ_HIP(hipMemcpyAsync(q->dead_d.p, q->dead_h.data(), sizeof(int) * (size_t)R * m, hipMemcpyHostToDevice, st));
         dsb_matrix(q.get(), st, P, Pu.p, n, order == PQ_COL_MAJOR ? 2 : 3, nullptr, 0, mem);
         dsb_matrix(q.get(), st, A, AT.p, p, order == PQ_COL_MAJOR ? 1 : 0, nullptr, 0, mem);
-        dsb_matrix(q.get(), st, G, GT.p, m, order == PQ_COL_MAJOR ? 1 : 0, q->dead_d.p, 0, mem);
+        dsb_matrix(q.get(), st, G, GT.p, m, order == PQ_COL_MAJOR ? 1 : 0, q->dead_d.p, dead_stride, mem);
         auto up = [&](DBuf<double>& d, const std::vector<double>& v, size_t count) {
             d.alloc(count);
             if (count) PQ_HIP(hipMemcpyAsync(d.p, v.data(), sizeof(double) * count, hipMemcpyHostToDevice, st));
@@ -1253,8 +1372,11 @@ int pq_solver_batch_setup_dense(pq_solver_batch* s, int batch, int n, int p, int
         dsb_launch_ruiz(s, q.get(), st, Pu.p, AT.p, GT.p, 0);
         stream_wait(st);
         pq_kktsys_batch* ks = nullptr;
-        if (int rc = pq_kktsys_batch_create_dense(&ks, s->device, batch, n, p, m, Pu.p, AT.p, GT.p, q->cnt[0], q->cnt[1], q->cnt[2], q->cnt[3], q->idx[0].data(), q->idx[1].data(),
-                                                  q->idx[2].data(), q->idx[3].data(), q->xbs.p, &s->settings, PQ_MEM_DEVICE))
+        const int* cn = q->cnt_h.data();
+        if (int rc = q->per_inst ? pq_kktsys_batch_create_dense_lists(&ks, s->device, batch, n, p, m, Pu.p, AT.p, GT.p, cn, q->list(0, 0), q->list(1, 0), q->list(2, 0), q->list(3, 0),
+                                                                      q->xbs.p, &s->settings, PQ_MEM_DEVICE)
+                                 : pq_kktsys_batch_create_dense(&ks, s->device, batch, n, p, m, Pu.p, AT.p, GT.p, cn[0], cn[1], cn[2], cn[3], q->list(0, 0), q->list(1, 0), q->list(2, 0),
+                                                                q->list(3, 0), q->xbs.p, &s->settings, PQ_MEM_DEVICE))
             return rc;
         q->ks.reset(ks);
         hipStream_t kst = ksb_stream(ks);
@@ -1293,7 +1415,7 @@ int pq_solver_batch_update_dense(pq_solver_batch* s, const double* P, const doub
         pq_kktsys_batch* ks = q->ks.get();
         pq_kkt_batch* kb = pq_kktsys_batch_backend(ks);
         hipStream_t st = ksb_stream(ks);
-        // ---- the host: the lists the reference would hold after this call (dense/data.hpp:98-207) must be the setup's, which the KKT system and `tab` carry
+        // ---- the host: the lists the reference would hold after this call (dsb_bound_lists): with shared sets they must be the setup's, else they replace the instance's own
         const double* given[4] = {h_l, h_u, x_l, x_u};
         const double* hv[4];
         double* packed[4];
@@ -1309,48 +1431,71 @@ int pq_solver_batch_update_dense(pq_solver_batch* s, const double* P, const doub
             }
         }
         if (fetched) stream_wait(st);
-        std::vector<char> in[4] = {std::vector<char>(m, 0), std::vector<char>(m, 0), std::vector<char>(n, 0), std::vector<char>(n, 0)};  // stored finite: in the list
-        for (int k = 0; k < 4; ++k)
-            for (int j : q->idx[k]) in[k][j] = 1;
         const bool rows = h_l || h_u;
-        std::vector<int> dead;
-        bool any_dead = false;
-        if (rows) dead.assign(B * m, 0);
-        for (size_t i = 0; i < B; ++i) {
-            for (int j = 0; j < m && rows; ++j) {
-                const bool fl = h_l ? hv[0][i * m + j] > -DSB_INF : (bool)in[0][j], fu = h_u ? hv[1][i * m + j] < DSB_INF : (bool)in[1][j];
-                const bool dd = !fl && !fu;  // disable_inf_constraints: the row of G is zeroed, its bounds become -1 / 1
-                if ((fl || dd) != (bool)in[0][j] || (fu || dd) != (bool)in[1][j])
-                    return fail(PQ_ERR_INVALID, "dense solver batch: update: the set of finite bounds of row %d of G changes in instance %zu (it is fixed at setup)", j, i);
-                dead[i * m + j] = dd;
-                any_dead = any_dead || dd;
-                if (h_l) packed[0][i * m + j] = dd ? -1.0 : fl ? hv[0][i * m + j] : -DSB_INF;
-                if (h_u) packed[1][i * m + j] = dd ? 1.0 : fu ? hv[1][i * m + j] : DSB_INF;
+        // sets per instance: the host images are rewritten below, before the device and the KKT system follow.  Should a call on the way fail, they go back to what
+        // the device still holds (a failure after the new tables are on their way leaves the device ahead of the host: then only a new setup helps)
+        struct Keep {
+            DsbProblem* q;
+            bool done = false;
+            explicit Keep(DsbProblem* p) : q(p)
+            {
+                if (!q->per_inst) return;
+                std::copy(q->cnt_h.begin(), q->cnt_h.end(), q->keep_h.begin());
+                std::copy(q->lists_h.begin(), q->lists_h.end(), q->keep_h.begin() + q->cnt_h.size());
             }
-            for (int k = 2; k < 4; ++k) {
-                if (!given[k]) continue;
-                for (int j = 0; j < n; ++j) {
-                    const double v = hv[k][i * n + j];
-                    if ((k == 2 ? v > -DSB_INF : v < DSB_INF) != (bool)in[k][j])
-                        return fail(PQ_ERR_INVALID, "dense solver batch: update: the set of finite bounds of variable %d changes in instance %zu (it is fixed at setup)", j, i);
-                    packed[k][i * n + j] = 0.0;
-                }
-                for (int e = 0; e < q->cnt[k]; ++e) packed[k][i * n + e] = hv[k][i * n + q->idx[k][e]];
+            ~Keep()
+            {
+                if (done || !q->per_inst) return;
+                std::copy(q->keep_h.begin(), q->keep_h.begin() + q->cnt_h.size(), q->cnt_h.begin());
+                std::copy(q->keep_h.begin() + q->cnt_h.size(), q->keep_h.end(), q->lists_h.begin());
+                q->fill_fin();
+                q->fill_tab();
+            }
+        } keep(q);
+        bool any_dead = false;
+        for (size_t i = 0; i < B; ++i) {
+            const size_t r = q->per_inst ? i : 0;
+            const int* fin[4] = {q->fin(0, r), q->fin(1, r), q->fin(2, r), q->fin(3, r)};
+            int* t = q->try_h.data();
+            int* idx[4] = {q->per_inst ? q->list(0, i) : t, q->per_inst ? q->list(1, i) : t + m, q->per_inst ? q->list(2, i) : t + 2 * (size_t)m,
+                           q->per_inst ? q->list(3, i) : t + 2 * (size_t)m + n};
+            int* cnt = q->per_inst ? q->cnt_h.data() + 4 * i : t + 2 * (size_t)m + 2 * (size_t)n;
+            double* out[4] = {packed[0] + i * m, packed[1] + i * m, packed[2] + i * n, packed[3] + i * n};
+            dsb_bound_lists(m, n, h_l ? hv[0] + i * m : nullptr, h_u ? hv[1] + i * m : nullptr, x_l ? hv[2] + i * n : nullptr, x_u ? hv[3] + i * n : nullptr, fin, cnt, idx,
+                            q->dead_h.data() + i * m, out);
+            for (int j = 0; j < m && rows && !any_dead; ++j) any_dead = q->dead_h[i * m + j] != 0;
+            if (q->per_inst) continue;
+            for (int k = 0; k < 4; ++k) {  // shared sets: the lists are the setup's, which the KKT system and `tab` carry
+                const int* old = q->list(k, 0);
+                const int co = q->cnt_h[k];
+                int e = 0;
+                while (e < cnt[k] && e < co && idx[k][e] == old[e]) ++e;
+                if (e == cnt[k] && e == co) continue;
+                const int j = e == cnt[k] ? old[e] : e == co ? idx[k][e] : std::min(idx[k][e], old[e]);
+                return fail(PQ_ERR_INVALID, "dense solver batch: update: the set of finite bounds of %s %d%s changes in instance %zu (it is fixed at setup)", k < 2 ? "row" : "variable", j,
+                            k < 2 ? " of G" : "", i);
             }
         }
+        if (q->per_inst) { q->fill_fin(); q->fill_tab(); }
         // ---- the device: unscale, assign, rescale, all where the data stand
         PQ_HIP(hipEventRecord(q->ev[0], st));
         const int* dd = nullptr;
         if (any_dead) {
-            PQ_HIP(hipMemcpyAsync(q->dead_d.p, dead.data(), sizeof(int) * dead.size(), hipMemcpyHostToDevice, st));
+            PQ_HIP(hipMemcpyAsync(q->dead_d.p, q->dead_h.data(), sizeof(int) * B * m, hipMemcpyHostToDevice, st));
             dd = q->dead_d.p;
         }
         DsbUnscaleArgs u;
-        u.n = n; u.p = p; u.m = m; u.nxl = q->cnt[2]; u.nxu = q->cnt[3];
+        u.n = n; u.p = p; u.m = m; u.bd = q->bounds();  // (the device still holds the tables of before this call)
         u.Pu = kb->Pu.p; u.AT = kb->AT.p; u.GT = kb->GT.p; u.c = q->c.p; u.b = q->b.p; u.h_l = q->h_l.p; u.h_u = q->h_u.p; u.x_l = q->x_l.p; u.x_u = q->x_u.p; u.xbs = q->xbs.p;
-        u.pdi = q->pdi.p; u.pdbi = q->pdbi.p; u.pc_inv = q->pc_inv.p; u.xl_idx = q->xl_idx(); u.xu_idx = q->xu_idx(); u.dead = dd;
-        k_dsb_unscale<<<batch, DSB_RUIZ_T, 0, st>>>(u);
+        u.pdi = q->pdi.p; u.pdbi = q->pdbi.p; u.pc_inv = q->pc_inv.p; u.dead = dd;
+        if (q->per_inst) k_dsb_unscale<true><<<batch, DSB_RUIZ_T, 0, st>>>(u);
+        else k_dsb_unscale<false><<<batch, DSB_RUIZ_T, 0, st>>>(u);
         PQ_HIP(hipGetLastError());
+        if (q->per_inst) {  // the sets of after this call: the tables here (behind the unscaling on the stream) and the KKT system's
+            PQ_HIP(hipMemcpyAsync(q->tab.p, q->tab_h.data(), sizeof(int) * q->tab_h.size(), hipMemcpyHostToDevice, st));
+            PQ_HIP(hipMemcpyAsync(q->cnt_d.p, q->cnt_h.data(), sizeof(int) * 4 * B, hipMemcpyHostToDevice, st));
+            if (int rc = pq_kktsys_batch_set_lists(ks, q->cnt_h.data(), q->list(0, 0), q->list(1, 0), q->list(2, 0), q->list(3, 0))) return rc;
+        }
         int opt = PQ_KKT_UPDATE_NONE;
         if (P) { dsb_matrix(q, st, P, kb->Pu.p, n, order == PQ_COL_MAJOR ? 2 : 3, nullptr, 0, mem); opt |= PQ_KKT_UPDATE_P; }
         if (A) { dsb_matrix(q, st, A, kb->AT.p, p, order == PQ_COL_MAJOR ? 1 : 0, nullptr, 0, mem); opt |= PQ_KKT_UPDATE_A; }
@@ -1372,6 +1517,7 @@ int pq_solver_batch_update_dense(pq_solver_batch* s, const double* P, const doub
         for (int i = 0; i < batch; ++i) q->state_h.p[i].info.update_time = wall * 1e-3;  // (the batch's)
         s->update_wall_ms = wall; s->update_device_ms = ms;
         s->updated = true;
+        keep.done = true;
         return 1;
     });
 }
@@ -1413,12 +1559,11 @@ int pq_solver_batch_solve(pq_solver_batch* s)
         PQ_HIP(hipMemcpyAsync(q->state.p, q->state_h.p, sizeof(DsbState) * batch, hipMemcpyHostToDevice, st));
         PQ_HIP(hipMemsetAsync(q->counters.p, 0, sizeof(int) * 8, st));
         DsbArgs a;
-        a.n = n; a.p = p; a.m = m; a.nhl = q->cnt[0]; a.nhu = q->cnt[1]; a.nxl = q->cnt[2]; a.nxu = q->cnt[3]; a.batch = batch; a.trace_max = q->trace_max; a.slot = 0;
+        a.n = n; a.p = p; a.m = m; a.bd = q->bounds(); a.batch = batch; a.trace_max = q->trace_max; a.slot = 0;
         a.set = s->settings;
         a.Pu = kb->Pu.p; a.AT = kb->AT.p; a.GT = kb->GT.p;
         a.c = q->c.p; a.b = q->b.p; a.h_l = q->h_l.p; a.h_u = q->h_u.p; a.x_l = q->x_l.p; a.x_u = q->x_u.p; a.xbs = q->xbs.p;
         a.pd = q->pd.p; a.pdb = q->pdb.p; a.pdi = q->pdi.p; a.pdbi = q->pdbi.p; a.pc_inv = q->pc_inv.p;
-        a.has_l = q->has_l(); a.has_u = q->has_u(); a.xl_idx = q->xl_idx(); a.xu_idx = q->xu_idx();
         a.r = q->sets[0].v; a.nr = q->sets[1].v; a.res = q->sets[2].v; a.st = q->sets[3].v; a.px = q->sets[4].v;
         a.state = q->state.p; a.rho = q->rho.p; a.delta = q->delta.p; a.flags = q->flags.p; a.act_f = q->act.p; a.act_s = q->act.p + batch; a.counters = q->counters.p;
         a.fstatus = ksb_factor_status(ks); a.sinfo = ksb_solve_info(ks);
@@ -1437,7 +1582,8 @@ int pq_solver_batch_solve(pq_solver_batch* s)
         for (; round < bound && !done; ++round) {
             a.slot = (int)(round & 1);
             PQ_HIP(hipEventRecord(q->ev[0], st));
-            k_dsb_advance<<<batch, DSB_T, 0, st>>>(a);
+            if (q->per_inst) k_dsb_advance<true><<<batch, DSB_T, 0, st>>>(a);
+            else k_dsb_advance<false><<<batch, DSB_T, 0, st>>>(a);
             PQ_HIP(hipGetLastError());
             PQ_HIP(hipEventRecord(q->ev[1], st));
             PQ_HIP(hipMemcpyAsync(q->counters_h.p, q->counters.p + 4 * a.slot, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
@@ -1450,6 +1596,8 @@ int pq_solver_batch_solve(pq_solver_batch* s)
             if (nd == batch) { done = true; continue; }
             if (nf > 0) {
                 PQ_HIP(hipEventRecord(q->ev[2], st));
+                // (any factor launch, masked or not, ends the KKT system's `stale` state after pq_kktsys_batch_set_lists: right here, because after an update every
+                // instance starts at INIT and the first round's launch factors them all)
                 ksb_launch_factor(ks, q->flags.p, q->rho.p, q->delta.p, q->sets[0].v, a.act_f);
                 PQ_HIP(hipEventRecord(q->ev[3], st));
                 pend_f = true;
@@ -1464,11 +1612,12 @@ int pq_solver_batch_solve(pq_solver_batch* s)
             }
         }
         DsbFinishArgs f;
-        f.n = n; f.p = p; f.m = m; f.nxl = q->cnt[2]; f.nxu = q->cnt[3];
-        f.pd = q->pd.p; f.pdb = q->pdb.p; f.pdi = q->pdi.p; f.pdbi = q->pdbi.p; f.pc_inv = q->pc_inv.p; f.xl_idx = q->xl_idx(); f.xu_idx = q->xu_idx();
+        f.n = n; f.p = p; f.m = m; f.bd = q->bounds();
+        f.pd = q->pd.p; f.pdb = q->pdb.p; f.pdi = q->pdi.p; f.pdbi = q->pdbi.p; f.pc_inv = q->pc_inv.p;
         f.r = q->sets[0].v; f.out = q->sets[5].v;
         PQ_HIP(hipEventRecord(q->ev[6], st));
-        k_dsb_finish<<<batch, DSB_T, 0, st>>>(f);
+        if (q->per_inst) k_dsb_finish<true><<<batch, DSB_T, 0, st>>>(f);
+        else k_dsb_finish<false><<<batch, DSB_T, 0, st>>>(f);
         PQ_HIP(hipGetLastError());
         PQ_HIP(hipEventRecord(q->ev[7], st));
         ++launches;
