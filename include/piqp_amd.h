@@ -582,12 +582,19 @@ enum { PQ_KKT_BATCH_DENSE_MAX_N = 128 };
 typedef struct pq_kkt_batch pq_kkt_batch;
 /* Arguments are checked before the device is touched: PQ_ERR_UNSUPPORTED for n > PQ_KKT_BATCH_DENSE_MAX_N; PQ_ERR_INVALID for batch < 1, n < 1, p < 0, m < 0, a
  * kkt_solver other than the two, a mem other than the two, a null out or P_utri, a null AT with p > 0 or a null GT with m > 0.  Allocates everything the handle will
- * ever need (the staging of host-mode calls included: pq_debug_alloc_count() moves in no later call except pq_kkt_batch_clone) and computes AT_A[i] = AT[i] AT[i]'
+ * ever need (the staging of host-mode calls included: pq_debug_alloc_count() moves in no later call except pq_kkt_batch_clone / _clone_select) and computes AT_A[i] = AT[i] AT[i]'
  * (dense/kkt.hpp:53) when p > 0. */
 int pq_kkt_batch_create_dense(pq_kkt_batch **out, int device, int batch, int n, int p, int m, int kkt_solver, const double *P_utri, const double *AT,
                               const double *GT, int mem);
 void pq_kkt_batch_destroy(pq_kkt_batch *k);
 int pq_kkt_batch_clone(const pq_kkt_batch *k, pq_kkt_batch **out);
+/* Clone by a list of instances: the new handle has batch = count and its instance j is instance idx[j] of k -- its data, A'A, its stored factor, the scalings of
+ * its last factorisation and its status, bit for bit, so a clone taken after a factorisation solves without factoring.  idx: HOST memory in either mode, repeats
+ * allowed, count smaller or larger than k's batch.  The new handle lives on the same device with a stream of its own and is independent of k, which is only waited
+ * for and read.  One gather launch per buffer (the status is two arrays in one buffer: two), the list uploaded once; the staging and the events are sized for
+ * count, not copied.  The call allocates everything the new handle will ever need.  PQ_ERR_INVALID before the device is touched, with *out left alone: a NULL k,
+ * out or idx, count < 1, an idx[j] outside [0, batch) (the text names j and the value). */
+int pq_kkt_batch_clone_select(const pq_kkt_batch *k, const int *idx, int count, pq_kkt_batch **out);
 int pq_kkt_batch_dims(const pq_kkt_batch *k, int *batch, int *n, int *p, int *m);
 /* dense/kkt.hpp:62-71, per instance.  options: PQ_KKT_UPDATE_* mask; a flagged matrix is re-read from its argument (null there: PQ_ERR_INVALID, the handle stays as
  * it was), an unflagged one is ignored and its pointer may be null; PQ_KKT_UPDATE_A recomputes AT_A. */
@@ -630,7 +637,7 @@ typedef struct pq_kktsys_batch pq_kktsys_batch;
 /* Arguments are checked before the device is touched.  Refuses what pq_kkt_batch_create_dense refuses (PQ_ERR_UNSUPPORTED for n > PQ_KKT_BATCH_DENSE_MAX_N), and
  * with PQ_ERR_INVALID: a NULL settings, iterative_refinement_max_iter outside [0, 64] (a safety cap on the in-kernel loop), a negative count, a count above its
  * vector's length, a NULL list with a positive count, a list that is not strictly ascending or has an index out of range, a row of G in neither h_l_idx nor
- * h_u_idx.  Allocates everything the handle will ever need, host-mode staging included: pq_debug_alloc_count() moves in no later call except _clone. */
+ * h_u_idx.  Allocates everything the handle will ever need, host-mode staging included: pq_debug_alloc_count() moves in no later call except _clone / _clone_select. */
 int pq_kktsys_batch_create_dense(pq_kktsys_batch **out, int device, int batch, int n, int p, int m, const double *P_utri, const double *AT, const double *GT,
                                  int n_h_l, int n_h_u, int n_x_l, int n_x_u, const int *h_l_idx, const int *h_u_idx, const int *x_l_idx, const int *x_u_idx,
                                  const double *x_b_scaling, const pq_settings *settings, int mem);
@@ -648,6 +655,11 @@ int pq_kktsys_batch_create_dense_lists(pq_kktsys_batch **out, int device, int ba
 int pq_kktsys_batch_set_lists(pq_kktsys_batch *k, const int *counts, const int *h_l_idx, const int *h_u_idx, const int *x_l_idx, const int *x_u_idx);
 void pq_kktsys_batch_destroy(pq_kktsys_batch *k);
 int pq_kktsys_batch_clone(const pq_kktsys_batch *k, pq_kktsys_batch **out); /* kkt_system.hpp:70-95: the scalings state is copied, the backend cloned; so are the kind of the lists and the tables */
+/* Clone by a list of instances, under the rules and refusals of pq_kkt_batch_clone_select, over a backend cloned by the same list: instance j of the new handle
+ * is instance idx[j] of k in every state vector (the P_diag of the last update_data that carried P and x_b_scaling included), its refinement flag and the
+ * diagnostics of its last solve; with lists per instance it takes that instance's row of the tables (2 m + 4 n ints) and its four counts, with shared lists the
+ * one table is copied.  The settings are copied as they stand.  A clone taken after update_scalings_and_factor solves and multiplies without factoring. */
+int pq_kktsys_batch_clone_select(const pq_kktsys_batch *k, const int *idx, int count, pq_kktsys_batch **out);
 int pq_kktsys_batch_dims(const pq_kktsys_batch *k, int *batch, int *n, int *p, int *m);
 pq_kkt_batch *pq_kktsys_batch_backend(pq_kktsys_batch *k); /* borrowed; NULL for a NULL handle */
 /* kkt_system.hpp:134-141: pq_kkt_batch_update_data_dense on the backend; a non-NULL x_b_scaling is re-read */
@@ -682,7 +694,7 @@ int pq_kktsys_batch_last_ms(const pq_kktsys_batch *k, double out3[3]);
  * one pq_settings and, unless pq_solver_batch_set_bound_sets says otherwise, the set of finite bounds.  The solve runs in rounds clocked by the host: a small kernel advances every instance to its next KKTSystem call, then
  * the factor launch and the solve launch of pq_kktsys_batch_* run on the instances that asked for them; the host reads three counters per round.  The instances need
  * not run in lock step; an instance that has ended is not touched again.
- * There is no clone() yet.  pq_solver_batch_update_dense is DenseSolver::update (solver.hpp:218-308): per instance it un-scales everything stored, assigns what is
+ * pq_solver_batch_update_dense is DenseSolver::update (solver.hpp:218-308): per instance it un-scales everything stored, assigns what is
  * given, and scales again -- with the stored scalings when preconditioner_reuse_on_update is set or no matrix is given, else by a new equilibration -- so an update of
  * c alone moves P, A' and G' by roundings, as in the reference.  ONE RULE IS NOT THE REFERENCE'S: its dense backend recomputes A'A only when A is given
  * (dense/kkt.hpp:62-71); when P or G comes without A and the scalings are recomputed, A' is rescaled and A'A stays that of the old scalings, which turns solvable
@@ -696,6 +708,23 @@ typedef struct pq_solver_batch pq_solver_batch;
 int pq_solver_batch_create(pq_solver_batch **out, int device);
 void pq_solver_batch_destroy(pq_solver_batch *s);
 pq_settings *pq_solver_batch_settings(pq_solver_batch *s); /* shared by all instances; kkt_solver and the preconditioner fields are read by setup */
+/* A second handle in the state of s, without a new setup: the settings as they stand, the trace rows, the bound-set mode, solved / updated and the stored times
+ * are copied, and the problem is cloned whole (_clone: the identity list) or by a list of instances (_clone_select: batch = count, instance j of the new handle is
+ * instance idx[j] of s; idx in HOST memory, repeats allowed, count smaller or larger than the batch of s).  Per instance everything a later call can read goes
+ * along bit for bit: the backend and the KKT system (pq_kktsys_batch_clone_select), the interior-point state, the results handed out, the info fields and the
+ * trace, the scaled vectors, x_b_scaling, the preconditioner and, with PQ_BOUND_SETS_PER_INSTANCE, the instance's lists (tab has rows of 2 m + 2 n ints here) --
+ * with shared sets the one table is copied.  So a clone taken after a solve answers info, get_result_mem and get_trace for its instances without solving, and an
+ * update on it unscales with the stored scalings of its instances.  The new handle is on the same device with a stream of its own and is independent: it survives
+ * pq_solver_batch_destroy(s), and no call on either is seen by the other; s is only waited for and read.  The call is the only one on the new handle that
+ * allocates: update, solve and the getters after it leave pq_debug_alloc_count() where it is, as after a setup.
+ * _clone of a handle that was never set up gives a handle with those scalars and no problem, and touches no device; _clone_select of one is PQ_ERR_INVALID, as
+ * are, before the device is touched and with *out left alone: a NULL s, out or idx, count < 1, an idx[j] outside [0, batch) (the text names j and the value). */
+int pq_solver_batch_clone(const pq_solver_batch *s, pq_solver_batch **out);
+int pq_solver_batch_clone_select(const pq_solver_batch *s, const int *idx, int count, pq_solver_batch **out);
+/* of the clone call that made s: out2 = { wall ms of the call from the upload of the list to the last wait, device ms of the gathers of the three layers (hipEvents
+ * of the new handles around them; the memsets of a layer's fresh buffers that run between its events count) }; both 0 on a handle that pq_solver_batch_create made
+ * or whose source was never set up.  Wall minus device is the allocation and the host images. */
+int pq_solver_batch_clone_ms(const pq_solver_batch *s, double out2[2]);
 /* Who owns the set of finite bounds.  PQ_BOUND_SETS_SHARED (the default): one set for the batch, a checked promise -- setup refuses an instance that differs from
  * instance 0 and update refuses a bound that turns infinite or finite, as described at those calls.  PQ_BOUND_SETS_PER_INSTANCE: every instance has the lists
  * DenseSolver would hold for its own vectors (dense/data.hpp:98-207), at setup and after every update, so constraints can be switched off per instance with
@@ -759,7 +788,8 @@ pq_kktsys_batch *pq_solver_batch_kktsys(pq_solver_batch *s);
 /* ===================== small utilities used by the measurement harness ===================== */
 /* fp64 MFMA / HBM micro-benchmarks on `device` (used once by bench.py to report measured peaks) */
 /* number of device / pinned-host allocations the library has made in this process.  Contract (the reference's tests assert allocation-free
- * factor / solve, fwd.hpp:44-52): the counter moves only inside *_create / *_clone / *_setup / *_update_data / *_partition calls, never in
+ * factor / solve, fwd.hpp:44-52): the counter moves only inside *_create / *_clone / *_clone_select (pq_kkt_batch_, pq_kktsys_batch_ and pq_solver_batch_clone_select, pq_solver_batch_clone) /
+ * *_setup / *_update_data / *_partition calls, never in
  * update_scalings_and_factor, solve, eval_*, mul or condensed_residual, in either pointer mode */
 long long pq_debug_alloc_count(void);
 /* host-only (no device needed): the ticket-ordered task list of the persistent dense factorisation for a T x T grid of 128 x 128 tiles (csrc/dense_kernels.hip

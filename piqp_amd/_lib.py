@@ -127,6 +127,7 @@ SYMBOLS = [
     "pq_solver_batch_create", "pq_solver_batch_destroy", "pq_solver_batch_settings", "pq_solver_batch_setup_dense", "pq_solver_batch_solve", "pq_solver_batch_info",
     "pq_solver_batch_get_result_mem", "pq_solver_batch_set_trace", "pq_solver_batch_get_trace", "pq_solver_batch_dims", "pq_solver_batch_last_ms", "pq_solver_batch_scaled_data",
     "pq_solver_batch_kktsys", "pq_solver_batch_update_dense", "pq_solver_batch_last_update_ms", "pq_solver_batch_set_bound_sets", "pq_debug_bound_lists",
+    "pq_kkt_batch_clone_select", "pq_kktsys_batch_clone_select", "pq_solver_batch_clone", "pq_solver_batch_clone_select", "pq_solver_batch_clone_ms",
     "pq_debug_alloc_count", "pq_debug_chol_plan", "pq_debug_syrk_plan", "pq_debug_device_sqrt", "pq_kkt_set_exchange_norm", "pq_kkt_sharded_calls", "pq_kkt_sharded_solve_calls", "pq_solver_sharded_solve_calls", "pq_solver_set_exchange_norm", "pq_solver_sharded_calls", "pq_microbench_mfma_f64", "pq_microbench_hbm_copy", "pq_microbench_potrf_block", "pq_debug_potrf_block", "pq_debug_csc_ops", "pq_debug_ruiz","pq_rccl_unique_id", "pq_kkt_set_comm_rccl", "pq_solver_set_comm_rccl", "pq_kkt_native_exchange_calls", "pq_kkt_min_abs_pivot", "pq_solver_native_exchange_calls",
     "pq_solver_setup_sparse_mem", "pq_solver_update_sparse_mem", "pq_debug_sparse_ingest_maps",
     "pq_solver_setup_dense_mem", "pq_solver_update_dense_mem", "pq_solver_get_result_mem", "pq_solver_last_ingest", "pq_batch_update_mem", "pq_batch_update_data_mem",
@@ -224,6 +225,7 @@ def load():
     L.pq_kkt_batch_destroy.argtypes = [vp]
     L.pq_kkt_batch_destroy.restype = None
     L.pq_kkt_batch_clone.argtypes = [vp, C.POINTER(vp)]
+    L.pq_kkt_batch_clone_select.argtypes = [vp, vp, C.c_int, C.POINTER(vp)]
     L.pq_kkt_batch_dims.argtypes = [vp, _ip, _ip, _ip, _ip]
     L.pq_kkt_batch_update_data_dense.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int]
     L.pq_kkt_batch_update_scalings_and_factor.argtypes = [vp, vp, vp, vp, C.c_int]
@@ -241,6 +243,7 @@ def load():
     L.pq_kktsys_batch_create_dense_lists.argtypes = [C.POINTER(vp)] + [C.c_int] * 5 + [vp, vp, vp] + [vp] * 5 + [vp, C.POINTER(Settings), C.c_int]
     L.pq_kktsys_batch_set_lists.argtypes = [vp] * 6
     L.pq_kktsys_batch_clone.argtypes = [vp, C.POINTER(vp)]
+    L.pq_kktsys_batch_clone_select.argtypes = [vp, vp, C.c_int, C.POINTER(vp)]
     L.pq_kktsys_batch_dims.argtypes = [vp, _ip, _ip, _ip, _ip]
     L.pq_kktsys_batch_backend.argtypes = [vp]
     L.pq_kktsys_batch_backend.restype = vp
@@ -255,6 +258,9 @@ def load():
     L.pq_solver_batch_create.argtypes = [C.POINTER(vp), C.c_int]
     L.pq_solver_batch_destroy.argtypes = [vp]
     L.pq_solver_batch_destroy.restype = None
+    L.pq_solver_batch_clone.argtypes = [vp, C.POINTER(vp)]
+    L.pq_solver_batch_clone_select.argtypes = [vp, vp, C.c_int, C.POINTER(vp)]
+    L.pq_solver_batch_clone_ms.argtypes = [vp, vp]
     L.pq_solver_batch_settings.argtypes = [vp]
     L.pq_solver_batch_settings.restype = C.POINTER(Settings)
     L.pq_solver_batch_setup_dense.argtypes = [vp] + [C.c_int] * 4 + [vp] * 9 + [C.c_int, C.c_int]

@@ -7,7 +7,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import VAR_NAMES, check
-from .batch_kkt import KKT_BATCH_DENSE_MAX_N, _BatchHandle, var_shapes
+from .batch_kkt import KKT_BATCH_DENSE_MAX_N, _BatchHandle, select_list, var_shapes
 from .batch_kktsys import BatchKKTSystem, _copy_settings
 from .kkt import (COL_MAJOR, DENSE_CHOLESKY, DENSE_LDLT_NO_PIVOT, MEM_DEVICE, MEM_HOST, ROW_MAJOR, _is_torch, check_device_tensor, device_call,
                   sync_current_stream, to_device_args)
@@ -36,7 +36,9 @@ class BatchDenseSolver(_BatchHandle):
     instance has the finite-bound lists DenseSolver would hold for its own vectors, at setup and after every update (-/+ inf switches a bound off).  s.solve() returns the number of instances that ended SOLVED.
     s.update(P=None, c=None, A=None, b=None, G=None, h_l=None, h_u=None, x_l=None, x_u=None): DenseSolver::update on the device, without a new setup; any subset of
     the arguments, under the rules of setup; with shared bounds the set of finite bounds must stay the setup's (RuntimeError otherwise, the handle is as it was).
-    There is no clone()."""
+    s.clone(instances=None): a second solver in the state of this one, without a new setup -- whole, or instance j of the clone being instance instances[j] of this
+    one (repeats allowed, any length >= 1): settings, scaled data, stored scalings, bound sets, statuses, results and traces go along, so update() on the clone gives
+    each copy its scenario and a clone of the instances that did not end SOLVED can be solved again with other settings."""
     _destroy = "pq_solver_batch_destroy"
 
     def __init__(self, device=0, kkt_solver=DENSE_CHOLESKY, bounds="shared"):
@@ -59,6 +61,20 @@ class BatchDenseSolver(_BatchHandle):
     @property
     def settings(self):
         return self.L.pq_solver_batch_settings(self.h).contents
+
+    def clone(self, instances=None):
+        h = C.c_void_p()
+        if instances is None:
+            check(self.L.pq_solver_batch_clone(self.h, C.byref(h)), "pq_solver_batch_clone")
+            batch = self.batch
+        else:
+            idx = select_list(instances)
+            check(self.L.pq_solver_batch_clone_select(self.h, idx.ctypes.data, len(idx), C.byref(h)), "pq_solver_batch_clone_select")
+            batch = len(idx)
+        c = type(self).__new__(type(self))
+        c.L, c.device, c.kkt_solver, c.bounds, c.h = self.L, self.device, self.kkt_solver, self.bounds, h
+        c.batch, c.n, c.p, c.m = batch, self.n, self.p, self.m
+        return c
 
     # ---- argument handling: no library call in here
     @staticmethod
@@ -137,6 +153,12 @@ class BatchDenseSolver(_BatchHandle):
         if mem == MEM_DEVICE:
             sync_current_stream(self.device)
         return check(self.L.pq_solver_batch_update_dense(self.h, *[self._p(v) for v in arrs], mem, order), "pq_solver_batch_update_dense") == 1
+
+    def clone_ms(self):
+        """of the clone() that made this solver: dict(wall_ms, device_ms); zeros on a solver that is no clone"""
+        o = np.zeros(2)
+        check(self.L.pq_solver_batch_clone_ms(self.h, o.ctypes.data), "pq_solver_batch_clone_ms")
+        return dict(wall_ms=float(o[0]), device_ms=float(o[1]))
 
     def last_update_ms(self):
         """of the last update: dict(wall_ms, device_ms)"""

@@ -18,6 +18,20 @@ def var_shapes(b, n, p, m):
     return dict(zip(VAR_NAMES, ((b, n), (b, p), (b, m), (b, m), (b, n), (b, n), (b, m), (b, m), (b, n), (b, n))))
 
 
+def select_list(instances):
+    """the list of a clone(instances) as the library takes it: a contiguous C-int array, one-dimensional and non-empty, made from anything np.asarray takes whose
+    entries are integers (ValueError otherwise; no library call in here -- the range of the entries is the library's check)"""
+    try:
+        a = np.asarray(instances)
+    except Exception:
+        raise ValueError("instances: a one-dimensional list of integers expected") from None
+    if a.ndim != 1 or a.size == 0:
+        raise ValueError(f"instances: shape {a.shape}, a one-dimensional, non-empty list expected")
+    if not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"instances: dtype {a.dtype}, integers expected")
+    return np.ascontiguousarray(a, dtype=np.intc)
+
+
 class _BatchHandle(_Handle):
     """what the batched wrappers share: the argument handling and the one way to wrap a handle that exists already"""
     _dims_fn = None  # the library's getter of (batch, n, p, m) for this kind of handle
@@ -134,9 +148,15 @@ class BatchDenseKKT(_BatchHandle):
         return self._args(("P", P, (b, n, n), True), ("A", A, (b, self.p, n)), ("G", G, (b, self.m, n)))
 
     # ---- the KKTSolverBase surface, per instance
-    def clone(self):
+    def clone(self, instances=None):
+        """a handle of its own in the state of this one; instances: None = every instance, else a list of instances (repeats allowed, any length >= 1): instance j
+        of the clone is instance instances[j] of this handle"""
         h = C.c_void_p()
-        check(self.L.pq_kkt_batch_clone(self.h, C.byref(h)), "pq_kkt_batch_clone")
+        if instances is None:
+            check(self.L.pq_kkt_batch_clone(self.h, C.byref(h)), "pq_kkt_batch_clone")
+        else:
+            idx = select_list(instances)
+            check(self.L.pq_kkt_batch_clone_select(self.h, idx.ctypes.data, len(idx), C.byref(h)), "pq_kkt_batch_clone_select")
         return self._adopt(h, self.device, self.kkt_solver)
 
     def update_data(self, P=None, A=None, G=None):

@@ -7,7 +7,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import VAR_NAMES, check
-from .batch_kkt import BatchDenseKKT, _BatchHandle, var_shapes
+from .batch_kkt import BatchDenseKKT, _BatchHandle, select_list, var_shapes
 from .kkt import DENSE_CHOLESKY, KKT_UPDATE_A, KKT_UPDATE_G, KKT_UPDATE_P, MEM_DEVICE, MEM_HOST, _is_torch, default_settings, sync_current_stream
 
 STATE_X_REG, STATE_Z_REG, STATE_RHS_X_BAR, STATE_RHS_Z_BAR = 0, 1, 2, 3  # PQ_KKTSYS_BATCH_*
@@ -158,10 +158,19 @@ class BatchKKTSystem(_BatchHandle):
         return {k: np.zeros(s) for k, s in self.var_shapes().items()}
 
     # ---- the KKTSystem surface, per instance
-    def clone(self):
+    def clone(self, instances=None):
+        """a system of its own in the state of this one; instances: None = every instance, else a list of instances (repeats allowed, any length >= 1): instance j
+        of the clone is instance instances[j] of this system, with that instance's lists when every instance has its own"""
         h = C.c_void_p()
-        check(self.L.pq_kktsys_batch_clone(self.h, C.byref(h)), "pq_kktsys_batch_clone")
-        return self._adopt(h, self.device, self.kkt_solver, lists=self.lists, per_inst=self.per_inst, settings=_copy_settings(self.settings))
+        lists = self.lists
+        if instances is None:
+            check(self.L.pq_kktsys_batch_clone(self.h, C.byref(h)), "pq_kktsys_batch_clone")
+        else:
+            idx = select_list(instances)
+            check(self.L.pq_kktsys_batch_clone_select(self.h, idx.ctypes.data, len(idx), C.byref(h)), "pq_kktsys_batch_clone_select")
+            if self.per_inst and lists is not None:
+                lists = [lists[i] for i in idx]
+        return self._adopt(h, self.device, self.kkt_solver, lists=lists, per_inst=self.per_inst, settings=_copy_settings(self.settings))
 
     def backend(self):
         """the BatchDenseKKT this system owns (borrowed: it lives as long as this object)"""

@@ -257,6 +257,33 @@ int pq::kb_factor_done(pq_kkt_batch* k, const std::chrono::steady_clock::time_po
     return good;
 }
 
+// instance j of the new handle is instance sel.host[j] of k: the data, A'A, the factor store, the stored scalings and both halves of the status ([0, batch): info,
+// [batch, 2 batch): the first bad column -- two arrays in one buffer, one gather each) are gathered; the staging, mat_d and the events are only sized.  The new
+// handle's stream is waited for before it is handed out, so the list at sel.dev may be released by the caller.
+pq_kkt_batch* pq::kb_clone_rows(const pq_kkt_batch* k, const KbSelect& sel)
+{
+    PQ_HIP(hipSetDevice(k->device));
+    stream_wait(k->st);
+    std::unique_ptr<pq_kkt_batch> c(new pq_kkt_batch);
+    c->device = k->device; c->batch = sel.count; c->n = k->n; c->p = k->p; c->m = k->m; c->kind = k->kind;
+    kb_alloc(c.get());
+    const size_t b = (size_t)sel.count, n = (size_t)k->n, nn = n * n;
+    hipStream_t st = c->st;
+    auto rows = [&](DBuf<double>& dst, const DBuf<double>& src, size_t len) { if (src.n) kb_gather_rows(st, dst.p, src.p, sel.dev, b, sizeof(double) * len); };
+    PQ_HIP(hipEventRecord(c->ev[0], st));
+    rows(c->Pu, k->Pu, nn); rows(c->AT, k->AT, n * k->p); rows(c->GT, k->GT, n * k->m); rows(c->ATA, k->ATA, nn); rows(c->fac, k->fac, nn);
+    rows(c->delta_s, k->delta_s, 1); rows(c->x_reg_s, k->x_reg_s, n); rows(c->zinv_s, k->zinv_s, (size_t)k->m);
+    for (int h = 0; h < 2; ++h) {
+        kb_gather_rows(st, c->status.p + h * b, k->status.p + (size_t)h * k->batch, sel.dev, b, sizeof(int));
+        kb_gather_host(c->status_h.p + h * b, k->status_h.p + (size_t)h * k->batch, sel.host, sel.count, 1);
+    }
+    c->computed = k->computed;
+    for (int j = 0; j < sel.count && k->computed; ++j) c->n_ok += c->status_h.p[j] == 0;
+    PQ_HIP(hipEventRecord(c->ev[1], st));
+    kb_gather_timed(sel, st, c->ev[0], c->ev[1]);
+    return c.release();
+}
+
 extern "C" {
 
 int pq_kkt_batch_create_dense(pq_kkt_batch** out, int device, int batch, int n, int p, int m, int kkt_solver, const double* P_utri, const double* AT,
@@ -301,6 +328,19 @@ int pq_kkt_batch_clone(const pq_kkt_batch* k, pq_kkt_batch** out)
         std::memcpy(c->status_h.p, k->status_h.p, sizeof(int) * 2 * (size_t)k->batch);
         stream_wait(c->st);
         *out = c.release();
+        return (int)PQ_OK;
+    });
+}
+
+int pq_kkt_batch_clone_select(const pq_kkt_batch* k, const int* idx, int count, pq_kkt_batch** out)
+{
+    if (!k || !out) return fail(PQ_ERR_INVALID, "null argument");
+    if (int rc = kb_check_select("dense KKT batch", k->batch, idx, count)) return rc;
+    return guarded([&] {
+        PQ_HIP(hipSetDevice(k->device));
+        DBuf<int> idx_d((size_t)count);
+        PQ_HIP(hipMemcpy(idx_d.p, idx, sizeof(int) * (size_t)count, hipMemcpyHostToDevice));
+        *out = kb_clone_rows(k, KbSelect{idx, idx_d.p, count, nullptr});
         return (int)PQ_OK;
     });
 }

@@ -211,4 +211,38 @@ __device__ __forceinline__ KbBounds kb_bound_row(const KbBounds& B, long long in
     return r;
 }
 
+// ---- clone by a list of instances (pq_*_batch_clone_select of the three layers): row j of dst is row idx[j] of src, rows of wpr words of W -- uint4, unsigned
+// long long or unsigned, the widest that divides the row's bytes and both bases (kb_gather_rows, dense_kkt_batch_internal.hpp).  A copy of bits: a word is loaded and
+// stored, nothing is computed on it.  Rows of 256 words and more: a workgroup moves one chunk of 1024 words of one row per step, consecutive lanes consecutive words
+// (16 KiB with uint4; the 128 KiB row of Pu at n = 128 is 8 chunks).  Shorter rows: a workgroup moves 256 / wpr whole rows per step, lane t word t % wpr of row
+// t / wpr, so the lanes of a row still read consecutive words (a row of one word: 256 rows per step).  The row index comes from blockIdx.x and a grid-stride loop and
+// is held in 64 bits, as is every offset; idx has been checked against the source's batch on the host.
+constexpr int KB_GATHER_THREADS = 256;
+constexpr int KB_GATHER_CHUNK = 4 * KB_GATHER_THREADS;
+constexpr int KB_GATHER_MAX_GRID = 8192;
+template <class W>
+__global__ __launch_bounds__(KB_GATHER_THREADS) void k_kb_gather_rows(W* __restrict__ dst, const W* __restrict__ src, const int* __restrict__ idx, size_t count,
+                                                                      size_t wpr)
+{
+    const unsigned t = threadIdx.x;
+    if (wpr >= (size_t)KB_GATHER_THREADS) {
+        const size_t cpr = (wpr + KB_GATHER_CHUNK - 1) / KB_GATHER_CHUNK, units = count * cpr;
+        for (size_t u = blockIdx.x; u < units; u += gridDim.x) {
+            const size_t row = u / cpr, w0 = (u % cpr) * KB_GATHER_CHUNK;
+            const size_t w1 = w0 + KB_GATHER_CHUNK < wpr ? w0 + KB_GATHER_CHUNK : wpr;
+            const W* s = src + (size_t)idx[row] * wpr;
+            W* d = dst + row * wpr;
+            for (size_t w = w0 + t; w < w1; w += KB_GATHER_THREADS) d[w] = s[w];
+        }
+        return;
+    }
+    const unsigned len = (unsigned)wpr, rpb = KB_GATHER_THREADS / len, r = t / len, w = t % len;
+    if (r >= rpb) return;  // (the lanes past the last whole row; no barrier below)
+    const size_t groups = (count + rpb - 1) / rpb;
+    for (size_t g = blockIdx.x; g < groups; g += gridDim.x) {
+        const size_t row = g * rpb + r;
+        if (row < count) dst[row * wpr + w] = src[(size_t)idx[row] * wpr + w];
+    }
+}
+
 }  // namespace pq

@@ -7,6 +7,8 @@
 #pragma once
 
 #include <chrono>
+#include <cstdint>
+#include <stdexcept>
 
 #include "common.hpp"
 #include "dense_kkt_batch_device.hpp"
@@ -59,6 +61,67 @@ inline void kb_back(hipStream_t st, double* host, const double* dev, size_t coun
 {
     if (mem != PQ_MEM_DEVICE && count) PQ_HIP(hipMemcpyAsync(host, dev, sizeof(double) * count, hipMemcpyDeviceToHost, st));
 }
+
+// ---- clone by a list of instances, the three layers' one way: instance j of the new handle is instance host[j] of the source.  The public call of the layer that
+// is asked checks the list (kb_check_select, before the device is touched) and uploads it ONCE (dev, `count` ints, complete when the layers below are called); each
+// layer gathers its own per-instance buffers on the new handle's stream with kb_gather_rows, one launch per array, and its host images with kb_gather_host.
+// kb_gather_timed closes a layer's gathers: it waits for the stream and adds the time between the two events to sel.gather_ms.
+struct KbSelect {
+    const int *host, *dev;
+    int count;
+    double* gather_ms;  // null, or where every layer adds the device time of its gathers (hipEvents of the new handle around them, read after its wait)
+};
+inline int kb_check_list(const char* who, const int* idx, int count)
+{
+    if (!idx) return fail(PQ_ERR_INVALID, "%s: clone_select: idx is null", who);
+    if (count < 1) return fail(PQ_ERR_INVALID, "%s: clone_select: count = %d, count >= 1 wanted", who, count);
+    return PQ_OK;
+}
+inline int kb_check_select(const char* who, int batch, const int* idx, int count)
+{
+    if (int rc = kb_check_list(who, idx, count)) return rc;
+    for (int j = 0; j < count; ++j)
+        if (idx[j] < 0 || idx[j] >= batch) return fail(PQ_ERR_INVALID, "%s: clone_select: idx[%d] = %d outside [0, %d)", who, j, idx[j], batch);
+    return PQ_OK;
+}
+template <class W>
+void kb_gather_launch(hipStream_t st, void* dst, const void* src, const int* idx_d, size_t count, size_t row_bytes)
+{
+    const size_t wpr = row_bytes / sizeof(W);
+    const size_t work = wpr >= (size_t)KB_GATHER_THREADS ? count * ((wpr + KB_GATHER_CHUNK - 1) / KB_GATHER_CHUNK)
+                                                         : (count + KB_GATHER_THREADS / wpr - 1) / (KB_GATHER_THREADS / wpr);
+    const unsigned grid = (unsigned)(work < (size_t)KB_GATHER_MAX_GRID ? work : (size_t)KB_GATHER_MAX_GRID);
+    k_kb_gather_rows<W><<<grid, KB_GATHER_THREADS, 0, st>>>((W*)dst, (const W*)src, idx_d, count, wpr);
+    PQ_HIP(hipGetLastError());
+}
+// dst[j][0 .. row_bytes) = src[idx_d[j]][0 .. row_bytes) for j < count, device memory, on `st`.  An empty buffer launches nothing.  16-byte words when the row and
+// both bases allow (an array that stands behind another one in its allocation, as the fields of a VarSet do, need not be aligned to more than its element), else 8,
+// else 4.
+inline void kb_gather_rows(hipStream_t st, void* dst, const void* src, const int* idx_d, size_t count, size_t row_bytes)
+{
+    if (!count || !row_bytes) return;
+    const size_t a = row_bytes | (size_t)(uintptr_t)dst | (size_t)(uintptr_t)src;
+    if (a % 16 == 0) kb_gather_launch<uint4>(st, dst, src, idx_d, count, row_bytes);
+    else if (a % 8 == 0) kb_gather_launch<unsigned long long>(st, dst, src, idx_d, count, row_bytes);
+    else if (a % 4 == 0) kb_gather_launch<unsigned>(st, dst, src, idx_d, count, row_bytes);
+    else throw std::runtime_error("gather: a row that is no multiple of 4 bytes");
+}
+template <class T>
+void kb_gather_host(T* dst, const T* src, const int* idx, int count, size_t len)
+{
+    for (int j = 0; j < count && len; ++j) std::memcpy(dst + (size_t)j * len, src + (size_t)idx[j] * len, sizeof(T) * len);
+}
+inline void kb_gather_timed(const KbSelect& sel, hipStream_t st, hipEvent_t begin, hipEvent_t end)
+{
+    stream_wait(st);
+    if (!sel.gather_ms) return;
+    float ms = 0.f;
+    PQ_HIP(hipEventElapsedTime(&ms, begin, end));
+    *sel.gather_ms += ms;
+}
+// the layers below the one that was asked: a new handle that the caller owns from here on; they throw (nothing is left behind: the parts are held by their owners)
+pq_kkt_batch* kb_clone_rows(const pq_kkt_batch* k, const KbSelect& sel);
+pq_kktsys_batch* ksb_clone_rows(const pq_kktsys_batch* k, const KbSelect& sel);
 
 // ---- the end of every factorisation launch on k->st (dense_kkt_batch.hip): the status is read back, then `n_more` further read-backs of the caller ride on the same
 // wait, the stream is WAITED for, and the host side of the handle is left factored (computed, n_ok).  w0: when the call that the handle's events ev[0], ev[1] time

@@ -820,6 +820,61 @@ void ksb_refresh_host(pq_kktsys_batch* k)
     k->n_solved = solved; k->solved = true;
 }
 
+// instance j of the new handle is instance sel.host[j] of k, over a backend cloned by the same list.  Gathered: every state vector (P_diag and x_b_scaling
+// included), use_ref, the diagnostics of the last solve -- sinfo is three arrays of [batch] in one buffer and dinfo two, on the device and in their pinned images, one
+// gather each -- and with lists per instance the rows of tab (2 m + 4 n ints) and cnt_d with their host images, from which the summary counts are taken again.  Shared
+// lists: the one table is copied.  The work vectors, the refinement flags' staging, the host-mode staging and the events are only sized.
+pq_kktsys_batch* ksb_clone_rows(const pq_kktsys_batch* k, const KbSelect& sel)
+{
+    std::unique_ptr<pq_kkt_batch, KbDeleter> own(kb_clone_rows(k->kb.get(), sel));
+    PQ_HIP(hipSetDevice(k->device));
+    stream_wait(k->kb->st);
+    std::unique_ptr<pq_kktsys_batch> c(new pq_kktsys_batch);
+    const int count = sel.count;
+    const size_t b = (size_t)count, sb = (size_t)k->batch, stride = 2 * (size_t)k->m + 4 * (size_t)k->n;
+    c->device = k->device; c->batch = count; c->n = k->n; c->p = k->p; c->m = k->m;
+    c->settings = k->settings;
+    c->per_inst = k->per_inst; c->stale = k->stale; c->solved = k->solved; c->seen = k->seen;
+    if (k->per_inst) {
+        c->tab_h.resize(b * stride); c->cnt_h.resize(4 * b);
+        kb_gather_host(c->tab_h.data(), k->tab_h.data(), sel.host, count, stride);
+        kb_gather_host(c->cnt_h.data(), k->cnt_h.data(), sel.host, count, 4);
+        c->box_min[0] = c->box_min[1] = k->n;
+        for (int j = 0; j < count; ++j) {
+            const int* cj = c->cnt_h.data() + 4 * (size_t)j;
+            for (int q = 0; q < 4; ++q) c->cnt[q] = std::max(c->cnt[q], cj[q]);
+            c->box_min[0] = std::min(c->box_min[0], cj[2]);
+            c->box_min[1] = std::min(c->box_min[1], cj[3]);
+        }
+    } else {
+        for (int q = 0; q < 4; ++q) { c->cnt[q] = k->cnt[q]; c->idx[q] = k->idx[q]; }
+        c->box_min[0] = k->box_min[0]; c->box_min[1] = k->box_min[1];
+    }
+    c->kb = std::move(own);
+    ksb_alloc(c.get());
+    hipStream_t st = c->kb->st;
+    PQ_HIP(hipEventRecord(c->ev[0], st));
+    if (k->per_inst) {
+        kb_gather_rows(st, c->tab.p, k->tab.p, sel.dev, b, sizeof(int) * stride);
+        kb_gather_rows(st, c->cnt_d.p, k->cnt_d.p, sel.dev, b, sizeof(int) * 4);
+    } else if (k->tab.n) PQ_HIP(hipMemcpyAsync(c->tab.p, k->tab.p, k->tab.bytes(), hipMemcpyDeviceToDevice, st));
+    for (int s = 0; s < S_COUNT; ++s)
+        if (k->state[s].n) kb_gather_rows(st, c->state[s].p, k->state[s].p, sel.dev, b, sizeof(double) * ksb_state_len(k, s));
+    kb_gather_rows(st, c->use_ref.p, k->use_ref.p, sel.dev, b, sizeof(int));
+    for (int h = 0; h < 3; ++h) {
+        kb_gather_rows(st, c->sinfo.p + h * b, k->sinfo.p + h * sb, sel.dev, b, sizeof(int));
+        kb_gather_host(c->sinfo_h.p + h * b, k->sinfo_h.p + h * sb, sel.host, count, 1);
+    }
+    for (int h = 0; h < 2; ++h) {
+        kb_gather_rows(st, c->dinfo.p + h * b, k->dinfo.p + h * sb, sel.dev, b, sizeof(double));
+        kb_gather_host(c->dinfo_h.p + h * b, k->dinfo_h.p + h * sb, sel.host, count, 1);
+    }
+    for (int j = 0; j < count && k->solved; ++j) c->n_solved += c->sinfo_h.p[j] != 0;
+    PQ_HIP(hipEventRecord(c->ev[1], st));
+    kb_gather_timed(sel, st, c->ev[0], c->ev[1]);
+    return c.release();
+}
+
 }  // namespace pq
 
 extern "C" {
@@ -941,6 +996,19 @@ int pq_kktsys_batch_clone(const pq_kktsys_batch* k, pq_kktsys_batch** out)
         std::memcpy(c->dinfo_h.p, k->dinfo_h.p, sizeof(double) * 2 * (size_t)k->batch);
         stream_wait(st);
         *out = c.release();
+        return (int)PQ_OK;
+    });
+}
+
+int pq_kktsys_batch_clone_select(const pq_kktsys_batch* k, const int* idx, int count, pq_kktsys_batch** out)
+{
+    if (!k || !out) return fail(PQ_ERR_INVALID, "null argument");
+    if (int rc = kb_check_select("dense KKT system batch", k->batch, idx, count)) return rc;
+    return guarded([&] {
+        PQ_HIP(hipSetDevice(k->device));
+        DBuf<int> idx_d((size_t)count);
+        PQ_HIP(hipMemcpy(idx_d.p, idx, sizeof(int) * (size_t)count, hipMemcpyHostToDevice));
+        *out = ksb_clone_rows(k, KbSelect{idx, idx_d.p, count, nullptr});
         return (int)PQ_OK;
     });
 }

@@ -1068,6 +1068,8 @@ struct DsbProblem {
     size_t tab_stride() const { return 2 * (size_t)m + (per_inst ? 2 * (size_t)n : (size_t)cnt_h[2] + (size_t)cnt_h[3]); }
     int* list(int k, size_t row) { return lists_h.data() + (k == 0 ? 0 : k == 1 ? (size_t)rows * m : k == 2 ? 2 * (size_t)rows * m : 2 * (size_t)rows * m + (size_t)rows * n) + row * (k < 2 ? m : n); }
     int* fin(int k, size_t row) { return fin_h.data() + (list(k, row) - lists_h.data()); }
+    const int* list(int k, size_t row) const { return const_cast<DsbProblem*>(this)->list(k, row); }
+    const int* fin(int k, size_t row) const { return const_cast<DsbProblem*>(this)->fin(k, row); }
     KbBounds bounds() const
     {
         KbBounds b;
@@ -1117,6 +1119,7 @@ struct pq_solver_batch {
     double update_wall_ms = 0.0, update_device_ms = 0.0;
     double wall_ms = 0.0, device_ms = 0.0, factor_ms = 0.0, solve_ms = 0.0;
     int rounds = 0, launches = 0;
+    double clone_wall_ms = 0.0, clone_device_ms = 0.0;  // of the clone call that made this handle (0: it was created)
     pq_info invalid_info;  // what pq_solver_batch_info answers before a setup
     std::unique_ptr<DsbProblem> pr;
 };
@@ -1229,6 +1232,91 @@ void dsb_reset_state(pq_solver_batch* s)
     }
 }
 
+// ---- clone: the per-handle scalars as they stand (the settings, the trace rows and the bound-set mode a next setup would read, solved / updated and the stored
+// times); no device is touched
+pq_solver_batch* dsb_clone_scalars(const pq_solver_batch* s)
+{
+    std::unique_ptr<pq_solver_batch> c(new pq_solver_batch);
+    c->device = s->device; c->settings = s->settings; c->trace_max = s->trace_max; c->bound_sets = s->bound_sets;
+    c->solved = s->solved; c->updated = s->updated;
+    c->update_wall_ms = s->update_wall_ms; c->update_device_ms = s->update_device_ms;
+    c->wall_ms = s->wall_ms; c->device_ms = s->device_ms; c->factor_ms = s->factor_ms; c->solve_ms = s->solve_ms;
+    c->rounds = s->rounds; c->launches = s->launches;
+    c->invalid_info = s->invalid_info;
+    return c.release();
+}
+
+// the problem of s, instance idx[j] as instance j, into c (the list has been checked).  The KKT system and its backend are cloned by the same list
+// (ksb_clone_rows), which is uploaded once, here.  Gathered on the new system's stream: the ten fields of each of the six VarSets (each field is an array of
+// [batch][len] inside the set's one allocation, so one gather per field), the scaled vectors, x_b_scaling, the preconditioner, rho, delta, the state records and the
+// trace; with sets per instance the rows of tab (2 m + 2 n ints here) and cnt_d.  Shared sets: the one table is copied.  The host images follow by plain loops
+// (lists_h and fin_h are four arrays of `rows` rows each).  Sized as a setup sizes them and not copied: flags, the activity words, the counters, raw, dead_d,
+// bnd_h, try_h, keep_h and the events.
+void dsb_clone_problem(const pq_solver_batch* s, pq_solver_batch* c, const int* idx, int count)
+{
+    const DsbProblem* q = s->pr.get();
+    PQ_HIP(hipSetDevice(s->device));
+    DBuf<int> idx_d((size_t)count);
+    PQ_HIP(hipMemcpy(idx_d.p, idx, sizeof(int) * (size_t)count, hipMemcpyHostToDevice));
+    const auto w0 = std::chrono::steady_clock::now();
+    c->clone_device_ms = 0.0;
+    const KbSelect sel{idx, idx_d.p, count, &c->clone_device_ms};
+    const int n = q->n, p = q->p, m = q->m;
+    const size_t B = (size_t)count, N = (size_t)n + p + m;
+    std::unique_ptr<DsbProblem> d(new DsbProblem);
+    d->batch = count; d->n = n; d->p = p; d->m = m; d->trace_max = q->trace_max; d->per_inst = q->per_inst;
+    const int R = d->rows = q->per_inst ? count : 1;
+    d->try_h.assign(q->try_h.size(), 0);
+    d->dead_h.resize(B * m);
+    kb_gather_host(d->dead_h.data(), q->dead_h.data(), idx, count, (size_t)m);
+    if (q->per_inst) {
+        d->cnt_h.resize(4 * (size_t)R); d->lists_h.resize((size_t)R * (2 * (size_t)m + 2 * (size_t)n)); d->fin_h.resize(d->lists_h.size());
+        d->keep_h.assign(d->cnt_h.size() + d->lists_h.size(), 0);
+        kb_gather_host(d->cnt_h.data(), q->cnt_h.data(), idx, count, 4);
+        for (int k = 0; k < 4; ++k) {
+            kb_gather_host(d->list(k, 0), q->list(k, 0), idx, count, (size_t)(k < 2 ? m : n));
+            kb_gather_host(d->fin(k, 0), q->fin(k, 0), idx, count, (size_t)(k < 2 ? m : n));
+        }
+        d->tab_h.resize((size_t)R * d->tab_stride());
+        kb_gather_host(d->tab_h.data(), q->tab_h.data(), idx, count, d->tab_stride());
+    } else {
+        d->cnt_h = q->cnt_h; d->lists_h = q->lists_h; d->fin_h = q->fin_h; d->tab_h = q->tab_h;
+    }
+    d->ks.reset(ksb_clone_rows(q->ks.get(), sel));  // (waits for the source's stream first)
+    hipStream_t st = ksb_stream(d->ks.get());
+    for (Event& e : d->ev) e = Event(0);
+    size_t len[10];
+    vars_lens((size_t)n, (size_t)p, (size_t)m, len);
+    PQ_HIP(hipEventRecord(d->ev[0], st));
+    for (int v = 0; v < 6; ++v) {
+        d->sets[v].alloc(B, n, p, m, st);
+        for (int f = 0; f < 10; ++f) kb_gather_rows(st, vars_field(d->sets[v].v, f), vars_field(q->sets[v].v, f), sel.dev, B, sizeof(double) * len[f]);
+    }
+    auto rows = [&](DBuf<double>& dst, const DBuf<double>& src, size_t l) {
+        dst.alloc(B * l);
+        kb_gather_rows(st, dst.p, src.p, sel.dev, B, sizeof(double) * l);
+    };
+    rows(d->c, q->c, n); rows(d->b, q->b, p); rows(d->h_l, q->h_l, m); rows(d->h_u, q->h_u, m); rows(d->x_l, q->x_l, n); rows(d->x_u, q->x_u, n); rows(d->xbs, q->xbs, n);
+    rows(d->pd, q->pd, N); rows(d->pdi, q->pdi, N); rows(d->pdb, q->pdb, n); rows(d->pdbi, q->pdbi, n); rows(d->pc, q->pc, 1); rows(d->pc_inv, q->pc_inv, 1);
+    rows(d->rho, q->rho, 1); rows(d->delta, q->delta, 1); rows(d->trace, q->trace, (size_t)q->trace_max * 11);
+    d->tab.alloc(d->tab_h.size());
+    if (q->per_inst) {
+        d->cnt_d.alloc(4 * B);
+        kb_gather_rows(st, d->tab.p, q->tab.p, sel.dev, B, sizeof(int) * d->tab_stride());
+        kb_gather_rows(st, d->cnt_d.p, q->cnt_d.p, sel.dev, B, sizeof(int) * 4);
+    } else if (q->tab.n) PQ_HIP(hipMemcpyAsync(d->tab.p, q->tab.p, q->tab.bytes(), hipMemcpyDeviceToDevice, st));
+    d->flags.alloc(B); d->act.alloc(2 * B); d->counters.alloc(8); d->counters_h.alloc(4);
+    d->flags.zero(st); d->act.zero(st); d->counters.zero(st);
+    d->dead_d.alloc(B * m); d->raw.alloc(B * n * (size_t)std::max(n, std::max(p, m))); d->bnd_h.alloc(2 * B * (2 * (size_t)m + 2 * (size_t)n));
+    d->state.alloc(B); d->state_h.alloc(B);
+    kb_gather_rows(st, d->state.p, q->state.p, sel.dev, B, sizeof(DsbState));
+    kb_gather_host(d->state_h.p, q->state_h.p, idx, count, 1);
+    PQ_HIP(hipEventRecord(d->ev[1], st));
+    kb_gather_timed(sel, st, d->ev[0], d->ev[1]);
+    c->clone_wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
+    c->pr = std::move(d);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1253,6 +1341,35 @@ void pq_solver_batch_destroy(pq_solver_batch* s)
     if (!s) return;
     (void)hipSetDevice(s->device);
     delete s;
+}
+
+int pq_solver_batch_clone(const pq_solver_batch* s, pq_solver_batch** out)
+{
+    if (!s || !out) return fail(PQ_ERR_INVALID, "null argument");
+    return guarded([&] {
+        std::unique_ptr<pq_solver_batch> c(dsb_clone_scalars(s));
+        if (s->pr) {  // the identity list
+            std::vector<int> all((size_t)s->pr->batch);
+            for (size_t i = 0; i < all.size(); ++i) all[i] = (int)i;
+            dsb_clone_problem(s, c.get(), all.data(), (int)all.size());
+        }
+        *out = c.release();
+        return (int)PQ_OK;
+    });
+}
+
+int pq_solver_batch_clone_select(const pq_solver_batch* s, const int* idx, int count, pq_solver_batch** out)
+{
+    if (!s || !out) return fail(PQ_ERR_INVALID, "null argument");
+    if (int rc = kb_check_list("dense solver batch", idx, count)) return rc;
+    if (!s->pr) return fail(PQ_ERR_INVALID, "dense solver batch: clone_select before setup (there is no instance to select)");
+    if (int rc = kb_check_select("dense solver batch", s->pr->batch, idx, count)) return rc;
+    return guarded([&] {
+        std::unique_ptr<pq_solver_batch> c(dsb_clone_scalars(s));
+        dsb_clone_problem(s, c.get(), idx, count);
+        *out = c.release();
+        return (int)PQ_OK;
+    });
 }
 
 pq_settings* pq_solver_batch_settings(pq_solver_batch* s)
@@ -1694,6 +1811,13 @@ int pq_solver_batch_dims(const pq_solver_batch* s, int* batch, int* n, int* p, i
     if (n) *n = s->pr->n;
     if (p) *p = s->pr->p;
     if (m) *m = s->pr->m;
+    return PQ_OK;
+}
+
+int pq_solver_batch_clone_ms(const pq_solver_batch* s, double out2[2])
+{
+    if (!s || !out2) return fail(PQ_ERR_INVALID, "null argument");
+    out2[0] = s->clone_wall_ms; out2[1] = s->clone_device_ms;
     return PQ_OK;
 }
 
