@@ -341,6 +341,10 @@ int pq_kktsys_last_solve_stats(const pq_kktsys *k, int *refine_steps, int *backe
 /* ||rhs_bar - K_cond * lhs||_inf and ||rhs_bar||_inf of the last solve, recomputed on device via
  * mul_condensed_kkt (kkt_system.hpp:507-536); the harness's parity metric (SURVEY.md 8b last row) */
 int pq_kktsys_condensed_residual(pq_kktsys *k, double *res_inf, double *rhs_inf);
+/* test read-back of a state vector into HOST memory, after the handle's stream: x_reg (n; static regularisation of the refinement branch included), z_reg (m; without
+ * it), rhs_x_bar (n), rhs_z_bar (m) and lhs_z (m) of the last solve.  PQ_ERR_INVALID before the first factorisation, and for the last three before the first solve. */
+enum { PQ_KKTSYS_X_REG = 0, PQ_KKTSYS_Z_REG = 1, PQ_KKTSYS_RHS_X_BAR = 2, PQ_KKTSYS_RHS_Z_BAR = 3, PQ_KKTSYS_LHS_Z = 4 };
+int pq_kktsys_state(pq_kktsys *k, int what, double *out_host);
 int pq_kktsys_synchronize(pq_kktsys *k);
 
 /* ===================== Solver: piqp::DenseSolver / SparseSolver front-end (caller of the hot path) ===== */

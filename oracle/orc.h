@@ -231,11 +231,23 @@ int orc_kkt_system_solve(orc_kkt_system *k, const orc_data *d, const orc_setting
                          orc_vars *lhs); /* :213-369 ; lhs pointers may be swapped */
 void orc_kkt_system_mul(orc_kkt_system *k, const orc_data *d, const orc_vars *lhs, orc_vars *rhs); /* :392-425 */
 int orc_kkt_system_last_refine_steps(const orc_kkt_system *k);
+/* records of the refinement loop of the last solve (:256-301): the refine error of the iterate it kept, rhs_norm (:259), and how it ended */
+enum {
+    ORC_REFINE_EXIT_TOL_AT_ONCE = 0,   /* tolerance met before any step */
+    ORC_REFINE_EXIT_TOL = 1,           /* tolerance met after at least one step */
+    ORC_REFINE_EXIT_STALL_KEPT = 2,    /* improvement rate in (1, min_improvement_rate): the last iterate is kept */
+    ORC_REFINE_EXIT_STALL_DROPPED = 3, /* improvement rate <= 1: the last iterate is dropped */
+    ORC_REFINE_EXIT_MAX_ITER = 4       /* iterative_refinement_max_iter used up */
+};
+double orc_kkt_system_last_refine_error(const orc_kkt_system *k);
+double orc_kkt_system_last_rhs_norm(const orc_kkt_system *k);
+int orc_kkt_system_last_refine_exit(const orc_kkt_system *k); /* -1: no refinement, or a non-finite refine error */
 int orc_kkt_system_solve_copy(orc_kkt_system *k, const orc_data *d, const orc_settings *s, const orc_vars *rhs, orc_vars *out);
 const double *orc_kkt_system_x_reg(const orc_kkt_system *k);
 const double *orc_kkt_system_z_reg(const orc_kkt_system *k);
 const double *orc_kkt_system_rhs_x_bar(const orc_kkt_system *k);
 const double *orc_kkt_system_rhs_z_bar(const orc_kkt_system *k);
+const double *orc_kkt_system_lhs_z(const orc_kkt_system *k);
 /* flat dispatch through the backend vtable (FFI convenience) */
 orc_kkt *orc_kkt_clone(const orc_kkt *k);
 void orc_kkt_destroy(orc_kkt *k);

@@ -27,6 +27,10 @@ struct orc_kkt_system {
     orc_kkt *kkt_solver;
     int last_refine_steps;
     int backend_solves;
+    /* records of the last solve's refinement loop (nothing below is computed for them) */
+    double last_refine_error; /* the refine error of the iterate the loop kept; 0 without refinement */
+    double last_rhs_norm;     /* :259; 0 without refinement */
+    int last_refine_exit;     /* how the loop ended, ORC_REFINE_EXIT_*; -1 without refinement or after a non-finite error */
 };
 
 static double *dz(size_t n)
@@ -129,6 +133,9 @@ void orc_kkt_system_free(orc_kkt_system *k)
 orc_kkt *orc_kkt_system_backend(orc_kkt_system *k) { return k->kkt_solver; }
 int orc_kkt_system_last_refine_steps(const orc_kkt_system *k) { return k->last_refine_steps; }
 int orc_kkt_system_backend_solves(const orc_kkt_system *k) { return k->backend_solves; }
+double orc_kkt_system_last_refine_error(const orc_kkt_system *k) { return k->last_refine_error; }
+double orc_kkt_system_last_rhs_norm(const orc_kkt_system *k) { return k->last_rhs_norm; }
+int orc_kkt_system_last_refine_exit(const orc_kkt_system *k) { return k->last_refine_exit; }
 
 /* kkt_system.hpp:134-141 */
 void orc_kkt_system_update_data(orc_kkt_system *k, const orc_data *d, int options)
@@ -249,6 +256,7 @@ int orc_kkt_system_solve(orc_kkt_system *k, const orc_data *d, const orc_setting
     orc_kkt *b = k->kkt_solver;
     double **lhs_z = &k->work_z; /* Vec<T>& lhs_z = work_z (may be swapped with ref_lhs_z) */
     k->last_refine_steps = 0;
+    k->last_refine_error = 0.0; k->last_rhs_norm = 0.0; k->last_refine_exit = -1;
 
     /* :219-234 rhs_z_bar */
     for (int i = 0; i < m; i++) k->rhs_z_bar[i] = 0.0;
@@ -282,9 +290,15 @@ int orc_kkt_system_solve(orc_kkt_system *k, const orc_data *d, const orc_setting
         double rhs_norm = inf_norm3(k->rhs_x_bar, n, rhs->y, d->p, k->rhs_z_bar, m);
         double refine_error = get_refine_error(k, d, lhs->x, lhs->y, *lhs_z, k->rhs_x_bar, rhs->y, k->rhs_z_bar,
                                                k->ref_err_x, k->ref_err_y, k->ref_err_z);
+        k->last_rhs_norm = rhs_norm;
+        k->last_refine_error = refine_error;
         if (!isfinite(refine_error)) return 0;
+        k->last_refine_exit = ORC_REFINE_EXIT_MAX_ITER;
         for (int it = 0; it < s->iterative_refinement_max_iter; it++) {
-            if (refine_error <= s->iterative_refinement_eps_abs + s->iterative_refinement_eps_rel * rhs_norm) break;
+            if (refine_error <= s->iterative_refinement_eps_abs + s->iterative_refinement_eps_rel * rhs_norm) {
+                k->last_refine_exit = it == 0 ? ORC_REFINE_EXIT_TOL_AT_ONCE : ORC_REFINE_EXIT_TOL;
+                break;
+            }
             double prev_refine_error = refine_error;
             b->solve(b, d, k->ref_err_x, k->ref_err_y, k->ref_err_z, k->ref_lhs_x, k->ref_lhs_y, k->ref_lhs_z);
             k->backend_solves++;
@@ -294,15 +308,20 @@ int orc_kkt_system_solve(orc_kkt_system *k, const orc_data *d, const orc_setting
             for (int i = 0; i < m; i++) k->ref_lhs_z[i] += (*lhs_z)[i];
             refine_error = get_refine_error(k, d, k->ref_lhs_x, k->ref_lhs_y, k->ref_lhs_z, k->rhs_x_bar, rhs->y,
                                             k->rhs_z_bar, k->ref_err_x, k->ref_err_y, k->ref_err_z);
-            if (!isfinite(refine_error)) return 0;
+            if (!isfinite(refine_error)) { k->last_refine_exit = -1; return 0; }
             double improvement_rate = prev_refine_error / refine_error;
             if (improvement_rate < s->iterative_refinement_min_improvement_rate) {
                 if (improvement_rate > 1.0) {
                     SWAPP(lhs->x, k->ref_lhs_x); SWAPP(lhs->y, k->ref_lhs_y); SWAPP(*lhs_z, k->ref_lhs_z);
+                    k->last_refine_error = refine_error;
+                    k->last_refine_exit = ORC_REFINE_EXIT_STALL_KEPT;
+                } else {
+                    k->last_refine_exit = ORC_REFINE_EXIT_STALL_DROPPED;
                 }
                 break;
             }
             SWAPP(lhs->x, k->ref_lhs_x); SWAPP(lhs->y, k->ref_lhs_y); SWAPP(*lhs_z, k->ref_lhs_z);
+            k->last_refine_error = refine_error;
         }
     } else {
         if (!all_finite(lhs->x, n) || !all_finite(lhs->y, d->p) || !all_finite(*lhs_z, m)) return 0;
@@ -430,3 +449,5 @@ const double *orc_kkt_system_x_reg(const orc_kkt_system *k) { return k->m_x_reg;
 const double *orc_kkt_system_z_reg(const orc_kkt_system *k) { return k->m_z_reg; }
 const double *orc_kkt_system_rhs_x_bar(const orc_kkt_system *k) { return k->rhs_x_bar; }
 const double *orc_kkt_system_rhs_z_bar(const orc_kkt_system *k) { return k->rhs_z_bar; }
+/* lhs_z of the last solve (the reference's work_z, after the refinement loop's swaps) */
+const double *orc_kkt_system_lhs_z(const orc_kkt_system *k) { return k->work_z; }

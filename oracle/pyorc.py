@@ -167,7 +167,13 @@ def _bind(L):
     L.orc_kkt_system_last_refine_steps.argtypes = [vp]
     L.orc_kkt_system_backend_solves.restype = C.c_int
     L.orc_kkt_system_backend_solves.argtypes = [vp]
-    for nm in ("x_reg", "z_reg", "rhs_x_bar", "rhs_z_bar"):
+    L.orc_kkt_system_last_refine_error.restype = C.c_double
+    L.orc_kkt_system_last_refine_error.argtypes = [vp]
+    L.orc_kkt_system_last_rhs_norm.restype = C.c_double
+    L.orc_kkt_system_last_rhs_norm.argtypes = [vp]
+    L.orc_kkt_system_last_refine_exit.restype = C.c_int
+    L.orc_kkt_system_last_refine_exit.argtypes = [vp]
+    for nm in ("x_reg", "z_reg", "rhs_x_bar", "rhs_z_bar", "lhs_z"):
         f = getattr(L, "orc_kkt_system_" + nm)
         f.restype = _dp
         f.argtypes = [vp]
@@ -490,7 +496,12 @@ class KKTSystem:
     def z_reg(self): return _view(self.L.orc_kkt_system_z_reg(self.ptr), self.data.m).copy()
     def rhs_x_bar(self): return _view(self.L.orc_kkt_system_rhs_x_bar(self.ptr), self.data.n).copy()
     def rhs_z_bar(self): return _view(self.L.orc_kkt_system_rhs_z_bar(self.ptr), self.data.m).copy()
+    def lhs_z(self): return _view(self.L.orc_kkt_system_lhs_z(self.ptr), self.data.m).copy()
     def last_refine_steps(self): return self.L.orc_kkt_system_last_refine_steps(self.ptr)
+    def last_refine_error(self): return self.L.orc_kkt_system_last_refine_error(self.ptr)
+    def last_rhs_norm(self): return self.L.orc_kkt_system_last_rhs_norm(self.ptr)
+    def last_refine_exit(self): return self.L.orc_kkt_system_last_refine_exit(self.ptr)
+    def backend_solves(self): return self.L.orc_kkt_system_backend_solves(self.ptr)
 
 
 class Solver:

@@ -108,7 +108,7 @@ SYMBOLS = [
     "pq_kktsys_create_dense", "pq_kktsys_create_sparse", "pq_kktsys_clone", "pq_kktsys_destroy",
     "pq_kktsys_set_pointer_mode", "pq_kktsys_backend", "pq_kktsys_update_data_dense", "pq_kktsys_update_data_sparse",
     "pq_kktsys_update_scalings_and_factor", "pq_kktsys_solve", "pq_kktsys_mul", "pq_kktsys_last_solve_stats",
-    "pq_kktsys_condensed_residual", "pq_kktsys_synchronize",
+    "pq_kktsys_condensed_residual", "pq_kktsys_synchronize", "pq_kktsys_state",
     "pq_solver_create", "pq_solver_destroy", "pq_solver_clone", "pq_solver_settings", "pq_solver_setup_dense",
     "pq_solver_setup_sparse", "pq_solver_update_dense", "pq_solver_update_sparse", "pq_solver_solve", "pq_solver_info",
     "pq_solver_get_result", "pq_solver_dims", "pq_solver_set_trace", "pq_solver_trace_rows", "pq_solver_partition", "pq_solver_set_exchange",
@@ -296,6 +296,7 @@ def load():
     L.pq_kktsys_mul.argtypes = [vp, C.POINTER(Vars), C.POINTER(Vars)]
     L.pq_kktsys_last_solve_stats.argtypes = [vp, _ip, _ip, _dp, _dp]
     L.pq_kktsys_condensed_residual.argtypes = [vp, _dp, _dp]
+    L.pq_kktsys_state.argtypes = [vp, C.c_int, vp]
     L.pq_kktsys_synchronize.argtypes = [vp]
     L.pq_solver_create.argtypes = [C.POINTER(vp), C.c_int]
     L.pq_solver_destroy.argtypes = [vp]

@@ -831,6 +831,15 @@ int pq_kktsys_condensed_residual(pq_kktsys* k, double* res_inf, double* rhs_inf)
     return guarded([&] { k->impl->condensed_residual(k->last_lhs_x, k->last_lhs_y, res_inf, rhs_inf); return (int)PQ_OK; });
 }
 
+int pq_kktsys_state(pq_kktsys* k, int what, double* out_host)
+{
+    if (!k || !out_host) return fail(PQ_ERR_INVALID, "null argument");
+    if (what < PQ_KKTSYS_X_REG || what > PQ_KKTSYS_LHS_Z) return fail(PQ_ERR_INVALID, "KKT system: state %d: 0 .. 4 wanted", what);
+    if (!k->impl->factored) return fail(PQ_ERR_INVALID, "KKT system: no factorisation yet");
+    if (what >= PQ_KKTSYS_RHS_X_BAR && !k->impl->solved) return fail(PQ_ERR_INVALID, "KKT system: no solve yet");
+    return guarded([&] { k->impl->state(what, out_host); return (int)PQ_OK; });
+}
+
 int pq_kktsys_synchronize(pq_kktsys* k)
 {
     if (!k) return fail(PQ_ERR_INVALID, "null argument");

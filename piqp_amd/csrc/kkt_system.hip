@@ -26,42 +26,6 @@ __global__ void k_scatter_pos(int cnt, const int* __restrict__ idx, int* __restr
     if (i < cnt) pos[idx[i]] = i;
 }
 
-// ---- kkt_system.hpp:150-159 copies + reciprocals -------------------------------------------------
-__global__ void k_copy_and_invert(int n, const double* __restrict__ s, const double* __restrict__ z, double* __restrict__ s_out, double* __restrict__ zinv_out)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) { s_out[i] = s[i]; zinv_out[i] = 1.0 / z[i]; }
-}
-
-// ---- kkt_system.hpp:161-175 x_reg ----------------------------------------------------------------
-__global__ void k_x_reg(int n, double rho, double delta, const int* __restrict__ pos_l, const int* __restrict__ pos_u, const double* __restrict__ xbs,
-                        const double* __restrict__ s_bl, const double* __restrict__ zinv_bl, const double* __restrict__ s_bu, const double* __restrict__ zinv_bu,
-                        double* __restrict__ x_reg)
-{
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= n) return;
-    double v = rho;
-    const double sc = xbs[idx];
-    const int il = pos_l[idx], iu = pos_u[idx];
-    if (il >= 0) v += sc * sc / (zinv_bl[il] * s_bl[il] + delta);
-    if (iu >= 0) v += sc * sc / (zinv_bu[iu] * s_bu[iu] + delta);
-    x_reg[idx] = v;
-}
-
-// ---- kkt_system.hpp:177-193 z_reg ----------------------------------------------------------------
-__global__ void k_z_reg(int m, double delta, const int* __restrict__ has_l, const int* __restrict__ has_u, const double* __restrict__ s_l, const double* __restrict__ zinv_l,
-                        const double* __restrict__ s_u, const double* __restrict__ zinv_u, double* __restrict__ z_reg, double* __restrict__ z_reg_iter_ref)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m) return;
-    double v = 0.0;
-    if (has_l[i] >= 0) v += 1.0 / (zinv_l[i] * s_l[i] + delta);
-    if (has_u[i] >= 0) v += 1.0 / (zinv_u[i] * s_u[i] + delta);
-    v = 1.0 / v;
-    z_reg[i] = v;
-    z_reg_iter_ref[i] = v;
-}
-
 // ---- inf-norm reductions (NaN-propagating), result atomically max-combined as ordered bits ---------
 __device__ __forceinline__ double wave_max_nan(double a)
 {
@@ -100,37 +64,8 @@ __global__ void k_add_scalar(int n, double v, double* __restrict__ a)
     if (i < n) a[i] += v;
 }
 
-// ---- kkt_system.hpp:219-234 rhs_z_bar ---------------------------------------------------------------
-__global__ void k_rhs_z_bar(int m, double delta, const int* __restrict__ has_l, const int* __restrict__ has_u, const double* __restrict__ s_l, const double* __restrict__ zinv_l,
-                            const double* __restrict__ s_u, const double* __restrict__ zinv_u, const double* __restrict__ z_reg, const double* __restrict__ r_z_l,
-                            const double* __restrict__ r_s_l, const double* __restrict__ r_z_u, const double* __restrict__ r_s_u, double* __restrict__ out)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m) return;
-    double v = 0.0;
-    if (has_l[i] >= 0) v -= 1.0 / (zinv_l[i] * s_l[i] + delta) * (r_z_l[i] - zinv_l[i] * r_s_l[i]);
-    if (has_u[i] >= 0) v += 1.0 / (zinv_u[i] * s_u[i] + delta) * (r_z_u[i] - zinv_u[i] * r_s_u[i]);
-    out[i] = v * z_reg[i];
-}
-
-// ---- kkt_system.hpp:236-252 rhs_x_bar ---------------------------------------------------------------
-__global__ void k_rhs_x_bar(int n, double delta, const int* __restrict__ pos_l, const int* __restrict__ pos_u, const double* __restrict__ xbs, const double* __restrict__ s_bl,
-                            const double* __restrict__ zinv_bl, const double* __restrict__ s_bu, const double* __restrict__ zinv_bu, const double* __restrict__ r_x,
-                            const double* __restrict__ r_z_bl, const double* __restrict__ r_s_bl, const double* __restrict__ r_z_bu, const double* __restrict__ r_s_bu,
-                            double* __restrict__ out)
-{
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= n) return;
-    double v = r_x[idx];
-    const int il = pos_l[idx], iu = pos_u[idx];
-    if (il >= 0) v -= xbs[idx] * (r_z_bl[il] - zinv_bl[il] * r_s_bl[il]) / (s_bl[il] * zinv_bl[il] + delta);
-    if (iu >= 0) v += xbs[idx] * (r_z_bu[iu] - zinv_bu[iu] * r_s_bu[iu]) / (s_bu[iu] * zinv_bu[iu] + delta);
-    out[idx] = v;
-}
-
-
-// ---- fused launches of the per-iteration elementwise work (one launch instead of six / two / six; every formula is the one of the
-// single-purpose kernel above it replaces, same operand order, so the values are bitwise the same) -------------------------------
+// ---- fused launches of the per-iteration elementwise work (one launch instead of six / two / six; every formula keeps the operand order of
+// the reference loop body it restates, so the values are bitwise the reference's) -------------------------------------------------
 // kkt_system.hpp:150-193: copies + reciprocals + x_reg + z_reg.  x_reg needs the box slacks of OTHER indices, so it recomputes their
 // reciprocals from the caller's z instead of reading what a neighbouring thread is writing.
 __global__ void k_scalings_fused(int n, int m, int nxl, int nxu, double rho, double delta, const double* __restrict__ v_s_l, const double* __restrict__ v_z_l,
@@ -451,6 +386,7 @@ std::unique_ptr<KKTSystem> KKTSystem::clone() const
     auto k = std::make_unique<KKTSystem>(kkt_solver->clone(), settings_);
     k->m_rho = m_rho; k->m_delta = m_delta; k->use_iterative_refinement = use_iterative_refinement;
     k->n_h_l = n_h_l; k->n_h_u = n_h_u; k->n_x_l = n_x_l; k->n_x_u = n_x_u;
+    k->factored = factored;  // (solved stays false: lhs_z_buf is a work buffer, not copied)
     auto cpd = [&](DBuf<double>& d, const DBuf<double>& s) { if (s.n) PQ_HIP(hipMemcpyAsync(d.p, s.p, s.bytes(), hipMemcpyDeviceToDevice, k->st_)); };
     auto cpi = [&](DBuf<int>& d, const DBuf<int>& s) { if (s.n) PQ_HIP(hipMemcpyAsync(d.p, s.p, s.bytes(), hipMemcpyDeviceToDevice, k->st_)); };
     cpd(k->m_s_l, m_s_l); cpd(k->m_s_u, m_s_u); cpd(k->m_s_bl, m_s_bl); cpd(k->m_s_bu, m_s_bu);
@@ -500,6 +436,7 @@ bool KKTSystem::update_scalings_and_factor(bool iterative_refinement, double rho
         LAUNCH1(k_add_scalar, m, st_, m, reg, m_z_reg_iter_ref);
     }
     use_iterative_refinement = iterative_refinement;
+    factored = true;
     return kkt_solver->update_scalings_and_factor(delta_reg, m_x_reg.p, m_z_reg_iter_ref);
 }
 
@@ -548,6 +485,7 @@ bool KKTSystem::solve(const pq_vars& rhs, pq_vars& lhs)
     kkt_solver->solve(rhs_x_bar.p, rhs.y, rhs_z_bar.p, lhs.x, lhs.y, lhs_z);
     last_backend_solves++;
     last_rhs_y = rhs_y_keep.p;
+    solved = true;
 
     if (use_iterative_refinement) {
         // :259  rhs_norm
@@ -628,6 +566,17 @@ void KKTSystem::condensed_residual(const double* lhs_x, const double* lhs_y, dou
     LAUNCH1(k_absmax, m_, st_, m_, rhs_z_bar.p, (const double*)nullptr, scal_d.p);
     *rhs_inf = read_scalar_max(0);
     *res_inf = get_refine_error(lhs_x, lhs_y, lhs_z_buf.p, rhs_x_bar.p, last_rhs_y, rhs_z_bar.p, ref_err_x.p, ref_err_y.p, ref_err_z.p);
+}
+
+// read-back of a state vector for tests: x_reg as handed to the backend (static regularisation included), z_reg without it, the condensed right-hand side
+// and lhs_z of the last solve
+void KKTSystem::state(int what, double* out_host)
+{
+    PQ_HIP(hipSetDevice(dev_));
+    const DBuf<double>& src = what == PQ_KKTSYS_X_REG ? m_x_reg : what == PQ_KKTSYS_Z_REG ? m_z_reg : what == PQ_KKTSYS_RHS_X_BAR ? rhs_x_bar : what == PQ_KKTSYS_RHS_Z_BAR ? rhs_z_bar : lhs_z_buf;
+    const int len = (what == PQ_KKTSYS_X_REG || what == PQ_KKTSYS_RHS_X_BAR) ? n_ : m_;
+    if (len > 0) PQ_HIP(hipMemcpyAsync(out_host, src.p, sizeof(double) * len, hipMemcpyDeviceToHost, st_));
+    stream_wait(st_);
 }
 
 // kkt_system.hpp:392-425

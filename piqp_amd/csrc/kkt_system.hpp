@@ -30,6 +30,7 @@ public:
     // kkt_system.hpp:392-425
     void mul(const pq_vars& lhs, pq_vars& rhs);
     void condensed_residual(const double* lhs_x, const double* lhs_y, double* res_inf, double* rhs_inf);
+    void state(int what, double* out_host);  // PQ_KKTSYS_X_REG .. PQ_KKTSYS_LHS_Z, copied to host memory after the handle's stream
 
     KKTSolverBase* backend() { return kkt_solver.get(); }
     hipStream_t stream() const { return st_; }
@@ -44,6 +45,7 @@ public:
     int last_refine_steps = 0, last_backend_solves = 0;
     double last_refine_error = 0.0, last_rhs_norm = 0.0;
     const double* last_rhs_y = nullptr;
+    bool factored = false, solved = false;  // update_scalings_and_factor / solve has been called on this object
 
 private:
     void alloc();

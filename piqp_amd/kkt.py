@@ -518,6 +518,7 @@ class KKTSystem(_Handle):
             if self._mode == MEM_DEVICE:
                 import torch
                 lhs = {k: torch.zeros(sz, dtype=torch.float64, device=rhs["x"].device) for k, sz in var_sizes(self.n, self.p, self.m).items()}
+                sync_current_stream(rhs["x"].device)  # (torch zeroes them on its own stream; the handle writes them on another)
             else:
                 lhs = Variables.zeros(self.n, self.p, self.m)
         rs, ls = Variables.to_struct(rhs), Variables.to_struct(lhs)
@@ -529,6 +530,7 @@ class KKTSystem(_Handle):
         if self._mode == MEM_DEVICE:
             import torch
             rhs = {k: torch.zeros(sz, dtype=torch.float64, device=lhs["x"].device) for k, sz in var_sizes(self.n, self.p, self.m).items()}
+            sync_current_stream(lhs["x"].device)  # (as in solve)
         else:
             rhs = Variables.zeros(self.n, self.p, self.m)
         ls, rs = Variables.to_struct(lhs), Variables.to_struct(rhs)
@@ -544,6 +546,16 @@ class KKTSystem(_Handle):
         r, q = C.c_double(), C.c_double()
         check(self.L.pq_kktsys_condensed_residual(self.h, C.byref(r), C.byref(q)))
         return r.value, q.value
+
+    STATE = dict(X_REG=0, Z_REG=1, RHS_X_BAR=2, RHS_Z_BAR=3, LHS_Z=4)  # PQ_KKTSYS_*
+
+    def state(self, what):
+        """a state vector as a numpy array (pq_kktsys_state): "X_REG" (static regularisation included), "Z_REG" (without it), and of the last solve
+        "RHS_X_BAR", "RHS_Z_BAR", "LHS_Z"; `what` may also be the number"""
+        what = self.STATE.get(what, what)
+        a = np.zeros(max(self.n if what in (0, 2) else self.m, 1))
+        check(self.L.pq_kktsys_state(self.h, int(what), a.ctypes.data), "pq_kktsys_state")
+        return a[:self.n if what in (0, 2) else self.m]
 
     def synchronize(self):
         check(self.L.pq_kktsys_synchronize(self.h))
