@@ -456,8 +456,8 @@ int pq_solver_comm_info(pq_solver *s, int out[4]); /* as pq_kkt_comm_info */
 /* The reference has no batch API (one SolverBase per QP, solver.hpp:42); this is the device-side equivalent of
  *     for (i < batch) { SparseSolver s; s.settings() = settings; s.setup(P_i, c_i, A_i, ...); s.solve(); }
  * with kkt_solver = sparse_multistage (the default of pq_batch_create), sparse_ldlt or sparse_ldlt_exact: one workgroup runs the whole
- * interior-point method (solver.hpp:379-1259) of one QP, the batch is the grid.  All instances share the sparsity patterns and the set of
- * finite bounds.  settings->kkt_solver, read by pq_batch_setup_sparse, picks the KKT backend of the handle:
+ * interior-point method (solver.hpp:379-1259) of one QP, the batch is the grid.  All instances share the sparsity patterns and, unless
+ * pq_batch_set_bound_sets says otherwise, the set of finite bounds.  settings->kkt_solver, read by pq_batch_setup_sparse, picks the KKT backend of the handle:
  *   PQ_SPARSE_MULTISTAGE                    the multistage chain Cholesky (sparse/multistage_kkt.hpp) of the stage structure found in the pattern;
  *   PQ_SPARSE_LDLT / PQ_SPARSE_LDLT_EXACT   the reference's sparse_ldlt: the full KKT matrix in AMD order, up-looking LDLt (sparse/kkt.hpp, ldlt.hpp),
  *                                           every factor and every solve bitwise the reference's; one 64-thread workgroup per QP, n + p + m <= 8192.
@@ -467,6 +467,28 @@ typedef struct pq_batch pq_batch;
 int pq_batch_create(pq_batch **out, int device);
 void pq_batch_destroy(pq_batch *s);
 pq_settings *pq_batch_settings(pq_batch *s); /* solver.hpp:65 settings(), shared by all instances */
+/* Who owns the set of finite bounds: PQ_BOUND_SETS_SHARED (the default) or PQ_BOUND_SETS_PER_INSTANCE, the constants and their meaning as at
+ * pq_solver_batch_set_bound_sets.  Shared: setup refuses an instance whose finite bounds differ from instance 0's and the updates refuse a bound that turns
+ * finite or infinite.  Per instance: every instance has the lists SparseSolver would hold for its own vectors (sparse/data.hpp:103-210) at setup and after every
+ * update, so a row of G or a box can be switched off in some instances with -/+ infinity and come back later; nothing is refused on finiteness.  The mode is read by
+ * pq_batch_setup_sparse; a handle that is set up keeps the mode its setup read.  The kernel variant, the working-set mode and the threads per QP do not depend on
+ * it.  PQ_ERR_INVALID for a NULL handle or any other value.
+ * UPDATES IN PER-INSTANCE MODE (pq_batch_update, pq_batch_update_data and their _mem forms): the lists the reference would hold after the call REPLACE the
+ * instance's own, by the rules stated at pq_solver_batch_update_dense -- set_h_l / set_h_u with the given vector for a given side and the stored finiteness for the
+ * other, a row dropped earlier being stored finite on both sides as -1 / 1; then disable_inf_constraints, set_x_l, set_x_u; a given box vector is packed to its
+ * new list; a stored infinite bound IS infinite.  The lists are built by a kernel on the vectors where they are: in device mode nothing is allocated and no
+ * vector crosses the link.  Two behaviours follow from this solver keeping ONE copy of G', from which every KKT matrix is assembled:
+ *   1. A row dropped by an update WITHOUT G values has its entries of G' zeroed in that copy (and, multistage backend, in the grouped-row arena the fronts are
+ *      assembled from), so the KKT backend sees the row gone.  The reference zeroes GT but does not tell its KKT backend, which keeps factorising the old row
+ *      against the bounds -1 / 1.  The state here is the reference's after update(G = its own G, h_l, h_u, ...) with preconditioner_reuse_on_update = 1, up to the
+ *      roundings of its unscale / rescale.
+ *   2. A row that comes back keeps zero entries of G' until G values are given, as in the reference: pass Gx together with bounds that re-enable a row, or the row
+ *      reads h_l <= 0 <= h_u.  Values of G given for a row that is dropped (now, or by the same call) are not stored. */
+int pq_batch_set_bound_sets(pq_batch *s, int mode);
+/* test hook: the lists the handle holds for one instance NOW (in shared mode: the shared ones), read back from the device tables the kernels use, to HOST memory.
+ * counts = n_h_l, n_h_u, n_x_l, n_x_u; the four ascending lists ([m], [m], [n], [n]; counts[k] entries are written); dropped [m]: 1 on the rows of G without a
+ * finite bound, whose entries of G' are zeroed (such a row is in both lists, with the bounds -1 / 1).  Any output but counts may be NULL. */
+int pq_batch_bound_lists(const pq_batch *s, int instance, int counts[4], int *h_l_idx, int *h_u_idx, int *x_l_idx, int *x_u_idx, int *dropped);
 /* SparseSolver::setup (solver.hpp:1297-1308) per instance.  Patterns (CSC, HOST): P n x n (upper triangle taken),
  * A p x n, G m x n; NULL pattern = absent.  Values / vectors are [batch][nnz] resp. [batch][len] row-major HOST
  * arrays; NULL h_l/h_u/x_l/x_u = nullopt.  Returns 1 when set up. */
@@ -476,7 +498,8 @@ int pq_batch_setup_sparse(pq_batch *s, int batch, int n, int p, int m, const int
                           const double *x_l, const double *x_u);
 /* update() of every instance with new VECTORS only (solver.hpp:218-308 with every optional matrix empty; the Ruiz scaling of the
  * setup is reused, :283-285).  [batch][len] HOST arrays, NULL = unchanged.  The set of finite bounds is part of the shared
- * structure and must not change (error otherwise); a doubly-infinite row of G stays as it was at setup. */
+ * structure and must not change (error otherwise); a doubly-infinite row of G stays as it was at setup.  With PQ_BOUND_SETS_PER_INSTANCE: see
+ * pq_batch_set_bound_sets. */
 int pq_batch_update(pq_batch *s, const double *c, const double *b, const double *h_l, const double *h_u,
                     const double *x_l, const double *x_u);
 /* update() of every instance with new MATRIX VALUES and / or vectors (solver.hpp:218-308 with update_P / update_A / update_G of
@@ -488,7 +511,8 @@ int pq_batch_update_data(pq_batch *s, const double *Px, const double *Ax, const 
                          const double *h_l, const double *h_u, const double *x_l, const double *x_u);
 /* pq_batch_update / pq_batch_update_data with the arrays in host or device memory (mem, ordering contract: see pq_solver_setup_dense_mem).  Device mode: the
  * kernels read the caller's [batch][len] / [batch][nnz] arrays in place -- no device allocation (pq_debug_alloc_count does not move), no copy across the link; the
- * check that the set of finite bounds is unchanged runs as a kernel over the caller's arrays and one flag word comes back (same error as in host mode). */
+ * check that the set of finite bounds is unchanged runs as a kernel over the caller's arrays and one flag word comes back (same error as in host mode; with
+ * PQ_BOUND_SETS_PER_INSTANCE there is no such check, a kernel builds every instance's new lists from the arrays instead). */
 int pq_batch_update_mem(pq_batch *s, const double *c, const double *b, const double *h_l, const double *h_u,
                         const double *x_l, const double *x_u, int mem);
 int pq_batch_update_data_mem(pq_batch *s, const double *Px, const double *Ax, const double *Gx, const double *c, const double *b,

@@ -13,11 +13,20 @@ from ._lib import VAR_NAMES, check
 from .kkt import MEM_DEVICE, _Handle, _ptr, device_call, sync_current_stream, to_device_args
 
 
+BOUND_SETS = {"shared": 0, "per_instance": 1}  # PQ_BOUND_SETS_*
+
+
 class BatchSparseSolver(_Handle):
     _destroy = "pq_batch_destroy"
 
-    def __init__(self, device=0, kkt_solver=None):
-        """kkt_solver: None (sparse_multistage), SPARSE_MULTISTAGE, SPARSE_LDLT or SPARSE_LDLT_EXACT; settings.kkt_solver may also be set before setup()"""
+    def __init__(self, device=0, kkt_solver=None, bounds="shared"):
+        """kkt_solver: None (sparse_multistage), SPARSE_MULTISTAGE, SPARSE_LDLT or SPARSE_LDLT_EXACT; settings.kkt_solver may also be set before setup().
+        bounds: "shared" -- one set of finite bounds for the batch: setup and the updates refuse an instance that differs -- or "per_instance": every instance has
+        the lists SparseSolver would hold for its own vectors, at setup and after every update (pq_batch_set_bound_sets), so a row of G or a box can be switched
+        off per instance with -/+ inf and come back later.  In that mode pass G_values to update_data() together with bounds that re-enable a row that had no
+        finite bound: its entries of G were zeroed when it was dropped and stay zero until new values are given (the row then reads h_l <= 0 <= h_u)."""
+        if bounds not in BOUND_SETS:
+            raise ValueError(f"bounds must be one of {sorted(BOUND_SETS)}, got {bounds!r}")
         self.L = _lib.load()
         h = C.c_void_p()
         check(self.L.pq_batch_create(C.byref(h), device), "pq_batch_create")
@@ -25,8 +34,11 @@ class BatchSparseSolver(_Handle):
         self.device = device
         self.batch = self.n = self.p = self.m = 0
         self._nnz = (0, 0, 0)
+        self.bounds = bounds
         if kkt_solver is not None:
             self.settings.kkt_solver = int(kkt_solver)
+        if bounds != "shared":
+            check(self.L.pq_batch_set_bound_sets(self.h, BOUND_SETS[bounds]), "pq_batch_set_bound_sets")
 
     @property
     def settings(self):
@@ -79,7 +91,8 @@ class BatchSparseSolver(_Handle):
         return keep
 
     def update(self, c=None, b=None, h_l=None, h_u=None, x_l=None, x_u=None):
-        """new vectors for every instance ([batch, len] arrays, None = unchanged); matrices and the set of finite bounds stay.
+        """new vectors for every instance ([batch, len] arrays, None = unchanged); matrices and the set of finite bounds stay (bounds="per_instance": the
+        lists follow the vectors, see __init__).
         If any argument is a torch CUDA tensor the kernels read the data where it is (pq_batch_update_mem)."""
         if device_call((c, b, h_l, h_u, x_l, x_u)):
             keep = self._device_args(dict(c=c, b=b, h_l=h_l, h_u=h_u, x_l=x_l, x_u=x_u))
@@ -168,6 +181,16 @@ class BatchSparseSolver(_Handle):
         out = {key: item(what, dt, ln) for key, what, dt, ln in (("L_cols", 1, np.int32, N + 1), ("L_ind", 2, np.int32, nnz), ("L_vals", 3, np.float64, nnz),
                                                                   ("D", 4, np.float64, N), ("D_inv", 5, np.float64, N), ("perm", 7, np.int32, N))}
         out["PKPt_val"] = item(6, np.float64, self.L.pq_batch_ldlt_factor(self.h, i, 6, None))
+        return out
+
+    def bound_lists(self, i):
+        """the lists the kernels read for instance i now (the shared ones with bounds="shared"), from the device tables: dict(h_l_idx, h_u_idx, x_l_idx, x_u_idx --
+        ascending int arrays --, dropped: bool [m], True on the rows of G without a finite bound, whose entries of G are zeroed)"""
+        counts = np.zeros(4, dtype=np.int32)
+        bufs = [np.zeros(max(ln, 1), dtype=np.int32) for ln in (self.m, self.m, self.n, self.n, self.m)]
+        check(self.L.pq_batch_bound_lists(self.h, i, counts.ctypes.data, *[b.ctypes.data for b in bufs]), "pq_batch_bound_lists")
+        out = {k: bufs[j][:counts[j]].copy() for j, k in enumerate(("h_l_idx", "h_u_idx", "x_l_idx", "x_u_idx"))}
+        out["dropped"] = bufs[4][:self.m] != 0
         return out
 
     def profile(self, i):

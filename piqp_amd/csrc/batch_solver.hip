@@ -14,7 +14,9 @@
 //                 (msdev::solve_chain), residuals and termination tests; unscale + restore_dual at the end.
 // With kkt_solver = sparse_ldlt / sparse_ldlt_exact (MODE_LDLT) the backend is instead the reference's up-looking LDLt of the full KKT matrix in AMD order
 // (sparse/kkt.hpp + ldlt.hpp, uplooking_wave.hpp): factor and solves bitwise the reference's, one 64-thread workgroup per QP, n + p + m <= 8192.
-// All instances must share the sparsity patterns AND the set of finite bounds (checked at setup).
+// All instances share the sparsity patterns.  The set of finite bounds is shared too and checked at setup and at every update (PQ_BOUND_SETS_SHARED, the
+// default), or every instance has lists of its own (PQ_BOUND_SETS_PER_INSTANCE, pq_batch_set_bound_sets): a table with one row per instance, which the kernels
+// read in place of the shared lists and which k_batch_bound_lists rewrites at an update.
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -58,6 +60,8 @@ enum {
 struct BatchShared {
     int n, p, m, n_h_l, n_h_u, n_x_l, n_x_u;
     const int *h_l_idx, *h_u_idx, *x_l_idx, *x_u_idx, *has_l, *has_u, *pos_l, *pos_u;
+    const int* bl_tab;      // PQ_BOUND_SETS_PER_INSTANCE: [batch][bl_stride] ints, the four counts and the lists of every instance (bl_off); null: the shared ones above
+    long long bl_stride;
     const int *Pf_p, *Pf_i, *Pf_src, *AT_p, *AT_i, *A_p, *A_i, *A_src, *GT_p, *GT_i, *G_p, *G_i, *G_src;
     int nzP, nzA, nzG;
     MsMeta M;
@@ -82,6 +86,38 @@ struct BatchShared {
     long long stride;
     pq_settings set;
 };
+
+// A row of the per-instance table of bound lists: n_h_l, n_h_u, n_x_l, n_x_u, then the arrays in the order of this enum.  `dropped` marks the rows of G without a
+// finite bound (data.hpp:144-169): their entries of G' are zero, their bounds -1 / 1, and they are in both lists.
+enum { BL_H_L_IDX = 0, BL_H_U_IDX, BL_HAS_L, BL_HAS_U, BL_DROPPED, BL_X_L_IDX, BL_X_U_IDX, BL_POS_L, BL_POS_U, BL_NARR };
+__host__ __device__ inline long long bl_off(int what, int n, int m)
+{
+    return 4 + (what <= BL_X_L_IDX ? (long long)what * m : 5LL * m + (long long)(what - BL_X_L_IDX) * n);
+}
+__host__ __device__ inline long long bl_row_ints(int n, int m) { return 4 + 5LL * m + 4LL * n; }
+
+// What the kernels outside k_batch_ipm need of an instance's lists: the shared ones, or row q of the table
+struct BoxLists {
+    int n_x_l, n_x_u;
+    const int *x_l_idx, *x_u_idx, *dropped;
+};
+__device__ __forceinline__ BoxLists box_lists(const BatchShared& S, int q, const int* shared_dropped)
+{
+    if (!S.bl_tab) return BoxLists{S.n_x_l, S.n_x_u, S.x_l_idx, S.x_u_idx, shared_dropped};
+    const int* r = S.bl_tab + (long long)q * S.bl_stride;
+    return BoxLists{r[2], r[3], r + bl_off(BL_X_L_IDX, S.n, S.m), r + bl_off(BL_X_U_IDX, S.n, S.m), r + bl_off(BL_DROPPED, S.n, S.m)};
+}
+// k_batch_ipm and the k_batch_ldlt_* kernels, one thread, on the descriptor's copy in LDS: the counts and the list pointers become those of instance q.  Everything
+// after it reads the lists through that copy, so the body of the solve is the same code in both modes.
+__device__ __forceinline__ void use_instance_lists(BatchShared& S, int q)
+{
+    if (!S.bl_tab) return;
+    const int* r = S.bl_tab + (long long)q * S.bl_stride;
+    const int n = S.n, m = S.m;
+    S.n_h_l = r[0]; S.n_h_u = r[1]; S.n_x_l = r[2]; S.n_x_u = r[3];
+    S.h_l_idx = r + bl_off(BL_H_L_IDX, n, m); S.h_u_idx = r + bl_off(BL_H_U_IDX, n, m); S.has_l = r + bl_off(BL_HAS_L, n, m); S.has_u = r + bl_off(BL_HAS_U, n, m);
+    S.x_l_idx = r + bl_off(BL_X_L_IDX, n, m); S.x_u_idx = r + bl_off(BL_X_U_IDX, n, m); S.pos_l = r + bl_off(BL_POS_L, n, m); S.pos_u = r + bl_off(BL_POS_U, n, m);
+}
 
 // Everything in the per-instance arena and every shared index array is device memory, and the interior-point code says so in its pointer types: through
 // generic pointers (what a pointer read from a struct or passed to an out-of-line member is to the compiler) every access was a FLAT instruction, which
@@ -1343,13 +1379,15 @@ __global__ void k_batch_update_vectors(const BatchShared* __restrict__ Sp, doubl
     const double* dl = base + S.off[D_DL];
     const double* db = base + S.off[D_DB];
     const double rc = ruiz_c[q];
+    const BoxLists L = box_lists(S, q, disabled);
+    disabled = L.dropped;
     if (c) for (int i = threadIdx.x; i < n; i += blockDim.x) base[S.off[D_C] + i] = c[(size_t)q * n + i] * (rc * dl[i]);
     if (b) for (int i = threadIdx.x; i < p; i += blockDim.x) base[S.off[D_B] + i] = b[(size_t)q * p + i] * dl[n + i];
     // (rows of G without any finite bound stay disabled: zero row, h = (-1, 1), data.hpp:144-169)
     if (h_l) for (int i = threadIdx.x; i < m; i += blockDim.x) { const double v = h_l[(size_t)q * m + i]; base[S.off[D_HL] + i] = (disabled[i] ? -1.0 : (v > -1e30 ? v : -1e30)) * dl[n + p + i]; }
     if (h_u) for (int i = threadIdx.x; i < m; i += blockDim.x) { const double v = h_u[(size_t)q * m + i]; base[S.off[D_HU] + i] = (disabled[i] ? 1.0 : (v < 1e30 ? v : 1e30)) * dl[n + p + i]; }
-    if (x_l) for (int k = threadIdx.x; k < S.n_x_l; k += blockDim.x) { const int idx = S.x_l_idx[k]; base[S.off[D_XL] + k] = x_l[(size_t)q * n + idx] * db[idx]; }
-    if (x_u) for (int k = threadIdx.x; k < S.n_x_u; k += blockDim.x) { const int idx = S.x_u_idx[k]; base[S.off[D_XU] + k] = x_u[(size_t)q * n + idx] * db[idx]; }
+    if (x_l) for (int k = threadIdx.x; k < L.n_x_l; k += blockDim.x) { const int idx = L.x_l_idx[k]; base[S.off[D_XL] + k] = x_l[(size_t)q * n + idx] * db[idx]; }
+    if (x_u) for (int k = threadIdx.x; k < L.n_x_u; k += blockDim.x) { const int idx = L.x_u_idx[k]; base[S.off[D_XU] + k] = x_u[(size_t)q * n + idx] * db[idx]; }
 }
 
 // update() with matrices (solver.hpp:218-308, update_P / update_A / update_G of :317-358): the caller's new values, in the CSC order they had at
@@ -1359,6 +1397,7 @@ __global__ void k_batch_update_vectors(const BatchShared* __restrict__ Sp, doubl
 struct BatchAssignArgs {
     int nzP_in, nzA_in, nzG_in;
     const int *mapP, *mapA, *mapG, *disabled;
+    const int* Grow;  // per-instance bound sets: the row of the caller's k-th value of G (mapG then has no -1: the row is tested against the instance's `dropped`); else null
     const double *Px, *Ax, *Gx, *c, *b, *h_l, *h_u, *x_l, *x_u;
 };
 __global__ void k_batch_assign(const BatchShared* __restrict__ Sp, double* __restrict__ arena, BatchAssignArgs a)
@@ -1368,13 +1407,75 @@ __global__ void k_batch_assign(const BatchShared* __restrict__ Sp, double* __res
     double* base = arena + (long long)q * S.stride;
     if (a.Px) for (int k = t; k < a.nzP_in; k += NT) { const int d = a.mapP[k]; if (d >= 0) base[S.off[D_PX] + d] = a.Px[(size_t)q * a.nzP_in + k]; }
     if (a.Ax) for (int k = t; k < a.nzA_in; k += NT) { const int d = a.mapA[k]; if (d >= 0) base[S.off[D_ATX] + d] = a.Ax[(size_t)q * a.nzA_in + k]; }
-    if (a.Gx) for (int k = t; k < a.nzG_in; k += NT) { const int d = a.mapG[k]; if (d >= 0) base[S.off[D_GTX] + d] = a.Gx[(size_t)q * a.nzG_in + k]; }
+    const BoxLists L = box_lists(S, q, a.disabled);
+    if (a.Gx) for (int k = t; k < a.nzG_in; k += NT) { const int d = a.mapG[k]; if (d >= 0 && !(a.Grow && L.dropped[a.Grow[k]])) base[S.off[D_GTX] + d] = a.Gx[(size_t)q * a.nzG_in + k]; }
     if (a.c) for (int i = t; i < n; i += NT) base[S.off[D_C] + i] = a.c[(size_t)q * n + i];
     if (a.b) for (int i = t; i < p; i += NT) base[S.off[D_B] + i] = a.b[(size_t)q * p + i];
-    if (a.h_l) for (int i = t; i < m; i += NT) { const double v = a.h_l[(size_t)q * m + i]; base[S.off[D_HL] + i] = a.disabled[i] ? -1.0 : (v > -1e30 ? v : -1e30); }
-    if (a.h_u) for (int i = t; i < m; i += NT) { const double v = a.h_u[(size_t)q * m + i]; base[S.off[D_HU] + i] = a.disabled[i] ? 1.0 : (v < 1e30 ? v : 1e30); }
-    if (a.x_l) for (int k = t; k < S.n_x_l; k += NT) base[S.off[D_XL] + k] = a.x_l[(size_t)q * n + S.x_l_idx[k]];
-    if (a.x_u) for (int k = t; k < S.n_x_u; k += NT) base[S.off[D_XU] + k] = a.x_u[(size_t)q * n + S.x_u_idx[k]];
+    if (a.h_l) for (int i = t; i < m; i += NT) { const double v = a.h_l[(size_t)q * m + i]; base[S.off[D_HL] + i] = L.dropped[i] ? -1.0 : (v > -1e30 ? v : -1e30); }
+    if (a.h_u) for (int i = t; i < m; i += NT) { const double v = a.h_u[(size_t)q * m + i]; base[S.off[D_HU] + i] = L.dropped[i] ? 1.0 : (v < 1e30 ? v : 1e30); }
+    if (a.x_l) for (int k = t; k < L.n_x_l; k += NT) base[S.off[D_XL] + k] = a.x_l[(size_t)q * n + L.x_l_idx[k]];
+    if (a.x_u) for (int k = t; k < L.n_x_u; k += NT) base[S.off[D_XU] + k] = a.x_u[(size_t)q * n + L.x_u_idx[k]];
+}
+
+// PQ_BOUND_SETS_PER_INSTANCE, before the two kernels above at every update that gives a bound vector: the lists the reference would hold after the call (the rules
+// stated at pq_solver_batch_update_dense, dsb_bound_lists on the host) replace row q of the table.  One wave per instance, on the caller's [batch][len] vectors
+// where they are; a vector that is not given (null) keeps the stored finiteness, a row dropped earlier being in both lists.  Ascending lists by an order-preserving
+// compaction: a ballot per 64 entries and the count of set bits below the lane.  Rows that lose their last finite bound get -1 / 1 (times the row's scaling where the
+// arena holds scaled data) and have their entries of G' zeroed, in the arena and (multistage backend) in the grouped-row arena the KKT assembly reads.
+__global__ __launch_bounds__(64) void k_batch_bound_lists(const BatchShared* __restrict__ Sp, double* __restrict__ arena, int* __restrict__ tab, const double* __restrict__ h_l,
+                                                          const double* __restrict__ h_u, const double* __restrict__ x_l, const double* __restrict__ x_u, int scaled, int grouped)
+{
+    const BatchShared& S = *Sp;
+    const int q = blockIdx.x, n = S.n, p = S.p, m = S.m, lane = threadIdx.x;
+    double* base = arena + (long long)q * S.stride;
+    int* r = tab + (long long)q * S.bl_stride;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    if (h_l || h_u) {
+        int *hli = r + bl_off(BL_H_L_IDX, n, m), *hui = r + bl_off(BL_H_U_IDX, n, m), *has_l = r + bl_off(BL_HAS_L, n, m), *has_u = r + bl_off(BL_HAS_U, n, m);
+        int* dropped = r + bl_off(BL_DROPPED, n, m);
+        int cl = 0, cu = 0;
+        for (int i0 = 0; i0 < m; i0 += 64) {
+            const int i = i0 + lane;
+            const bool in = i < m;
+            bool fl = false, fu = false;
+            if (in) {
+                fl = h_l ? h_l[(size_t)q * m + i] > -1e30 : has_l[i] != 0;
+                fu = h_u ? h_u[(size_t)q * m + i] < 1e30 : has_u[i] != 0;
+            }
+            const bool dd = in && !fl && !fu, il = in && (fl || dd), iu = in && (fu || dd);
+            const unsigned long long bl = __ballot(il), bu = __ballot(iu);
+            if (il) hli[cl + __popcll(bl & below)] = i;
+            if (iu) hui[cu + __popcll(bu & below)] = i;
+            cl += __popcll(bl); cu += __popcll(bu);
+            if (in) { has_l[i] = il; has_u[i] = iu; dropped[i] = dd; }
+            if (dd) {
+                const double sc = scaled ? base[S.off[D_DL] + n + p + i] : 1.0;
+                base[S.off[D_HL] + i] = -1.0 * sc; base[S.off[D_HU] + i] = 1.0 * sc;
+                for (int e = S.GT_p[i]; e < S.GT_p[i + 1]; ++e) {
+                    base[S.off[D_GTX] + e] = 0.0;
+                    if (grouped) base[S.off[B_XG] + S.G_dst[e]] = 0.0;
+                }
+            }
+        }
+        if (lane == 0) { r[0] = cl; r[1] = cu; }
+    }
+    for (int side = 0; side < 2; ++side) {
+        const double* v = side == 0 ? x_l : x_u;
+        if (!v) continue;  // (uniform)
+        int *idx = r + bl_off(side == 0 ? BL_X_L_IDX : BL_X_U_IDX, n, m), *pos = r + bl_off(side == 0 ? BL_POS_L : BL_POS_U, n, m);
+        int cnt = 0;
+        for (int j0 = 0; j0 < n; j0 += 64) {
+            const int j = j0 + lane;
+            const bool in = j < n;
+            const bool f = in && (side == 0 ? v[(size_t)q * n + j] > -1e30 : v[(size_t)q * n + j] < 1e30);
+            const unsigned long long bf = __ballot(f);
+            const int k = cnt + __popcll(bf & below);
+            if (f) idx[k] = j;
+            if (in) pos[j] = f ? k : -1;
+            cnt += __popcll(bf);
+        }
+        if (lane == 0) r[2 + side] = cnt;
+    }
 }
 
 // per instance: caller's (Ruiz-scaled) values -> front / grouped-row arenas and the AtA fronts (multistage ctor, :76-135)
@@ -1406,6 +1507,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
     // The shared descriptor and the per-stage structure tables are read on every stage of every chain sweep: keep them in
     // LDS (a dependent chain of global loads per stage was the largest single latency of the first version).
     __shared__ BatchShared Ssh;
+    const int q = order[blockIdx.x];  // workgroups start in block order: the instances expected to take longest first (pq_batch::solve)
     {
         const int words = (int)(sizeof(BatchShared) / sizeof(int));
         const int* src = reinterpret_cast<const int*>(Sp);
@@ -1423,11 +1525,11 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
         if (threadIdx.x == 0) {
             Ssh.M.w = mi; Ssh.M.off = mi + N; Ssh.M.h = mi + 2 * N; Ssh.M.start = mi + 3 * N;
             Ssh.M.front_off = ml; Ssh.M.pan_off = ml + N;
+            use_instance_lists(Ssh, q);
         }
         __syncthreads();
     }
     const BatchShared& S = Ssh;
-    const int q = order[blockIdx.x];  // workgroups start in block order: the instances expected to take longest first (pq_batch::solve)
     __shared__ IpmState state[NT / 64 > 0 ? NT / 64 : 1];
     IpmState& my = state[threadIdx.x >> 6];
     Ipm<NT, MODE, WPE> ipm(S, (gdbl*)(arena + (long long)q * S.stride), sm, red, my);
@@ -1462,6 +1564,10 @@ __device__ __forceinline__ void copy_shared(const BatchShared* Sp, BatchShared& 
     int* dst = reinterpret_cast<int*>(&Ssh);
     for (int i = threadIdx.x; i < words; i += blockDim.x) dst[i] = src[i];
     __syncthreads();
+    if (Ssh.bl_tab) {  // (uniform)
+        if (threadIdx.x == 0) use_instance_lists(Ssh, blockIdx.x);
+        __syncthreads();
+    }
 }
 __global__ __launch_bounds__(64) void k_batch_ldlt_factor(const BatchShared* __restrict__ Sp, double* __restrict__ arena, const double* __restrict__ delta,
                                                           const double* __restrict__ x_reg, const double* __restrict__ z_reg, int* __restrict__ ok)
@@ -1509,6 +1615,7 @@ public:
         ev0_ = Event(0); ev1_ = Event(0);
     }
     pq_settings& settings() { return settings_; }
+    void set_bound_sets(int mode) { bound_sets_ = mode; }  // read by the next setup
     int batch() const { return batch_; }
     int n() const { return n_; }
     int p() const { return p_; }
@@ -1522,15 +1629,19 @@ public:
         if (settings_.kkt_solver != PQ_SPARSE_MULTISTAGE && settings_.kkt_solver != PQ_SPARSE_LDLT && settings_.kkt_solver != PQ_SPARSE_LDLT_EXACT)
             throw std::runtime_error("batch mode: kkt_solver must be sparse_multistage, sparse_ldlt or sparse_ldlt_exact");
         ldlt_ = settings_.kkt_solver != PQ_SPARSE_MULTISTAGE;
+        per_inst_ = bound_sets_ == PQ_BOUND_SETS_PER_INSTANCE;
+        const bool per_inst = per_inst_;
         PQ_HIP(hipSetDevice(dev_));
         batch_ = batch;
         const int nzP = Pp[n], nzA = Ap ? Ap[n] : 0, nzG = Gp ? Gp[n] : 0;
         // ---- which bounds are finite is part of the shared structure: the caller's pattern must be the same in every instance ----
+        // (PQ_BOUND_SETS_PER_INSTANCE: nothing is refused, every instance keeps the lists make_sparse_host_data builds for it; the vectors below are then instance
+        // 0's and only size the shared fallbacks)
         auto finite_pattern = [&](const double* v, int len, bool lower, std::vector<char>& out) {
             out.assign(len, 0);
             if (!v) return;
             for (int i = 0; i < len; ++i) out[i] = lower ? v[i] > -1e30 : v[i] < 1e30;
-            for (int q = 1; q < batch; ++q)
+            for (int q = 1; q < batch && !per_inst; ++q)
                 for (int i = 0; i < len; ++i)
                     if ((lower ? v[(size_t)q * len + i] > -1e30 : v[(size_t)q * len + i] < 1e30) != (out[i] != 0)) throw std::runtime_error("batch setup: instances differ in which bounds are finite");
         };
@@ -1565,7 +1676,7 @@ public:
                               std::equal(d.h_u_idx.begin(), d.h_u_idx.begin() + d.n_h_u, d0.h_u_idx.begin()) &&
                               std::equal(d.x_l_idx.begin(), d.x_l_idx.begin() + d.n_x_l, d0.x_l_idx.begin()) &&
                               std::equal(d.x_u_idx.begin(), d.x_u_idx.begin() + d.n_x_u, d0.x_u_idx.begin());
-            if (!same) throw std::runtime_error("batch setup: instances differ in which bounds are finite");
+            if (!same && !per_inst) throw std::runtime_error("batch setup: instances differ in which bounds are finite");
         }
         fin_hl_.resize(m_, 0); fin_hu_.resize(m_, 0);
         // ---- shared structure ----
@@ -1584,6 +1695,8 @@ public:
         }
         build_shared(d0);
         build_update_maps(n, p, m, Pp, Pi, c, Ap, Ai, b, Gp, Gi, h_l, h_u, x_l, x_u, d0);
+        bl_tab_ = DBuf<int>();
+        if (per_inst) build_bound_table(data, m_ > 0 ? h_l : nullptr, m_ > 0 ? h_u : nullptr);
         // ---- per-instance arena ----
         if (ldlt_) {
             size_t free_b = 0, total_b = 0;
@@ -1656,13 +1769,14 @@ public:
         }
         return solved;
     }
-    // update() of every instance, vectors only; the set of finite bounds must be the one given at setup (it is part of the shared structure)
+    // update() of every instance, vectors only; the set of finite bounds must be the one given at setup (it is part of the shared structure) -- or, with
+    // PQ_BOUND_SETS_PER_INSTANCE, whatever the vectors say: k_batch_bound_lists rewrites every instance's lists first
     // mem = PQ_MEM_DEVICE: the kernels read the caller's device arrays in place (no staging buffers, no copies)
     bool update_vectors(const double* c, const double* b, const double* h_l, const double* h_u, const double* x_l, const double* x_u, int mem = PQ_MEM_HOST)
     {
         if (!setup_done_) throw std::runtime_error("batch solver not set up");
         PQ_HIP(hipSetDevice(dev_));
-        if (mem == PQ_MEM_DEVICE) check_patterns_device(h_l, h_u, x_l, x_u); else check_patterns(h_l, h_u, x_l, x_u);
+        if (!per_inst_) { if (mem == PQ_MEM_DEVICE) check_patterns_device(h_l, h_u, x_l, x_u); else check_patterns(h_l, h_u, x_l, x_u); }
         DBuf<double> dc, dbv, dhl, dhu, dxl, dxu;
         auto up = [&](DBuf<double>& d, const double* v, int len) -> const double* {
             if (!v || len == 0) return nullptr;
@@ -1672,6 +1786,7 @@ public:
             return d.p;
         };
         const double *pc = up(dc, c, n_), *pb = up(dbv, b, p_), *phl = up(dhl, h_l, m_), *phu = up(dhu, h_u, m_), *pxl = up(dxl, x_l, n_), *pxu = up(dxu, x_u, n_);
+        launch_bound_lists(phl, phu, pxl, pxu, true);
         hipLaunchKernelGGL(k_batch_update_vectors, dim3(batch_), dim3(128), 0, st_, shared_.p, arena_.p, ruiz_c_.p, disabled_d_, pc, pb, phl, phu, pxl, pxu);
         PQ_HIP(hipGetLastError());
         stream_wait(st_);
@@ -1685,7 +1800,7 @@ public:
         if (!Px && !Ax && !Gx) return update_vectors(c, b, h_l, h_u, x_l, x_u, mem);
         if (!setup_done_) throw std::runtime_error("batch solver not set up");
         PQ_HIP(hipSetDevice(dev_));
-        if (mem == PQ_MEM_DEVICE) check_patterns_device(h_l, h_u, x_l, x_u); else check_patterns(h_l, h_u, x_l, x_u);
+        if (!per_inst_) { if (mem == PQ_MEM_DEVICE) check_patterns_device(h_l, h_u, x_l, x_u); else check_patterns(h_l, h_u, x_l, x_u); }
         DBuf<double> dP, dA, dG, dc, dbv, dhl, dhu, dxl, dxu;
         auto up = [&](DBuf<double>& d, const double* v, int len) -> const double* {
             if (!v || len == 0) return nullptr;
@@ -1696,10 +1811,11 @@ public:
         };
         BatchAssignArgs a{};
         a.nzP_in = nzP_in_; a.nzA_in = nzA_in_; a.nzG_in = nzG_in_;
-        a.mapP = mapP_; a.mapA = mapA_; a.mapG = mapG_; a.disabled = disabled_d_;
+        a.mapP = mapP_; a.mapA = mapA_; a.mapG = mapG_; a.disabled = disabled_d_; a.Grow = Grow_;
         a.Px = up(dP, Px, nzP_in_); a.Ax = up(dA, Ax, nzA_in_); a.Gx = up(dG, Gx, nzG_in_);
         a.c = up(dc, c, n_); a.b = up(dbv, b, p_); a.h_l = up(dhl, h_l, m_); a.h_u = up(dhu, h_u, m_); a.x_l = up(dxl, x_l, n_); a.x_u = up(dxu, x_u, n_);
-        launch_ruiz(RUIZ_UNSCALE);
+        launch_ruiz(RUIZ_UNSCALE);  // (with the lists as they stood: the box vectors are packed to them)
+        launch_bound_lists(a.h_l, a.h_u, a.x_l, a.x_u, false);
         hipLaunchKernelGGL(k_batch_assign, dim3(batch_), dim3(128), 0, st_, shared_.p, arena_.p, a);
         PQ_HIP(hipGetLastError());
         launch_ruiz(settings_.preconditioner_reuse_on_update ? RUIZ_REUSE : RUIZ_COMPUTE);
@@ -1748,6 +1864,28 @@ public:
     }
     int threads_per_qp() const { return nt_; }
     int mode() const { return mode_; }
+    // pq_batch_bound_lists: the lists the kernels read for one instance, copied out of the device tables (the descriptor included: no host shadow is consulted)
+    void bound_lists(int instance, int counts[4], int* h_l_idx, int* h_u_idx, int* x_l_idx, int* x_u_idx, int* dropped)
+    {
+        if (!setup_done_) throw std::runtime_error("batch solver not set up");
+        if (instance < 0 || instance >= batch_) throw std::runtime_error("pq_batch_bound_lists: instance out of range");
+        PQ_HIP(hipSetDevice(dev_));
+        BatchShared S;
+        PQ_HIP(hipMemcpy(&S, shared_.p, sizeof(BatchShared), hipMemcpyDeviceToHost));
+        const int n = S.n, m = S.m;
+        const int *src[5] = {S.h_l_idx, S.h_u_idx, S.x_l_idx, S.x_u_idx, disabled_d_};
+        counts[0] = S.n_h_l; counts[1] = S.n_h_u; counts[2] = S.n_x_l; counts[3] = S.n_x_u;
+        if (S.bl_tab) {
+            const int* r = S.bl_tab + (long long)instance * S.bl_stride;
+            PQ_HIP(hipMemcpy(counts, r, sizeof(int) * 4, hipMemcpyDeviceToHost));
+            src[0] = r + bl_off(BL_H_L_IDX, n, m); src[1] = r + bl_off(BL_H_U_IDX, n, m); src[2] = r + bl_off(BL_X_L_IDX, n, m); src[3] = r + bl_off(BL_X_U_IDX, n, m);
+            src[4] = r + bl_off(BL_DROPPED, n, m);
+        }
+        int* const dst[5] = {h_l_idx, h_u_idx, x_l_idx, x_u_idx, dropped};
+        const int len[5] = {counts[0], counts[1], counts[2], counts[3], m};
+        for (int k = 0; k < 5; ++k)
+            if (dst[k] && len[k] > 0) PQ_HIP(hipMemcpy(dst[k], src[k], sizeof(int) * (size_t)len[k], hipMemcpyDeviceToHost));
+    }
 
     // KKTSolverBase::update_scalings_and_factor of every instance on its stored (scaled) data (sparse_ldlt backend only); host arrays, ok [batch] out
     void kkt_factor(const double* delta, const double* x_reg, const double* z_reg, int* ok)
@@ -1870,7 +2008,11 @@ private:
         for (int k = 0; k < nzP_in_; ++k) iP[k] = k + 1;
         for (int k = 0; k < nzA_in_; ++k) iA[k] = k + 1;
         for (int k = 0; k < nzG_in_; ++k) iG[k] = k + 1;
-        auto probe = make_sparse_host_data(n, p, m, Pp, Pi, iP.data(), c, Ap, Ai, Ap ? iA.data() : nullptr, b, Gp, Gi, Gp ? iG.data() : nullptr, h_l, h_u, x_l, x_u);
+        // (per-instance bound sets: no row of the probe is dropped -- finite bounds everywhere --, k_batch_assign tests the row of an entry against the instance's table)
+        const Vec hfin(std::max(m, 1), 0.0);
+        auto probe = make_sparse_host_data(n, p, m, Pp, Pi, iP.data(), c, Ap, Ai, Ap ? iA.data() : nullptr, b, Gp, Gi, Gp ? iG.data() : nullptr, per_inst_ ? hfin.data() : h_l,
+                                           per_inst_ ? hfin.data() : h_u, x_l, x_u);
+        Grow_ = (per_inst_ && Gp && nzG_in_ > 0) ? up(ibufs_, std::vector<int>(Gi, Gi + nzG_in_)) : nullptr;
         auto invert = [&](const Vec& stored, int nz_in) {
             std::vector<int> map(std::max(nz_in, 1), -1);
             for (size_t t = 0; t < stored.size(); ++t) if (stored[t] > 0.0) map[(int)stored[t] - 1] = (int)t;
@@ -1905,9 +2047,44 @@ private:
         a.delta = at(D_DL); a.delta_inv = at(D_DLI); a.delta_b = at(D_DB); a.delta_b_inv = at(D_DBI); a.tmp = at(K_WX);
         a.b = at(D_B); a.h_l = at(D_HL); a.h_u = at(D_HU); a.x_l = at(D_XL); a.x_u = at(D_XU);
         a.x_l_idx = S.x_l_idx; a.x_u_idx = S.x_u_idx; a.n_x_l = S.n_x_l; a.n_x_u = S.n_x_u;
+        if (per_inst_) { a.lists = bl_tab_.p; a.lists_stride = S.bl_stride; a.lists_x_l = bl_off(BL_X_L_IDX, n_, m_); a.lists_x_u = bl_off(BL_X_U_IDX, n_, m_); }
         a.c_scale = ruiz_c_.p;
         a.mode = mode; a.scale_cost = settings_.preconditioner_scale_cost != 0; a.max_iter = settings_.preconditioner_iter;
         launch_ruiz_sparse(a, batch_, n_ + p_ + m_ <= 512 ? 64 : 256, st_);
+    }
+
+    // PQ_BOUND_SETS_PER_INSTANCE: the table of every instance's lists from its own HostData (rows as bl_off says), and the descriptor that points to it
+    void build_bound_table(const std::vector<std::unique_ptr<HostData>>& data, const double* h_l, const double* h_u)
+    {
+        const int n = n_, m = m_;
+        const long long R = bl_row_ints(n, m);
+        std::vector<int> tab((size_t)R * batch_, 0);
+        for (int q = 0; q < batch_; ++q) {
+            const HostData& d = *data[(size_t)q];
+            int* r = tab.data() + (size_t)R * q;
+            r[0] = d.n_h_l; r[1] = d.n_h_u; r[2] = d.n_x_l; r[3] = d.n_x_u;
+            int *hli = r + bl_off(BL_H_L_IDX, n, m), *hui = r + bl_off(BL_H_U_IDX, n, m), *has_l = r + bl_off(BL_HAS_L, n, m), *has_u = r + bl_off(BL_HAS_U, n, m);
+            int *dropped = r + bl_off(BL_DROPPED, n, m), *xli = r + bl_off(BL_X_L_IDX, n, m), *xui = r + bl_off(BL_X_U_IDX, n, m);
+            int *pos_l = r + bl_off(BL_POS_L, n, m), *pos_u = r + bl_off(BL_POS_U, n, m);
+            for (int i = 0; i < d.n_h_l; ++i) { hli[i] = d.h_l_idx[i]; has_l[d.h_l_idx[i]] = 1; }
+            for (int i = 0; i < d.n_h_u; ++i) { hui[i] = d.h_u_idx[i]; has_u[d.h_u_idx[i]] = 1; }
+            // a dropped row is one the caller gave no finite bound (disable_inf_constraints has set its bounds to -1 / 1 in d: they no longer tell)
+            for (int i = 0; i < m; ++i) dropped[i] = !(h_l && h_l[(size_t)q * m + i] > -1e30) && !(h_u && h_u[(size_t)q * m + i] < 1e30);
+            for (int j = 0; j < n; ++j) pos_l[j] = pos_u[j] = -1;
+            for (int i = 0; i < d.n_x_l; ++i) { xli[i] = d.x_l_idx[i]; pos_l[d.x_l_idx[i]] = i; }
+            for (int i = 0; i < d.n_x_u; ++i) { xui[i] = d.x_u_idx[i]; pos_u[d.x_u_idx[i]] = i; }
+        }
+        upload_vec(bl_tab_, tab, st_);
+        shared_h_.bl_tab = bl_tab_.p;
+        shared_h_.bl_stride = R;
+        PQ_HIP(hipMemcpyAsync(shared_.p, &shared_h_, sizeof(BatchShared), hipMemcpyHostToDevice, st_));
+        stream_wait(st_);
+    }
+    void launch_bound_lists(const double* h_l, const double* h_u, const double* x_l, const double* x_u, bool scaled)
+    {
+        if (!per_inst_ || (!h_l && !h_u && !x_l && !x_u)) return;
+        hipLaunchKernelGGL(k_batch_bound_lists, dim3(batch_), dim3(64), 0, st_, shared_.p, arena_.p, bl_tab_.p, h_l, h_u, x_l, x_u, scaled ? 1 : 0, ldlt_ ? 0 : 1);
+        PQ_HIP(hipGetLastError());
     }
 
     template <class T>
@@ -2192,6 +2369,10 @@ private:
     int dev_, batch_ = 0, n_ = 0, p_ = 0, m_ = 0, nt_ = 64;
     int mode_ = MODE_STAGED, wpe_ = 4, forced_mode_ = -1;
     bool setup_done_ = false;
+    int bound_sets_ = PQ_BOUND_SETS_SHARED;  // pq_batch_set_bound_sets: read by the next setup, which records it in per_inst_
+    bool per_inst_ = false;
+    DBuf<int> bl_tab_;                       // per_inst_: [batch][bl_row_ints] (BatchShared::bl_tab)
+    const int* Grow_ = nullptr;              // per_inst_: the row of the caller's k-th value of G (device, owned by ibufs_)
     bool ldlt_ = false;  // backend fixed at setup: sparse_ldlt (MODE_LDLT) or sparse_multistage
     sparse::UpLooking ul_;
     std::vector<char> fin_hl_, fin_hu_, fin_xl_, fin_xu_;  // which of the caller's bounds are finite (shared by all instances)
@@ -2239,6 +2420,19 @@ int pq_batch_create(pq_batch** out, int device)
 }
 void pq_batch_destroy(pq_batch* s) { delete s; }
 pq_settings* pq_batch_settings(pq_batch* s) { return s ? &s->impl->settings() : nullptr; }
+int pq_batch_set_bound_sets(pq_batch* s, int mode)
+{
+    if (!s) return fail(PQ_ERR_INVALID, "null argument");
+    if (mode != PQ_BOUND_SETS_SHARED && mode != PQ_BOUND_SETS_PER_INSTANCE)
+        return fail(PQ_ERR_INVALID, "batch: bound sets %d: PQ_BOUND_SETS_SHARED or PQ_BOUND_SETS_PER_INSTANCE wanted", mode);
+    s->impl->set_bound_sets(mode);  // (a handle that is set up keeps the mode its setup read)
+    return PQ_OK;
+}
+int pq_batch_bound_lists(const pq_batch* s, int instance, int counts[4], int* h_l_idx, int* h_u_idx, int* x_l_idx, int* x_u_idx, int* dropped)
+{
+    if (!s || !counts) return fail(PQ_ERR_INVALID, "null argument");
+    return guarded([&] { s->impl->bound_lists(instance, counts, h_l_idx, h_u_idx, x_l_idx, x_u_idx, dropped); return (int)PQ_OK; });
+}
 int pq_batch_setup_sparse(pq_batch* s, int batch, int n, int p, int m, const int* Pp, const int* Pi, const double* Px, const double* c, const int* Ap, const int* Ai,
                           const double* Ax, const double* b, const int* Gp, const int* Gi, const double* Gx, const double* h_l, const double* h_u, const double* x_l,
                           const double* x_u)

@@ -28,6 +28,10 @@ struct RuizSparseArgs {
     double *b = nullptr, *h_l = nullptr, *h_u = nullptr, *x_l = nullptr, *x_u = nullptr;                   // optional tail (preconditioner.hpp:208-221); x_l / x_u compressed
     const int *x_l_idx = nullptr, *x_u_idx = nullptr;
     int n_x_l = 0, n_x_u = 0;
+    // box lists per instance instead (the batched solver with PQ_BOUND_SETS_PER_INSTANCE): row i of `lists` has n_x_l, n_x_u in its ints 2 and 3 and the two index
+    // lists at the offsets lists_x_l / lists_x_u; null: the shared lists above
+    const int* lists = nullptr;
+    long long lists_stride = 0, lists_x_l = 0, lists_x_u = 0;
     double* c_scale = nullptr;  // [batch], not strided: the cost scaling c of every instance (out for RUIZ_COMPUTE, in otherwise)
     int mode = RUIZ_COMPUTE, scale_cost = 0, max_iter = 10;
     double eps = 1e-3;

@@ -213,8 +213,11 @@ __global__ void k_ruiz_sparse(RuizSparseArgs a)
     if (a.b) for (int i = t; i < p; i += NT) a.b[o + i] *= s[n + i];
     if (a.h_l) for (int i = t; i < m; i += NT) a.h_l[o + i] *= s[n + p + i];
     if (a.h_u) for (int i = t; i < m; i += NT) a.h_u[o + i] *= s[n + p + i];
-    if (a.x_l) for (int k = t; k < a.n_x_l; k += NT) a.x_l[o + k] *= sb[a.x_l_idx[k]];
-    if (a.x_u) for (int k = t; k < a.n_x_u; k += NT) a.x_u[o + k] *= sb[a.x_u_idx[k]];
+    const int* row = (!GRID && a.lists) ? a.lists + (long long)inst * a.lists_stride : nullptr;
+    const int n_x_l = row ? row[2] : a.n_x_l, n_x_u = row ? row[3] : a.n_x_u;
+    const int *x_l_idx = row ? row + a.lists_x_l : a.x_l_idx, *x_u_idx = row ? row + a.lists_x_u : a.x_u_idx;
+    if (a.x_l) for (int k = t; k < n_x_l; k += NT) a.x_l[o + k] *= sb[x_l_idx[k]];
+    if (a.x_u) for (int k = t; k < n_x_u; k += NT) a.x_u[o + k] *= sb[x_u_idx[k]];
 }
 
 // ------------------------------------------------------------------------------------------------ dense, tiled
