@@ -467,6 +467,30 @@ typedef struct pq_batch pq_batch;
 int pq_batch_create(pq_batch **out, int device);
 void pq_batch_destroy(pq_batch *s);
 pq_settings *pq_batch_settings(pq_batch *s); /* solver.hpp:65 settings(), shared by all instances */
+/* A second handle in the state of s, without a new setup, under the rules of pq_solver_batch_clone / _clone_select: the whole batch (_clone: the identity list) or
+ * a list of instances (_clone_select: batch = count, instance j of the new handle is instance idx[j] of s; idx in HOST memory, repeats allowed, count smaller or
+ * larger than the batch of s).  Copied: the settings as they stand, the bound-set mode, the start-order flag.  Per instance everything a later call can read goes
+ * along bit for bit -- the arena row (scaled data, the stored Ruiz scalings, x_b_scaling, the interior-point state, the ten result vectors, the grouped-row and
+ * front arenas of sparse_multistage, C / L / D / D^-1 of sparse_ldlt), its cost scaling, its pq_info, its profile row and, with PQ_BOUND_SETS_PER_INSTANCE, its
+ * lists with the dropped flags.  So a clone taken after a solve answers pq_batch_info, pq_batch_get_result(_mem) and pq_batch_get_profile without solving, after a
+ * pq_batch_kkt_factor it answers pq_batch_ldlt_factor and pq_batch_kkt_solve, and an update on it unscales with the stored scalings of its instances.  The patterns,
+ * the symbolic analysis, the update maps and the shared bound lists are those of s: nothing is analysed again, no host data are needed, and their device arrays,
+ * which no kernel writes, are held by both handles and released by the last one.  The new handle is on the same device with a stream of its own and is
+ * independent: it survives pq_batch_destroy(s) and a new pq_batch_setup_sparse on s, and no call on either is seen by the other; s is only waited for and read.
+ * The MODE_WAVE kernel variant (waves per SIMD) is chosen for count, as setup chooses it for its batch; the start order of the next launch is computed from the
+ * gathered infos as pq_batch_solve leaves it.  The call is the only one on the new handle that allocates beyond what the same call allocates after a setup; the
+ * sparse_ldlt backend repeats setup's free-memory refusal for the new arena.  One gather launch for the arena (16-byte words; 8 with an odd row), one for each of
+ * the small per-instance arrays; the call ends with a wait.
+ * _clone of a handle that was never set up gives a handle with the copied scalars and no problem; _clone_select of one is PQ_ERR_INVALID, as are, before any device
+ * call and with *out left alone: a NULL s, out or idx, count < 1, an idx[j] outside [0, batch) (the text names j and the value). */
+int pq_batch_clone(const pq_batch *s, pq_batch **out);
+int pq_batch_clone_select(const pq_batch *s, const int *idx, int count, pq_batch **out);
+/* of the clone call that made s: out2 = { wall ms of the call, device ms of the gathers (hipEvents of the new handle around them) }; both 0 on a handle that
+ * pq_batch_create made or whose source was never set up.  Wall minus device is the allocation, the host images and the waits. */
+int pq_batch_clone_ms(const pq_batch *s, double out2[2]);
+/* measurement and test hook: the doubles of one instance's row of the arena -- what a clone gathers per instance, 8 x this many bytes read and as many written; 0
+ * before a setup, PQ_ERR_INVALID for a NULL handle.  Even at every shape (every slot of the row is padded to an even count), so rows are 16-byte aligned. */
+long long pq_batch_arena_stride(const pq_batch *s);
 /* Who owns the set of finite bounds: PQ_BOUND_SETS_SHARED (the default) or PQ_BOUND_SETS_PER_INSTANCE, the constants and their meaning as at
  * pq_solver_batch_set_bound_sets.  Shared: setup refuses an instance whose finite bounds differ from instance 0's and the updates refuse a bound that turns
  * finite or infinite.  Per instance: every instance has the lists SparseSolver would hold for its own vectors (sparse/data.hpp:103-210) at setup and after every

@@ -10,6 +10,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import VAR_NAMES, check
+from .batch_kkt import select_list
 from .kkt import MEM_DEVICE, _Handle, _ptr, device_call, sync_current_stream, to_device_args
 
 
@@ -44,6 +45,30 @@ class BatchSparseSolver(_Handle):
     def settings(self):
         return self.L.pq_batch_settings(self.h).contents
 
+    def clone(self, instances=None):
+        """a second solver in the state of this one without a new setup (pq_batch_clone / pq_batch_clone_select): the whole batch, or instance j of the new solver is
+        instance instances[j] of this one (repeats allowed, any count).  Settings, data, scalings, iterates, results, infos and the factors of kkt_factor() go along
+        bit for bit; the two solvers are independent afterwards.  Scenario fan-out: s.clone([0] * S).update(b=...); stragglers:
+        s.clone(np.flatnonzero(s.statuses() != SOLVED))."""
+        h = C.c_void_p()
+        if instances is None:
+            check(self.L.pq_batch_clone(self.h, C.byref(h)), "pq_batch_clone")
+            batch = self.batch
+        else:
+            idx = select_list(instances)
+            check(self.L.pq_batch_clone_select(self.h, idx.ctypes.data, len(idx), C.byref(h)), "pq_batch_clone_select")
+            batch = len(idx)
+        c = type(self).__new__(type(self))
+        c.L, c.h, c.device, c.bounds = self.L, h, self.device, self.bounds
+        c.batch, c.n, c.p, c.m, c._nnz = batch, self.n, self.p, self.m, self._nnz
+        return c
+
+    def clone_ms(self):
+        """of the clone() that made this solver: dict(wall_ms, device_ms -- the gathers); zeros on a solver that is no clone"""
+        o = np.zeros(2)
+        check(self.L.pq_batch_clone_ms(self.h, o.ctypes.data), "pq_batch_clone_ms")
+        return dict(wall_ms=float(o[0]), device_ms=float(o[1]))
+
     @staticmethod
     def _pattern(M):
         import scipy.sparse as sp
@@ -60,6 +85,10 @@ class BatchSparseSolver(_Handle):
         a = np.ascontiguousarray(a, dtype=np.float64)
         assert a.shape == (batch, length), (a.shape, (batch, length))
         return a
+
+    def arena_stride(self):
+        """doubles per instance of the device arena: what a clone gathers per instance (pq_batch_arena_stride)"""
+        return int(check(self.L.pq_batch_arena_stride(self.h), "pq_batch_arena_stride"))
 
     def setup(self, P_pattern, P_values, c, A_pattern=None, A_values=None, b=None, G_pattern=None, G_values=None, h_l=None, h_u=None, x_l=None, x_u=None):
         """*_pattern: scipy sparse matrices giving the (sorted CSC) patterns of P (n x n), A (p x n), G (m x n);

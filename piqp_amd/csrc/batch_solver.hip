@@ -17,9 +17,13 @@
 // All instances share the sparsity patterns.  The set of finite bounds is shared too and checked at setup and at every update (PQ_BOUND_SETS_SHARED, the
 // default), or every instance has lists of its own (PQ_BOUND_SETS_PER_INSTANCE, pq_batch_set_bound_sets): a table with one row per instance, which the kernels
 // read in place of the shared lists and which k_batch_bound_lists rewrites at an update.
+// pq_batch_clone / pq_batch_clone_select make a second handle from a set-up one without a new setup, whole or by a list of instances: the structure is shared by
+// reference count, the per-instance rows are gathered by k_batch_gather_rows (the clone constructor of BatchSolver).
 #include <algorithm>
 #include <cfloat>
+#include <chrono>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <memory>
 #include <stdexcept>
@@ -1597,9 +1601,53 @@ __global__ __launch_bounds__(64) void k_batch_ldlt_solve(const BatchShared* __re
     ipm.be_solve((const gdbl*)(rx + q * n), (const gdbl*)(ry + q * p), (const gdbl*)(rz + q * m), (gdbl*)(lx + q * n), (gdbl*)(ly + q * p), (gdbl*)(lz + q * m));
 }
 
+// ---- pq_batch_clone / pq_batch_clone_select: row j of dst is row idx[j] of src, rows of wpr words of W (uint4, unsigned long long or unsigned: the widest that
+// divides the row's bytes and both bases, BatchSolver::gather_rows).  A copy of bits.  Rows of a chunk and more (the arena: 84.5 KB a row at C4, growing with nnz(L) for
+// sparse_ldlt): the units are (row, chunk of 1024 words), taken grid-stride, so three rows and 8192 rows both spread over the whole device; a thread issues its four
+// loads of a unit before its four stores (16 KiB in flight per workgroup with uint4), consecutive lanes consecutive words, every word read once and written once.
+// Shorter rows (ruiz_c, pq_info, the profile, the bound table): the words of all rows as one flat range.  Every index is held in 64 bits; idx has been checked
+// against the source's batch on the host, and dst has `count` rows.
+constexpr int GATHER_THREADS = 256;
+constexpr int GATHER_UNROLL = 4;
+constexpr int GATHER_CHUNK = GATHER_THREADS * GATHER_UNROLL;
+static_assert(GATHER_UNROLL == 4, "k_batch_gather_rows writes its four loads out by hand");
+template <class W>
+__global__ __launch_bounds__(GATHER_THREADS) void k_batch_gather_rows(W* __restrict__ dst, const W* __restrict__ src, const int* __restrict__ idx, long long count,
+                                                                      long long wpr)
+{
+    const int t = threadIdx.x;
+    if (wpr >= GATHER_CHUNK) {
+        const long long cpr = (wpr + GATHER_CHUNK - 1) / GATHER_CHUNK, units = count * cpr;
+        for (long long u = blockIdx.x; u < units; u += gridDim.x) {
+            const long long row = u / cpr, w0 = (u - row * cpr) * GATHER_CHUNK + t;
+            const W* s = src + (long long)idx[row] * wpr;
+            W* d = dst + row * wpr;
+            if (w0 + 3 * GATHER_THREADS < wpr) {  // a whole unit for this lane: four loads in flight, then four stores
+                const W v0 = s[w0], v1 = s[w0 + GATHER_THREADS], v2 = s[w0 + 2 * GATHER_THREADS], v3 = s[w0 + 3 * GATHER_THREADS];
+                d[w0] = v0; d[w0 + GATHER_THREADS] = v1; d[w0 + 2 * GATHER_THREADS] = v2; d[w0 + 3 * GATHER_THREADS] = v3;
+            } else {  // the last unit of a row
+                for (long long w = w0; w < wpr; w += GATHER_THREADS) d[w] = s[w];
+            }
+        }
+        return;
+    }
+    const long long words = count * wpr;
+    for (long long g = (long long)blockIdx.x * GATHER_THREADS + t; g < words; g += (long long)gridDim.x * GATHER_THREADS) {
+        const long long row = g / wpr;
+        dst[g] = src[(long long)idx[row] * wpr + (g - row * wpr)];
+    }
+}
+
 struct Layout {
     long long off[NSLOT];
     long long stride = 0;
+};
+
+// The index arrays of a setup -- the patterns, the symbolic analysis, the update maps, the shared bound lists -- which no kernel writes: a handle and its clones hold
+// them together, and the last one to go releases them.  (BatchShared and the update-map members keep raw pointers into them.)
+struct StructBufs {
+    std::vector<DBuf<int>> i;
+    std::vector<DBuf<long long>> l;
 };
 
 }  // namespace
@@ -1757,18 +1805,91 @@ public:
         // iteration counts (7 .. 11 at C4), and the last ones to start decide when the launch ends; receding-horizon batches repeat their counts from one
         // solve to the next almost exactly, so the instances that took longest start first next time (a stable counting sort: deterministic; the results of
         // an instance do not depend on where it starts).  8192 QPs: the tail behind the second round of workgroups 0.87 -> ~0.4 ms.
-        if (lpt_ && !debug_token("batch_no_lpt")) {
-            const int cap = std::max(settings_.max_iter, 1) + 1;
-            std::vector<int> cnt((size_t)cap + 1, 0);
-            for (const auto& i : infos_h_) cnt[(size_t)std::min(std::max(i.iter, 0), cap - 1)]++;
-            std::vector<int> first((size_t)cap, 0);
-            int run = 0;
-            for (int it = cap - 1; it >= 0; --it) { first[(size_t)it] = run; run += cnt[(size_t)it]; }
-            for (int i = 0; i < batch_; ++i) order_h_[(size_t)first[(size_t)std::min(std::max(infos_h_[(size_t)i].iter, 0), cap - 1)]++] = i;
-            PQ_HIP(hipMemcpyAsync(order_.p, order_h_.data(), sizeof(int) * (size_t)batch_, hipMemcpyHostToDevice, st_));
-        }
+        if (lpt_ && !debug_token("batch_no_lpt")) longest_first_order();
         return solved;
     }
+    // pq_batch_clone (idx null: the whole batch) / pq_batch_clone_select: a second handle whose instance j is instance idx[j] of s, without a new setup.  The
+    // structure -- sbufs_, the analyses, the layout, the kernel mode -- is s's (shared by reference count, nothing is analysed again); per instance the arena row,
+    // ruiz_c, the info, the profile row and, with lists per instance, the row of the bound table are gathered on this handle's stream; the descriptor, the bound
+    // table and the flag word of check_patterns_device are this handle's own.  idx has been checked by the caller.  s is waited for and read.
+    BatchSolver(const BatchSolver& s, const int* idx, int count) : dev_(s.dev_)
+    {
+        settings_ = s.settings_;
+        bound_sets_ = s.bound_sets_;
+        lpt_ = s.lpt_;
+        forced_mode_ = s.forced_mode_;
+        PQ_HIP(hipSetDevice(dev_));
+        st_ = Stream(dev_);
+        ev0_ = Event(0); ev1_ = Event(0);
+        if (!s.setup_done_) return;  // the scalars and no problem
+        const auto w0 = std::chrono::steady_clock::now();
+        std::vector<int> all;
+        if (!idx) {
+            all.resize((size_t)s.batch_);
+            for (int i = 0; i < s.batch_; ++i) all[(size_t)i] = i;
+            idx = all.data();
+            count = s.batch_;
+        }
+        batch_ = count; n_ = s.n_; p_ = s.p_; m_ = s.m_; nt_ = s.nt_; mode_ = s.mode_;
+        per_inst_ = s.per_inst_; ldlt_ = s.ldlt_;
+        // the register budget of the launch follows THIS batch (build_multistage_shared); the variants agree bit for bit (tests/test_batch_variants_gpu.py)
+        wpe_ = (mode_ == MODE_WAVE && !debug_token("batch_wpe")) ? wave_budget(count) : s.wpe_;
+        ul_ = s.ul_; sym_ = s.sym_; layout_ = s.layout_;
+        fin_hl_ = s.fin_hl_; fin_hu_ = s.fin_hu_; fin_xl_ = s.fin_xl_; fin_xu_ = s.fin_xu_;
+        sbufs_ = s.sbufs_;
+        fin_hl_d_ = s.fin_hl_d_; fin_hu_d_ = s.fin_hu_d_; fin_xl_d_ = s.fin_xl_d_; fin_xu_d_ = s.fin_xu_d_;
+        nzP_in_ = s.nzP_in_; nzA_in_ = s.nzA_in_; nzG_in_ = s.nzG_in_;
+        mapP_ = s.mapP_; mapA_ = s.mapA_; mapG_ = s.mapG_; disabled_d_ = s.disabled_d_; rzPp_ = s.rzPp_; rzPi_ = s.rzPi_; Grow_ = s.Grow_;
+        last_kernel_ms_ = s.last_kernel_ms_;
+        if (ldlt_) {
+            size_t free_b = 0, total_b = 0;
+            const double need = (double)layout_.stride * count * sizeof(double);
+            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > 0.9 * (double)free_b)
+                throw std::runtime_error("batch clone: sparse_ldlt backend: the arena of " + std::to_string(count) + " instances needs " + std::to_string(need / 1e9) +
+                                         " GB of device memory, " + std::to_string((double)free_b / 1e9) + " GB free");
+        }
+        const long long R = per_inst_ ? bl_row_ints(n_, m_) : 0;
+        arena_.alloc((size_t)layout_.stride * count);
+        ruiz_c_.alloc(count);
+        infos_.alloc(count);
+        order_.alloc(count);
+        prof_.alloc((size_t)count * NPROF);
+        shared_.alloc(1);
+        fin_flag_.alloc(1);
+        if (per_inst_) bl_tab_.alloc((size_t)R * count);
+        DBuf<int> idx_d((size_t)count);
+        infos_h_.resize((size_t)count);
+        for (int j = 0; j < count; ++j) infos_h_[(size_t)j] = s.infos_h_[(size_t)idx[j]];
+        order_h_.resize((size_t)count);
+        shared_h_ = s.shared_h_;
+        shared_h_.set = settings_;
+        shared_h_.bl_tab = per_inst_ ? bl_tab_.p : nullptr;
+        stream_wait(s.st_);
+        PQ_HIP(hipMemcpyAsync(idx_d.p, idx, sizeof(int) * (size_t)count, hipMemcpyHostToDevice, st_));
+        PQ_HIP(hipMemcpyAsync(shared_.p, &shared_h_, sizeof(BatchShared), hipMemcpyHostToDevice, st_));
+        PQ_HIP(hipEventRecord(ev0_, st_));
+        gather_rows(arena_.p, s.arena_.p, idx_d.p, count, sizeof(double) * (size_t)layout_.stride, true);
+        gather_rows(ruiz_c_.p, s.ruiz_c_.p, idx_d.p, count, sizeof(double));
+        gather_rows(infos_.p, s.infos_.p, idx_d.p, count, sizeof(pq_info));
+        gather_rows(prof_.p, s.prof_.p, idx_d.p, count, sizeof(double) * NPROF);
+        if (per_inst_) gather_rows(bl_tab_.p, s.bl_tab_.p, idx_d.p, count, sizeof(int) * (size_t)R);
+        PQ_HIP(hipEventRecord(ev1_, st_));
+        // the order of the next launch from the gathered infos, as solve() leaves it (the identity before the first solve: the sort is stable)
+        if (lpt_ && !debug_token("batch_no_lpt")) longest_first_order();
+        else {
+            for (int i = 0; i < count; ++i) order_h_[(size_t)i] = i;
+            PQ_HIP(hipMemcpyAsync(order_.p, order_h_.data(), sizeof(int) * (size_t)count, hipMemcpyHostToDevice, st_));
+        }
+        stream_wait(st_);
+        float ms = 0.f;
+        PQ_HIP(hipEventElapsedTime(&ms, ev0_, ev1_));
+        clone_ms_[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
+        clone_ms_[1] = ms;
+        setup_done_ = true;
+    }
+    bool is_set_up() const { return setup_done_; }
+    long long arena_stride() const { return setup_done_ ? layout_.stride : 0; }
+    const double* clone_ms() const { return clone_ms_; }
     // update() of every instance, vectors only; the set of finite bounds must be the one given at setup (it is part of the shared structure) -- or, with
     // PQ_BOUND_SETS_PER_INSTANCE, whatever the vectors say: k_batch_bound_lists rewrites every instance's lists first
     // mem = PQ_MEM_DEVICE: the kernels read the caller's device arrays in place (no staging buffers, no copies)
@@ -1944,6 +2065,53 @@ private:
     static constexpr int STAGE_INST = 256;
     static constexpr int LDLT_MAX_N = 8192;  // the single-QP sparse_ldlt takes the reference-order engine up to this size too; y and D in LDS: 128 KB at most
 
+    // Waves per SIMD the MODE_WAVE kernel is launched for, from the batch size (the measurements: build_multistage_shared)
+    static int wave_budget(int batch)
+    {
+        int dev = 0, cus = 256;
+        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        const long long per_cu = ((long long)batch + cus - 1) / std::max(cus, 1);
+        return per_cu <= 8 ? 2 : (per_cu <= 12 ? 3 : 4);
+    }
+    // order_ from infos_h_: the instances that took most iterations first, ties in index order (see solve())
+    void longest_first_order()
+    {
+        const int cap = std::max(settings_.max_iter, 1) + 1;
+        std::vector<int> cnt((size_t)cap + 1, 0);
+        for (const auto& i : infos_h_) cnt[(size_t)std::min(std::max(i.iter, 0), cap - 1)]++;
+        std::vector<int> first((size_t)cap, 0);
+        int run = 0;
+        for (int it = cap - 1; it >= 0; --it) { first[(size_t)it] = run; run += cnt[(size_t)it]; }
+        for (int i = 0; i < batch_; ++i) order_h_[(size_t)first[(size_t)std::min(std::max(infos_h_[(size_t)i].iter, 0), cap - 1)]++] = i;
+        PQ_HIP(hipMemcpyAsync(order_.p, order_h_.data(), sizeof(int) * (size_t)batch_, hipMemcpyHostToDevice, st_));
+    }
+    // dst[j][0 .. row_bytes) = src[idx_d[j]][0 .. row_bytes) for j < count on st_ (k_batch_gather_rows): 16-byte words when the row and both bases allow, else 8,
+    // else 4.  The arena's rows are doubles and its stride is even by layout_shared, so they take 16-byte words; PIQP_AMD_DEBUG=batch_clone_words=8 holds the arena
+    // to 8-byte words (the path of an odd stride, for the tests).  At most 8 workgroups per compute unit, the rest grid-stride.
+    template <class W>
+    void gather_launch(void* dst, const void* src, const int* idx_d, long long count, size_t row_bytes)
+    {
+        const long long wpr = (long long)(row_bytes / sizeof(W));
+        const long long work = wpr >= GATHER_CHUNK ? count * ((wpr + GATHER_CHUNK - 1) / GATHER_CHUNK) : (count * wpr + GATHER_THREADS - 1) / GATHER_THREADS;
+        int dev = 0, cus = 256;
+        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        const long long cap = 8LL * std::max(cus, 1);
+        hipLaunchKernelGGL(k_batch_gather_rows<W>, dim3((unsigned)std::max(1LL, std::min(work, cap))), dim3(GATHER_THREADS), 0, st_, (W*)dst, (const W*)src, idx_d, count, wpr);
+        PQ_HIP(hipGetLastError());
+    }
+    void gather_rows(void* dst, const void* src, const int* idx_d, long long count, size_t row_bytes, bool arena = false)
+    {
+        if (count <= 0 || !row_bytes) return;
+        size_t a = row_bytes | (size_t)(uintptr_t)dst | (size_t)(uintptr_t)src;
+        if (arena) if (const char* e = debug_token("batch_clone_words")) if (std::atoi(e) == 8) a |= 8;
+        if (a % 16 == 0) gather_launch<uint4>(dst, src, idx_d, count, row_bytes);
+        else if (a % 8 == 0) gather_launch<unsigned long long>(dst, src, idx_d, count, row_bytes);
+        else if (a % 4 == 0) gather_launch<unsigned>(dst, src, idx_d, count, row_bytes);
+        else throw std::runtime_error("batch clone: a row that is no multiple of 4 bytes");
+        if (arena && debug_token("batch_clone_info"))
+            std::fprintf(stderr, "[piqp_amd] batch clone: %lld rows of %zu bytes in %d-byte words\n", count, row_bytes, a % 16 == 0 ? 16 : 8);
+    }
+
     void require_ldlt(const char* what) const
     {
         if (!setup_done_) throw std::runtime_error("batch solver not set up");
@@ -1987,13 +2155,13 @@ private:
     void check_patterns_device(const double* h_l, const double* h_u, const double* x_l, const double* x_u)
     {
         if (!h_l && !h_u && !x_l && !x_u) return;
-        PQ_HIP(hipMemsetAsync(fin_flag_, 0, sizeof(int), st_));
-        if (h_l) ingest_check_finite_pattern(h_l, fin_hl_d_, batch_, m_, true, fin_flag_, st_);
-        if (h_u) ingest_check_finite_pattern(h_u, fin_hu_d_, batch_, m_, false, fin_flag_, st_);
-        if (x_l) ingest_check_finite_pattern(x_l, fin_xl_d_, batch_, n_, true, fin_flag_, st_);
-        if (x_u) ingest_check_finite_pattern(x_u, fin_xu_d_, batch_, n_, false, fin_flag_, st_);
+        PQ_HIP(hipMemsetAsync(fin_flag_.p, 0, sizeof(int), st_));
+        if (h_l) ingest_check_finite_pattern(h_l, fin_hl_d_, batch_, m_, true, fin_flag_.p, st_);
+        if (h_u) ingest_check_finite_pattern(h_u, fin_hu_d_, batch_, m_, false, fin_flag_.p, st_);
+        if (x_l) ingest_check_finite_pattern(x_l, fin_xl_d_, batch_, n_, true, fin_flag_.p, st_);
+        if (x_u) ingest_check_finite_pattern(x_u, fin_xu_d_, batch_, n_, false, fin_flag_.p, st_);
         int flag = 0;
-        PQ_HIP(hipMemcpyAsync(&flag, fin_flag_, sizeof(int), hipMemcpyDeviceToHost, st_));
+        PQ_HIP(hipMemcpyAsync(&flag, fin_flag_.p, sizeof(int), hipMemcpyDeviceToHost, st_));
         stream_wait(st_);
         if (flag) throw std::runtime_error("batch update: the set of finite bounds differs from the one given at setup");
     }
@@ -2012,25 +2180,23 @@ private:
         const Vec hfin(std::max(m, 1), 0.0);
         auto probe = make_sparse_host_data(n, p, m, Pp, Pi, iP.data(), c, Ap, Ai, Ap ? iA.data() : nullptr, b, Gp, Gi, Gp ? iG.data() : nullptr, per_inst_ ? hfin.data() : h_l,
                                            per_inst_ ? hfin.data() : h_u, x_l, x_u);
-        Grow_ = (per_inst_ && Gp && nzG_in_ > 0) ? up(ibufs_, std::vector<int>(Gi, Gi + nzG_in_)) : nullptr;
+        Grow_ = (per_inst_ && Gp && nzG_in_ > 0) ? up(sbufs_->i, std::vector<int>(Gi, Gi + nzG_in_)) : nullptr;
         auto invert = [&](const Vec& stored, int nz_in) {
             std::vector<int> map(std::max(nz_in, 1), -1);
             for (size_t t = 0; t < stored.size(); ++t) if (stored[t] > 0.0) map[(int)stored[t] - 1] = (int)t;
             return map;
         };
-        mapP_ = up(ibufs_, invert(probe->sP_utri.val, nzP_in_));
-        mapA_ = up(ibufs_, invert(probe->sAT.val, nzA_in_));
-        mapG_ = up(ibufs_, invert(probe->sGT.val, nzG_in_));
+        mapP_ = up(sbufs_->i, invert(probe->sP_utri.val, nzP_in_));
+        mapA_ = up(sbufs_->i, invert(probe->sAT.val, nzA_in_));
+        mapG_ = up(sbufs_->i, invert(probe->sGT.val, nzG_in_));
         std::vector<int> dis(std::max(m_, 1), 0);
         for (int i = 0; i < m_; ++i) dis[i] = !fin_hl_[i] && !fin_hu_[i];
-        disabled_d_ = up(ibufs_, dis);
+        disabled_d_ = up(sbufs_->i, dis);
         auto as_int = [](const std::vector<char>& f) { std::vector<int> v(std::max<size_t>(f.size(), 1), 0); for (size_t i = 0; i < f.size(); ++i) v[i] = f[i] != 0; return v; };
-        fin_hl_d_ = up(ibufs_, as_int(fin_hl_)); fin_hu_d_ = up(ibufs_, as_int(fin_hu_)); fin_xl_d_ = up(ibufs_, as_int(fin_xl_)); fin_xu_d_ = up(ibufs_, as_int(fin_xu_));
-        ibufs_.emplace_back();
-        ibufs_.back().alloc(1);
-        fin_flag_ = ibufs_.back().p;
-        rzPp_ = up(ibufs_, d0.sP_utri.colptr);
-        rzPi_ = up(ibufs_, d0.sP_utri.rowind.empty() ? std::vector<int>(1, 0) : d0.sP_utri.rowind);
+        fin_hl_d_ = up(sbufs_->i, as_int(fin_hl_)); fin_hu_d_ = up(sbufs_->i, as_int(fin_hu_)); fin_xl_d_ = up(sbufs_->i, as_int(fin_xl_)); fin_xu_d_ = up(sbufs_->i, as_int(fin_xu_));
+        fin_flag_.alloc(1);
+        rzPp_ = up(sbufs_->i, d0.sP_utri.colptr);
+        rzPi_ = up(sbufs_->i, d0.sP_utri.rowind.empty() ? std::vector<int>(1, 0) : d0.sP_utri.rowind);
         stream_wait(st_);
     }
 
@@ -2101,15 +2267,15 @@ private:
         BatchShared& S = shared_h_;
         S = BatchShared{};
         S.n = n; S.p = p; S.m = m; S.n_h_l = d.n_h_l; S.n_h_u = d.n_h_u; S.n_x_l = d.n_x_l; S.n_x_u = d.n_x_u;
-        ibufs_.clear(); lbufs_.clear();
-        ibufs_.reserve(64); lbufs_.reserve(16);
+        sbufs_ = std::make_shared<StructBufs>();  // (a clone may still hold the set of the last setup)
+        sbufs_->i.reserve(64); sbufs_->l.reserve(16);
         std::vector<int> has_l(std::max(m, 1), 0), has_u(std::max(m, 1), 0), pos_l(n, -1), pos_u(n, -1);
         for (int i = 0; i < d.n_h_l; ++i) has_l[d.h_l_idx[i]] = 1;
         for (int i = 0; i < d.n_h_u; ++i) has_u[d.h_u_idx[i]] = 1;
         for (int i = 0; i < d.n_x_l; ++i) pos_l[d.x_l_idx[i]] = i;
         for (int i = 0; i < d.n_x_u; ++i) pos_u[d.x_u_idx[i]] = i;
-        S.h_l_idx = up(ibufs_, d.h_l_idx); S.h_u_idx = up(ibufs_, d.h_u_idx); S.x_l_idx = up(ibufs_, d.x_l_idx); S.x_u_idx = up(ibufs_, d.x_u_idx);
-        S.has_l = up(ibufs_, has_l); S.has_u = up(ibufs_, has_u); S.pos_l = up(ibufs_, pos_l); S.pos_u = up(ibufs_, pos_u);
+        S.h_l_idx = up(sbufs_->i, d.h_l_idx); S.h_u_idx = up(sbufs_->i, d.h_u_idx); S.x_l_idx = up(sbufs_->i, d.x_l_idx); S.x_u_idx = up(sbufs_->i, d.x_u_idx);
+        S.has_l = up(sbufs_->i, has_l); S.has_u = up(sbufs_->i, has_u); S.pos_l = up(sbufs_->i, pos_l); S.pos_u = up(sbufs_->i, pos_u);
         // symmetrised P and row-oriented A, G with value-source maps
         const Csc& U = d.sP_utri;
         S.nzP = U.nnz(); S.nzA = d.sAT.nnz(); S.nzG = d.sGT.nnz();
@@ -2120,19 +2286,19 @@ private:
             std::vector<int> fi(fp[n]), src(fp[n]), nx(fp.begin(), fp.end() - 1);
             for (int j = 0; j < n; ++j) for (int q = U.colptr[j]; q < U.colptr[j + 1]; ++q) { const int t = nx[j]++; fi[t] = U.rowind[q]; src[t] = q; }
             for (int j = 0; j < n; ++j) for (int q = U.colptr[j]; q < U.colptr[j + 1]; ++q) { const int i = U.rowind[q]; if (i != j) { const int t = nx[i]++; fi[t] = j; src[t] = q; } }
-            S.Pf_p = up(ibufs_, fp); S.Pf_i = up(ibufs_, fi); S.Pf_src = up(ibufs_, src);
+            S.Pf_p = up(sbufs_->i, fp); S.Pf_i = up(sbufs_->i, fi); S.Pf_src = up(sbufs_->i, src);
         }
         auto rows_of = [&](const Csc& T, const int*& Tp, const int*& Ti, const int*& Rp, const int*& Ri, const int*& Rs) {
             std::vector<int> tp(T.colptr), ti(T.rowind);
             if (tp.empty()) tp.assign(1, 0);
-            Tp = up(ibufs_, tp); Ti = up(ibufs_, ti);
+            Tp = up(sbufs_->i, tp); Ti = up(sbufs_->i, ti);
             const int cols = T.cols, nnz = T.nnz();
             std::vector<int> rp(n + 1, 0), ri(nnz), rs(nnz);
             for (int q = 0; q < nnz; ++q) rp[T.rowind[q] + 1]++;
             for (int j = 0; j < n; ++j) rp[j + 1] += rp[j];
             std::vector<int> nx(rp.begin(), rp.end() - 1);
             for (int k = 0; k < cols; ++k) for (int q = T.colptr[k]; q < T.colptr[k + 1]; ++q) { const int t = nx[T.rowind[q]]++; ri[t] = k; rs[t] = q; }
-            Rp = up(ibufs_, rp); Ri = up(ibufs_, ri); Rs = up(ibufs_, rs);
+            Rp = up(sbufs_->i, rp); Ri = up(sbufs_->i, ri); Rs = up(sbufs_->i, rs);
         };
         rows_of(d.sAT, S.AT_p, S.AT_i, S.A_p, S.A_i, S.A_src);
         rows_of(d.sGT, S.GT_p, S.GT_i, S.G_p, S.G_i, S.G_src);
@@ -2148,10 +2314,10 @@ private:
         // multistage structure
         std::vector<int> start(sym_.N);
         for (int b = 0; b < sym_.N; ++b) start[b] = sym_.block_info[b].start;
-        S.M = MsMeta{sym_.N, sym_.arrow, n, up(ibufs_, sym_.w), up(ibufs_, sym_.off), up(ibufs_, sym_.h), up(ibufs_, start), up(lbufs_, sym_.front_off), up(lbufs_, sym_.pan_off)};
-        S.GA = GroupMeta{up(ibufs_, sym_.A.row_ptr), up(ibufs_, sym_.A.rows), up(lbufs_, sym_.A.x_off)};
-        S.GG = GroupMeta{up(ibufs_, sym_.G.row_ptr), up(ibufs_, sym_.G.rows), up(lbufs_, sym_.G.x_off)};
-        S.P_dst = up(lbufs_, sym_.P_dst); S.A_dst = up(lbufs_, sym_.A.dst); S.G_dst = up(lbufs_, sym_.G.dst);
+        S.M = MsMeta{sym_.N, sym_.arrow, n, up(sbufs_->i, sym_.w), up(sbufs_->i, sym_.off), up(sbufs_->i, sym_.h), up(sbufs_->i, start), up(sbufs_->l, sym_.front_off), up(sbufs_->l, sym_.pan_off)};
+        S.GA = GroupMeta{up(sbufs_->i, sym_.A.row_ptr), up(sbufs_->i, sym_.A.rows), up(sbufs_->l, sym_.A.x_off)};
+        S.GG = GroupMeta{up(sbufs_->i, sym_.G.row_ptr), up(sbufs_->i, sym_.G.rows), up(sbufs_->l, sym_.G.x_off)};
+        S.P_dst = up(sbufs_->l, sym_.P_dst); S.A_dst = up(sbufs_->l, sym_.A.dst); S.G_dst = up(sbufs_->l, sym_.G.dst);
         {
             std::vector<int> eb, erc;
             for (int b = 0; b < sym_.N; ++b) {
@@ -2160,7 +2326,7 @@ private:
                 for (int c = 0; c < h; ++c) for (int r = c; r < h; ++r) { eb.push_back(b); erc.push_back(r | (c << 16)); }
             }
             S.n_ent = (int)eb.size();
-            S.ent_b = up(ibufs_, eb); S.ent_rc = up(ibufs_, erc);
+            S.ent_b = up(sbufs_->i, eb); S.ent_rc = up(sbufs_->i, erc);
             // the same entries as absolute front-arena offsets + the x_reg entry that lands on them (-1: none): what a QP without inequality rows needs of
             // the assembly (no per-stage row loop), two loads instead of a chain through the stage tables
             std::vector<int> eat(eb.size()), exr(eb.size());
@@ -2170,7 +2336,7 @@ private:
                 eat[e] = (int)(sym_.front_off[b] + r + (long long)c * sym_.h[b]);
                 exr[e] = (r == c && c < sym_.w[b]) ? sym_.block_info[b].start + c : -1;
             }
-            S.ent_at = up(ibufs_, eat); S.ent_xr = up(ibufs_, exr);
+            S.ent_at = up(sbufs_->i, eat); S.ent_xr = up(sbufs_->i, exr);
             S.ent_flat = fits ? 1 : 0;
         }
         // chain workspace: front + carried update + inverse (factor) / 2 vectors + panel (solve)
@@ -2199,12 +2365,7 @@ private:
             // of them wait: 8192 QPs 6.77 ms compiled for four waves per SIMD (128 registers, 16 workgroups per CU), 7.25 for five (18 per CU, the LDS
             // bound), 7.54 for three, 8.97 for six.  A batch that fits in one round of workgroups anyway takes the largest budget that still holds it:
             // 1024 QPs 2.41 ms for two waves per SIMD, 2.43 three, 2.52 four, 2.67 five.
-            if (!debug_token("batch_wpe")) {
-                int dev = 0, cus = 256;
-                if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-                const long long per_cu = ((long long)batch_ + cus - 1) / std::max(cus, 1);
-                wpe_ = per_cu <= 8 ? 2 : (per_cu <= 12 ? 3 : 4);
-            }
+            if (!debug_token("batch_wpe")) wpe_ = wave_budget(batch_);
             S.res_f = 0; S.res_pan = 0; S.res_x = (int)sym_.qpan_doubles; S.res_chain = S.res_x + n;
             S.fcap = 0; S.lofs = 0;
             S.chain_lds_doubles = (int)wave_doubles;
@@ -2248,7 +2409,7 @@ private:
             if (small_chain * (long long)sizeof(double) > LDS_LIMIT_BYTES) throw std::runtime_error("batch setup: a stage is too wide for this backend");
             S.chain_lds_doubles = (int)small_chain;
         }
-        if (wave_pan) S.M.pan_off = up(lbufs_, sym_.qpan_off);  // compact Linv | Q panels
+        if (wave_pan) S.M.pan_off = up(sbufs_->l, sym_.qpan_off);  // compact Linv | Q panels
         S.meta_ofs = S.chain_lds_doubles;
         S.chain_lds_doubles += 4 * sym_.N + 2;  // 4 int + 2 int64 tables of N entries
     }
@@ -2270,13 +2431,13 @@ private:
             for (int q = P.colptr[j]; q < P.colptr[j + 1]; ++q)
                 if (P.rowind[q] == j) { pdiag[j] = q; mapP[q] = -1; }
         auto nz = [](const std::vector<int>& v) { return v.empty() ? std::vector<int>(1, 0) : v; };
-        S.ul_Cp = up(ibufs_, U.Cp); S.ul_Ci = up(ibufs_, nz(U.Ci)); S.ul_diag = up(ibufs_, nz(U.diag_pos)); S.ul_pdiag = up(ibufs_, pdiag);
-        S.ul_mapP = up(ibufs_, nz(mapP)); S.ul_mapA = up(ibufs_, nz(U.mapA)); S.ul_mapG = up(ibufs_, nz(U.mapG));
-        S.ul_perm = up(ibufs_, nz(U.perm)); S.ul_Lp = up(ibufs_, U.Lp); S.ul_Li = up(ibufs_, nz(U.Li)); S.ul_Lcol = up(ibufs_, nz(U.Lcol));
-        S.ul_Rp = up(ibufs_, U.Rp); S.ul_Rcol = up(ibufs_, nz(U.Rcol)); S.ul_Rpos = up(ibufs_, nz(U.Rpos));
+        S.ul_Cp = up(sbufs_->i, U.Cp); S.ul_Ci = up(sbufs_->i, nz(U.Ci)); S.ul_diag = up(sbufs_->i, nz(U.diag_pos)); S.ul_pdiag = up(sbufs_->i, pdiag);
+        S.ul_mapP = up(sbufs_->i, nz(mapP)); S.ul_mapA = up(sbufs_->i, nz(U.mapA)); S.ul_mapG = up(sbufs_->i, nz(U.mapG));
+        S.ul_perm = up(sbufs_->i, nz(U.perm)); S.ul_Lp = up(sbufs_->i, U.Lp); S.ul_Li = up(sbufs_->i, nz(U.Li)); S.ul_Lcol = up(sbufs_->i, nz(U.Lcol));
+        S.ul_Rp = up(sbufs_->i, U.Rp); S.ul_Rcol = up(sbufs_->i, nz(U.Rcol)); S.ul_Rpos = up(sbufs_->i, nz(U.Rpos));
         const std::vector<int> grp = ul_backward_groups(U.Lp, N);
         S.ul_nbgroup = (int)grp.size() / 4;
-        S.ul_bgroup = reinterpret_cast<const int4*>(up(ibufs_, grp.empty() ? std::vector<int>(4, 0) : grp));
+        S.ul_bgroup = reinterpret_cast<const int4*>(up(sbufs_->i, grp.empty() ? std::vector<int>(4, 0) : grp));
         // dynamic LDS: the work vector (factorisation) / the solution (substitution), then D
         S.chain_lds_doubles = 2 * N;
         S.meta_ofs = S.chain_lds_doubles;
@@ -2372,23 +2533,23 @@ private:
     int bound_sets_ = PQ_BOUND_SETS_SHARED;  // pq_batch_set_bound_sets: read by the next setup, which records it in per_inst_
     bool per_inst_ = false;
     DBuf<int> bl_tab_;                       // per_inst_: [batch][bl_row_ints] (BatchShared::bl_tab)
-    const int* Grow_ = nullptr;              // per_inst_: the row of the caller's k-th value of G (device, owned by ibufs_)
+    const int* Grow_ = nullptr;              // per_inst_: the row of the caller's k-th value of G (device, owned by sbufs_->i)
     bool ldlt_ = false;  // backend fixed at setup: sparse_ldlt (MODE_LDLT) or sparse_multistage
     sparse::UpLooking ul_;
     std::vector<char> fin_hl_, fin_hu_, fin_xl_, fin_xu_;  // which of the caller's bounds are finite (shared by all instances)
     const int *fin_hl_d_ = nullptr, *fin_hu_d_ = nullptr, *fin_xl_d_ = nullptr, *fin_xu_d_ = nullptr;  // device copies (0 / 1 per entry) and the flag word of
-    int* fin_flag_ = nullptr;                                                                            // check_patterns_device; owned by ibufs_
+    DBuf<int> fin_flag_;                                                                                 // check_patterns_device (the flag: this handle's own)
     int nzP_in_ = 0, nzA_in_ = 0, nzG_in_ = 0;             // the caller's nonzero counts (P may carry its lower triangle)
-    const int *mapP_ = nullptr, *mapA_ = nullptr, *mapG_ = nullptr, *disabled_d_ = nullptr, *rzPp_ = nullptr, *rzPi_ = nullptr;  // device, owned by ibufs_
+    const int *mapP_ = nullptr, *mapA_ = nullptr, *mapG_ = nullptr, *disabled_d_ = nullptr, *rzPp_ = nullptr, *rzPi_ = nullptr;  // device, owned by sbufs_->i
     double last_kernel_ms_ = 0.0;
+    double clone_ms_[2] = {0.0, 0.0};  // of the clone call that made this handle: wall, device time of the gathers (pq_batch_clone_ms)
     bool lpt_ = true;
     pq_settings settings_;
     multistage::Symbolic sym_;
     Layout layout_;
     BatchShared shared_h_{};
     DBuf<BatchShared> shared_;
-    std::vector<DBuf<int>> ibufs_;
-    std::vector<DBuf<long long>> lbufs_;
+    std::shared_ptr<StructBufs> sbufs_;
     DBuf<double> arena_, ruiz_c_, prof_;
     DBuf<pq_info> infos_;
     DBuf<int> order_;            // block -> instance of the next launch
@@ -2419,6 +2580,44 @@ int pq_batch_create(pq_batch** out, int device)
     return guarded([&] { auto* h = new pq_batch; h->impl.reset(new BatchSolver(device)); *out = h; return (int)PQ_OK; });
 }
 void pq_batch_destroy(pq_batch* s) { delete s; }
+int pq_batch_clone(const pq_batch* s, pq_batch** out)
+{
+    if (!s || !out) return fail(PQ_ERR_INVALID, "pq_batch_clone: null argument");
+    return guarded([&] {
+        std::unique_ptr<pq_batch> h(new pq_batch);
+        h->impl.reset(new BatchSolver(*s->impl, nullptr, 0));
+        *out = h.release();
+        return (int)PQ_OK;
+    });
+}
+int pq_batch_clone_select(const pq_batch* s, const int* idx, int count, pq_batch** out)
+{
+    if (!s || !out) return fail(PQ_ERR_INVALID, "pq_batch_clone_select: null argument");
+    if (!idx) return fail(PQ_ERR_INVALID, "pq_batch_clone_select: idx is null");
+    if (count < 1) return fail(PQ_ERR_INVALID, "pq_batch_clone_select: count = %d, count >= 1 wanted", count);
+    if (!s->impl->is_set_up()) return fail(PQ_ERR_INVALID, "pq_batch_clone_select: the handle has no problem (no setup yet)");
+    const int batch = s->impl->batch();
+    for (int j = 0; j < count; ++j)
+        if (idx[j] < 0 || idx[j] >= batch) return fail(PQ_ERR_INVALID, "pq_batch_clone_select: idx[%d] = %d outside [0, %d)", j, idx[j], batch);
+    return guarded([&] {
+        std::unique_ptr<pq_batch> h(new pq_batch);
+        h->impl.reset(new BatchSolver(*s->impl, idx, count));
+        *out = h.release();
+        return (int)PQ_OK;
+    });
+}
+int pq_batch_clone_ms(const pq_batch* s, double out2[2])
+{
+    if (!s || !out2) return fail(PQ_ERR_INVALID, "pq_batch_clone_ms: null argument");
+    out2[0] = s->impl->clone_ms()[0];
+    out2[1] = s->impl->clone_ms()[1];
+    return PQ_OK;
+}
+long long pq_batch_arena_stride(const pq_batch* s)
+{
+    if (!s) return fail(PQ_ERR_INVALID, "pq_batch_arena_stride: null argument");
+    return s->impl->arena_stride();
+}
 pq_settings* pq_batch_settings(pq_batch* s) { return s ? &s->impl->settings() : nullptr; }
 int pq_batch_set_bound_sets(pq_batch* s, int mode)
 {
