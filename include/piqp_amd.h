@@ -361,7 +361,7 @@ int pq_solver_setup_dense(pq_solver *s, int n, int p, int m, const double *P, co
                           const double *x_u);
 /* ---- problem data that already lives in GPU memory, results returned there ----
  * The *_mem entry points below are the calls above / below them with two more arguments; pq_solver_setup_dense, pq_solver_update_dense, pq_solver_get_result,
- * pq_batch_update, pq_batch_update_data and pq_batch_get_result forward to them with PQ_MEM_HOST (and PQ_COL_MAJOR).
+ * pq_batch_setup_sparse, pq_batch_update, pq_batch_update_data and pq_batch_get_result forward to them with PQ_MEM_HOST (and PQ_COL_MAJOR).
  *   mem     PQ_MEM_HOST, or PQ_MEM_DEVICE: EVERY non-NULL array pointer of the call is device memory on the handle's device.
  *   layout  storage order of the matrices P (n x n), A (p x n), G (m x n) only: PQ_COL_MAJOR, or PQ_ROW_MAJOR (what a contiguous torch tensor is).  The solver
  *           keeps upper(P), A^T, G^T column-major: a row-major A already is the column-major A^T (plain copy), a column-major one goes through a transpose
@@ -515,11 +515,38 @@ int pq_batch_set_bound_sets(pq_batch *s, int mode);
 int pq_batch_bound_lists(const pq_batch *s, int instance, int counts[4], int *h_l_idx, int *h_u_idx, int *x_l_idx, int *x_u_idx, int *dropped);
 /* SparseSolver::setup (solver.hpp:1297-1308) per instance.  Patterns (CSC, HOST): P n x n (upper triangle taken),
  * A p x n, G m x n; NULL pattern = absent.  Values / vectors are [batch][nnz] resp. [batch][len] row-major HOST
- * arrays; NULL h_l/h_u/x_l/x_u = nullopt.  Returns 1 when set up. */
+ * arrays; NULL h_l/h_u/x_l/x_u = nullopt.  Returns 1 when set up.  Forwards to pq_batch_setup_sparse_mem with PQ_MEM_HOST: one HostData per instance
+ * on host threads, packed into a staging buffer, the arena copied up in slices. */
 int pq_batch_setup_sparse(pq_batch *s, int batch, int n, int p, int m, const int *Pp, const int *Pi, const double *Px,
                           const double *c, const int *Ap, const int *Ai, const double *Ax, const double *b,
                           const int *Gp, const int *Gi, const double *Gx, const double *h_l, const double *h_u,
                           const double *x_l, const double *x_u);
+/* The same with the problem data in host or device memory (mem; ordering contract: see pq_solver_setup_dense_mem; any other value: PQ_ERR_INVALID, the handle
+ * as it was).  PQ_MEM_DEVICE: Px, Ax, Gx and the six vectors are [batch][nnz] / [batch][len] DEVICE arrays on the handle's device; the six index arrays stay HOST
+ * memory, as in pq_solver_setup_sparse_mem.  The shared structure is analysed from the patterns -- no analysis reads a value -- and from instance 0's h_l, h_u, x_l,
+ * x_u, which are fetched to the host: 8 x (the lengths of those of the four that are given) bytes, 8 (2 m + 2 n) at most, in either bound-set mode.  Nothing else
+ * of the problem data comes to the host and none of it crosses host to device: no HostData is built for the instances 1 and up, no staging buffer is filled.  Kernels
+ * read the caller's arrays where they are: with shared bound sets the check that every instance has instance 0's finiteness pattern (one flag word comes back; the
+ * error text of the host mode), with PQ_BOUND_SETS_PER_INSTANCE the table of every instance's lists (a vector that is not given has no finite entry; a row of G
+ * with no finite bound is dropped: in both lists, -1 / 1, its entries of G' zero); then the fill of the zeroed arena -- upper(P), A', G' through the entry maps the
+ * updates use, the vectors by the rules of set_h_l / set_h_u, the box vectors packed to the lists, x_b_scaling = 1.  Entries of P below the diagonal are never
+ * loaded.  The equilibration and everything after it are the kernels of the host mode on the same bits, so the two modes agree bit for bit; so do the refusals
+ * and the state of the handle after one. */
+int pq_batch_setup_sparse_mem(pq_batch *s, int batch, int n, int p, int m, const int *Pp, const int *Pi, const double *Px,
+                              const double *c, const int *Ap, const int *Ai, const double *Ax, const double *b,
+                              const int *Gp, const int *Gi, const double *Gx, const double *h_l, const double *h_u,
+                              const double *x_l, const double *x_u, int mem);
+/* Figures of the last setup / update of the handle, computed from the shapes of what the call was given (not counted by the runtime).  out[0] = bytes of problem
+ * data moved across the host-device link: host mode 8 x batch x the lengths given (nnz of the matrices as the caller passes them); device mode 0 for an update and
+ * the fetch stated at pq_batch_setup_sparse_mem -- device to host -- for a setup.  out[1] = bytes the ingest kernels write into the arena: 8 x batch x (the stored
+ * nonzeros of the matrices given + the lengths of the vectors given; a device-mode setup writes both bounds of G and x_b_scaling whatever is given: 2 m + n in place
+ * of the lengths of h_l, h_u); box vectors count in full although they are packed to their lists; 0 for a host-mode setup, whose arena is copied up.  A NULL handle
+ * or out: PQ_ERR_INVALID, out untouched. */
+int pq_batch_last_ingest(const pq_batch *s, long long out[2]);
+/* Of the last pq_batch_setup_sparse(_mem) of the handle, milliseconds: out3[0] wall time of the call, out3[1] of it the host analysis (symbolic analysis, entry maps,
+ * descriptor and tables), out3[2] device time by the handle's events from the fill of the arena (host mode: the staged copies) to the end of the equilibration and
+ * prepare kernels.  Zeros before the first setup and on a clone.  A NULL handle or out3: PQ_ERR_INVALID, out3 untouched. */
+int pq_batch_setup_ms(const pq_batch *s, double out3[3]);
 /* update() of every instance with new VECTORS only (solver.hpp:218-308 with every optional matrix empty; the Ruiz scaling of the
  * setup is reused, :283-285).  [batch][len] HOST arrays, NULL = unchanged.  The set of finite bounds is part of the shared
  * structure and must not change (error otherwise); a doubly-infinite row of G stays as it was at setup.  With PQ_BOUND_SETS_PER_INSTANCE: see

@@ -116,6 +116,7 @@ SYMBOLS = [
     "pq_batch_dims", "pq_batch_block_info", "pq_batch_get_profile", "pq_batch_last_kernel_ms", "pq_batch_set_start_order",
     "pq_batch_kkt_factor", "pq_batch_kkt_solve", "pq_batch_ldlt_factor", "pq_batch_set_bound_sets", "pq_batch_bound_lists",
     "pq_batch_clone", "pq_batch_clone_select", "pq_batch_clone_ms", "pq_batch_arena_stride",
+    "pq_batch_setup_sparse_mem", "pq_batch_last_ingest", "pq_batch_setup_ms",
     "pq_dense_factor_create", "pq_dense_factor_destroy", "pq_dense_factor_compute", "pq_dense_factor_info", "pq_dense_factor_solve_in_place", "pq_dense_factor_matrix", "pq_dense_factor_last_ms",
     "pq_dense_factor_batch_create", "pq_dense_factor_batch_destroy", "pq_dense_factor_batch_compute", "pq_dense_factor_batch_info", "pq_dense_factor_batch_solve_in_place",
     "pq_dense_factor_batch_matrix", "pq_dense_factor_batch_last_ms",
@@ -213,6 +214,9 @@ def load():
     L.pq_batch_clone_ms.argtypes = [vp, vp]
     L.pq_batch_arena_stride.argtypes = [vp]
     L.pq_batch_arena_stride.restype = C.c_longlong
+    L.pq_batch_setup_sparse_mem.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int] + [vp] * 15 + [C.c_int]
+    L.pq_batch_last_ingest.argtypes = [vp, vp]
+    L.pq_batch_setup_ms.argtypes = [vp, vp]
     L.pq_dense_factor_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int]
     L.pq_dense_factor_destroy.argtypes = [vp]
     L.pq_dense_factor_destroy.restype = None

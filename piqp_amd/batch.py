@@ -92,14 +92,30 @@ class BatchSparseSolver(_Handle):
 
     def setup(self, P_pattern, P_values, c, A_pattern=None, A_values=None, b=None, G_pattern=None, G_values=None, h_l=None, h_u=None, x_l=None, x_u=None):
         """*_pattern: scipy sparse matrices giving the (sorted CSC) patterns of P (n x n), A (p x n), G (m x n);
-        *_values: [batch, nnz] arrays in that CSC order; vectors: [batch, len]."""
+        *_values: [batch, nnz] arrays in that CSC order; vectors: [batch, len].
+        If any of the value stacks or vectors is a torch CUDA tensor (float64, on the solver's GPU) the setup reads them all where they are
+        (pq_batch_setup_sparse_mem): numpy arguments beside them are moved to the GPU, strided views are made contiguous, torch's current stream is drained.
+        Nothing but instance 0's four bound vectors comes back to the host; the result is bit for bit the host-fed one."""
         Pp, Pi, Pm = self._pattern(P_pattern)
         Ap, Ai, Am = self._pattern(A_pattern)
         Gp, Gi, Gm = self._pattern(G_pattern)
         n = Pm.shape[0]
         p = 0 if Am is None else Am.shape[0]
         m = 0 if Gm is None else Gm.shape[0]
-        batch = np.asarray(c).shape[0]
+        nnz = (Pm.nnz, 0 if Am is None else Am.nnz, 0 if Gm is None else Gm.nnz)
+        batch = c.shape[0] if hasattr(c, "shape") else np.asarray(c).shape[0]
+        if device_call((P_values, c, A_values, b, G_values, h_l, h_u, x_l, x_u)):
+            no_A, no_G = Am is None, Gm is None
+            args = dict(P_values=P_values, c=c, A_values=None if no_A else A_values, b=None if no_A else b, G_values=None if no_G else G_values,
+                        h_l=None if no_G else h_l, h_u=None if no_G else h_u, x_l=x_l, x_u=x_u)
+            shapes = dict(P_values=(batch, nnz[0]), A_values=(batch, nnz[1]), G_values=(batch, nnz[2]), c=(batch, n), b=(batch, p), h_l=(batch, m), h_u=(batch, m),
+                          x_l=(batch, n), x_u=(batch, n))
+            k, _ = to_device_args(args, shapes, self.device)
+            sync_current_stream(self.device)
+            keep = [Pp, Pi, k["P_values"], k["c"], Ap, Ai, k["A_values"], k["b"], Gp, Gi, k["G_values"], k["h_l"], k["h_u"], k["x_l"], k["x_u"]]
+            ok = bool(check(self.L.pq_batch_setup_sparse_mem(self.h, batch, n, p, m, *[_ptr(a) for a in keep], MEM_DEVICE), "pq_batch_setup_sparse"))
+            self.batch, self.n, self.p, self.m, self._nnz = batch, n, p, m, nnz
+            return ok
         keep = [Pp, Pi, self._stack(P_values, batch, Pm.nnz), self._stack(c, batch, n),
                 Ap, Ai, None if Am is None else self._stack(A_values, batch, Am.nnz), None if Am is None else self._stack(b, batch, p),
                 Gp, Gi, None if Gm is None else self._stack(G_values, batch, Gm.nnz),
@@ -109,6 +125,19 @@ class BatchSparseSolver(_Handle):
         self.batch, self.n, self.p, self.m = batch, n, p, m
         self._nnz = (Pm.nnz, 0 if Am is None else Am.nnz, 0 if Gm is None else Gm.nnz)
         return ok
+
+    def last_ingest(self):
+        """of the last setup / update, from the shapes (pq_batch_last_ingest): dict(link_bytes -- problem data moved across the host-device link: 8 x batch x the
+        lengths given in a host call, 0 in a device update, the fetch of instance 0's bound vectors in a device setup --, kernel_bytes -- written by the ingest kernels)"""
+        o = np.zeros(2, dtype=np.int64)
+        check(self.L.pq_batch_last_ingest(self.h, o.ctypes.data), "pq_batch_last_ingest")
+        return dict(link_bytes=int(o[0]), kernel_bytes=int(o[1]))
+
+    def setup_ms(self):
+        """of the last setup(): dict(wall_ms, analysis_ms -- host: symbolic analysis, maps, tables --, device_ms -- arena fill, equilibration, prepare)"""
+        o = np.zeros(3)
+        check(self.L.pq_batch_setup_ms(self.h, o.ctypes.data), "pq_batch_setup_ms")
+        return dict(wall_ms=float(o[0]), analysis_ms=float(o[1]), device_ms=float(o[2]))
 
     def _device_args(self, args):
         """torch CUDA tensors (numpy arguments beside them are moved to the GPU), checked and contiguous; torch's current stream is drained"""

@@ -19,6 +19,8 @@
 // read in place of the shared lists and which k_batch_bound_lists rewrites at an update.
 // pq_batch_clone / pq_batch_clone_select make a second handle from a set-up one without a new setup, whole or by a list of instances: the structure is shared by
 // reference count, the per-instance rows are gathered by k_batch_gather_rows (the clone constructor of BatchSolver).
+// pq_batch_setup_sparse_mem with PQ_MEM_DEVICE sets a handle up from value stacks and vectors in device memory (setup_from_device): the structure from the patterns and
+// instance 0's bound vectors, the arena filled by k_batch_setup_ingest, no HostData for the other instances and no staging; from the arena on it is the host-fed setup.
 #include <algorithm>
 #include <cfloat>
 #include <chrono>
@@ -1404,9 +1406,11 @@ struct BatchAssignArgs {
     const int* Grow;  // per-instance bound sets: the row of the caller's k-th value of G (mapG then has no -1: the row is tested against the instance's `dropped`); else null
     const double *Px, *Ax, *Gx, *c, *b, *h_l, *h_u, *x_l, *x_u;
 };
-__global__ void k_batch_assign(const BatchShared* __restrict__ Sp, double* __restrict__ arena, BatchAssignArgs a)
+// SETUP (k_batch_setup_ingest): the arena is zero and a vector that is not given means what it means to SparseSolver::setup -- no finite bound on that side, b = 0 --,
+// so both bounds of every row of G are written (set_h_l / set_h_u, a dropped row -1 / 1) and x_b_scaling becomes 1; nothing else differs from an update.
+template <bool SETUP>
+__device__ __forceinline__ void batch_assign(const BatchShared& S, double* __restrict__ arena, const BatchAssignArgs& a)
 {
-    const BatchShared& S = *Sp;
     const int q = blockIdx.x, n = S.n, p = S.p, m = S.m, t = threadIdx.x, NT = blockDim.x;
     double* base = arena + (long long)q * S.stride;
     if (a.Px) for (int k = t; k < a.nzP_in; k += NT) { const int d = a.mapP[k]; if (d >= 0) base[S.off[D_PX] + d] = a.Px[(size_t)q * a.nzP_in + k]; }
@@ -1415,17 +1419,25 @@ __global__ void k_batch_assign(const BatchShared* __restrict__ Sp, double* __res
     if (a.Gx) for (int k = t; k < a.nzG_in; k += NT) { const int d = a.mapG[k]; if (d >= 0 && !(a.Grow && L.dropped[a.Grow[k]])) base[S.off[D_GTX] + d] = a.Gx[(size_t)q * a.nzG_in + k]; }
     if (a.c) for (int i = t; i < n; i += NT) base[S.off[D_C] + i] = a.c[(size_t)q * n + i];
     if (a.b) for (int i = t; i < p; i += NT) base[S.off[D_B] + i] = a.b[(size_t)q * p + i];
-    if (a.h_l) for (int i = t; i < m; i += NT) { const double v = a.h_l[(size_t)q * m + i]; base[S.off[D_HL] + i] = L.dropped[i] ? -1.0 : (v > -1e30 ? v : -1e30); }
-    if (a.h_u) for (int i = t; i < m; i += NT) { const double v = a.h_u[(size_t)q * m + i]; base[S.off[D_HU] + i] = L.dropped[i] ? 1.0 : (v < 1e30 ? v : 1e30); }
+    if (a.h_l || SETUP) for (int i = t; i < m; i += NT) { const double v = a.h_l ? a.h_l[(size_t)q * m + i] : -1e30; base[S.off[D_HL] + i] = L.dropped[i] ? -1.0 : (v > -1e30 ? v : -1e30); }
+    if (a.h_u || SETUP) for (int i = t; i < m; i += NT) { const double v = a.h_u ? a.h_u[(size_t)q * m + i] : 1e30; base[S.off[D_HU] + i] = L.dropped[i] ? 1.0 : (v < 1e30 ? v : 1e30); }
     if (a.x_l) for (int k = t; k < L.n_x_l; k += NT) base[S.off[D_XL] + k] = a.x_l[(size_t)q * n + L.x_l_idx[k]];
     if (a.x_u) for (int k = t; k < L.n_x_u; k += NT) base[S.off[D_XU] + k] = a.x_u[(size_t)q * n + L.x_u_idx[k]];
+    if (SETUP) for (int i = t; i < n; i += NT) base[S.off[D_XBS] + i] = 1.0;
 }
+__global__ void k_batch_assign(const BatchShared* __restrict__ Sp, double* __restrict__ arena, BatchAssignArgs a) { batch_assign<false>(*Sp, arena, a); }
+// pq_batch_setup_sparse_mem, device mode: what pack_instance copies out of an instance's HostData, taken from the caller's [batch][nnz] / [batch][len] device arrays
+// where they are (one workgroup per instance, consecutive lanes on consecutive entries of its row of each array) into the zeroed arena
+__global__ void k_batch_setup_ingest(const BatchShared* __restrict__ Sp, double* __restrict__ arena, BatchAssignArgs a) { batch_assign<true>(*Sp, arena, a); }
 
 // PQ_BOUND_SETS_PER_INSTANCE, before the two kernels above at every update that gives a bound vector: the lists the reference would hold after the call (the rules
 // stated at pq_solver_batch_update_dense, dsb_bound_lists on the host) replace row q of the table.  One wave per instance, on the caller's [batch][len] vectors
 // where they are; a vector that is not given (null) keeps the stored finiteness, a row dropped earlier being in both lists.  Ascending lists by an order-preserving
 // compaction: a ballot per 64 entries and the count of set bits below the lane.  Rows that lose their last finite bound get -1 / 1 (times the row's scaling where the
 // arena holds scaled data) and have their entries of G' zeroed, in the arena and (multistage backend) in the grouped-row arena the KKT assembly reads.
+// SETUP (a device-fed setup, on a zeroed table and arena): there is no stored finiteness, a vector that is not given has no finite entry -- the table build_bound_table
+// makes from the instances' HostData.
+template <bool SETUP>
 __global__ __launch_bounds__(64) void k_batch_bound_lists(const BatchShared* __restrict__ Sp, double* __restrict__ arena, int* __restrict__ tab, const double* __restrict__ h_l,
                                                           const double* __restrict__ h_u, const double* __restrict__ x_l, const double* __restrict__ x_u, int scaled, int grouped)
 {
@@ -1434,7 +1446,7 @@ __global__ __launch_bounds__(64) void k_batch_bound_lists(const BatchShared* __r
     double* base = arena + (long long)q * S.stride;
     int* r = tab + (long long)q * S.bl_stride;
     const unsigned long long below = (1ull << lane) - 1ull;
-    if (h_l || h_u) {
+    if (h_l || h_u || SETUP) {
         int *hli = r + bl_off(BL_H_L_IDX, n, m), *hui = r + bl_off(BL_H_U_IDX, n, m), *has_l = r + bl_off(BL_HAS_L, n, m), *has_u = r + bl_off(BL_HAS_U, n, m);
         int* dropped = r + bl_off(BL_DROPPED, n, m);
         int cl = 0, cu = 0;
@@ -1443,8 +1455,8 @@ __global__ __launch_bounds__(64) void k_batch_bound_lists(const BatchShared* __r
             const bool in = i < m;
             bool fl = false, fu = false;
             if (in) {
-                fl = h_l ? h_l[(size_t)q * m + i] > -1e30 : has_l[i] != 0;
-                fu = h_u ? h_u[(size_t)q * m + i] < 1e30 : has_u[i] != 0;
+                fl = h_l ? h_l[(size_t)q * m + i] > -1e30 : !SETUP && has_l[i] != 0;
+                fu = h_u ? h_u[(size_t)q * m + i] < 1e30 : !SETUP && has_u[i] != 0;
             }
             const bool dd = in && !fl && !fu, il = in && (fl || dd), iu = in && (fu || dd);
             const unsigned long long bl = __ballot(il), bu = __ballot(iu);
@@ -1465,13 +1477,13 @@ __global__ __launch_bounds__(64) void k_batch_bound_lists(const BatchShared* __r
     }
     for (int side = 0; side < 2; ++side) {
         const double* v = side == 0 ? x_l : x_u;
-        if (!v) continue;  // (uniform)
+        if (!v && !SETUP) continue;  // (uniform)
         int *idx = r + bl_off(side == 0 ? BL_X_L_IDX : BL_X_U_IDX, n, m), *pos = r + bl_off(side == 0 ? BL_POS_L : BL_POS_U, n, m);
         int cnt = 0;
         for (int j0 = 0; j0 < n; j0 += 64) {
             const int j = j0 + lane;
             const bool in = j < n;
-            const bool f = in && (side == 0 ? v[(size_t)q * n + j] > -1e30 : v[(size_t)q * n + j] < 1e30);
+            const bool f = in && v && (side == 0 ? v[(size_t)q * n + j] > -1e30 : v[(size_t)q * n + j] < 1e30);
             const unsigned long long bf = __ballot(f);
             const int k = cnt + __popcll(bf & below);
             if (f) idx[k] = j;
@@ -1669,18 +1681,34 @@ public:
     int p() const { return p_; }
     int m() const { return m_; }
 
-    // SparseSolver::setup (solver.hpp:1297-1308) for every instance; patterns shared, values [batch][nnz] / [batch][len]
+    // SparseSolver::setup (solver.hpp:1297-1308) for every instance; patterns shared (host), values [batch][nnz] / [batch][len] in host or device memory
     bool setup(int batch, int n, int p, int m, const int* Pp, const int* Pi, const double* Px, const double* c, const int* Ap, const int* Ai, const double* Ax, const double* b,
-               const int* Gp, const int* Gi, const double* Gx, const double* h_l, const double* h_u, const double* x_l, const double* x_u)
+               const int* Gp, const int* Gi, const double* Gx, const double* h_l, const double* h_u, const double* x_l, const double* x_u, int mem = PQ_MEM_HOST)
     {
+        const auto w0 = std::chrono::steady_clock::now();
         if (batch <= 0 || n <= 0) throw std::runtime_error("batch setup: bad dimensions");
         if (settings_.kkt_solver != PQ_SPARSE_MULTISTAGE && settings_.kkt_solver != PQ_SPARSE_LDLT && settings_.kkt_solver != PQ_SPARSE_LDLT_EXACT)
             throw std::runtime_error("batch mode: kkt_solver must be sparse_multistage, sparse_ldlt or sparse_ldlt_exact");
         ldlt_ = settings_.kkt_solver != PQ_SPARSE_MULTISTAGE;
         per_inst_ = bound_sets_ == PQ_BOUND_SETS_PER_INSTANCE;
-        const bool per_inst = per_inst_;
         PQ_HIP(hipSetDevice(dev_));
         batch_ = batch;
+        setup_ms_[1] = 0.0;
+        if (mem == PQ_MEM_DEVICE) setup_from_device(batch, n, p, m, Pp, Pi, Px, c, Ap, Ai, Ax, b, Gp, Gi, Gx, h_l, h_u, x_l, x_u);
+        else setup_from_host(batch, n, p, m, Pp, Pi, Px, c, Ap, Ai, Ax, b, Gp, Gi, Gx, h_l, h_u, x_l, x_u);
+        float ms = 0.f;
+        PQ_HIP(hipEventElapsedTime(&ms, ev0_, ev1_));
+        setup_ms_[2] = ms;
+        setup_ms_[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
+        return true;
+    }
+
+private:
+    // Host memory: one HostData per instance on host threads, packed into a staging buffer and copied up in slices
+    void setup_from_host(int batch, int n, int p, int m, const int* Pp, const int* Pi, const double* Px, const double* c, const int* Ap, const int* Ai, const double* Ax,
+                         const double* b, const int* Gp, const int* Gi, const double* Gx, const double* h_l, const double* h_u, const double* x_l, const double* x_u)
+    {
+        const bool per_inst = per_inst_;
         const int nzP = Pp[n], nzA = Ap ? Ap[n] : 0, nzG = Gp ? Gp[n] : 0;
         // ---- which bounds are finite is part of the shared structure: the caller's pattern must be the same in every instance ----
         // (PQ_BOUND_SETS_PER_INSTANCE: nothing is refused, every instance keeps the lists make_sparse_host_data builds for it; the vectors below are then instance
@@ -1716,7 +1744,6 @@ public:
             for (auto& e : errs) if (e) std::rethrow_exception(e);
         }
         const HostData& d0 = *data[0];
-        n_ = d0.n; p_ = d0.p; m_ = d0.m;
         for (int i = 1; i < batch; ++i) {
             const HostData& d = *data[i];
             const bool same = d.n_h_l == d0.n_h_l && d.n_h_u == d0.n_h_u && d.n_x_l == d0.n_x_l && d.n_x_u == d0.n_x_u &&
@@ -1726,6 +1753,31 @@ public:
                               std::equal(d.x_u_idx.begin(), d.x_u_idx.begin() + d.n_x_u, d0.x_u_idx.begin());
             if (!same && !per_inst) throw std::runtime_error("batch setup: instances differ in which bounds are finite");
         }
+        const auto a0 = std::chrono::steady_clock::now();
+        analyse_structure(d0, n, p, m, Pp, Pi, c, Ap, Ai, b, Gp, Gi, h_l, h_u, x_l, x_u, nullptr);
+        if (per_inst) build_bound_table(data, m_ > 0 ? h_l : nullptr, m_ > 0 ? h_u : nullptr);
+        setup_ms_[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a0).count();
+        alloc_instance_buffers(batch);
+        PQ_HIP(hipEventRecord(ev0_, st_));
+        std::vector<double> stage((size_t)layout_.stride * std::min(batch, STAGE_INST));
+        for (int i0 = 0; i0 < batch; i0 += STAGE_INST) {
+            const int cnt = std::min(STAGE_INST, batch - i0);
+            std::fill(stage.begin(), stage.begin() + (size_t)layout_.stride * cnt, 0.0);
+            for (int k = 0; k < cnt; ++k) pack_instance(*data[i0 + k], stage.data() + (size_t)layout_.stride * k);
+            PQ_HIP(hipMemcpyAsync(arena_.p + (size_t)layout_.stride * i0, stage.data(), sizeof(double) * (size_t)layout_.stride * cnt, hipMemcpyHostToDevice, st_));
+            stream_wait(st_);
+        }
+        note_ingest(PQ_MEM_HOST, true, Px, Ap ? Ax : nullptr, Gp ? Gx : nullptr, c, Ap ? b : nullptr, Gp ? h_l : nullptr, Gp ? h_u : nullptr, x_l, x_u, 0);
+        scale_and_prepare();
+    }
+
+    // The part of a setup that reads no value: the symbolic analysis of the backend, the descriptor and the layout of the arena, the update maps.  d0: instance 0's
+    // HostData (its patterns and bound lists are read); c .. x_u: host vectors of instance 0 for the probe of build_update_maps, c and b may be null.
+    // fin_ready: see build_update_maps.
+    void analyse_structure(const HostData& d0, int n, int p, int m, const int* Pp, const int* Pi, const double* c, const int* Ap, const int* Ai, const double* b, const int* Gp,
+                           const int* Gi, const double* h_l, const double* h_u, const double* x_l, const double* x_u, std::vector<DBuf<int>>* fin_ready)
+    {
+        n_ = d0.n; p_ = d0.p; m_ = d0.m;
         fin_hl_.resize(m_, 0); fin_hu_.resize(m_, 0);
         // ---- shared structure ----
         pq_sparse_data desc = d0.sparse_descriptor();
@@ -1742,10 +1794,12 @@ public:
             multistage::analyse(&desc, sym_);
         }
         build_shared(d0);
-        build_update_maps(n, p, m, Pp, Pi, c, Ap, Ai, b, Gp, Gi, h_l, h_u, x_l, x_u, d0);
+        build_update_maps(n, p, m, Pp, Pi, c, Ap, Ai, b, Gp, Gi, h_l, h_u, x_l, x_u, d0, fin_ready);
         bl_tab_ = DBuf<int>();
-        if (per_inst) build_bound_table(data, m_ > 0 ? h_l : nullptr, m_ > 0 ? h_u : nullptr);
-        // ---- per-instance arena ----
+    }
+    // ---- per-instance arena (zeroed) and what goes with it ----
+    void alloc_instance_buffers(int batch)
+    {
         if (ldlt_) {
             size_t free_b = 0, total_b = 0;
             const double need = (double)layout_.stride * batch * sizeof(double);
@@ -1763,21 +1817,108 @@ public:
         PQ_HIP(hipMemcpyAsync(order_.p, order_h_.data(), sizeof(int) * (size_t)batch, hipMemcpyHostToDevice, st_));
         prof_.alloc((size_t)batch * NPROF);
         infos_h_.resize(batch);
-        std::vector<double> stage((size_t)layout_.stride * std::min(batch, STAGE_INST));
-        for (int i0 = 0; i0 < batch; i0 += STAGE_INST) {
-            const int cnt = std::min(STAGE_INST, batch - i0);
-            std::fill(stage.begin(), stage.begin() + (size_t)layout_.stride * cnt, 0.0);
-            for (int k = 0; k < cnt; ++k) pack_instance(*data[i0 + k], stage.data() + (size_t)layout_.stride * k);
-            PQ_HIP(hipMemcpyAsync(arena_.p + (size_t)layout_.stride * i0, stage.data(), sizeof(double) * (size_t)layout_.stride * cnt, hipMemcpyHostToDevice, st_));
-            stream_wait(st_);
-        }
-        // RuizEquilibration::scale_data of every instance (sparse/preconditioner.hpp:65-222) in one launch, then the front arenas
+    }
+    // RuizEquilibration::scale_data of every instance (sparse/preconditioner.hpp:65-222) in one launch, then the front arenas
+    void scale_and_prepare(bool record_end = true)
+    {
         launch_ruiz(RUIZ_COMPUTE);
         if (!ldlt_) launch_prepare();
+        if (record_end) PQ_HIP(hipEventRecord(ev1_, st_));
         stream_wait(st_);
         setup_done_ = true;
-        return true;
     }
+    // pq_batch_last_ingest, from the shapes of what the call was given (null: not given, or of length 0).  fetched: the bytes a device-fed setup brought to the host.
+    void note_ingest(int mem, bool is_setup, const double* Px, const double* Ax, const double* Gx, const double* c, const double* b, const double* h_l, const double* h_u,
+                     const double* x_l, const double* x_u, long long fetched)
+    {
+        const long long vec = (c ? n_ : 0) + (b ? p_ : 0) + (x_l ? n_ : 0) + (x_u ? n_ : 0);
+        const long long given = (Px ? nzP_in_ : 0) + (Ax ? nzA_in_ : 0) + (Gx ? nzG_in_ : 0) + vec + ((h_l ? 1 : 0) + (h_u ? 1 : 0)) * (long long)m_;
+        const long long written = (Px ? shared_h_.nzP : 0) + (Ax ? shared_h_.nzA : 0) + (Gx ? shared_h_.nzG : 0) + vec +
+                                  (is_setup ? 2LL * m_ + n_ : ((h_l ? 1 : 0) + (h_u ? 1 : 0)) * (long long)m_);
+        ingest_[0] = mem == PQ_MEM_DEVICE ? fetched : 8LL * batch_ * given;
+        ingest_[1] = is_setup && mem != PQ_MEM_DEVICE ? 0 : 8LL * batch_ * written;
+    }
+
+    // Device memory: the structure from the patterns and instance 0's four bound vectors -- the only problem data that comes to the host --, no HostData for the other
+    // instances and no staging: the bound check / the table of lists and the fill of the zeroed arena are kernels on the caller's arrays.  From the arena on, the
+    // setup is the host-fed one: the same Ruiz and prepare kernels on the same bits.
+    void setup_from_device(int batch, int n, int p, int m, const int* Pp, const int* Pi, const double* Px, const double* c, const int* Ap, const int* Ai, const double* Ax,
+                           const double* b, const int* Gp, const int* Gi, const double* Gx, const double* h_l, const double* h_u, const double* x_l, const double* x_u)
+    {
+        const bool per_inst = per_inst_;
+        const int nzP = Pp[n], nzA = Ap ? Ap[n] : 0, nzG = Gp ? Gp[n] : 0;
+        if (!Ap) { Ax = nullptr; b = nullptr; }
+        if (!Gp) { Gx = nullptr; h_l = nullptr; h_u = nullptr; m = 0; }
+        if (m <= 0) { h_l = nullptr; h_u = nullptr; }
+        // ---- instance 0's bound vectors: the shared lists (or, with lists per instance, the fallbacks they size) and the finiteness every instance must share ----
+        Vec hv[4];
+        const double* dv[4] = {h_l, h_u, x_l, x_u};
+        const double* v0[4] = {nullptr, nullptr, nullptr, nullptr};
+        const int vlen[4] = {m, m, n, n};
+        long long fetched = 0;
+        for (int k = 0; k < 4; ++k) {
+            if (!dv[k]) continue;
+            hv[k].resize((size_t)vlen[k]);
+            PQ_HIP(hipMemcpyAsync(hv[k].data(), dv[k], sizeof(double) * (size_t)vlen[k], hipMemcpyDeviceToHost, st_));
+            v0[k] = hv[k].data();
+            fetched += 8LL * vlen[k];
+        }
+        stream_wait(st_);
+        std::vector<char>* fin[4] = {&fin_hl_, &fin_hu_, &fin_xl_, &fin_xu_};
+        for (int k = 0; k < 4; ++k) {
+            fin[k]->assign((size_t)vlen[k], 0);
+            if (v0[k]) for (int i = 0; i < vlen[k]; ++i) (*fin[k])[(size_t)i] = (k % 2 == 0) ? v0[k][i] > -1e30 : v0[k][i] < 1e30;
+        }
+        // (the device copies of the four patterns and the flag word: the ones the updates check against later, made here instead of in build_update_maps)
+        std::vector<DBuf<int>> fin_d(4);
+        for (int k = 0; k < 4; ++k) upload_vec(fin_d[(size_t)k], finite_as_int(*fin[k]), st_);
+        fin_flag_.alloc(1);
+        if (!per_inst) {
+            PQ_HIP(hipMemsetAsync(fin_flag_.p, 0, sizeof(int), st_));
+            for (int k = 0; k < 4; ++k)
+                if (dv[k]) ingest_check_finite_pattern(dv[k], fin_d[(size_t)k].p, batch, vlen[k], k % 2 == 0, fin_flag_.p, st_);
+            int flag = 0;
+            PQ_HIP(hipMemcpyAsync(&flag, fin_flag_.p, sizeof(int), hipMemcpyDeviceToHost, st_));
+            stream_wait(st_);
+            if (flag) throw std::runtime_error("batch setup: instances differ in which bounds are finite");
+        }
+        // ---- the shared structure reads no value: instance 0's HostData from the patterns and placeholder values ----
+        const auto a0 = std::chrono::steady_clock::now();
+        const Vec ones((size_t)std::max({nzP, nzA, nzG, 1}), 1.0);
+        const auto d0 = make_sparse_host_data(n, p, m, Pp, Pi, ones.data(), nullptr, Ap, Ai, Ap ? ones.data() : nullptr, nullptr, Gp, Gi, Gp ? ones.data() : nullptr, v0[0], v0[1],
+                                              v0[2], v0[3]);
+        analyse_structure(*d0, n, p, m, Pp, Pi, nullptr, Ap, Ai, nullptr, Gp, Gi, v0[0], v0[1], v0[2], v0[3], &fin_d);
+        if (per_inst) {
+            const long long R = bl_row_ints(n_, m_);
+            bl_tab_.alloc((size_t)R * batch);
+            bl_tab_.zero(st_);
+            shared_h_.bl_tab = bl_tab_.p;
+            shared_h_.bl_stride = R;
+            PQ_HIP(hipMemcpyAsync(shared_.p, &shared_h_, sizeof(BatchShared), hipMemcpyHostToDevice, st_));
+            stream_wait(st_);
+        }
+        setup_ms_[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a0).count();
+        alloc_instance_buffers(batch);
+        PQ_HIP(hipEventRecord(ev0_, st_));
+        if (per_inst) {
+            hipLaunchKernelGGL(k_batch_bound_lists<true>, dim3(batch), dim3(64), 0, st_, shared_.p, arena_.p, bl_tab_.p, h_l, h_u, x_l, x_u, 0, 0);
+            PQ_HIP(hipGetLastError());
+        }
+        BatchAssignArgs a{};
+        a.nzP_in = nzP_in_; a.nzA_in = nzA_in_; a.nzG_in = nzG_in_;
+        a.mapP = mapP_; a.mapA = mapA_; a.mapG = mapG_; a.disabled = disabled_d_; a.Grow = Grow_;
+        a.Px = nzP_in_ > 0 ? Px : nullptr; a.Ax = nzA_in_ > 0 ? Ax : nullptr; a.Gx = nzG_in_ > 0 ? Gx : nullptr;
+        a.c = c; a.b = p_ > 0 ? b : nullptr; a.h_l = h_l; a.h_u = h_u; a.x_l = x_l; a.x_u = x_u;
+        hipLaunchKernelGGL(k_batch_setup_ingest, dim3(batch), dim3(128), 0, st_, shared_.p, arena_.p, a);
+        PQ_HIP(hipGetLastError());
+        // measurement aid (tools/batch_setup_timing.py): the device time of pq_batch_setup_ms ends here, after the ingest kernels, instead of after prepare
+        const bool ingest_only = debug_token("batch_setup_ms_ingest") != nullptr;
+        if (ingest_only) PQ_HIP(hipEventRecord(ev1_, st_));
+        note_ingest(PQ_MEM_DEVICE, true, a.Px, a.Ax, a.Gx, a.c, a.b, a.h_l, a.h_u, a.x_l, a.x_u, fetched);
+        scale_and_prepare(!ingest_only);
+    }
+
+public:
 
     // solve() of every instance; returns the number of instances that ended PIQP_SOLVED
     int solve()
@@ -1890,6 +2031,8 @@ public:
     bool is_set_up() const { return setup_done_; }
     long long arena_stride() const { return setup_done_ ? layout_.stride : 0; }
     const double* clone_ms() const { return clone_ms_; }
+    const double* setup_ms() const { return setup_ms_; }
+    const long long* last_ingest() const { return ingest_; }
     // update() of every instance, vectors only; the set of finite bounds must be the one given at setup (it is part of the shared structure) -- or, with
     // PQ_BOUND_SETS_PER_INSTANCE, whatever the vectors say: k_batch_bound_lists rewrites every instance's lists first
     // mem = PQ_MEM_DEVICE: the kernels read the caller's device arrays in place (no staging buffers, no copies)
@@ -1907,6 +2050,7 @@ public:
             return d.p;
         };
         const double *pc = up(dc, c, n_), *pb = up(dbv, b, p_), *phl = up(dhl, h_l, m_), *phu = up(dhu, h_u, m_), *pxl = up(dxl, x_l, n_), *pxu = up(dxu, x_u, n_);
+        note_ingest(mem, false, nullptr, nullptr, nullptr, pc, pb, phl, phu, pxl, pxu, 0);
         launch_bound_lists(phl, phu, pxl, pxu, true);
         hipLaunchKernelGGL(k_batch_update_vectors, dim3(batch_), dim3(128), 0, st_, shared_.p, arena_.p, ruiz_c_.p, disabled_d_, pc, pb, phl, phu, pxl, pxu);
         PQ_HIP(hipGetLastError());
@@ -1935,6 +2079,7 @@ public:
         a.mapP = mapP_; a.mapA = mapA_; a.mapG = mapG_; a.disabled = disabled_d_; a.Grow = Grow_;
         a.Px = up(dP, Px, nzP_in_); a.Ax = up(dA, Ax, nzA_in_); a.Gx = up(dG, Gx, nzG_in_);
         a.c = up(dc, c, n_); a.b = up(dbv, b, p_); a.h_l = up(dhl, h_l, m_); a.h_u = up(dhu, h_u, m_); a.x_l = up(dxl, x_l, n_); a.x_u = up(dxu, x_u, n_);
+        note_ingest(mem, false, a.Px, a.Ax, a.Gx, a.c, a.b, a.h_l, a.h_u, a.x_l, a.x_u, 0);
         launch_ruiz(RUIZ_UNSCALE);  // (with the lists as they stood: the box vectors are packed to them)
         launch_bound_lists(a.h_l, a.h_u, a.x_l, a.x_u, false);
         hipLaunchKernelGGL(k_batch_assign, dim3(batch_), dim3(128), 0, st_, shared_.p, arena_.p, a);
@@ -2168,8 +2313,15 @@ private:
 
     // Where the caller's k-th value of P / A / G lives in the arena: found by pushing the values 1, 2, 3, ... through the same host path the real
     // values took at setup (make_sparse_host_data: upper-triangle extraction, transposes, disabled rows of G zeroed).
+    // fin_ready (a device-fed setup, which has checked the caller's arrays against them already): the device copies of fin_hl_ .. fin_xu_, taken over; the flag word exists.
+    static std::vector<int> finite_as_int(const std::vector<char>& f)
+    {
+        std::vector<int> v(std::max<size_t>(f.size(), 1), 0);
+        for (size_t i = 0; i < f.size(); ++i) v[i] = f[i] != 0;
+        return v;
+    }
     void build_update_maps(int n, int p, int m, const int* Pp, const int* Pi, const double* c, const int* Ap, const int* Ai, const double* b, const int* Gp, const int* Gi,
-                           const double* h_l, const double* h_u, const double* x_l, const double* x_u, const HostData& d0)
+                           const double* h_l, const double* h_u, const double* x_l, const double* x_u, const HostData& d0, std::vector<DBuf<int>>* fin_ready)
     {
         nzP_in_ = Pp[n]; nzA_in_ = Ap ? Ap[n] : 0; nzG_in_ = Gp ? Gp[n] : 0;
         Vec iP(std::max(nzP_in_, 1)), iA(std::max(nzA_in_, 1)), iG(std::max(nzG_in_, 1));
@@ -2192,9 +2344,15 @@ private:
         std::vector<int> dis(std::max(m_, 1), 0);
         for (int i = 0; i < m_; ++i) dis[i] = !fin_hl_[i] && !fin_hu_[i];
         disabled_d_ = up(sbufs_->i, dis);
-        auto as_int = [](const std::vector<char>& f) { std::vector<int> v(std::max<size_t>(f.size(), 1), 0); for (size_t i = 0; i < f.size(); ++i) v[i] = f[i] != 0; return v; };
-        fin_hl_d_ = up(sbufs_->i, as_int(fin_hl_)); fin_hu_d_ = up(sbufs_->i, as_int(fin_hu_)); fin_xl_d_ = up(sbufs_->i, as_int(fin_xl_)); fin_xu_d_ = up(sbufs_->i, as_int(fin_xu_));
-        fin_flag_.alloc(1);
+        if (fin_ready) {
+            const int* f[4];
+            for (int k = 0; k < 4; ++k) { sbufs_->i.push_back(std::move((*fin_ready)[(size_t)k])); f[k] = sbufs_->i.back().p; }
+            fin_hl_d_ = f[0]; fin_hu_d_ = f[1]; fin_xl_d_ = f[2]; fin_xu_d_ = f[3];
+        } else {
+            fin_hl_d_ = up(sbufs_->i, finite_as_int(fin_hl_)); fin_hu_d_ = up(sbufs_->i, finite_as_int(fin_hu_));
+            fin_xl_d_ = up(sbufs_->i, finite_as_int(fin_xl_)); fin_xu_d_ = up(sbufs_->i, finite_as_int(fin_xu_));
+            fin_flag_.alloc(1);
+        }
         rzPp_ = up(sbufs_->i, d0.sP_utri.colptr);
         rzPi_ = up(sbufs_->i, d0.sP_utri.rowind.empty() ? std::vector<int>(1, 0) : d0.sP_utri.rowind);
         stream_wait(st_);
@@ -2249,7 +2407,7 @@ private:
     void launch_bound_lists(const double* h_l, const double* h_u, const double* x_l, const double* x_u, bool scaled)
     {
         if (!per_inst_ || (!h_l && !h_u && !x_l && !x_u)) return;
-        hipLaunchKernelGGL(k_batch_bound_lists, dim3(batch_), dim3(64), 0, st_, shared_.p, arena_.p, bl_tab_.p, h_l, h_u, x_l, x_u, scaled ? 1 : 0, ldlt_ ? 0 : 1);
+        hipLaunchKernelGGL(k_batch_bound_lists<false>, dim3(batch_), dim3(64), 0, st_, shared_.p, arena_.p, bl_tab_.p, h_l, h_u, x_l, x_u, scaled ? 1 : 0, ldlt_ ? 0 : 1);
         PQ_HIP(hipGetLastError());
     }
 
@@ -2543,6 +2701,8 @@ private:
     const int *mapP_ = nullptr, *mapA_ = nullptr, *mapG_ = nullptr, *disabled_d_ = nullptr, *rzPp_ = nullptr, *rzPi_ = nullptr;  // device, owned by sbufs_->i
     double last_kernel_ms_ = 0.0;
     double clone_ms_[2] = {0.0, 0.0};  // of the clone call that made this handle: wall, device time of the gathers (pq_batch_clone_ms)
+    double setup_ms_[3] = {0.0, 0.0, 0.0};  // of the last setup: wall, host analysis (symbolic, maps, tables), device time from the fill of the arena to prepare (pq_batch_setup_ms)
+    long long ingest_[2] = {0, 0};           // of the last setup / update: note_ingest (pq_batch_last_ingest)
     bool lpt_ = true;
     pq_settings settings_;
     multistage::Symbolic sym_;
@@ -2636,8 +2796,27 @@ int pq_batch_setup_sparse(pq_batch* s, int batch, int n, int p, int m, const int
                           const double* Ax, const double* b, const int* Gp, const int* Gi, const double* Gx, const double* h_l, const double* h_u, const double* x_l,
                           const double* x_u)
 {
+    return pq_batch_setup_sparse_mem(s, batch, n, p, m, Pp, Pi, Px, c, Ap, Ai, Ax, b, Gp, Gi, Gx, h_l, h_u, x_l, x_u, PQ_MEM_HOST);
+}
+int pq_batch_setup_sparse_mem(pq_batch* s, int batch, int n, int p, int m, const int* Pp, const int* Pi, const double* Px, const double* c, const int* Ap, const int* Ai,
+                              const double* Ax, const double* b, const int* Gp, const int* Gi, const double* Gx, const double* h_l, const double* h_u, const double* x_l,
+                              const double* x_u, int mem)
+{
     if (!s || !Pp || !Pi || !Px || !c) return fail(PQ_ERR_INVALID, "null argument");
-    return guarded([&] { return s->impl->setup(batch, n, p, m, Pp, Pi, Px, c, Ap, Ai, Ax, b, Gp, Gi, Gx, h_l, h_u, x_l, x_u) ? 1 : 0; });
+    if (mem != PQ_MEM_HOST && mem != PQ_MEM_DEVICE) return fail(PQ_ERR_INVALID, "mem must be PQ_MEM_HOST or PQ_MEM_DEVICE");
+    return guarded([&] { return s->impl->setup(batch, n, p, m, Pp, Pi, Px, c, Ap, Ai, Ax, b, Gp, Gi, Gx, h_l, h_u, x_l, x_u, mem) ? 1 : 0; });
+}
+int pq_batch_last_ingest(const pq_batch* s, long long out[2])
+{
+    if (!s || !out) return fail(PQ_ERR_INVALID, "pq_batch_last_ingest: null argument");
+    out[0] = s->impl->last_ingest()[0]; out[1] = s->impl->last_ingest()[1];
+    return PQ_OK;
+}
+int pq_batch_setup_ms(const pq_batch* s, double out3[3])
+{
+    if (!s || !out3) return fail(PQ_ERR_INVALID, "pq_batch_setup_ms: null argument");
+    for (int k = 0; k < 3; ++k) out3[k] = s->impl->setup_ms()[k];
+    return PQ_OK;
 }
 int pq_batch_update_mem(pq_batch* s, const double* c, const double* b, const double* h_l, const double* h_u, const double* x_l, const double* x_u, int mem)
 {
