@@ -576,6 +576,38 @@ const pq_info *pq_batch_info(const pq_batch *s, int instance); /* result().info 
 int pq_batch_get_result(pq_batch *s, int field, double *out_host);
 /* the same into a host or a DEVICE array [batch][len] (device mode: one strided device-to-device copy out of the arena, no allocation) */
 int pq_batch_get_result_mem(pq_batch *s, int field, double *out, int mem);
+/* ACTING ON A LIST OF INSTANCES, IN PLACE (the _select forms of pq_batch_solve, pq_batch_update_mem, pq_batch_update_data_mem and pq_batch_get_result_mem): the
+ * same handle, the same arena, the same result arrays -- no second handle as with pq_batch_clone_select.  idx: `count` instances in HOST memory; the value arrays
+ * and out are [count][len] / [count][nnz], row j belongs to instance idx[j]; mem says where the value arrays / out live, as in the _mem calls.
+ * A LISTED instance ends in the state the whole-batch call would leave it in when given the same row, bit for bit (arena row, cost scaling, pq_info, profile row,
+ * its lists with PQ_BOUND_SETS_PER_INSTANCE): the same kernels run on the same row, one workgroup per listed instance, which finds its instance through the list.
+ * Of an UNLISTED instance no byte is written: arena row, cost scaling, device and host pq_info, profile row, row of the bound table.
+ * _solve_select: returns how many of the listed instances ended PQ_SOLVED.  The settings as they stand at the call (a straggler is run again in place with another
+ * max_iter); invalid settings: the listed infos alone become PQ_INVALID_SETTINGS, 0 is returned.  pq_batch_last_kernel_ms reports this launch.  The kernel variant
+ * stays the one the handle chose at setup.  Start order: with pq_batch_set_start_order on, the listed instances that took most iterations in their previous solve
+ * first, ties in list order; off: list order; results do not depend on it.  The stored order of the next WHOLE solve stays a permutation of the batch: the list goes
+ * into a buffer of its own, and after the call the whole order is recomputed from all infos as pq_batch_solve leaves it.
+ * _update_select_mem / _update_data_select_mem: the sequences of pq_batch_update / pq_batch_update_data (unscale, bound lists, assign, equilibrate, prepare) on the
+ * listed rows.  Shared bound sets: the finiteness check runs over the `count` rows given, a mismatch is refused with pq_batch_update's text and the handle stays as
+ * it was; per-instance sets: the lists of the listed instances are rebuilt and no others.  With Px, Ax and Gx all NULL the data form is the vector form.  An updated
+ * instance keeps the results and the info of its last solve until it is solved again, as after the whole-batch calls.  Return 1.
+ * _get_result_select_mem: field k (as pq_batch_get_result) of the listed instances -> out [count][len] by one gather kernel; repeats are allowed, count may exceed
+ * the batch; a field of length 0 writes nothing and returns 0.
+ * ALLOCATION: the first _select call on a handle allocates one int buffer of `batch` entries (setup and clone allocate nothing for it); after that _solve_select
+ * and the device-memory forms of the other three allocate nothing (pq_debug_alloc_count does not move); host-memory updates stage [count][len], a host-memory
+ * result [count][len].
+ * REFUSED with PQ_ERR_INVALID before any device call, the handle untouched, the text naming j and the value where there is one: a NULL s or idx (or out), count < 1,
+ * an unknown mem or field, a handle that is not set up, an idx[j] outside [0, batch), and -- _solve_select and the two updates only -- an instance listed twice
+ * (two workgroups on one arena row would race). */
+int pq_batch_solve_select(pq_batch *s, const int *idx, int count);
+int pq_batch_update_select_mem(pq_batch *s, const int *idx, int count, const double *c, const double *b, const double *h_l, const double *h_u,
+                               const double *x_l, const double *x_u, int mem);
+int pq_batch_update_data_select_mem(pq_batch *s, const int *idx, int count, const double *Px, const double *Ax, const double *Gx, const double *c,
+                                    const double *b, const double *h_l, const double *h_u, const double *x_l, const double *x_u, int mem);
+int pq_batch_get_result_select_mem(pq_batch *s, const int *idx, int count, int field, double *out, int mem);
+/* test hook: one instance's row of the arena, pq_batch_arena_stride() doubles, to HOST memory; PQ_ERR_INVALID for a NULL argument, a handle that is not set up or
+ * an instance outside [0, batch) */
+int pq_batch_arena_row(const pq_batch *s, int instance, double *out_host);
 int pq_batch_dims(const pq_batch *s, int *batch, int *n, int *p, int *m);
 int pq_batch_block_info(const pq_batch *s, int *out_host, int capacity); /* as pq_kkt_multistage_block_info; sparse_multistage only (error otherwise) */
 /* in-kernel device-clock seconds of one instance's last solve: out8 = {KKT assembly, factorisation (chain / LDLt),

@@ -117,6 +117,7 @@ SYMBOLS = [
     "pq_batch_kkt_factor", "pq_batch_kkt_solve", "pq_batch_ldlt_factor", "pq_batch_set_bound_sets", "pq_batch_bound_lists",
     "pq_batch_clone", "pq_batch_clone_select", "pq_batch_clone_ms", "pq_batch_arena_stride",
     "pq_batch_setup_sparse_mem", "pq_batch_last_ingest", "pq_batch_setup_ms",
+    "pq_batch_solve_select", "pq_batch_update_select_mem", "pq_batch_update_data_select_mem", "pq_batch_get_result_select_mem", "pq_batch_arena_row",
     "pq_dense_factor_create", "pq_dense_factor_destroy", "pq_dense_factor_compute", "pq_dense_factor_info", "pq_dense_factor_solve_in_place", "pq_dense_factor_matrix", "pq_dense_factor_last_ms",
     "pq_dense_factor_batch_create", "pq_dense_factor_batch_destroy", "pq_dense_factor_batch_compute", "pq_dense_factor_batch_info", "pq_dense_factor_batch_solve_in_place",
     "pq_dense_factor_batch_matrix", "pq_dense_factor_batch_last_ms",
@@ -217,6 +218,11 @@ def load():
     L.pq_batch_setup_sparse_mem.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int] + [vp] * 15 + [C.c_int]
     L.pq_batch_last_ingest.argtypes = [vp, vp]
     L.pq_batch_setup_ms.argtypes = [vp, vp]
+    L.pq_batch_solve_select.argtypes = [vp, vp, C.c_int]
+    L.pq_batch_update_select_mem.argtypes = [vp, vp, C.c_int] + [vp] * 6 + [C.c_int]
+    L.pq_batch_update_data_select_mem.argtypes = [vp, vp, C.c_int] + [vp] * 9 + [C.c_int]
+    L.pq_batch_get_result_select_mem.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int]
+    L.pq_batch_arena_row.argtypes = [vp, C.c_int, vp]
     L.pq_dense_factor_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int]
     L.pq_dense_factor_destroy.argtypes = [vp]
     L.pq_dense_factor_destroy.restype = None

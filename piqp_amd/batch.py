@@ -11,7 +11,7 @@ import numpy as np
 from . import _lib
 from ._lib import VAR_NAMES, check
 from .batch_kkt import select_list
-from .kkt import MEM_DEVICE, _Handle, _ptr, device_call, sync_current_stream, to_device_args
+from .kkt import MEM_DEVICE, MEM_HOST, _Handle, _ptr, device_call, sync_current_stream, to_device_args
 
 
 BOUND_SETS = {"shared": 0, "per_instance": 1}  # PQ_BOUND_SETS_*
@@ -139,19 +139,64 @@ class BatchSparseSolver(_Handle):
         check(self.L.pq_batch_setup_ms(self.h, o.ctypes.data), "pq_batch_setup_ms")
         return dict(wall_ms=float(o[0]), analysis_ms=float(o[1]), device_ms=float(o[2]))
 
-    def _device_args(self, args):
-        """torch CUDA tensors (numpy arguments beside them are moved to the GPU), checked and contiguous; torch's current stream is drained"""
-        B = self.batch
+    def _device_args(self, args, rows=None):
+        """torch CUDA tensors (numpy arguments beside them are moved to the GPU), checked and contiguous; torch's current stream is drained.
+        rows: the leading length of the stacks (None: the batch; the length of the list of a call with instances)"""
+        B = self.batch if rows is None else rows
         shapes = dict(P_values=(B, self._nnz[0]), A_values=(B, self._nnz[1]), G_values=(B, self._nnz[2]), c=(B, self.n), b=(B, self.p), h_l=(B, self.m), h_u=(B, self.m),
                       x_l=(B, self.n), x_u=(B, self.n))
         keep, _ = to_device_args(args, shapes, self.device)
         sync_current_stream(self.device)
         return keep
 
-    def update(self, c=None, b=None, h_l=None, h_u=None, x_l=None, x_u=None):
+    @staticmethod
+    def _instances(instances, unique):
+        """the list of a call with instances (select_list); unique: ValueError for an instance listed twice -- two workgroups would work on one instance.  No
+        library call in here: the range of the entries is the library's check."""
+        idx = select_list(instances)
+        if unique and len(np.unique(idx)) != len(idx):
+            seen = {}
+            for j, i in enumerate(idx.tolist()):
+                if i in seen:
+                    raise ValueError(f"instances[{j}] = {i} is listed twice (instances[{seen[i]}] too)")
+                seen[i] = j
+        return idx
+
+    @staticmethod
+    def _rows(name, a, rows, length):
+        """a host stack of a call with instances: float64, contiguous, (len(instances), length) -- ValueError otherwise"""
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.shape != (rows, length):
+            raise ValueError(f"{name}: shape {a.shape}, expected {(rows, length)} (one row per listed instance)")
+        return a
+
+    def _update_select(self, instances, mats, vecs):
+        """update(instances=...) / update_data(instances=...): row j of every stack is for instance instances[j]"""
+        idx = self._instances(instances, unique=True)
+        R = len(idx)
+        lens = dict(P_values=self._nnz[0], A_values=self._nnz[1], G_values=self._nnz[2], c=self.n, b=self.p, h_l=self.m, h_u=self.m, x_l=self.n, x_u=self.n)
+        args = {**(mats or {}), **vecs}
+        if device_call(args.values()):
+            keep = self._device_args(args, R)
+            mem = MEM_DEVICE
+        else:
+            keep = {k: self._rows(k, a, R, lens[k]) for k, a in args.items()}
+            mem = MEM_HOST
+        ptrs = [_ptr(a) for a in keep.values()]
+        if mats is None:
+            return bool(check(self.L.pq_batch_update_select_mem(self.h, idx.ctypes.data, R, *ptrs, mem), "pq_batch_update_select_mem"))
+        return bool(check(self.L.pq_batch_update_data_select_mem(self.h, idx.ctypes.data, R, *ptrs, mem), "pq_batch_update_data_select_mem"))
+
+    def update(self, c=None, b=None, h_l=None, h_u=None, x_l=None, x_u=None, instances=None):
         """new vectors for every instance ([batch, len] arrays, None = unchanged); matrices and the set of finite bounds stay (bounds="per_instance": the
         lists follow the vectors, see __init__).
-        If any argument is a torch CUDA tensor the kernels read the data where it is (pq_batch_update_mem)."""
+        If any argument is a torch CUDA tensor the kernels read the data where it is (pq_batch_update_mem).
+        instances: a list of distinct instances -- the arrays are [len(instances), len], row j for instance instances[j]; those instances alone are updated, in
+        place, bit for bit as the whole-batch call given the same rows would, and nothing of any other instance is written (pq_batch_update_select_mem)."""
+        if instances is not None:
+            return self._update_select(instances, None, dict(c=c, b=b, h_l=h_l, h_u=h_u, x_l=x_l, x_u=x_u))
         if device_call((c, b, h_l, h_u, x_l, x_u)):
             keep = self._device_args(dict(c=c, b=b, h_l=h_l, h_u=h_u, x_l=x_l, x_u=x_u))
             return bool(check(self.L.pq_batch_update_mem(self.h, *[_ptr(a) for a in keep.values()], MEM_DEVICE), "pq_batch_update"))
@@ -159,9 +204,12 @@ class BatchSparseSolver(_Handle):
                 self._stack(x_l, self.batch, self.n), self._stack(x_u, self.batch, self.n)]
         return bool(check(self.L.pq_batch_update(self.h, *[_ptr(a) for a in keep]), "pq_batch_update"))
 
-    def update_data(self, P_values=None, A_values=None, G_values=None, c=None, b=None, h_l=None, h_u=None, x_l=None, x_u=None):
+    def update_data(self, P_values=None, A_values=None, G_values=None, c=None, b=None, h_l=None, h_u=None, x_l=None, x_u=None, instances=None):
         """new matrix values ([batch, nnz] in the CSC order of the setup patterns) and / or vectors for every instance, None = unchanged:
-        unscale -> assign -> (fresh) Ruiz equilibration on the device, solver.hpp:218-308.  torch CUDA tensors are read where they are (pq_batch_update_data_mem)."""
+        unscale -> assign -> (fresh) Ruiz equilibration on the device, solver.hpp:218-308.  torch CUDA tensors are read where they are (pq_batch_update_data_mem).
+        instances: as at update() -- [len(instances), nnz] / [len(instances), len] stacks, the listed instances alone (pq_batch_update_data_select_mem)."""
+        if instances is not None:
+            return self._update_select(instances, dict(P_values=P_values, A_values=A_values, G_values=G_values), dict(c=c, b=b, h_l=h_l, h_u=h_u, x_l=x_l, x_u=x_u))
         if device_call((P_values, A_values, G_values, c, b, h_l, h_u, x_l, x_u)):
             keep = self._device_args(dict(P_values=P_values, A_values=A_values, G_values=G_values, c=c, b=b, h_l=h_l, h_u=h_u, x_l=x_l, x_u=x_u))
             return bool(check(self.L.pq_batch_update_data_mem(self.h, *[_ptr(a) for a in keep.values()], MEM_DEVICE), "pq_batch_update_data"))
@@ -172,8 +220,13 @@ class BatchSparseSolver(_Handle):
                 self._stack(h_u, self.batch, self.m), self._stack(x_l, self.batch, self.n), self._stack(x_u, self.batch, self.n)]
         return bool(check(self.L.pq_batch_update_data(self.h, *[_ptr(a) for a in keep]), "pq_batch_update_data"))
 
-    def solve(self):
-        """returns the number of instances that ended SOLVED"""
+    def solve(self, instances=None):
+        """returns the number of instances that ended SOLVED.
+        instances: a list of distinct instances -- they alone are solved again, in place, with the settings as they stand (stragglers: raise settings.max_iter, then
+        s.solve(np.flatnonzero(s.statuses() != SOLVED))); the others keep their results and infos; the count is of the listed ones (pq_batch_solve_select)."""
+        if instances is not None:
+            idx = self._instances(instances, unique=True)
+            return check(self.L.pq_batch_solve_select(self.h, idx.ctypes.data, len(idx)), "pq_batch_solve_select")
         return check(self.L.pq_batch_solve(self.h), "pq_batch_solve")
 
     def info(self, i):
@@ -188,21 +241,34 @@ class BatchSparseSolver(_Handle):
     def iterations(self):
         return np.array([self.info(i).iter for i in range(self.batch)])
 
-    def result(self, name, device=False):
-        """[batch, len] numpy array, or (device=True) a torch tensor on the solver's GPU, copied there without leaving it"""
+    def result(self, name, device=False, instances=None):
+        """[batch, len] numpy array, or (device=True) a torch tensor on the solver's GPU, copied there without leaving it.
+        instances: a list of instances, repeats allowed -- [len(instances), len], row j of instance instances[j] (pq_batch_get_result_select_mem)"""
         k = VAR_NAMES.index(name)
         length = {"x": self.n, "y": self.p, "z_bl": self.n, "z_bu": self.n, "s_bl": self.n, "s_bu": self.n}.get(name, self.m)
+        idx = None if instances is None else self._instances(instances, unique=False)
+        rows = self.batch if idx is None else len(idx)
         if device:
             import torch
-            out = torch.zeros((self.batch, length), dtype=torch.float64, device=f"cuda:{self.device}")
+            out = torch.zeros((rows, length), dtype=torch.float64, device=f"cuda:{self.device}")
             sync_current_stream(self.device)
-            if length:
+            if length and idx is None:
                 check(self.L.pq_batch_get_result_mem(self.h, k, out.data_ptr(), MEM_DEVICE), "pq_batch_get_result")
+            elif length:
+                check(self.L.pq_batch_get_result_select_mem(self.h, idx.ctypes.data, rows, k, out.data_ptr(), MEM_DEVICE), "pq_batch_get_result_select_mem")
             return out
-        out = np.zeros((self.batch, length))
-        if length:
+        out = np.zeros((rows, length))
+        if length and idx is None:
             check(self.L.pq_batch_get_result(self.h, k, out.ctypes.data), "pq_batch_get_result")
+        elif length:
+            check(self.L.pq_batch_get_result_select_mem(self.h, idx.ctypes.data, rows, k, out.ctypes.data, MEM_HOST), "pq_batch_get_result_select_mem")
         return out
+
+    def arena_row(self, i):
+        """test hook: instance i's row of the device arena, arena_stride() doubles (pq_batch_arena_row)"""
+        out = np.zeros(max(self.arena_stride(), 1))
+        check(self.L.pq_batch_arena_row(self.h, int(i), out.ctypes.data), "pq_batch_arena_row")
+        return out[:self.arena_stride()]
 
     def block_info(self):
         N = check(self.L.pq_batch_block_info(self.h, None, 0))

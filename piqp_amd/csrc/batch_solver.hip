@@ -1375,25 +1375,27 @@ struct Ipm {
 // update() of every instance with new vectors only (solver.hpp:218-308 with every optional matrix empty): the new values are scaled on
 // the device with the Ruiz factors the instance got at setup (reuse_prev_scaling is forced for such updates, :283-285) and written over
 // the scaled copies in the arena.  NULL = unchanged.  Non-finite bounds are stored as -/+1e30 times the scaling, like set_h_l / set_h_u.
+// list (this kernel, k_batch_assign, k_batch_bound_lists<false>, k_batch_prepare and k_ruiz_sparse<false>; the _select calls): workgroup r works on instance list[r]
+// -- its arena row, its row of the bound table, its ruiz_c -- and reads row r of the caller's [count][len] arrays; null: the identity, every instance of the batch.
 __global__ void k_batch_update_vectors(const BatchShared* __restrict__ Sp, double* __restrict__ arena, const double* __restrict__ ruiz_c, const int* __restrict__ disabled,
                                        const double* __restrict__ c, const double* __restrict__ b, const double* __restrict__ h_l, const double* __restrict__ h_u,
-                                       const double* __restrict__ x_l, const double* __restrict__ x_u)
+                                       const double* __restrict__ x_l, const double* __restrict__ x_u, const int* __restrict__ list)
 {
     const BatchShared& S = *Sp;
-    const int q = blockIdx.x, n = S.n, p = S.p, m = S.m;
+    const int r = blockIdx.x, q = list ? list[r] : r, n = S.n, p = S.p, m = S.m;
     double* base = arena + (long long)q * S.stride;
     const double* dl = base + S.off[D_DL];
     const double* db = base + S.off[D_DB];
     const double rc = ruiz_c[q];
     const BoxLists L = box_lists(S, q, disabled);
     disabled = L.dropped;
-    if (c) for (int i = threadIdx.x; i < n; i += blockDim.x) base[S.off[D_C] + i] = c[(size_t)q * n + i] * (rc * dl[i]);
-    if (b) for (int i = threadIdx.x; i < p; i += blockDim.x) base[S.off[D_B] + i] = b[(size_t)q * p + i] * dl[n + i];
+    if (c) for (int i = threadIdx.x; i < n; i += blockDim.x) base[S.off[D_C] + i] = c[(size_t)r * n + i] * (rc * dl[i]);
+    if (b) for (int i = threadIdx.x; i < p; i += blockDim.x) base[S.off[D_B] + i] = b[(size_t)r * p + i] * dl[n + i];
     // (rows of G without any finite bound stay disabled: zero row, h = (-1, 1), data.hpp:144-169)
-    if (h_l) for (int i = threadIdx.x; i < m; i += blockDim.x) { const double v = h_l[(size_t)q * m + i]; base[S.off[D_HL] + i] = (disabled[i] ? -1.0 : (v > -1e30 ? v : -1e30)) * dl[n + p + i]; }
-    if (h_u) for (int i = threadIdx.x; i < m; i += blockDim.x) { const double v = h_u[(size_t)q * m + i]; base[S.off[D_HU] + i] = (disabled[i] ? 1.0 : (v < 1e30 ? v : 1e30)) * dl[n + p + i]; }
-    if (x_l) for (int k = threadIdx.x; k < L.n_x_l; k += blockDim.x) { const int idx = L.x_l_idx[k]; base[S.off[D_XL] + k] = x_l[(size_t)q * n + idx] * db[idx]; }
-    if (x_u) for (int k = threadIdx.x; k < L.n_x_u; k += blockDim.x) { const int idx = L.x_u_idx[k]; base[S.off[D_XU] + k] = x_u[(size_t)q * n + idx] * db[idx]; }
+    if (h_l) for (int i = threadIdx.x; i < m; i += blockDim.x) { const double v = h_l[(size_t)r * m + i]; base[S.off[D_HL] + i] = (disabled[i] ? -1.0 : (v > -1e30 ? v : -1e30)) * dl[n + p + i]; }
+    if (h_u) for (int i = threadIdx.x; i < m; i += blockDim.x) { const double v = h_u[(size_t)r * m + i]; base[S.off[D_HU] + i] = (disabled[i] ? 1.0 : (v < 1e30 ? v : 1e30)) * dl[n + p + i]; }
+    if (x_l) for (int k = threadIdx.x; k < L.n_x_l; k += blockDim.x) { const int idx = L.x_l_idx[k]; base[S.off[D_XL] + k] = x_l[(size_t)r * n + idx] * db[idx]; }
+    if (x_u) for (int k = threadIdx.x; k < L.n_x_u; k += blockDim.x) { const int idx = L.x_u_idx[k]; base[S.off[D_XU] + k] = x_u[(size_t)r * n + idx] * db[idx]; }
 }
 
 // update() with matrices (solver.hpp:218-308, update_P / update_A / update_G of :317-358): the caller's new values, in the CSC order they had at
@@ -1405,24 +1407,25 @@ struct BatchAssignArgs {
     const int *mapP, *mapA, *mapG, *disabled;
     const int* Grow;  // per-instance bound sets: the row of the caller's k-th value of G (mapG then has no -1: the row is tested against the instance's `dropped`); else null
     const double *Px, *Ax, *Gx, *c, *b, *h_l, *h_u, *x_l, *x_u;
+    const int* list;  // the instances of the caller's rows (see k_batch_update_vectors); null: the identity
 };
 // SETUP (k_batch_setup_ingest): the arena is zero and a vector that is not given means what it means to SparseSolver::setup -- no finite bound on that side, b = 0 --,
 // so both bounds of every row of G are written (set_h_l / set_h_u, a dropped row -1 / 1) and x_b_scaling becomes 1; nothing else differs from an update.
 template <bool SETUP>
 __device__ __forceinline__ void batch_assign(const BatchShared& S, double* __restrict__ arena, const BatchAssignArgs& a)
 {
-    const int q = blockIdx.x, n = S.n, p = S.p, m = S.m, t = threadIdx.x, NT = blockDim.x;
+    const int r = blockIdx.x, q = a.list ? a.list[r] : r, n = S.n, p = S.p, m = S.m, t = threadIdx.x, NT = blockDim.x;
     double* base = arena + (long long)q * S.stride;
-    if (a.Px) for (int k = t; k < a.nzP_in; k += NT) { const int d = a.mapP[k]; if (d >= 0) base[S.off[D_PX] + d] = a.Px[(size_t)q * a.nzP_in + k]; }
-    if (a.Ax) for (int k = t; k < a.nzA_in; k += NT) { const int d = a.mapA[k]; if (d >= 0) base[S.off[D_ATX] + d] = a.Ax[(size_t)q * a.nzA_in + k]; }
+    if (a.Px) for (int k = t; k < a.nzP_in; k += NT) { const int d = a.mapP[k]; if (d >= 0) base[S.off[D_PX] + d] = a.Px[(size_t)r * a.nzP_in + k]; }
+    if (a.Ax) for (int k = t; k < a.nzA_in; k += NT) { const int d = a.mapA[k]; if (d >= 0) base[S.off[D_ATX] + d] = a.Ax[(size_t)r * a.nzA_in + k]; }
     const BoxLists L = box_lists(S, q, a.disabled);
-    if (a.Gx) for (int k = t; k < a.nzG_in; k += NT) { const int d = a.mapG[k]; if (d >= 0 && !(a.Grow && L.dropped[a.Grow[k]])) base[S.off[D_GTX] + d] = a.Gx[(size_t)q * a.nzG_in + k]; }
-    if (a.c) for (int i = t; i < n; i += NT) base[S.off[D_C] + i] = a.c[(size_t)q * n + i];
-    if (a.b) for (int i = t; i < p; i += NT) base[S.off[D_B] + i] = a.b[(size_t)q * p + i];
-    if (a.h_l || SETUP) for (int i = t; i < m; i += NT) { const double v = a.h_l ? a.h_l[(size_t)q * m + i] : -1e30; base[S.off[D_HL] + i] = L.dropped[i] ? -1.0 : (v > -1e30 ? v : -1e30); }
-    if (a.h_u || SETUP) for (int i = t; i < m; i += NT) { const double v = a.h_u ? a.h_u[(size_t)q * m + i] : 1e30; base[S.off[D_HU] + i] = L.dropped[i] ? 1.0 : (v < 1e30 ? v : 1e30); }
-    if (a.x_l) for (int k = t; k < L.n_x_l; k += NT) base[S.off[D_XL] + k] = a.x_l[(size_t)q * n + L.x_l_idx[k]];
-    if (a.x_u) for (int k = t; k < L.n_x_u; k += NT) base[S.off[D_XU] + k] = a.x_u[(size_t)q * n + L.x_u_idx[k]];
+    if (a.Gx) for (int k = t; k < a.nzG_in; k += NT) { const int d = a.mapG[k]; if (d >= 0 && !(a.Grow && L.dropped[a.Grow[k]])) base[S.off[D_GTX] + d] = a.Gx[(size_t)r * a.nzG_in + k]; }
+    if (a.c) for (int i = t; i < n; i += NT) base[S.off[D_C] + i] = a.c[(size_t)r * n + i];
+    if (a.b) for (int i = t; i < p; i += NT) base[S.off[D_B] + i] = a.b[(size_t)r * p + i];
+    if (a.h_l || SETUP) for (int i = t; i < m; i += NT) { const double v = a.h_l ? a.h_l[(size_t)r * m + i] : -1e30; base[S.off[D_HL] + i] = L.dropped[i] ? -1.0 : (v > -1e30 ? v : -1e30); }
+    if (a.h_u || SETUP) for (int i = t; i < m; i += NT) { const double v = a.h_u ? a.h_u[(size_t)r * m + i] : 1e30; base[S.off[D_HU] + i] = L.dropped[i] ? 1.0 : (v < 1e30 ? v : 1e30); }
+    if (a.x_l) for (int k = t; k < L.n_x_l; k += NT) base[S.off[D_XL] + k] = a.x_l[(size_t)r * n + L.x_l_idx[k]];
+    if (a.x_u) for (int k = t; k < L.n_x_u; k += NT) base[S.off[D_XU] + k] = a.x_u[(size_t)r * n + L.x_u_idx[k]];
     if (SETUP) for (int i = t; i < n; i += NT) base[S.off[D_XBS] + i] = 1.0;
 }
 __global__ void k_batch_assign(const BatchShared* __restrict__ Sp, double* __restrict__ arena, BatchAssignArgs a) { batch_assign<false>(*Sp, arena, a); }
@@ -1439,10 +1442,11 @@ __global__ void k_batch_setup_ingest(const BatchShared* __restrict__ Sp, double*
 // makes from the instances' HostData.
 template <bool SETUP>
 __global__ __launch_bounds__(64) void k_batch_bound_lists(const BatchShared* __restrict__ Sp, double* __restrict__ arena, int* __restrict__ tab, const double* __restrict__ h_l,
-                                                          const double* __restrict__ h_u, const double* __restrict__ x_l, const double* __restrict__ x_u, int scaled, int grouped)
+                                                          const double* __restrict__ h_u, const double* __restrict__ x_l, const double* __restrict__ x_u, int scaled, int grouped,
+                                                          const int* __restrict__ list)
 {
     const BatchShared& S = *Sp;
-    const int q = blockIdx.x, n = S.n, p = S.p, m = S.m, lane = threadIdx.x;
+    const int cr = blockIdx.x, q = list ? list[cr] : cr, n = S.n, p = S.p, m = S.m, lane = threadIdx.x;  // cr: the caller's row (see k_batch_update_vectors)
     double* base = arena + (long long)q * S.stride;
     int* r = tab + (long long)q * S.bl_stride;
     const unsigned long long below = (1ull << lane) - 1ull;
@@ -1455,8 +1459,8 @@ __global__ __launch_bounds__(64) void k_batch_bound_lists(const BatchShared* __r
             const bool in = i < m;
             bool fl = false, fu = false;
             if (in) {
-                fl = h_l ? h_l[(size_t)q * m + i] > -1e30 : !SETUP && has_l[i] != 0;
-                fu = h_u ? h_u[(size_t)q * m + i] < 1e30 : !SETUP && has_u[i] != 0;
+                fl = h_l ? h_l[(size_t)cr * m + i] > -1e30 : !SETUP && has_l[i] != 0;
+                fu = h_u ? h_u[(size_t)cr * m + i] < 1e30 : !SETUP && has_u[i] != 0;
             }
             const bool dd = in && !fl && !fu, il = in && (fl || dd), iu = in && (fu || dd);
             const unsigned long long bl = __ballot(il), bu = __ballot(iu);
@@ -1483,7 +1487,7 @@ __global__ __launch_bounds__(64) void k_batch_bound_lists(const BatchShared* __r
         for (int j0 = 0; j0 < n; j0 += 64) {
             const int j = j0 + lane;
             const bool in = j < n;
-            const bool f = in && v && (side == 0 ? v[(size_t)q * n + j] > -1e30 : v[(size_t)q * n + j] < 1e30);
+            const bool f = in && v && (side == 0 ? v[(size_t)cr * n + j] > -1e30 : v[(size_t)cr * n + j] < 1e30);
             const unsigned long long bf = __ballot(f);
             const int k = cnt + __popcll(bf & below);
             if (f) idx[k] = j;
@@ -1496,10 +1500,10 @@ __global__ __launch_bounds__(64) void k_batch_bound_lists(const BatchShared* __r
 
 // per instance: caller's (Ruiz-scaled) values -> front / grouped-row arenas and the AtA fronts (multistage ctor, :76-135)
 template <int NT>
-__global__ __launch_bounds__(NT) void k_batch_prepare(const BatchShared* __restrict__ Sp, double* __restrict__ arena)
+__global__ __launch_bounds__(NT) void k_batch_prepare(const BatchShared* __restrict__ Sp, double* __restrict__ arena, const int* __restrict__ list)
 {
     const BatchShared& S = *Sp;
-    double* base = arena + (long long)blockIdx.x * S.stride;
+    double* base = arena + (long long)(list ? list[blockIdx.x] : (int)blockIdx.x) * S.stride;
     const int tid = threadIdx.x;
     double *Pf = base + S.off[B_PF], *XA = base + S.off[B_XA], *XG = base + S.off[B_XG];
     const double *Px = base + S.off[D_PX], *Ax = base + S.off[D_ATX], *Gx = base + S.off[D_GTX];
@@ -1647,6 +1651,19 @@ __global__ __launch_bounds__(GATHER_THREADS) void k_batch_gather_rows(W* __restr
     for (long long g = (long long)blockIdx.x * GATHER_THREADS + t; g < words; g += (long long)gridDim.x * GATHER_THREADS) {
         const long long row = g / wpr;
         dst[g] = src[(long long)idx[row] * wpr + (g - row * wpr)];
+    }
+}
+
+// pq_batch_get_result_select_mem: out[j][0 .. len) = arena[idx[j] * stride + off + 0 .. len) for j < count -- one field of the listed instances, repeats allowed.
+// The elements of all rows as one flat range, taken grid-stride: consecutive lanes on consecutive entries of a row and of `out`, every entry read once and written
+// once.  Every index is held in 64 bits; idx has been checked against the batch on the host, and out has `count` rows.
+__global__ __launch_bounds__(GATHER_THREADS) void k_batch_gather_field(double* __restrict__ out, const double* __restrict__ arena, const int* __restrict__ idx,
+                                                                       long long count, long long len, long long stride, long long off)
+{
+    const long long total = count * len;
+    for (long long g = (long long)blockIdx.x * GATHER_THREADS + threadIdx.x; g < total; g += (long long)gridDim.x * GATHER_THREADS) {
+        const long long j = g / len;
+        out[g] = arena[(long long)idx[j] * stride + off + (g - j * len)];
     }
 }
 
@@ -1817,6 +1834,7 @@ private:
         PQ_HIP(hipMemcpyAsync(order_.p, order_h_.data(), sizeof(int) * (size_t)batch, hipMemcpyHostToDevice, st_));
         prof_.alloc((size_t)batch * NPROF);
         infos_h_.resize(batch);
+        sel_ = DBuf<int>();  // (of the batch before: the next _select call makes one for this batch)
     }
     // RuizEquilibration::scale_data of every instance (sparse/preconditioner.hpp:65-222) in one launch, then the front arenas
     void scale_and_prepare(bool record_end = true)
@@ -1829,14 +1847,15 @@ private:
     }
     // pq_batch_last_ingest, from the shapes of what the call was given (null: not given, or of length 0).  fetched: the bytes a device-fed setup brought to the host.
     void note_ingest(int mem, bool is_setup, const double* Px, const double* Ax, const double* Gx, const double* c, const double* b, const double* h_l, const double* h_u,
-                     const double* x_l, const double* x_u, long long fetched)
+                     const double* x_l, const double* x_u, long long fetched, int rows = -1)
     {
+        if (rows < 0) rows = batch_;  // (an update by list: the rows given)
         const long long vec = (c ? n_ : 0) + (b ? p_ : 0) + (x_l ? n_ : 0) + (x_u ? n_ : 0);
         const long long given = (Px ? nzP_in_ : 0) + (Ax ? nzA_in_ : 0) + (Gx ? nzG_in_ : 0) + vec + ((h_l ? 1 : 0) + (h_u ? 1 : 0)) * (long long)m_;
         const long long written = (Px ? shared_h_.nzP : 0) + (Ax ? shared_h_.nzA : 0) + (Gx ? shared_h_.nzG : 0) + vec +
                                   (is_setup ? 2LL * m_ + n_ : ((h_l ? 1 : 0) + (h_u ? 1 : 0)) * (long long)m_);
-        ingest_[0] = mem == PQ_MEM_DEVICE ? fetched : 8LL * batch_ * given;
-        ingest_[1] = is_setup && mem != PQ_MEM_DEVICE ? 0 : 8LL * batch_ * written;
+        ingest_[0] = mem == PQ_MEM_DEVICE ? fetched : 8LL * rows * given;
+        ingest_[1] = is_setup && mem != PQ_MEM_DEVICE ? 0 : 8LL * rows * written;
     }
 
     // Device memory: the structure from the patterns and instance 0's four bound vectors -- the only problem data that comes to the host --, no HostData for the other
@@ -1901,7 +1920,7 @@ private:
         alloc_instance_buffers(batch);
         PQ_HIP(hipEventRecord(ev0_, st_));
         if (per_inst) {
-            hipLaunchKernelGGL(k_batch_bound_lists<true>, dim3(batch), dim3(64), 0, st_, shared_.p, arena_.p, bl_tab_.p, h_l, h_u, x_l, x_u, 0, 0);
+            hipLaunchKernelGGL(k_batch_bound_lists<true>, dim3(batch), dim3(64), 0, st_, shared_.p, arena_.p, bl_tab_.p, h_l, h_u, x_l, x_u, 0, 0, (const int*)nullptr);
             PQ_HIP(hipGetLastError());
         }
         BatchAssignArgs a{};
@@ -1932,7 +1951,7 @@ public:
         shared_h_.set = settings_;
         PQ_HIP(hipMemcpyAsync(shared_.p, &shared_h_, sizeof(BatchShared), hipMemcpyHostToDevice, st_));
         PQ_HIP(hipEventRecord(ev0_, st_));
-        launch_ipm();
+        launch_ipm(batch_, order_.p);
         PQ_HIP(hipEventRecord(ev1_, st_));
         PQ_HIP(hipGetLastError());
         PQ_HIP(hipMemcpyAsync(infos_h_.data(), infos_.p, sizeof(pq_info) * batch_, hipMemcpyDeviceToHost, st_));
@@ -2036,42 +2055,50 @@ public:
     // update() of every instance, vectors only; the set of finite bounds must be the one given at setup (it is part of the shared structure) -- or, with
     // PQ_BOUND_SETS_PER_INSTANCE, whatever the vectors say: k_batch_bound_lists rewrites every instance's lists first
     // mem = PQ_MEM_DEVICE: the kernels read the caller's device arrays in place (no staging buffers, no copies)
-    bool update_vectors(const double* c, const double* b, const double* h_l, const double* h_u, const double* x_l, const double* x_u, int mem = PQ_MEM_HOST)
+    // idx (pq_batch_update_select_mem; HOST memory, checked by the caller: in range, no instance twice): the same sequence on the instances idx[0 .. count) alone, the
+    // arrays [count][len], row j for instance idx[j]; the pattern check runs over those rows, host arrays are staged as [count][len]; null: the whole batch
+    bool update_vectors(const double* c, const double* b, const double* h_l, const double* h_u, const double* x_l, const double* x_u, int mem = PQ_MEM_HOST,
+                        const int* idx = nullptr, int count = 0)
     {
         if (!setup_done_) throw std::runtime_error("batch solver not set up");
         PQ_HIP(hipSetDevice(dev_));
-        if (!per_inst_) { if (mem == PQ_MEM_DEVICE) check_patterns_device(h_l, h_u, x_l, x_u); else check_patterns(h_l, h_u, x_l, x_u); }
+        const int rows = idx ? count : batch_;
+        if (!per_inst_) { if (mem == PQ_MEM_DEVICE) check_patterns_device(h_l, h_u, x_l, x_u, rows); else check_patterns(h_l, h_u, x_l, x_u, rows); }
+        const int* list = idx ? list_to_device(idx, count) : nullptr;
         DBuf<double> dc, dbv, dhl, dhu, dxl, dxu;
         auto up = [&](DBuf<double>& d, const double* v, int len) -> const double* {
             if (!v || len == 0) return nullptr;
             if (mem == PQ_MEM_DEVICE) return v;
-            d.alloc((size_t)batch_ * len);
-            PQ_HIP(hipMemcpyAsync(d.p, v, sizeof(double) * (size_t)batch_ * len, hipMemcpyHostToDevice, st_));
+            d.alloc((size_t)rows * len);
+            PQ_HIP(hipMemcpyAsync(d.p, v, sizeof(double) * (size_t)rows * len, hipMemcpyHostToDevice, st_));
             return d.p;
         };
         const double *pc = up(dc, c, n_), *pb = up(dbv, b, p_), *phl = up(dhl, h_l, m_), *phu = up(dhu, h_u, m_), *pxl = up(dxl, x_l, n_), *pxu = up(dxu, x_u, n_);
-        note_ingest(mem, false, nullptr, nullptr, nullptr, pc, pb, phl, phu, pxl, pxu, 0);
-        launch_bound_lists(phl, phu, pxl, pxu, true);
-        hipLaunchKernelGGL(k_batch_update_vectors, dim3(batch_), dim3(128), 0, st_, shared_.p, arena_.p, ruiz_c_.p, disabled_d_, pc, pb, phl, phu, pxl, pxu);
+        note_ingest(mem, false, nullptr, nullptr, nullptr, pc, pb, phl, phu, pxl, pxu, 0, rows);
+        launch_bound_lists(phl, phu, pxl, pxu, true, list, rows);
+        hipLaunchKernelGGL(k_batch_update_vectors, dim3(rows), dim3(128), 0, st_, shared_.p, arena_.p, ruiz_c_.p, disabled_d_, pc, pb, phl, phu, pxl, pxu, list);
         PQ_HIP(hipGetLastError());
         stream_wait(st_);
         return true;
     }
     // update() of every instance with new matrix values (patterns and the set of finite bounds as given at setup) and / or vectors: per instance
     // unscale_data -> assign -> scale_data (fresh equilibration unless settings.preconditioner_reuse_on_update), all on the device
+    // idx (pq_batch_update_data_select_mem): as at update_vectors, every launch of the sequence on the listed instances alone
     bool update_data(const double* Px, const double* Ax, const double* Gx, const double* c, const double* b, const double* h_l, const double* h_u, const double* x_l,
-                     const double* x_u, int mem = PQ_MEM_HOST)
+                     const double* x_u, int mem = PQ_MEM_HOST, const int* idx = nullptr, int count = 0)
     {
-        if (!Px && !Ax && !Gx) return update_vectors(c, b, h_l, h_u, x_l, x_u, mem);
+        if (!Px && !Ax && !Gx) return update_vectors(c, b, h_l, h_u, x_l, x_u, mem, idx, count);
         if (!setup_done_) throw std::runtime_error("batch solver not set up");
         PQ_HIP(hipSetDevice(dev_));
-        if (!per_inst_) { if (mem == PQ_MEM_DEVICE) check_patterns_device(h_l, h_u, x_l, x_u); else check_patterns(h_l, h_u, x_l, x_u); }
+        const int rows = idx ? count : batch_;
+        if (!per_inst_) { if (mem == PQ_MEM_DEVICE) check_patterns_device(h_l, h_u, x_l, x_u, rows); else check_patterns(h_l, h_u, x_l, x_u, rows); }
+        const int* list = idx ? list_to_device(idx, count) : nullptr;
         DBuf<double> dP, dA, dG, dc, dbv, dhl, dhu, dxl, dxu;
         auto up = [&](DBuf<double>& d, const double* v, int len) -> const double* {
             if (!v || len == 0) return nullptr;
             if (mem == PQ_MEM_DEVICE) return v;
-            d.alloc((size_t)batch_ * len);
-            PQ_HIP(hipMemcpyAsync(d.p, v, sizeof(double) * (size_t)batch_ * len, hipMemcpyHostToDevice, st_));
+            d.alloc((size_t)rows * len);
+            PQ_HIP(hipMemcpyAsync(d.p, v, sizeof(double) * (size_t)rows * len, hipMemcpyHostToDevice, st_));
             return d.p;
         };
         BatchAssignArgs a{};
@@ -2079,15 +2106,90 @@ public:
         a.mapP = mapP_; a.mapA = mapA_; a.mapG = mapG_; a.disabled = disabled_d_; a.Grow = Grow_;
         a.Px = up(dP, Px, nzP_in_); a.Ax = up(dA, Ax, nzA_in_); a.Gx = up(dG, Gx, nzG_in_);
         a.c = up(dc, c, n_); a.b = up(dbv, b, p_); a.h_l = up(dhl, h_l, m_); a.h_u = up(dhu, h_u, m_); a.x_l = up(dxl, x_l, n_); a.x_u = up(dxu, x_u, n_);
-        note_ingest(mem, false, a.Px, a.Ax, a.Gx, a.c, a.b, a.h_l, a.h_u, a.x_l, a.x_u, 0);
-        launch_ruiz(RUIZ_UNSCALE);  // (with the lists as they stood: the box vectors are packed to them)
-        launch_bound_lists(a.h_l, a.h_u, a.x_l, a.x_u, false);
-        hipLaunchKernelGGL(k_batch_assign, dim3(batch_), dim3(128), 0, st_, shared_.p, arena_.p, a);
+        a.list = list;
+        note_ingest(mem, false, a.Px, a.Ax, a.Gx, a.c, a.b, a.h_l, a.h_u, a.x_l, a.x_u, 0, rows);
+        launch_ruiz(RUIZ_UNSCALE, list, rows);  // (with the lists as they stood: the box vectors are packed to them)
+        launch_bound_lists(a.h_l, a.h_u, a.x_l, a.x_u, false, list, rows);
+        hipLaunchKernelGGL(k_batch_assign, dim3(rows), dim3(128), 0, st_, shared_.p, arena_.p, a);
         PQ_HIP(hipGetLastError());
-        launch_ruiz(settings_.preconditioner_reuse_on_update ? RUIZ_REUSE : RUIZ_COMPUTE);
-        if (!ldlt_) launch_prepare();
+        launch_ruiz(settings_.preconditioner_reuse_on_update ? RUIZ_REUSE : RUIZ_COMPUTE, list, rows);
+        if (!ldlt_) launch_prepare(list, rows);
         stream_wait(st_);
         return true;
+    }
+    // pq_batch_solve_select: solve() of the instances idx[0 .. count) alone (HOST memory, checked by the caller: in range, no instance twice), with the settings as
+    // they stand; returns how many of them ended PIQP_SOLVED.  The launch is solve()'s kernel on `count` workgroups that find their instance through sel_; nothing of
+    // another instance is written, on the device or in infos_h_.  The launch order of the list: as given, or (start-order flag) the listed instances that took most
+    // iterations in their previous solve first, ties in list order.  order_ is not touched before the launch, and afterwards it is recomputed from ALL infos as solve()
+    // leaves it: at every moment it is a permutation of the whole batch.
+    int solve_select(const int* idx, int count)
+    {
+        if (!setup_done_) throw std::runtime_error("batch solver not set up");
+        if (!verify_settings(settings_)) {
+            for (int j = 0; j < count; ++j) { pq_info& i = infos_h_[(size_t)idx[j]]; i = pq_info{}; i.status = PQ_INVALID_SETTINGS; }
+            return 0;
+        }
+        PQ_HIP(hipSetDevice(dev_));
+        const bool lpt = lpt_ && !debug_token("batch_no_lpt");
+        const int cap = std::max(settings_.max_iter, 1) + 1;
+        auto key = [&](int i) { return std::min(std::max(infos_h_[(size_t)i].iter, 0), cap - 1); };  // (longest_first_order's)
+        sel_h_.assign(idx, idx + count);
+        if (lpt) std::stable_sort(sel_h_.begin(), sel_h_.end(), [&](int a, int b) { return key(a) > key(b); });
+        const int* order = list_to_device(sel_h_.data(), count);
+        sync_settings();
+        PQ_HIP(hipEventRecord(ev0_, st_));
+        launch_ipm(count, order);
+        PQ_HIP(hipEventRecord(ev1_, st_));
+        PQ_HIP(hipGetLastError());
+        // the listed infos alone reach infos_h_ (the host's infos of the others may differ from the device's: invalid settings are recorded on the host only)
+        const bool few = count <= 8;  // (a copy of one pq_info costs about a hundredth of the copy of 8192 of them)
+        if (few) {
+            for (int j = 0; j < count; ++j)
+                PQ_HIP(hipMemcpyAsync(&infos_h_[(size_t)idx[j]], infos_.p + idx[j], sizeof(pq_info), hipMemcpyDeviceToHost, st_));
+        } else {
+            infos_tmp_.resize((size_t)batch_);
+            PQ_HIP(hipMemcpyAsync(infos_tmp_.data(), infos_.p, sizeof(pq_info) * (size_t)batch_, hipMemcpyDeviceToHost, st_));
+        }
+        stream_wait(st_);
+        if (!few) for (int j = 0; j < count; ++j) infos_h_[(size_t)idx[j]] = infos_tmp_[(size_t)idx[j]];
+        float ms = 0.f;
+        PQ_HIP(hipEventElapsedTime(&ms, ev0_, ev1_));
+        last_kernel_ms_ = ms;
+        int solved = 0;
+        for (int j = 0; j < count; ++j) solved += infos_h_[(size_t)idx[j]].status == PQ_SOLVED;
+        if (lpt) longest_first_order();
+        stream_wait(st_);
+        return solved;
+    }
+    // pq_batch_get_result_select_mem: field k of the instances idx[0 .. count) (HOST memory, checked by the caller; repeats allowed, so count may exceed the batch)
+    // -> host or device [count][len].  k_batch_gather_field writes a device destination directly; a host one goes through a [count][len] staging buffer.
+    void get_result_select(const int* idx, int count, int field, double* out, int mem)
+    {
+        if (!setup_done_) throw std::runtime_error("batch solver not set up");
+        const int len = field_len(field);
+        if (len == 0) return;
+        PQ_HIP(hipSetDevice(dev_));
+        DBuf<double> stage;
+        double* dst = out;
+        if (mem != PQ_MEM_DEVICE) { stage.alloc((size_t)count * len); dst = stage.p; }
+        int dev = 0, cus = 256;
+        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        for (int j0 = 0; j0 < count; j0 += batch_) {  // (sel_ holds `batch` entries: a list with repeats goes in slices)
+            const int cnt = std::min(batch_, count - j0);
+            const int* list = list_to_device(idx + j0, cnt);
+            const long long work = ((long long)cnt * len + GATHER_THREADS - 1) / GATHER_THREADS;
+            hipLaunchKernelGGL(k_batch_gather_field, dim3((unsigned)std::max(1LL, std::min(work, 8LL * std::max(cus, 1)))), dim3(GATHER_THREADS), 0, st_,
+                               dst + (size_t)j0 * len, (const double*)arena_.p, list, (long long)cnt, (long long)len, (long long)layout_.stride, (long long)layout_.off[V_R + field]);
+            PQ_HIP(hipGetLastError());
+        }
+        if (mem != PQ_MEM_DEVICE) PQ_HIP(hipMemcpyAsync(out, stage.p, sizeof(double) * (size_t)count * len, hipMemcpyDeviceToHost, st_));
+        stream_wait(st_);
+    }
+    // pq_batch_arena_row (test hook): one instance's row of the arena, layout_.stride doubles, to host memory
+    void arena_row(int instance, double* out_host) const
+    {
+        PQ_HIP(hipSetDevice(dev_));
+        PQ_HIP(hipMemcpy(out_host, arena_.p + (size_t)layout_.stride * instance, sizeof(double) * (size_t)layout_.stride, hipMemcpyDeviceToHost));
     }
     double last_kernel_ms() const { return last_kernel_ms_; }
     void set_start_order(bool longest_first)
@@ -2257,6 +2359,14 @@ private:
             std::fprintf(stderr, "[piqp_amd] batch clone: %lld rows of %zu bytes in %d-byte words\n", count, row_bytes, a % 16 == 0 ? 16 : 8);
     }
 
+    // the list of a _select call (host, `count` <= batch entries, checked) in sel_ on st_; the buffer is made by the first such call on the handle -- setup() and
+    // clone() allocate nothing for it -- and holds `batch` entries, so no later call allocates.  The stream orders the upload behind the kernels that read the last one.
+    const int* list_to_device(const int* idx, int count)
+    {
+        if (!sel_.p) sel_.alloc((size_t)batch_);
+        PQ_HIP(hipMemcpyAsync(sel_.p, idx, sizeof(int) * (size_t)count, hipMemcpyHostToDevice, st_));
+        return sel_.p;
+    }
     void require_ldlt(const char* what) const
     {
         if (!setup_done_) throw std::runtime_error("batch solver not set up");
@@ -2281,11 +2391,12 @@ private:
         return bytes;
     }
 
-    void check_patterns(const double* h_l, const double* h_u, const double* x_l, const double* x_u) const
+    // rows: the rows the caller gave (the batch, or the length of the list of an update by list)
+    void check_patterns(const double* h_l, const double* h_u, const double* x_l, const double* x_u, int rows) const
     {
         auto pattern_ok = [&](const double* v, int len, const std::vector<char>& finite, bool lower) {
             if (!v) return true;
-            for (int q = 0; q < batch_; ++q)
+            for (int q = 0; q < rows; ++q)
                 for (int i = 0; i < len; ++i) {
                     const double x = v[(size_t)q * len + i];
                     if ((lower ? x > -1e30 : x < 1e30) != (finite[i] != 0)) return false;
@@ -2297,14 +2408,14 @@ private:
     }
 
     // the same check on the caller's DEVICE arrays: one small kernel per given bound vector, one flag word read back
-    void check_patterns_device(const double* h_l, const double* h_u, const double* x_l, const double* x_u)
+    void check_patterns_device(const double* h_l, const double* h_u, const double* x_l, const double* x_u, int rows)
     {
         if (!h_l && !h_u && !x_l && !x_u) return;
         PQ_HIP(hipMemsetAsync(fin_flag_.p, 0, sizeof(int), st_));
-        if (h_l) ingest_check_finite_pattern(h_l, fin_hl_d_, batch_, m_, true, fin_flag_.p, st_);
-        if (h_u) ingest_check_finite_pattern(h_u, fin_hu_d_, batch_, m_, false, fin_flag_.p, st_);
-        if (x_l) ingest_check_finite_pattern(x_l, fin_xl_d_, batch_, n_, true, fin_flag_.p, st_);
-        if (x_u) ingest_check_finite_pattern(x_u, fin_xu_d_, batch_, n_, false, fin_flag_.p, st_);
+        if (h_l) ingest_check_finite_pattern(h_l, fin_hl_d_, rows, m_, true, fin_flag_.p, st_);
+        if (h_u) ingest_check_finite_pattern(h_u, fin_hu_d_, rows, m_, false, fin_flag_.p, st_);
+        if (x_l) ingest_check_finite_pattern(x_l, fin_xl_d_, rows, n_, true, fin_flag_.p, st_);
+        if (x_u) ingest_check_finite_pattern(x_u, fin_xu_d_, rows, n_, false, fin_flag_.p, st_);
         int flag = 0;
         PQ_HIP(hipMemcpyAsync(&flag, fin_flag_.p, sizeof(int), hipMemcpyDeviceToHost, st_));
         stream_wait(st_);
@@ -2359,8 +2470,9 @@ private:
     }
 
     // sparse/preconditioner.hpp on the arena: one workgroup per instance (ruiz_kernels.hip)
-    void launch_ruiz(int mode)
+    void launch_ruiz(int mode, const int* list = nullptr, int rows = 0)
     {
+        if (!list) rows = batch_;
         const BatchShared& S = shared_h_;
         RuizSparseArgs a;
         a.n = n_; a.p = p_; a.m = m_;
@@ -2374,7 +2486,8 @@ private:
         if (per_inst_) { a.lists = bl_tab_.p; a.lists_stride = S.bl_stride; a.lists_x_l = bl_off(BL_X_L_IDX, n_, m_); a.lists_x_u = bl_off(BL_X_U_IDX, n_, m_); }
         a.c_scale = ruiz_c_.p;
         a.mode = mode; a.scale_cost = settings_.preconditioner_scale_cost != 0; a.max_iter = settings_.preconditioner_iter;
-        launch_ruiz_sparse(a, batch_, n_ + p_ + m_ <= 512 ? 64 : 256, st_);
+        a.inst_list = list;
+        launch_ruiz_sparse(a, rows, n_ + p_ + m_ <= 512 ? 64 : 256, st_);
     }
 
     // PQ_BOUND_SETS_PER_INSTANCE: the table of every instance's lists from its own HostData (rows as bl_off says), and the descriptor that points to it
@@ -2404,10 +2517,10 @@ private:
         PQ_HIP(hipMemcpyAsync(shared_.p, &shared_h_, sizeof(BatchShared), hipMemcpyHostToDevice, st_));
         stream_wait(st_);
     }
-    void launch_bound_lists(const double* h_l, const double* h_u, const double* x_l, const double* x_u, bool scaled)
+    void launch_bound_lists(const double* h_l, const double* h_u, const double* x_l, const double* x_u, bool scaled, const int* list, int rows)
     {
         if (!per_inst_ || (!h_l && !h_u && !x_l && !x_u)) return;
-        hipLaunchKernelGGL(k_batch_bound_lists<false>, dim3(batch_), dim3(64), 0, st_, shared_.p, arena_.p, bl_tab_.p, h_l, h_u, x_l, x_u, scaled ? 1 : 0, ldlt_ ? 0 : 1);
+        hipLaunchKernelGGL(k_batch_bound_lists<false>, dim3(rows), dim3(64), 0, st_, shared_.p, arena_.p, bl_tab_.p, h_l, h_u, x_l, x_u, scaled ? 1 : 0, ldlt_ ? 0 : 1, list);
         PQ_HIP(hipGetLastError());
     }
 
@@ -2635,14 +2748,16 @@ private:
         cp(D_C, d.c, n_); cp(D_B, d.b, p_); cp(D_HL, d.h_l, m_); cp(D_HU, d.h_u, m_); cp(D_XL, d.x_l, n_); cp(D_XU, d.x_u, n_); cp(D_XBS, d.x_b_scaling, n_);
     }
 
-    void launch_prepare()
+    void launch_prepare(const int* list = nullptr, int rows = 0)
     {
-        if (nt_ == 64) hipLaunchKernelGGL(k_batch_prepare<64>, dim3(batch_), dim3(64), 0, st_, shared_.p, arena_.p);
-        else hipLaunchKernelGGL(k_batch_prepare<256>, dim3(batch_), dim3(256), 0, st_, shared_.p, arena_.p);
+        if (!list) rows = batch_;
+        if (nt_ == 64) hipLaunchKernelGGL(k_batch_prepare<64>, dim3(rows), dim3(64), 0, st_, shared_.p, arena_.p, list);
+        else hipLaunchKernelGGL(k_batch_prepare<256>, dim3(rows), dim3(256), 0, st_, shared_.p, arena_.p, list);
         PQ_HIP(hipGetLastError());
     }
+    // grid workgroups, workgroup r on instance order[r]: the whole batch in its stored order (solve) or the listed instances (solve_select)
     template <int NTv, int MODEv, int WPEv>
-    void launch_ipm_with()
+    void launch_ipm_with(int grid, const int* order)
     {
         int bytes = shared_h_.chain_lds_doubles * (int)sizeof(double);
         if (const char* e = debug_token("batch_per_cu")) {
@@ -2655,33 +2770,33 @@ private:
         attr([&] {
             PQ_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_batch_ipm<NTv, MODEv, WPEv>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LIMIT_BYTES));
         });
-        hipLaunchKernelGGL((k_batch_ipm<NTv, MODEv, WPEv>), dim3(batch_), dim3(NTv), bytes, st_, shared_.p, arena_.p, ruiz_c_.p, infos_.p, prof_.p, order_.p);
+        hipLaunchKernelGGL((k_batch_ipm<NTv, MODEv, WPEv>), dim3(grid), dim3(NTv), bytes, st_, shared_.p, arena_.p, ruiz_c_.p, infos_.p, prof_.p, order);
     }
     template <int NTv, int MODEv>
-    void launch_ipm_as()
+    void launch_ipm_as(int grid, const int* order)
     {
         if constexpr (NTv == 64) {
-            if (wpe_ == 2) launch_ipm_with<NTv, MODEv, 2>();
-            else if (wpe_ == 3) launch_ipm_with<NTv, MODEv, 3>();
-            else if (wpe_ == 5 && MODEv == MODE_WAVE) launch_ipm_with<NTv, MODE_WAVE, 5>();
-            else if (wpe_ == 6 && MODEv == MODE_WAVE) launch_ipm_with<NTv, MODE_WAVE, 6>();
-            else launch_ipm_with<NTv, MODEv, 4>();
+            if (wpe_ == 2) launch_ipm_with<NTv, MODEv, 2>(grid, order);
+            else if (wpe_ == 3) launch_ipm_with<NTv, MODEv, 3>(grid, order);
+            else if (wpe_ == 5 && MODEv == MODE_WAVE) launch_ipm_with<NTv, MODE_WAVE, 5>(grid, order);
+            else if (wpe_ == 6 && MODEv == MODE_WAVE) launch_ipm_with<NTv, MODE_WAVE, 6>(grid, order);
+            else launch_ipm_with<NTv, MODEv, 4>(grid, order);
         } else {
-            launch_ipm_with<NTv, MODEv, 2>();
+            launch_ipm_with<NTv, MODEv, 2>(grid, order);
         }
     }
-    void launch_ipm()
+    void launch_ipm(int grid, const int* order)
     {
-        if (ldlt_) { launch_ipm_with<64, MODE_LDLT, 4>(); return; }
+        if (ldlt_) { launch_ipm_with<64, MODE_LDLT, 4>(grid, order); return; }
         if (nt_ == 64) {
-            if (mode_ == MODE_WAVE) launch_ipm_as<64, MODE_WAVE>();
-            else if (mode_ == MODE_RESIDENT) launch_ipm_as<64, MODE_RESIDENT>();
-            else if (mode_ == MODE_STAGED) launch_ipm_as<64, MODE_STAGED>();
-            else launch_ipm_as<64, MODE_HBM>();
+            if (mode_ == MODE_WAVE) launch_ipm_as<64, MODE_WAVE>(grid, order);
+            else if (mode_ == MODE_RESIDENT) launch_ipm_as<64, MODE_RESIDENT>(grid, order);
+            else if (mode_ == MODE_STAGED) launch_ipm_as<64, MODE_STAGED>(grid, order);
+            else launch_ipm_as<64, MODE_HBM>(grid, order);
         } else {
-            if (mode_ == MODE_RESIDENT) launch_ipm_as<256, MODE_RESIDENT>();
-            else if (mode_ == MODE_STAGED) launch_ipm_as<256, MODE_STAGED>();
-            else launch_ipm_as<256, MODE_HBM>();
+            if (mode_ == MODE_RESIDENT) launch_ipm_as<256, MODE_RESIDENT>(grid, order);
+            else if (mode_ == MODE_STAGED) launch_ipm_as<256, MODE_STAGED>(grid, order);
+            else launch_ipm_as<256, MODE_HBM>(grid, order);
         }
     }
 
@@ -2712,8 +2827,11 @@ private:
     std::shared_ptr<StructBufs> sbufs_;
     DBuf<double> arena_, ruiz_c_, prof_;
     DBuf<pq_info> infos_;
-    DBuf<int> order_;            // block -> instance of the next launch
+    DBuf<int> order_;            // block -> instance of the next WHOLE launch: a permutation of the batch at all times (no _select call writes it but through longest_first_order)
     std::vector<int> order_h_;
+    DBuf<int> sel_;              // the _select calls: [batch], made by the first of them (list_to_device): the caller's list, or block -> instance of a solve by list
+    std::vector<int> sel_h_;
+    std::vector<pq_info> infos_tmp_;  // solve_select: the device's infos on their way to the listed entries of infos_h_
     std::vector<pq_info> infos_h_;
     Event ev0_, ev1_;  // the timing bracket of solve() (last_kernel_ms)
     Stream st_;
@@ -2727,6 +2845,32 @@ using namespace pq;
 struct pq_batch {
     std::unique_ptr<BatchSolver> impl;
 };
+
+// The refusals the _select calls share, in the order of the header: select_args looks at nothing behind the handle (a NULL handle or list, count < 1), select_entries
+// at the handle and the entries (set up, every entry inside [0, batch), and for `unique` calls no instance twice: two workgroups on one arena row would race).
+// Both before any device call; PQ_OK or the failure.
+static int select_args(const char* fn, const pq_batch* s, const int* idx, int count)
+{
+    if (!s) return fail(PQ_ERR_INVALID, "%s: null handle", fn);
+    if (!idx) return fail(PQ_ERR_INVALID, "%s: idx is null", fn);
+    if (count < 1) return fail(PQ_ERR_INVALID, "%s: count = %d, count >= 1 wanted", fn, count);
+    return PQ_OK;
+}
+static int select_entries(const char* fn, const pq_batch* s, const int* idx, int count, bool unique)
+{
+    if (!s->impl->is_set_up()) return fail(PQ_ERR_INVALID, "%s: the handle has no problem (no setup yet)", fn);
+    const int batch = s->impl->batch();
+    for (int j = 0; j < count; ++j)
+        if (idx[j] < 0 || idx[j] >= batch) return fail(PQ_ERR_INVALID, "%s: idx[%d] = %d outside [0, %d)", fn, j, idx[j], batch);
+    if (unique) {
+        std::vector<int> at((size_t)batch, -1);
+        for (int j = 0; j < count; ++j) {
+            if (at[(size_t)idx[j]] >= 0) return fail(PQ_ERR_INVALID, "%s: idx[%d] = %d is listed twice (idx[%d] too)", fn, j, idx[j], at[(size_t)idx[j]]);
+            at[(size_t)idx[j]] = j;
+        }
+    }
+    return PQ_OK;
+}
 
 extern "C" {
 
@@ -2840,10 +2984,35 @@ int pq_batch_update_data(pq_batch* s, const double* Px, const double* Ax, const 
 {
     return pq_batch_update_data_mem(s, Px, Ax, Gx, c, b, h_l, h_u, x_l, x_u, PQ_MEM_HOST);
 }
+int pq_batch_update_data_select_mem(pq_batch* s, const int* idx, int count, const double* Px, const double* Ax, const double* Gx, const double* c, const double* b,
+                                    const double* h_l, const double* h_u, const double* x_l, const double* x_u, int mem)
+{
+    const char* fn = "pq_batch_update_data_select_mem";
+    if (int rc = select_args(fn, s, idx, count)) return rc;
+    if (mem != PQ_MEM_HOST && mem != PQ_MEM_DEVICE) return fail(PQ_ERR_INVALID, "%s: mem = %d, PQ_MEM_HOST or PQ_MEM_DEVICE wanted", fn, mem);
+    if (int rc = select_entries(fn, s, idx, count, true)) return rc;
+    return guarded([&] { return s->impl->update_data(Px, Ax, Gx, c, b, h_l, h_u, x_l, x_u, mem, idx, count) ? 1 : 0; });
+}
+int pq_batch_update_select_mem(pq_batch* s, const int* idx, int count, const double* c, const double* b, const double* h_l, const double* h_u, const double* x_l,
+                               const double* x_u, int mem)
+{
+    const char* fn = "pq_batch_update_select_mem";
+    if (int rc = select_args(fn, s, idx, count)) return rc;
+    if (mem != PQ_MEM_HOST && mem != PQ_MEM_DEVICE) return fail(PQ_ERR_INVALID, "%s: mem = %d, PQ_MEM_HOST or PQ_MEM_DEVICE wanted", fn, mem);
+    if (int rc = select_entries(fn, s, idx, count, true)) return rc;
+    return guarded([&] { return s->impl->update_vectors(c, b, h_l, h_u, x_l, x_u, mem, idx, count) ? 1 : 0; });
+}
 int pq_batch_solve(pq_batch* s)
 {
     if (!s) return fail(PQ_ERR_INVALID, "null argument");
     return guarded([&] { return s->impl->solve(); });
+}
+int pq_batch_solve_select(pq_batch* s, const int* idx, int count)
+{
+    const char* fn = "pq_batch_solve_select";
+    if (int rc = select_args(fn, s, idx, count)) return rc;
+    if (int rc = select_entries(fn, s, idx, count, true)) return rc;
+    return guarded([&] { return s->impl->solve_select(idx, count); });
 }
 const pq_info* pq_batch_info(const pq_batch* s, int instance)
 {
@@ -2857,6 +3026,23 @@ int pq_batch_get_result_mem(pq_batch* s, int field, double* out, int mem)
     return guarded([&] { s->impl->get_result(field, out, mem); return (int)PQ_OK; });
 }
 int pq_batch_get_result(pq_batch* s, int field, double* out_host) { return pq_batch_get_result_mem(s, field, out_host, PQ_MEM_HOST); }
+int pq_batch_get_result_select_mem(pq_batch* s, const int* idx, int count, int field, double* out, int mem)
+{
+    const char* fn = "pq_batch_get_result_select_mem";
+    if (int rc = select_args(fn, s, idx, count)) return rc;
+    if (!out) return fail(PQ_ERR_INVALID, "%s: out is null", fn);
+    if (field < 0 || field >= 10) return fail(PQ_ERR_INVALID, "%s: field = %d, 0 .. 9 wanted", fn, field);
+    if (mem != PQ_MEM_HOST && mem != PQ_MEM_DEVICE) return fail(PQ_ERR_INVALID, "%s: mem = %d, PQ_MEM_HOST or PQ_MEM_DEVICE wanted", fn, mem);
+    if (int rc = select_entries(fn, s, idx, count, false)) return rc;
+    return guarded([&] { s->impl->get_result_select(idx, count, field, out, mem); return (int)PQ_OK; });
+}
+int pq_batch_arena_row(const pq_batch* s, int instance, double* out_host)
+{
+    if (!s || !out_host) return fail(PQ_ERR_INVALID, "pq_batch_arena_row: null argument");
+    if (!s->impl->is_set_up()) return fail(PQ_ERR_INVALID, "pq_batch_arena_row: the handle has no problem (no setup yet)");
+    if (instance < 0 || instance >= s->impl->batch()) return fail(PQ_ERR_INVALID, "pq_batch_arena_row: instance %d outside [0, %d)", instance, s->impl->batch());
+    return guarded([&] { s->impl->arena_row(instance, out_host); return (int)PQ_OK; });
+}
 int pq_batch_dims(const pq_batch* s, int* batch, int* n, int* p, int* m)
 {
     if (!s) return fail(PQ_ERR_INVALID, "null argument");

@@ -33,6 +33,9 @@ struct RuizSparseArgs {
     const int* lists = nullptr;
     long long lists_stride = 0, lists_x_l = 0, lists_x_u = 0;
     double* c_scale = nullptr;  // [batch], not strided: the cost scaling c of every instance (out for RUIZ_COMPUTE, in otherwise)
+    // one-workgroup-per-instance launches only: workgroup r equilibrates instance inst_list[r] -- its stride offset, its row of `lists`, its c_scale -- of a larger
+    // arena (`batch` of launch_ruiz_sparse is then the length of the list); null: the identity
+    const int* inst_list = nullptr;
     int mode = RUIZ_COMPUTE, scale_cost = 0, max_iter = 10;
     double eps = 1e-3;
     unsigned long long* grid_ws = nullptr;  // optional, ruiz_grid_ws_words() words: with it a single instance (batch == 1) is equilibrated by a grid of workgroups

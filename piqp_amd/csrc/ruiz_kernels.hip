@@ -128,8 +128,8 @@ __global__ void k_ruiz_sparse(RuizSparseArgs a)
 {
     __shared__ double red[16];
     __shared__ double gsum;
-    const long long o = GRID ? 0 : (long long)blockIdx.x * a.stride;
-    const int inst = GRID ? 0 : (int)blockIdx.x;
+    const int inst = GRID ? 0 : (a.inst_list ? a.inst_list[blockIdx.x] : (int)blockIdx.x);
+    const long long o = (long long)inst * a.stride;
     const int n = a.n, p = a.p, m = a.m, N = n + p + m;
     const int t = GRID ? (int)(blockIdx.x * blockDim.x + threadIdx.x) : (int)threadIdx.x, NT = GRID ? (int)(gridDim.x * blockDim.x) : (int)blockDim.x;
     unsigned long long* ws = a.grid_ws;
