@@ -515,37 +515,44 @@ int pq_batch_set_bound_sets(pq_batch *s, int mode);
 int pq_batch_bound_lists(const pq_batch *s, int instance, int counts[4], int *h_l_idx, int *h_u_idx, int *x_l_idx, int *x_u_idx, int *dropped);
 /* SparseSolver::setup (solver.hpp:1297-1308) per instance.  Patterns (CSC, HOST): P n x n (upper triangle taken),
  * A p x n, G m x n; NULL pattern = absent.  Values / vectors are [batch][nnz] resp. [batch][len] row-major HOST
- * arrays; NULL h_l/h_u/x_l/x_u = nullopt.  Returns 1 when set up.  Forwards to pq_batch_setup_sparse_mem with PQ_MEM_HOST: one HostData per instance
- * on host threads, packed into a staging buffer, the arena copied up in slices. */
+ * arrays; NULL h_l/h_u/x_l/x_u = nullopt.  Returns 1 when set up.  Forwards to pq_batch_setup_sparse_mem with PQ_MEM_HOST: the arrays are uploaded into one
+ * device staging buffer and the setup reads them there. */
 int pq_batch_setup_sparse(pq_batch *s, int batch, int n, int p, int m, const int *Pp, const int *Pi, const double *Px,
                           const double *c, const int *Ap, const int *Ai, const double *Ax, const double *b,
                           const int *Gp, const int *Gi, const double *Gx, const double *h_l, const double *h_u,
                           const double *x_l, const double *x_u);
 /* The same with the problem data in host or device memory (mem; ordering contract: see pq_solver_setup_dense_mem; any other value: PQ_ERR_INVALID, the handle
- * as it was).  PQ_MEM_DEVICE: Px, Ax, Gx and the six vectors are [batch][nnz] / [batch][len] DEVICE arrays on the handle's device; the six index arrays stay HOST
- * memory, as in pq_solver_setup_sparse_mem.  The shared structure is analysed from the patterns -- no analysis reads a value -- and from instance 0's h_l, h_u, x_l,
- * x_u, which are fetched to the host: 8 x (the lengths of those of the four that are given) bytes, 8 (2 m + 2 n) at most, in either bound-set mode.  Nothing else
- * of the problem data comes to the host and none of it crosses host to device: no HostData is built for the instances 1 and up, no staging buffer is filled.  Kernels
- * read the caller's arrays where they are: with shared bound sets the check that every instance has instance 0's finiteness pattern (one flag word comes back; the
- * error text of the host mode), with PQ_BOUND_SETS_PER_INSTANCE the table of every instance's lists (a vector that is not given has no finite entry; a row of G
- * with no finite bound is dropped: in both lists, -1 / 1, its entries of G' zero); then the fill of the zeroed arena -- upper(P), A', G' through the entry maps the
- * updates use, the vectors by the rules of set_h_l / set_h_u, the box vectors packed to the lists, x_b_scaling = 1.  Entries of P below the diagonal are never
- * loaded.  The equilibration and everything after it are the kernels of the host mode on the same bits, so the two modes agree bit for bit; so do the refusals
- * and the state of the handle after one. */
+ * as it was).  Both modes are one setup; they differ in how the data reaches the kernels.  The shared structure is analysed from the patterns -- no analysis reads
+ * a value -- and from instance 0's h_l, h_u, x_l, x_u; no HostData is built for the instances 1 and up.  With shared bound sets every instance must have instance
+ * 0's finiteness pattern ("batch setup: instances differ in which bounds are finite" otherwise); with PQ_BOUND_SETS_PER_INSTANCE a kernel builds the table of
+ * every instance's lists (a vector that is not given has no finite entry; a row of G with no finite bound is dropped: in both lists, -1 / 1, its entries of G'
+ * zero).  Then kernels fill the zeroed arena from [batch][nnz] / [batch][len] device arrays -- upper(P), A', G' through the entry maps the updates use, the vectors
+ * by the rules of set_h_l / set_h_u, the box vectors packed to the lists, x_b_scaling = 1; entries of P below the diagonal are never loaded -- and the
+ * equilibration and prepare kernels follow.  The two modes agree bit for bit; so do the refusals and the state of the handle after one: a setup gives up the
+ * handle's previous problem when it starts, so a handle whose setup was refused has none.
+ * PQ_MEM_DEVICE: Px, Ax, Gx and the six vectors are DEVICE arrays on the handle's device, read where they are; the six index arrays stay HOST memory, as in
+ * pq_solver_setup_sparse_mem.  Instance 0's four bound vectors are fetched to the host: 8 x (the lengths of those of the four that are given) bytes, 8 (2 m + 2 n)
+ * at most, in either bound-set mode.  Nothing else of the problem data comes to the host and none of it crosses host to device; the finiteness check is a kernel
+ * on the caller's arrays (one flag word comes back).
+ * PQ_MEM_HOST: nothing is fetched, instance 0's vectors are the first rows of the caller's arrays, and the finiteness check is a host loop that runs before the call
+ * allocates anything on the device.  The arrays that are given and not empty are then copied into ONE device staging buffer, which the kernels read; it is
+ * released before the call returns, and the call returns only after the copies have read the caller's memory.  Peak device memory of a host-fed setup is so higher
+ * by the size of the caller's data (57 MB beside a 692 MB arena for 8192 MPC QPs); the buffer is allocated before the free-memory check of the sparse_ldlt backend,
+ * which accounts for it. */
 int pq_batch_setup_sparse_mem(pq_batch *s, int batch, int n, int p, int m, const int *Pp, const int *Pi, const double *Px,
                               const double *c, const int *Ap, const int *Ai, const double *Ax, const double *b,
                               const int *Gp, const int *Gi, const double *Gx, const double *h_l, const double *h_u,
                               const double *x_l, const double *x_u, int mem);
 /* Figures of the last setup / update of the handle, computed from the shapes of what the call was given (not counted by the runtime).  out[0] = bytes of problem
- * data moved across the host-device link: host mode 8 x batch x the lengths given (nnz of the matrices as the caller passes them); device mode 0 for an update and
- * the fetch stated at pq_batch_setup_sparse_mem -- device to host -- for a setup.  out[1] = bytes the ingest kernels write into the arena: 8 x batch x (the stored
- * nonzeros of the matrices given + the lengths of the vectors given; a device-mode setup writes both bounds of G and x_b_scaling whatever is given: 2 m + n in place
- * of the lengths of h_l, h_u); box vectors count in full although they are packed to their lists; 0 for a host-mode setup, whose arena is copied up.  A NULL handle
- * or out: PQ_ERR_INVALID, out untouched. */
+ * data moved across the host-device link: host mode 8 x batch x the lengths given (nnz of the matrices as the caller passes them), for a setup -- the upload of
+ * its staging buffer; nothing is fetched -- as for an update; device mode 0 for an update and the fetch stated at pq_batch_setup_sparse_mem -- device to host -- for
+ * a setup.  out[1] = bytes the ingest kernels write into the arena, the same figure in both modes: 8 x batch x (the stored nonzeros of the matrices given + the
+ * lengths of the vectors given; a setup writes both bounds of G and x_b_scaling whatever is given: 2 m + n in place of the lengths of h_l, h_u); box vectors count
+ * in full although they are packed to their lists.  A NULL handle or out: PQ_ERR_INVALID, out untouched. */
 int pq_batch_last_ingest(const pq_batch *s, long long out[2]);
 /* Of the last pq_batch_setup_sparse(_mem) of the handle, milliseconds: out3[0] wall time of the call, out3[1] of it the host analysis (symbolic analysis, entry maps,
- * descriptor and tables), out3[2] device time by the handle's events from the fill of the arena (host mode: the staged copies) to the end of the equilibration and
- * prepare kernels.  Zeros before the first setup and on a clone.  A NULL handle or out3: PQ_ERR_INVALID, out3 untouched. */
+ * descriptor and tables), out3[2] device time by the handle's events from the fill of the arena (host mode: the staged copies, that is from before the upload of the
+ * staging buffer, the host analysis running meanwhile) to the end of the equilibration and prepare kernels.  Zeros before the first setup and on a clone.  A NULL handle or out3: PQ_ERR_INVALID, out3 untouched. */
 int pq_batch_setup_ms(const pq_batch *s, double out3[3]);
 /* update() of every instance with new VECTORS only (solver.hpp:218-308 with every optional matrix empty; the Ruiz scaling of the
  * setup is reused, :283-285).  [batch][len] HOST arrays, NULL = unchanged.  The set of finite bounds is part of the shared

@@ -95,7 +95,8 @@ class BatchSparseSolver(_Handle):
         *_values: [batch, nnz] arrays in that CSC order; vectors: [batch, len].
         If any of the value stacks or vectors is a torch CUDA tensor (float64, on the solver's GPU) the setup reads them all where they are
         (pq_batch_setup_sparse_mem): numpy arguments beside them are moved to the GPU, strided views are made contiguous, torch's current stream is drained.
-        Nothing but instance 0's four bound vectors comes back to the host; the result is bit for bit the host-fed one."""
+        Nothing but instance 0's four bound vectors comes back to the host.  NumPy arguments alone take the same path behind one upload (pq_batch_setup_sparse):
+        the result is the same bit for bit."""
         Pp, Pi, Pm = self._pattern(P_pattern)
         Ap, Ai, Am = self._pattern(A_pattern)
         Gp, Gi, Gm = self._pattern(G_pattern)
@@ -128,13 +129,15 @@ class BatchSparseSolver(_Handle):
 
     def last_ingest(self):
         """of the last setup / update, from the shapes (pq_batch_last_ingest): dict(link_bytes -- problem data moved across the host-device link: 8 x batch x the
-        lengths given in a host call, 0 in a device update, the fetch of instance 0's bound vectors in a device setup --, kernel_bytes -- written by the ingest kernels)"""
+        lengths given in a host call (a setup included: the upload of its staging buffer), 0 in a device update, the fetch of instance 0's bound vectors in a device
+        setup --, kernel_bytes -- written into the arena by the ingest kernels: the same figure for a host and a device call of the same data)"""
         o = np.zeros(2, dtype=np.int64)
         check(self.L.pq_batch_last_ingest(self.h, o.ctypes.data), "pq_batch_last_ingest")
         return dict(link_bytes=int(o[0]), kernel_bytes=int(o[1]))
 
     def setup_ms(self):
-        """of the last setup(): dict(wall_ms, analysis_ms -- host: symbolic analysis, maps, tables --, device_ms -- arena fill, equilibration, prepare)"""
+        """of the last setup(): dict(wall_ms, analysis_ms -- host: symbolic analysis, maps, tables --, device_ms -- arena fill, equilibration, prepare; from host
+        arrays the interval starts before their upload into the staging buffer)"""
         o = np.zeros(3)
         check(self.L.pq_batch_setup_ms(self.h, o.ctypes.data), "pq_batch_setup_ms")
         return dict(wall_ms=float(o[0]), analysis_ms=float(o[1]), device_ms=float(o[2]))

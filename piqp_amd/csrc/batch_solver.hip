@@ -19,8 +19,9 @@
 // read in place of the shared lists and which k_batch_bound_lists rewrites at an update.
 // pq_batch_clone / pq_batch_clone_select make a second handle from a set-up one without a new setup, whole or by a list of instances: the structure is shared by
 // reference count, the per-instance rows are gathered by k_batch_gather_rows (the clone constructor of BatchSolver).
-// pq_batch_setup_sparse_mem with PQ_MEM_DEVICE sets a handle up from value stacks and vectors in device memory (setup_from_device): the structure from the patterns and
-// instance 0's bound vectors, the arena filled by k_batch_setup_ingest, no HostData for the other instances and no staging; from the arena on it is the host-fed setup.
+// pq_batch_setup_sparse_mem sets a handle up from value stacks and vectors in host or device memory by one path (BatchSolver::setup): the structure from the patterns
+// and instance 0's bound vectors, the arena filled by k_batch_setup_ingest from device arrays -- the caller's, or one staged copy of the host arrays --, no HostData for
+// the other instances.
 #include <algorithm>
 #include <cfloat>
 #include <chrono>
@@ -29,7 +30,6 @@
 #include <cstdio>
 #include <memory>
 #include <stdexcept>
-#include <thread>
 #include <type_traits>
 
 #include "ingest_kernels.hpp"
@@ -1429,8 +1429,9 @@ __device__ __forceinline__ void batch_assign(const BatchShared& S, double* __res
     if (SETUP) for (int i = t; i < n; i += NT) base[S.off[D_XBS] + i] = 1.0;
 }
 __global__ void k_batch_assign(const BatchShared* __restrict__ Sp, double* __restrict__ arena, BatchAssignArgs a) { batch_assign<false>(*Sp, arena, a); }
-// pq_batch_setup_sparse_mem, device mode: what pack_instance copies out of an instance's HostData, taken from the caller's [batch][nnz] / [batch][len] device arrays
-// where they are (one workgroup per instance, consecutive lanes on consecutive entries of its row of each array) into the zeroed arena
+// pq_batch_setup_sparse_mem: the data slots of an instance's arena row -- upper(P), A', G' without the entries of dropped rows, c, b, the bounds of G, the packed box
+// vectors, x_b_scaling -- from the [batch][nnz] / [batch][len] device arrays (the caller's where they are, or the staged copy of host arrays), one workgroup per
+// instance, consecutive lanes on consecutive entries of its row of each array, into the zeroed arena
 __global__ void k_batch_setup_ingest(const BatchShared* __restrict__ Sp, double* __restrict__ arena, BatchAssignArgs a) { batch_assign<true>(*Sp, arena, a); }
 
 // PQ_BOUND_SETS_PER_INSTANCE, before the two kernels above at every update that gives a bound vector: the lists the reference would hold after the call (the rules
@@ -1438,8 +1439,8 @@ __global__ void k_batch_setup_ingest(const BatchShared* __restrict__ Sp, double*
 // where they are; a vector that is not given (null) keeps the stored finiteness, a row dropped earlier being in both lists.  Ascending lists by an order-preserving
 // compaction: a ballot per 64 entries and the count of set bits below the lane.  Rows that lose their last finite bound get -1 / 1 (times the row's scaling where the
 // arena holds scaled data) and have their entries of G' zeroed, in the arena and (multistage backend) in the grouped-row arena the KKT assembly reads.
-// SETUP (a device-fed setup, on a zeroed table and arena): there is no stored finiteness, a vector that is not given has no finite entry -- the table build_bound_table
-// makes from the instances' HostData.
+// SETUP (on a zeroed table and arena): there is no stored finiteness, a vector that is not given has no finite entry; the lists are the indices of an instance's finite
+// bounds in ascending order, a row of G without one in both.
 template <bool SETUP>
 __global__ __launch_bounds__(64) void k_batch_bound_lists(const BatchShared* __restrict__ Sp, double* __restrict__ arena, int* __restrict__ tab, const double* __restrict__ h_l,
                                                           const double* __restrict__ h_u, const double* __restrict__ x_l, const double* __restrict__ x_u, int scaled, int grouped,
@@ -1698,7 +1699,10 @@ public:
     int p() const { return p_; }
     int m() const { return m_; }
 
-    // SparseSolver::setup (solver.hpp:1297-1308) for every instance; patterns shared (host), values [batch][nnz] / [batch][len] in host or device memory
+    // SparseSolver::setup (solver.hpp:1297-1308) for every instance; patterns shared (host), values [batch][nnz] / [batch][len] in host or device memory.  One path:
+    // the structure comes from the patterns and instance 0's four bound vectors, which are the only problem data the host reads -- no HostData for the other
+    // instances --, and kernels on device arrays do the rest: the bound check / the table of lists, the fill of the zeroed arena, equilibration and prepare.  Host
+    // arrays are uploaded into one staging buffer first and read there.
     bool setup(int batch, int n, int p, int m, const int* Pp, const int* Pi, const double* Px, const double* c, const int* Ap, const int* Ai, const double* Ax, const double* b,
                const int* Gp, const int* Gi, const double* Gx, const double* h_l, const double* h_u, const double* x_l, const double* x_u, int mem = PQ_MEM_HOST)
     {
@@ -1708,11 +1712,103 @@ public:
             throw std::runtime_error("batch mode: kkt_solver must be sparse_multistage, sparse_ldlt or sparse_ldlt_exact");
         ldlt_ = settings_.kkt_solver != PQ_SPARSE_MULTISTAGE;
         per_inst_ = bound_sets_ == PQ_BOUND_SETS_PER_INSTANCE;
+        const bool device = mem == PQ_MEM_DEVICE;
         PQ_HIP(hipSetDevice(dev_));
-        batch_ = batch;
+        setup_done_ = false;  // the problem of the setup before is given up here: a refusal further down leaves a handle without one
         setup_ms_[1] = 0.0;
-        if (mem == PQ_MEM_DEVICE) setup_from_device(batch, n, p, m, Pp, Pi, Px, c, Ap, Ai, Ax, b, Gp, Gi, Gx, h_l, h_u, x_l, x_u);
-        else setup_from_host(batch, n, p, m, Pp, Pi, Px, c, Ap, Ai, Ax, b, Gp, Gi, Gx, h_l, h_u, x_l, x_u);
+        // ---- absent arguments: no pattern, no matrix; an array of length 0 is not given ----
+        if (!Ap) p = 0;
+        if (!Gp) m = 0;
+        batch_ = batch; n_ = n; p_ = p; m_ = m;
+        const int nzP = Pp[n], nzA = Ap ? Ap[n] : 0, nzG = Gp ? Gp[n] : 0;
+        const double* v[N_IN] = {Px, Ax, Gx, c, b, h_l, h_u, x_l, x_u};
+        const int len[N_IN] = {nzP, nzA, nzG, n, p, m, m, n, n};
+        for (int k = 0; k < N_IN; ++k) if (len[k] <= 0) v[k] = nullptr;
+        // ---- instance 0's bound vectors: the shared lists (or, with lists per instance, the fallbacks they size) and the finiteness every instance must share ----
+        // (host arrays: their first rows; device arrays: fetched, the only problem data that comes to the host)
+        Vec fetch[4];
+        const double* v0[4] = {v[IN_HL], v[IN_HU], v[IN_XL], v[IN_XU]};
+        const int vlen[4] = {m, m, n, n};
+        long long fetched = 0;
+        if (device) {
+            for (int k = 0; k < 4; ++k) {
+                if (!v0[k]) continue;
+                fetch[k].resize((size_t)vlen[k]);
+                PQ_HIP(hipMemcpyAsync(fetch[k].data(), v0[k], sizeof(double) * (size_t)vlen[k], hipMemcpyDeviceToHost, st_));
+                v0[k] = fetch[k].data();
+                fetched += 8LL * vlen[k];
+            }
+            stream_wait(st_);
+        }
+        std::vector<char>* fin[4] = {&fin_hl_, &fin_hu_, &fin_xl_, &fin_xu_};
+        for (int k = 0; k < 4; ++k) {
+            fin[k]->assign((size_t)vlen[k], 0);
+            if (v0[k]) for (int i = 0; i < vlen[k]; ++i) (*fin[k])[(size_t)i] = (k % 2 == 0) ? v0[k][i] > -1e30 : v0[k][i] < 1e30;
+        }
+        // ---- shared bound sets: every instance has instance 0's pattern (host arrays: checked before the call allocates anything on the device) ----
+        const char* differ = "batch setup: instances differ in which bounds are finite";
+        if (!per_inst_ && !device) check_patterns(differ, v[IN_HL], v[IN_HU], v[IN_XL], v[IN_XU], batch);
+        // (the device copies of the four patterns and the flag word: the ones the updates check against later, in the set of index arrays of this setup)
+        sbufs_ = std::make_shared<StructBufs>();  // (a clone may still hold the set of the last setup)
+        sbufs_->i.reserve(64); sbufs_->l.reserve(16);
+        fin_hl_d_ = up(sbufs_->i, finite_as_int(fin_hl_)); fin_hu_d_ = up(sbufs_->i, finite_as_int(fin_hu_));
+        fin_xl_d_ = up(sbufs_->i, finite_as_int(fin_xl_)); fin_xu_d_ = up(sbufs_->i, finite_as_int(fin_xu_));
+        fin_flag_.alloc(1);
+        if (!per_inst_ && device) check_patterns_device(differ, v[IN_HL], v[IN_HU], v[IN_XL], v[IN_XU], batch);
+        // ---- host arrays: one staging buffer on the device, released when the call returns; from here on every pointer in v is a device pointer ----
+        DBuf<double> stage;
+        if (!device) {
+            size_t total = 0, at = 0;
+            for (int k = 0; k < N_IN; ++k) if (v[k]) total += (size_t)batch * len[k];
+            stage.alloc(total);
+            PQ_HIP(hipEventRecord(ev0_, st_));
+            for (int k = 0; k < N_IN; ++k) {
+                if (!v[k]) continue;
+                const size_t cnt = (size_t)batch * len[k];
+                PQ_HIP(hipMemcpyAsync(stage.p + at, v[k], sizeof(double) * cnt, hipMemcpyHostToDevice, st_));
+                v[k] = stage.p + at;
+                at += cnt;
+            }
+            stream_wait(st_);  // the caller's memory has been read
+        }
+        // ---- the shared structure reads no value: instance 0's HostData from the patterns and placeholder values ----
+        const auto a0 = std::chrono::steady_clock::now();
+        const Vec ones((size_t)std::max({nzP, nzA, nzG, 1}), 1.0);
+        const auto d0 = make_sparse_host_data(n, p, m, Pp, Pi, ones.data(), nullptr, Ap, Ai, Ap ? ones.data() : nullptr, nullptr, Gp, Gi, Gp ? ones.data() : nullptr, v0[0], v0[1],
+                                              v0[2], v0[3]);
+        analyse_structure(*d0, Pp, Pi, Ap, Ai, Gp, Gi, v0[0], v0[1], v0[2], v0[3]);
+        if (per_inst_) {
+            const long long R = bl_row_ints(n_, m_);
+            bl_tab_.alloc((size_t)R * batch);
+            bl_tab_.zero(st_);
+            shared_h_.bl_tab = bl_tab_.p;
+            shared_h_.bl_stride = R;
+            PQ_HIP(hipMemcpyAsync(shared_.p, &shared_h_, sizeof(BatchShared), hipMemcpyHostToDevice, st_));
+            stream_wait(st_);
+        }
+        setup_ms_[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a0).count();
+        // ---- per-instance arena (zeroed) and what goes with it ----
+        alloc_instance_buffers(batch, "setup");
+        arena_.zero(st_);
+        identity_order();
+        sel_ = DBuf<int>();  // (of the batch before: the next _select call makes one for this batch)
+        if (device) PQ_HIP(hipEventRecord(ev0_, st_));
+        if (per_inst_) {
+            hipLaunchKernelGGL(k_batch_bound_lists<true>, dim3(batch), dim3(64), 0, st_, shared_.p, arena_.p, bl_tab_.p, v[IN_HL], v[IN_HU], v[IN_XL], v[IN_XU], 0, 0, (const int*)nullptr);
+            PQ_HIP(hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_batch_setup_ingest, dim3(batch), dim3(128), 0, st_, shared_.p, arena_.p, assign_args(v, nullptr));
+        PQ_HIP(hipGetLastError());
+        // measurement aid (tools/batch_setup_timing.py): the device time of pq_batch_setup_ms ends here, after the ingest kernels, instead of after prepare
+        const bool ingest_only = debug_token("batch_setup_ms_ingest") != nullptr;
+        if (ingest_only) PQ_HIP(hipEventRecord(ev1_, st_));
+        note_ingest(mem, true, v, fetched, batch);
+        // RuizEquilibration::scale_data of every instance (sparse/preconditioner.hpp:65-222) in one launch, then the front arenas
+        launch_ruiz(RUIZ_COMPUTE);
+        if (!ldlt_) launch_prepare();
+        if (!ingest_only) PQ_HIP(hipEventRecord(ev1_, st_));
+        stream_wait(st_);
+        setup_done_ = true;
         float ms = 0.f;
         PQ_HIP(hipEventElapsedTime(&ms, ev0_, ev1_));
         setup_ms_[2] = ms;
@@ -1721,81 +1817,14 @@ public:
     }
 
 private:
-    // Host memory: one HostData per instance on host threads, packed into a staging buffer and copied up in slices
-    void setup_from_host(int batch, int n, int p, int m, const int* Pp, const int* Pi, const double* Px, const double* c, const int* Ap, const int* Ai, const double* Ax,
-                         const double* b, const int* Gp, const int* Gi, const double* Gx, const double* h_l, const double* h_u, const double* x_l, const double* x_u)
-    {
-        const bool per_inst = per_inst_;
-        const int nzP = Pp[n], nzA = Ap ? Ap[n] : 0, nzG = Gp ? Gp[n] : 0;
-        // ---- which bounds are finite is part of the shared structure: the caller's pattern must be the same in every instance ----
-        // (PQ_BOUND_SETS_PER_INSTANCE: nothing is refused, every instance keeps the lists make_sparse_host_data builds for it; the vectors below are then instance
-        // 0's and only size the shared fallbacks)
-        auto finite_pattern = [&](const double* v, int len, bool lower, std::vector<char>& out) {
-            out.assign(len, 0);
-            if (!v) return;
-            for (int i = 0; i < len; ++i) out[i] = lower ? v[i] > -1e30 : v[i] < 1e30;
-            for (int q = 1; q < batch && !per_inst; ++q)
-                for (int i = 0; i < len; ++i)
-                    if ((lower ? v[(size_t)q * len + i] > -1e30 : v[(size_t)q * len + i] < 1e30) != (out[i] != 0)) throw std::runtime_error("batch setup: instances differ in which bounds are finite");
-        };
-        finite_pattern(Gp ? h_l : nullptr, Gp ? m : 0, true, fin_hl_); finite_pattern(Gp ? h_u : nullptr, Gp ? m : 0, false, fin_hu_);
-        finite_pattern(x_l, n, true, fin_xl_); finite_pattern(x_u, n, false, fin_xu_);
-        // ---- per-instance Data on the host (transposes, bound lists; the instances are independent: one host thread per slice) ----
-        std::vector<std::unique_ptr<HostData>> data(batch);
-        auto build = [&](int lo, int hi) {
-            for (int i = lo; i < hi; ++i) {
-                data[i] = make_sparse_host_data(n, p, m, Pp, Pi, Px + (size_t)i * nzP, c + (size_t)i * n, Ap, Ai, Ax ? Ax + (size_t)i * nzA : nullptr, b ? b + (size_t)i * p : nullptr,
-                                                Gp, Gi, Gx ? Gx + (size_t)i * nzG : nullptr, h_l ? h_l + (size_t)i * m : nullptr, h_u ? h_u + (size_t)i * m : nullptr,
-                                                x_l ? x_l + (size_t)i * n : nullptr, x_u ? x_u + (size_t)i * n : nullptr);
-            }
-        };
-        {
-            const int nthreads = std::max(1, std::min<int>(batch, (int)std::thread::hardware_concurrency()));
-            std::vector<std::thread> pool;
-            std::vector<std::exception_ptr> errs(nthreads);
-            for (int t = 0; t < nthreads; ++t) {
-                const int lo = (int)((long long)batch * t / nthreads), hi = (int)((long long)batch * (t + 1) / nthreads);
-                pool.emplace_back([&, t, lo, hi] { try { build(lo, hi); } catch (...) { errs[t] = std::current_exception(); } });
-            }
-            for (auto& th : pool) th.join();
-            for (auto& e : errs) if (e) std::rethrow_exception(e);
-        }
-        const HostData& d0 = *data[0];
-        for (int i = 1; i < batch; ++i) {
-            const HostData& d = *data[i];
-            const bool same = d.n_h_l == d0.n_h_l && d.n_h_u == d0.n_h_u && d.n_x_l == d0.n_x_l && d.n_x_u == d0.n_x_u &&
-                              std::equal(d.h_l_idx.begin(), d.h_l_idx.begin() + d.n_h_l, d0.h_l_idx.begin()) &&
-                              std::equal(d.h_u_idx.begin(), d.h_u_idx.begin() + d.n_h_u, d0.h_u_idx.begin()) &&
-                              std::equal(d.x_l_idx.begin(), d.x_l_idx.begin() + d.n_x_l, d0.x_l_idx.begin()) &&
-                              std::equal(d.x_u_idx.begin(), d.x_u_idx.begin() + d.n_x_u, d0.x_u_idx.begin());
-            if (!same && !per_inst) throw std::runtime_error("batch setup: instances differ in which bounds are finite");
-        }
-        const auto a0 = std::chrono::steady_clock::now();
-        analyse_structure(d0, n, p, m, Pp, Pi, c, Ap, Ai, b, Gp, Gi, h_l, h_u, x_l, x_u, nullptr);
-        if (per_inst) build_bound_table(data, m_ > 0 ? h_l : nullptr, m_ > 0 ? h_u : nullptr);
-        setup_ms_[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a0).count();
-        alloc_instance_buffers(batch);
-        PQ_HIP(hipEventRecord(ev0_, st_));
-        std::vector<double> stage((size_t)layout_.stride * std::min(batch, STAGE_INST));
-        for (int i0 = 0; i0 < batch; i0 += STAGE_INST) {
-            const int cnt = std::min(STAGE_INST, batch - i0);
-            std::fill(stage.begin(), stage.begin() + (size_t)layout_.stride * cnt, 0.0);
-            for (int k = 0; k < cnt; ++k) pack_instance(*data[i0 + k], stage.data() + (size_t)layout_.stride * k);
-            PQ_HIP(hipMemcpyAsync(arena_.p + (size_t)layout_.stride * i0, stage.data(), sizeof(double) * (size_t)layout_.stride * cnt, hipMemcpyHostToDevice, st_));
-            stream_wait(st_);
-        }
-        note_ingest(PQ_MEM_HOST, true, Px, Ap ? Ax : nullptr, Gp ? Gx : nullptr, c, Ap ? b : nullptr, Gp ? h_l : nullptr, Gp ? h_u : nullptr, x_l, x_u, 0);
-        scale_and_prepare();
-    }
+    // The arrays of a setup or an update, in the order of the C ABI's arguments
+    enum { IN_PX, IN_AX, IN_GX, IN_C, IN_B, IN_HL, IN_HU, IN_XL, IN_XU, N_IN };
 
     // The part of a setup that reads no value: the symbolic analysis of the backend, the descriptor and the layout of the arena, the update maps.  d0: instance 0's
-    // HostData (its patterns and bound lists are read); c .. x_u: host vectors of instance 0 for the probe of build_update_maps, c and b may be null.
-    // fin_ready: see build_update_maps.
-    void analyse_structure(const HostData& d0, int n, int p, int m, const int* Pp, const int* Pi, const double* c, const int* Ap, const int* Ai, const double* b, const int* Gp,
-                           const int* Gi, const double* h_l, const double* h_u, const double* x_l, const double* x_u, std::vector<DBuf<int>>* fin_ready)
+    // HostData (its patterns and bound lists are read); h_l .. x_u: host vectors of instance 0 for the probe of build_update_maps.
+    void analyse_structure(const HostData& d0, const int* Pp, const int* Pi, const int* Ap, const int* Ai, const int* Gp, const int* Gi, const double* h_l, const double* h_u,
+                           const double* x_l, const double* x_u)
     {
-        n_ = d0.n; p_ = d0.p; m_ = d0.m;
-        fin_hl_.resize(m_, 0); fin_hu_.resize(m_, 0);
         // ---- shared structure ----
         pq_sparse_data desc = d0.sparse_descriptor();
         if (ldlt_) {
@@ -1811,130 +1840,55 @@ private:
             multistage::analyse(&desc, sym_);
         }
         build_shared(d0);
-        build_update_maps(n, p, m, Pp, Pi, c, Ap, Ai, b, Gp, Gi, h_l, h_u, x_l, x_u, d0, fin_ready);
+        build_update_maps(Pp, Pi, Ap, Ai, Gp, Gi, h_l, h_u, x_l, x_u, d0);
         bl_tab_ = DBuf<int>();
     }
-    // ---- per-instance arena (zeroed) and what goes with it ----
-    void alloc_instance_buffers(int batch)
+    // The device buffers that hold one entry per instance, for a setup or a clone (`call`, for the text) of `count` instances; the sparse_ldlt arena grows with
+    // nnz(L), so its size is held against the free memory first.  Nothing is written: the arena is zeroed by a setup and gathered by a clone.
+    void alloc_instance_buffers(int count, const char* call)
     {
         if (ldlt_) {
             size_t free_b = 0, total_b = 0;
-            const double need = (double)layout_.stride * batch * sizeof(double);
+            const double need = (double)layout_.stride * count * sizeof(double);
             if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > 0.9 * (double)free_b)
-                throw std::runtime_error("batch setup: sparse_ldlt backend: the arena of " + std::to_string(batch) + " instances needs " + std::to_string(need / 1e9) +
-                                         " GB of device memory, " + std::to_string((double)free_b / 1e9) + " GB free");
+                throw std::runtime_error(std::string("batch ") + call + ": sparse_ldlt backend: the arena of " + std::to_string(count) + " instances needs " +
+                                         std::to_string(need / 1e9) + " GB of device memory, " + std::to_string((double)free_b / 1e9) + " GB free");
         }
-        arena_.alloc((size_t)layout_.stride * batch);
-        arena_.zero(st_);
-        ruiz_c_.alloc(batch);
-        infos_.alloc(batch);
-        order_.alloc(batch);
-        order_h_.resize((size_t)batch);
-        for (int i = 0; i < batch; ++i) order_h_[(size_t)i] = i;
-        PQ_HIP(hipMemcpyAsync(order_.p, order_h_.data(), sizeof(int) * (size_t)batch, hipMemcpyHostToDevice, st_));
-        prof_.alloc((size_t)batch * NPROF);
-        infos_h_.resize(batch);
-        sel_ = DBuf<int>();  // (of the batch before: the next _select call makes one for this batch)
+        arena_.alloc((size_t)layout_.stride * count);
+        ruiz_c_.alloc(count);
+        infos_.alloc(count);
+        order_.alloc(count);
+        order_h_.resize((size_t)count);
+        prof_.alloc((size_t)count * NPROF);
+        infos_h_.resize((size_t)count);
     }
-    // RuizEquilibration::scale_data of every instance (sparse/preconditioner.hpp:65-222) in one launch, then the front arenas
-    void scale_and_prepare(bool record_end = true)
+    // order_ = the identity: the start order before the first solve, and whenever the longest-first order is off
+    void identity_order()
     {
-        launch_ruiz(RUIZ_COMPUTE);
-        if (!ldlt_) launch_prepare();
-        if (record_end) PQ_HIP(hipEventRecord(ev1_, st_));
-        stream_wait(st_);
-        setup_done_ = true;
+        for (int i = 0; i < batch_; ++i) order_h_[(size_t)i] = i;
+        PQ_HIP(hipMemcpyAsync(order_.p, order_h_.data(), sizeof(int) * (size_t)batch_, hipMemcpyHostToDevice, st_));
     }
-    // pq_batch_last_ingest, from the shapes of what the call was given (null: not given, or of length 0).  fetched: the bytes a device-fed setup brought to the host.
-    void note_ingest(int mem, bool is_setup, const double* Px, const double* Ax, const double* Gx, const double* c, const double* b, const double* h_l, const double* h_u,
-                     const double* x_l, const double* x_u, long long fetched, int rows = -1)
+    // k_batch_setup_ingest / k_batch_assign: the maps of the setup and the caller's arrays (device; null: not given)
+    BatchAssignArgs assign_args(const double* const v[N_IN], const int* list) const
     {
-        if (rows < 0) rows = batch_;  // (an update by list: the rows given)
-        const long long vec = (c ? n_ : 0) + (b ? p_ : 0) + (x_l ? n_ : 0) + (x_u ? n_ : 0);
-        const long long given = (Px ? nzP_in_ : 0) + (Ax ? nzA_in_ : 0) + (Gx ? nzG_in_ : 0) + vec + ((h_l ? 1 : 0) + (h_u ? 1 : 0)) * (long long)m_;
-        const long long written = (Px ? shared_h_.nzP : 0) + (Ax ? shared_h_.nzA : 0) + (Gx ? shared_h_.nzG : 0) + vec +
-                                  (is_setup ? 2LL * m_ + n_ : ((h_l ? 1 : 0) + (h_u ? 1 : 0)) * (long long)m_);
-        ingest_[0] = mem == PQ_MEM_DEVICE ? fetched : 8LL * rows * given;
-        ingest_[1] = is_setup && mem != PQ_MEM_DEVICE ? 0 : 8LL * rows * written;
-    }
-
-    // Device memory: the structure from the patterns and instance 0's four bound vectors -- the only problem data that comes to the host --, no HostData for the other
-    // instances and no staging: the bound check / the table of lists and the fill of the zeroed arena are kernels on the caller's arrays.  From the arena on, the
-    // setup is the host-fed one: the same Ruiz and prepare kernels on the same bits.
-    void setup_from_device(int batch, int n, int p, int m, const int* Pp, const int* Pi, const double* Px, const double* c, const int* Ap, const int* Ai, const double* Ax,
-                           const double* b, const int* Gp, const int* Gi, const double* Gx, const double* h_l, const double* h_u, const double* x_l, const double* x_u)
-    {
-        const bool per_inst = per_inst_;
-        const int nzP = Pp[n], nzA = Ap ? Ap[n] : 0, nzG = Gp ? Gp[n] : 0;
-        if (!Ap) { Ax = nullptr; b = nullptr; }
-        if (!Gp) { Gx = nullptr; h_l = nullptr; h_u = nullptr; m = 0; }
-        if (m <= 0) { h_l = nullptr; h_u = nullptr; }
-        // ---- instance 0's bound vectors: the shared lists (or, with lists per instance, the fallbacks they size) and the finiteness every instance must share ----
-        Vec hv[4];
-        const double* dv[4] = {h_l, h_u, x_l, x_u};
-        const double* v0[4] = {nullptr, nullptr, nullptr, nullptr};
-        const int vlen[4] = {m, m, n, n};
-        long long fetched = 0;
-        for (int k = 0; k < 4; ++k) {
-            if (!dv[k]) continue;
-            hv[k].resize((size_t)vlen[k]);
-            PQ_HIP(hipMemcpyAsync(hv[k].data(), dv[k], sizeof(double) * (size_t)vlen[k], hipMemcpyDeviceToHost, st_));
-            v0[k] = hv[k].data();
-            fetched += 8LL * vlen[k];
-        }
-        stream_wait(st_);
-        std::vector<char>* fin[4] = {&fin_hl_, &fin_hu_, &fin_xl_, &fin_xu_};
-        for (int k = 0; k < 4; ++k) {
-            fin[k]->assign((size_t)vlen[k], 0);
-            if (v0[k]) for (int i = 0; i < vlen[k]; ++i) (*fin[k])[(size_t)i] = (k % 2 == 0) ? v0[k][i] > -1e30 : v0[k][i] < 1e30;
-        }
-        // (the device copies of the four patterns and the flag word: the ones the updates check against later, made here instead of in build_update_maps)
-        std::vector<DBuf<int>> fin_d(4);
-        for (int k = 0; k < 4; ++k) upload_vec(fin_d[(size_t)k], finite_as_int(*fin[k]), st_);
-        fin_flag_.alloc(1);
-        if (!per_inst) {
-            PQ_HIP(hipMemsetAsync(fin_flag_.p, 0, sizeof(int), st_));
-            for (int k = 0; k < 4; ++k)
-                if (dv[k]) ingest_check_finite_pattern(dv[k], fin_d[(size_t)k].p, batch, vlen[k], k % 2 == 0, fin_flag_.p, st_);
-            int flag = 0;
-            PQ_HIP(hipMemcpyAsync(&flag, fin_flag_.p, sizeof(int), hipMemcpyDeviceToHost, st_));
-            stream_wait(st_);
-            if (flag) throw std::runtime_error("batch setup: instances differ in which bounds are finite");
-        }
-        // ---- the shared structure reads no value: instance 0's HostData from the patterns and placeholder values ----
-        const auto a0 = std::chrono::steady_clock::now();
-        const Vec ones((size_t)std::max({nzP, nzA, nzG, 1}), 1.0);
-        const auto d0 = make_sparse_host_data(n, p, m, Pp, Pi, ones.data(), nullptr, Ap, Ai, Ap ? ones.data() : nullptr, nullptr, Gp, Gi, Gp ? ones.data() : nullptr, v0[0], v0[1],
-                                              v0[2], v0[3]);
-        analyse_structure(*d0, n, p, m, Pp, Pi, nullptr, Ap, Ai, nullptr, Gp, Gi, v0[0], v0[1], v0[2], v0[3], &fin_d);
-        if (per_inst) {
-            const long long R = bl_row_ints(n_, m_);
-            bl_tab_.alloc((size_t)R * batch);
-            bl_tab_.zero(st_);
-            shared_h_.bl_tab = bl_tab_.p;
-            shared_h_.bl_stride = R;
-            PQ_HIP(hipMemcpyAsync(shared_.p, &shared_h_, sizeof(BatchShared), hipMemcpyHostToDevice, st_));
-            stream_wait(st_);
-        }
-        setup_ms_[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a0).count();
-        alloc_instance_buffers(batch);
-        PQ_HIP(hipEventRecord(ev0_, st_));
-        if (per_inst) {
-            hipLaunchKernelGGL(k_batch_bound_lists<true>, dim3(batch), dim3(64), 0, st_, shared_.p, arena_.p, bl_tab_.p, h_l, h_u, x_l, x_u, 0, 0, (const int*)nullptr);
-            PQ_HIP(hipGetLastError());
-        }
         BatchAssignArgs a{};
         a.nzP_in = nzP_in_; a.nzA_in = nzA_in_; a.nzG_in = nzG_in_;
         a.mapP = mapP_; a.mapA = mapA_; a.mapG = mapG_; a.disabled = disabled_d_; a.Grow = Grow_;
-        a.Px = nzP_in_ > 0 ? Px : nullptr; a.Ax = nzA_in_ > 0 ? Ax : nullptr; a.Gx = nzG_in_ > 0 ? Gx : nullptr;
-        a.c = c; a.b = p_ > 0 ? b : nullptr; a.h_l = h_l; a.h_u = h_u; a.x_l = x_l; a.x_u = x_u;
-        hipLaunchKernelGGL(k_batch_setup_ingest, dim3(batch), dim3(128), 0, st_, shared_.p, arena_.p, a);
-        PQ_HIP(hipGetLastError());
-        // measurement aid (tools/batch_setup_timing.py): the device time of pq_batch_setup_ms ends here, after the ingest kernels, instead of after prepare
-        const bool ingest_only = debug_token("batch_setup_ms_ingest") != nullptr;
-        if (ingest_only) PQ_HIP(hipEventRecord(ev1_, st_));
-        note_ingest(PQ_MEM_DEVICE, true, a.Px, a.Ax, a.Gx, a.c, a.b, a.h_l, a.h_u, a.x_l, a.x_u, fetched);
-        scale_and_prepare(!ingest_only);
+        a.Px = v[IN_PX]; a.Ax = v[IN_AX]; a.Gx = v[IN_GX];
+        a.c = v[IN_C]; a.b = v[IN_B]; a.h_l = v[IN_HL]; a.h_u = v[IN_HU]; a.x_l = v[IN_XL]; a.x_u = v[IN_XU];
+        a.list = list;
+        return a;
+    }
+    // pq_batch_last_ingest, from the shapes of what the call was given (v: null where an array is not given, or of length 0) for `rows` instances.  fetched: the
+    // bytes a device-fed setup brought to the host.
+    void note_ingest(int mem, bool is_setup, const double* const v[N_IN], long long fetched, int rows)
+    {
+        const long long vec = (v[IN_C] ? n_ : 0) + (v[IN_B] ? p_ : 0) + (v[IN_XL] ? n_ : 0) + (v[IN_XU] ? n_ : 0);
+        const long long hs = ((v[IN_HL] ? 1 : 0) + (v[IN_HU] ? 1 : 0)) * (long long)m_;
+        const long long given = (v[IN_PX] ? nzP_in_ : 0) + (v[IN_AX] ? nzA_in_ : 0) + (v[IN_GX] ? nzG_in_ : 0) + vec + hs;
+        const long long written = (v[IN_PX] ? shared_h_.nzP : 0) + (v[IN_AX] ? shared_h_.nzA : 0) + (v[IN_GX] ? shared_h_.nzG : 0) + vec + (is_setup ? 2LL * m_ + n_ : hs);
+        ingest_[0] = mem == PQ_MEM_DEVICE ? fetched : 8LL * rows * given;
+        ingest_[1] = 8LL * rows * written;
     }
 
 public:
@@ -1948,17 +1902,7 @@ public:
             return 0;
         }
         PQ_HIP(hipSetDevice(dev_));
-        shared_h_.set = settings_;
-        PQ_HIP(hipMemcpyAsync(shared_.p, &shared_h_, sizeof(BatchShared), hipMemcpyHostToDevice, st_));
-        PQ_HIP(hipEventRecord(ev0_, st_));
-        launch_ipm(batch_, order_.p);
-        PQ_HIP(hipEventRecord(ev1_, st_));
-        PQ_HIP(hipGetLastError());
-        PQ_HIP(hipMemcpyAsync(infos_h_.data(), infos_.p, sizeof(pq_info) * batch_, hipMemcpyDeviceToHost, st_));
-        stream_wait(st_);
-        float ms = 0.f;
-        PQ_HIP(hipEventElapsedTime(&ms, ev0_, ev1_));
-        last_kernel_ms_ = ms;
+        timed_launch(batch_, order_.p, [&] { PQ_HIP(hipMemcpyAsync(infos_h_.data(), infos_.p, sizeof(pq_info) * batch_, hipMemcpyDeviceToHost, st_)); });
         int solved = 0;
         for (const auto& i : infos_h_) solved += i.status == PQ_SOLVED;
         // Start order of the NEXT solve: a batch of more instances than the device holds at once runs as a list of workgroups whose durations follow their
@@ -2001,26 +1945,13 @@ public:
         nzP_in_ = s.nzP_in_; nzA_in_ = s.nzA_in_; nzG_in_ = s.nzG_in_;
         mapP_ = s.mapP_; mapA_ = s.mapA_; mapG_ = s.mapG_; disabled_d_ = s.disabled_d_; rzPp_ = s.rzPp_; rzPi_ = s.rzPi_; Grow_ = s.Grow_;
         last_kernel_ms_ = s.last_kernel_ms_;
-        if (ldlt_) {
-            size_t free_b = 0, total_b = 0;
-            const double need = (double)layout_.stride * count * sizeof(double);
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > 0.9 * (double)free_b)
-                throw std::runtime_error("batch clone: sparse_ldlt backend: the arena of " + std::to_string(count) + " instances needs " + std::to_string(need / 1e9) +
-                                         " GB of device memory, " + std::to_string((double)free_b / 1e9) + " GB free");
-        }
         const long long R = per_inst_ ? bl_row_ints(n_, m_) : 0;
-        arena_.alloc((size_t)layout_.stride * count);
-        ruiz_c_.alloc(count);
-        infos_.alloc(count);
-        order_.alloc(count);
-        prof_.alloc((size_t)count * NPROF);
+        alloc_instance_buffers(count, "clone");
         shared_.alloc(1);
         fin_flag_.alloc(1);
         if (per_inst_) bl_tab_.alloc((size_t)R * count);
         DBuf<int> idx_d((size_t)count);
-        infos_h_.resize((size_t)count);
         for (int j = 0; j < count; ++j) infos_h_[(size_t)j] = s.infos_h_[(size_t)idx[j]];
-        order_h_.resize((size_t)count);
         shared_h_ = s.shared_h_;
         shared_h_.set = settings_;
         shared_h_.bl_tab = per_inst_ ? bl_tab_.p : nullptr;
@@ -2036,10 +1967,7 @@ public:
         PQ_HIP(hipEventRecord(ev1_, st_));
         // the order of the next launch from the gathered infos, as solve() leaves it (the identity before the first solve: the sort is stable)
         if (lpt_ && !debug_token("batch_no_lpt")) longest_first_order();
-        else {
-            for (int i = 0; i < count; ++i) order_h_[(size_t)i] = i;
-            PQ_HIP(hipMemcpyAsync(order_.p, order_h_.data(), sizeof(int) * (size_t)count, hipMemcpyHostToDevice, st_));
-        }
+        else identity_order();
         stream_wait(st_);
         float ms = 0.f;
         PQ_HIP(hipEventElapsedTime(&ms, ev0_, ev1_));
@@ -2060,23 +1988,13 @@ public:
     bool update_vectors(const double* c, const double* b, const double* h_l, const double* h_u, const double* x_l, const double* x_u, int mem = PQ_MEM_HOST,
                         const int* idx = nullptr, int count = 0)
     {
-        if (!setup_done_) throw std::runtime_error("batch solver not set up");
-        PQ_HIP(hipSetDevice(dev_));
-        const int rows = idx ? count : batch_;
-        if (!per_inst_) { if (mem == PQ_MEM_DEVICE) check_patterns_device(h_l, h_u, x_l, x_u, rows); else check_patterns(h_l, h_u, x_l, x_u, rows); }
-        const int* list = idx ? list_to_device(idx, count) : nullptr;
-        DBuf<double> dc, dbv, dhl, dhu, dxl, dxu;
-        auto up = [&](DBuf<double>& d, const double* v, int len) -> const double* {
-            if (!v || len == 0) return nullptr;
-            if (mem == PQ_MEM_DEVICE) return v;
-            d.alloc((size_t)rows * len);
-            PQ_HIP(hipMemcpyAsync(d.p, v, sizeof(double) * (size_t)rows * len, hipMemcpyHostToDevice, st_));
-            return d.p;
-        };
-        const double *pc = up(dc, c, n_), *pb = up(dbv, b, p_), *phl = up(dhl, h_l, m_), *phu = up(dhu, h_u, m_), *pxl = up(dxl, x_l, n_), *pxu = up(dxu, x_u, n_);
-        note_ingest(mem, false, nullptr, nullptr, nullptr, pc, pb, phl, phu, pxl, pxu, 0, rows);
-        launch_bound_lists(phl, phu, pxl, pxu, true, list, rows);
-        hipLaunchKernelGGL(k_batch_update_vectors, dim3(rows), dim3(128), 0, st_, shared_.p, arena_.p, ruiz_c_.p, disabled_d_, pc, pb, phl, phu, pxl, pxu, list);
+        const double* in[N_IN] = {nullptr, nullptr, nullptr, c, b, h_l, h_u, x_l, x_u};
+        UpdateStage u;
+        begin_update(u, in, mem, idx, count);
+        const double* const* v = u.v;
+        launch_bound_lists(v[IN_HL], v[IN_HU], v[IN_XL], v[IN_XU], true, u.list, u.rows);
+        hipLaunchKernelGGL(k_batch_update_vectors, dim3(u.rows), dim3(128), 0, st_, shared_.p, arena_.p, ruiz_c_.p, disabled_d_, v[IN_C], v[IN_B], v[IN_HL], v[IN_HU], v[IN_XL],
+                           v[IN_XU], u.list);
         PQ_HIP(hipGetLastError());
         stream_wait(st_);
         return true;
@@ -2088,32 +2006,15 @@ public:
                      const double* x_u, int mem = PQ_MEM_HOST, const int* idx = nullptr, int count = 0)
     {
         if (!Px && !Ax && !Gx) return update_vectors(c, b, h_l, h_u, x_l, x_u, mem, idx, count);
-        if (!setup_done_) throw std::runtime_error("batch solver not set up");
-        PQ_HIP(hipSetDevice(dev_));
-        const int rows = idx ? count : batch_;
-        if (!per_inst_) { if (mem == PQ_MEM_DEVICE) check_patterns_device(h_l, h_u, x_l, x_u, rows); else check_patterns(h_l, h_u, x_l, x_u, rows); }
-        const int* list = idx ? list_to_device(idx, count) : nullptr;
-        DBuf<double> dP, dA, dG, dc, dbv, dhl, dhu, dxl, dxu;
-        auto up = [&](DBuf<double>& d, const double* v, int len) -> const double* {
-            if (!v || len == 0) return nullptr;
-            if (mem == PQ_MEM_DEVICE) return v;
-            d.alloc((size_t)rows * len);
-            PQ_HIP(hipMemcpyAsync(d.p, v, sizeof(double) * (size_t)rows * len, hipMemcpyHostToDevice, st_));
-            return d.p;
-        };
-        BatchAssignArgs a{};
-        a.nzP_in = nzP_in_; a.nzA_in = nzA_in_; a.nzG_in = nzG_in_;
-        a.mapP = mapP_; a.mapA = mapA_; a.mapG = mapG_; a.disabled = disabled_d_; a.Grow = Grow_;
-        a.Px = up(dP, Px, nzP_in_); a.Ax = up(dA, Ax, nzA_in_); a.Gx = up(dG, Gx, nzG_in_);
-        a.c = up(dc, c, n_); a.b = up(dbv, b, p_); a.h_l = up(dhl, h_l, m_); a.h_u = up(dhu, h_u, m_); a.x_l = up(dxl, x_l, n_); a.x_u = up(dxu, x_u, n_);
-        a.list = list;
-        note_ingest(mem, false, a.Px, a.Ax, a.Gx, a.c, a.b, a.h_l, a.h_u, a.x_l, a.x_u, 0, rows);
-        launch_ruiz(RUIZ_UNSCALE, list, rows);  // (with the lists as they stood: the box vectors are packed to them)
-        launch_bound_lists(a.h_l, a.h_u, a.x_l, a.x_u, false, list, rows);
-        hipLaunchKernelGGL(k_batch_assign, dim3(rows), dim3(128), 0, st_, shared_.p, arena_.p, a);
+        const double* in[N_IN] = {Px, Ax, Gx, c, b, h_l, h_u, x_l, x_u};
+        UpdateStage u;
+        begin_update(u, in, mem, idx, count);
+        launch_ruiz(RUIZ_UNSCALE, u.list, u.rows);  // (with the lists as they stood: the box vectors are packed to them)
+        launch_bound_lists(u.v[IN_HL], u.v[IN_HU], u.v[IN_XL], u.v[IN_XU], false, u.list, u.rows);
+        hipLaunchKernelGGL(k_batch_assign, dim3(u.rows), dim3(128), 0, st_, shared_.p, arena_.p, assign_args(u.v, u.list));
         PQ_HIP(hipGetLastError());
-        launch_ruiz(settings_.preconditioner_reuse_on_update ? RUIZ_REUSE : RUIZ_COMPUTE, list, rows);
-        if (!ldlt_) launch_prepare(list, rows);
+        launch_ruiz(settings_.preconditioner_reuse_on_update ? RUIZ_REUSE : RUIZ_COMPUTE, u.list, u.rows);
+        if (!ldlt_) launch_prepare(u.list, u.rows);
         stream_wait(st_);
         return true;
     }
@@ -2136,25 +2037,18 @@ public:
         sel_h_.assign(idx, idx + count);
         if (lpt) std::stable_sort(sel_h_.begin(), sel_h_.end(), [&](int a, int b) { return key(a) > key(b); });
         const int* order = list_to_device(sel_h_.data(), count);
-        sync_settings();
-        PQ_HIP(hipEventRecord(ev0_, st_));
-        launch_ipm(count, order);
-        PQ_HIP(hipEventRecord(ev1_, st_));
-        PQ_HIP(hipGetLastError());
         // the listed infos alone reach infos_h_ (the host's infos of the others may differ from the device's: invalid settings are recorded on the host only)
         const bool few = count <= 8;  // (a copy of one pq_info costs about a hundredth of the copy of 8192 of them)
-        if (few) {
-            for (int j = 0; j < count; ++j)
-                PQ_HIP(hipMemcpyAsync(&infos_h_[(size_t)idx[j]], infos_.p + idx[j], sizeof(pq_info), hipMemcpyDeviceToHost, st_));
-        } else {
-            infos_tmp_.resize((size_t)batch_);
-            PQ_HIP(hipMemcpyAsync(infos_tmp_.data(), infos_.p, sizeof(pq_info) * (size_t)batch_, hipMemcpyDeviceToHost, st_));
-        }
-        stream_wait(st_);
+        timed_launch(count, order, [&] {
+            if (few) {
+                for (int j = 0; j < count; ++j)
+                    PQ_HIP(hipMemcpyAsync(&infos_h_[(size_t)idx[j]], infos_.p + idx[j], sizeof(pq_info), hipMemcpyDeviceToHost, st_));
+            } else {
+                infos_tmp_.resize((size_t)batch_);
+                PQ_HIP(hipMemcpyAsync(infos_tmp_.data(), infos_.p, sizeof(pq_info) * (size_t)batch_, hipMemcpyDeviceToHost, st_));
+            }
+        });
         if (!few) for (int j = 0; j < count; ++j) infos_h_[(size_t)idx[j]] = infos_tmp_[(size_t)idx[j]];
-        float ms = 0.f;
-        PQ_HIP(hipEventElapsedTime(&ms, ev0_, ev1_));
-        last_kernel_ms_ = ms;
         int solved = 0;
         for (int j = 0; j < count; ++j) solved += infos_h_[(size_t)idx[j]].status == PQ_SOLVED;
         if (lpt) longest_first_order();
@@ -2172,8 +2066,7 @@ public:
         DBuf<double> stage;
         double* dst = out;
         if (mem != PQ_MEM_DEVICE) { stage.alloc((size_t)count * len); dst = stage.p; }
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        const int cus = compute_units();
         for (int j0 = 0; j0 < count; j0 += batch_) {  // (sel_ holds `batch` entries: a list with repeats goes in slices)
             const int cnt = std::min(batch_, count - j0);
             const int* list = list_to_device(idx + j0, cnt);
@@ -2197,8 +2090,7 @@ public:
         lpt_ = longest_first;
         if (!lpt_ && setup_done_) {
             PQ_HIP(hipSetDevice(dev_));
-            for (int i = 0; i < batch_; ++i) order_h_[(size_t)i] = i;
-            PQ_HIP(hipMemcpyAsync(order_.p, order_h_.data(), sizeof(int) * (size_t)batch_, hipMemcpyHostToDevice, st_));
+            identity_order();
             stream_wait(st_);
         }
     }
@@ -2309,14 +2201,67 @@ public:
     }
 
 private:
-    static constexpr int STAGE_INST = 256;
     static constexpr int LDLT_MAX_N = 8192;  // the single-QP sparse_ldlt takes the reference-order engine up to this size too; y and D in LDS: 128 KB at most
 
-    // Waves per SIMD the MODE_WAVE kernel is launched for, from the batch size (the measurements: build_multistage_shared)
-    static int wave_budget(int batch)
+    // Compute units of the current device (256 where the runtime does not say)
+    static int compute_units()
     {
         int dev = 0, cus = 256;
         if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        return cus;
+    }
+    // The bracket of solve() and solve_select(): the settings as they stand, the interior-point kernel on `grid` workgroups (launch_ipm) between the two events, the
+    // caller's read-back of the infos queued behind it, the wait, and the kernel's time in last_kernel_ms_
+    template <class ReadBack>
+    void timed_launch(int grid, const int* order, ReadBack queue_read_back)
+    {
+        sync_settings();
+        PQ_HIP(hipEventRecord(ev0_, st_));
+        launch_ipm(grid, order);
+        PQ_HIP(hipEventRecord(ev1_, st_));
+        PQ_HIP(hipGetLastError());
+        queue_read_back();
+        stream_wait(st_);
+        float ms = 0.f;
+        PQ_HIP(hipEventElapsedTime(&ms, ev0_, ev1_));
+        last_kernel_ms_ = ms;
+    }
+    // What update_vectors and update_data begin with.  rows: the rows the caller gave (the batch, or the length of the list); list: the list on the device, or null; v: the
+    // arrays as the kernels read them -- the caller's device arrays in place, or host arrays staged as [rows][len] in `own`, which lives until the stream has been
+    // waited for --, null where an array is not given or has length 0.  With shared bound sets the pattern check comes first: for host arrays before anything is allocated.
+    struct UpdateStage {
+        int rows = 0;
+        const int* list = nullptr;
+        const double* v[N_IN] = {};
+        DBuf<double> own[N_IN];
+    };
+    void begin_update(UpdateStage& u, const double* const in[N_IN], int mem, const int* idx, int count)
+    {
+        if (!setup_done_) throw std::runtime_error("batch solver not set up");
+        PQ_HIP(hipSetDevice(dev_));
+        u.rows = idx ? count : batch_;
+        if (!per_inst_) {
+            const char* differs = "batch update: the set of finite bounds differs from the one given at setup";
+            if (mem == PQ_MEM_DEVICE) check_patterns_device(differs, in[IN_HL], in[IN_HU], in[IN_XL], in[IN_XU], u.rows);
+            else check_patterns(differs, in[IN_HL], in[IN_HU], in[IN_XL], in[IN_XU], u.rows);
+        }
+        u.list = idx ? list_to_device(idx, count) : nullptr;
+        const int len[N_IN] = {nzP_in_, nzA_in_, nzG_in_, n_, p_, m_, m_, n_, n_};
+        for (int k = 0; k < N_IN; ++k) {
+            if (!in[k] || len[k] == 0) continue;
+            u.v[k] = in[k];
+            if (mem == PQ_MEM_DEVICE) continue;
+            const size_t cnt = (size_t)u.rows * len[k];
+            u.own[k].alloc(cnt);
+            PQ_HIP(hipMemcpyAsync(u.own[k].p, in[k], sizeof(double) * cnt, hipMemcpyHostToDevice, st_));
+            u.v[k] = u.own[k].p;
+        }
+        note_ingest(mem, false, u.v, 0, u.rows);
+    }
+    // Waves per SIMD the MODE_WAVE kernel is launched for, from the batch size (the measurements: build_multistage_shared)
+    static int wave_budget(int batch)
+    {
+        const int cus = compute_units();
         const long long per_cu = ((long long)batch + cus - 1) / std::max(cus, 1);
         return per_cu <= 8 ? 2 : (per_cu <= 12 ? 3 : 4);
     }
@@ -2340,9 +2285,7 @@ private:
     {
         const long long wpr = (long long)(row_bytes / sizeof(W));
         const long long work = wpr >= GATHER_CHUNK ? count * ((wpr + GATHER_CHUNK - 1) / GATHER_CHUNK) : (count * wpr + GATHER_THREADS - 1) / GATHER_THREADS;
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        const long long cap = 8LL * std::max(cus, 1);
+        const long long cap = 8LL * std::max(compute_units(), 1);
         hipLaunchKernelGGL(k_batch_gather_rows<W>, dim3((unsigned)std::max(1LL, std::min(work, cap))), dim3(GATHER_THREADS), 0, st_, (W*)dst, (const W*)src, idx_d, count, wpr);
         PQ_HIP(hipGetLastError());
     }
@@ -2391,8 +2334,9 @@ private:
         return bytes;
     }
 
-    // rows: the rows the caller gave (the batch, or the length of the list of an update by list)
-    void check_patterns(const double* h_l, const double* h_u, const double* x_l, const double* x_u, int rows) const
+    // Shared bound sets: every row of the caller's HOST arrays has the finiteness pattern fin_hl_ .. fin_xu_ -- instance 0's at a setup, the setup's at an update --,
+    // or the call is refused with `text`.  rows: the rows the caller gave (the batch, or the length of the list of an update by list)
+    void check_patterns(const char* text, const double* h_l, const double* h_u, const double* x_l, const double* x_u, int rows) const
     {
         auto pattern_ok = [&](const double* v, int len, const std::vector<char>& finite, bool lower) {
             if (!v) return true;
@@ -2404,11 +2348,11 @@ private:
             return true;
         };
         if (!pattern_ok(h_l, m_, fin_hl_, true) || !pattern_ok(h_u, m_, fin_hu_, false) || !pattern_ok(x_l, n_, fin_xl_, true) || !pattern_ok(x_u, n_, fin_xu_, false))
-            throw std::runtime_error("batch update: the set of finite bounds differs from the one given at setup");
+            throw std::runtime_error(text);
     }
 
     // the same check on the caller's DEVICE arrays: one small kernel per given bound vector, one flag word read back
-    void check_patterns_device(const double* h_l, const double* h_u, const double* x_l, const double* x_u, int rows)
+    void check_patterns_device(const char* text, const double* h_l, const double* h_u, const double* x_l, const double* x_u, int rows)
     {
         if (!h_l && !h_u && !x_l && !x_u) return;
         PQ_HIP(hipMemsetAsync(fin_flag_.p, 0, sizeof(int), st_));
@@ -2419,21 +2363,21 @@ private:
         int flag = 0;
         PQ_HIP(hipMemcpyAsync(&flag, fin_flag_.p, sizeof(int), hipMemcpyDeviceToHost, st_));
         stream_wait(st_);
-        if (flag) throw std::runtime_error("batch update: the set of finite bounds differs from the one given at setup");
+        if (flag) throw std::runtime_error(text);
     }
 
-    // Where the caller's k-th value of P / A / G lives in the arena: found by pushing the values 1, 2, 3, ... through the same host path the real
-    // values took at setup (make_sparse_host_data: upper-triangle extraction, transposes, disabled rows of G zeroed).
-    // fin_ready (a device-fed setup, which has checked the caller's arrays against them already): the device copies of fin_hl_ .. fin_xu_, taken over; the flag word exists.
     static std::vector<int> finite_as_int(const std::vector<char>& f)
     {
         std::vector<int> v(std::max<size_t>(f.size(), 1), 0);
         for (size_t i = 0; i < f.size(); ++i) v[i] = f[i] != 0;
         return v;
     }
-    void build_update_maps(int n, int p, int m, const int* Pp, const int* Pi, const double* c, const int* Ap, const int* Ai, const double* b, const int* Gp, const int* Gi,
-                           const double* h_l, const double* h_u, const double* x_l, const double* x_u, const HostData& d0, std::vector<DBuf<int>>* fin_ready)
+    // Where the caller's k-th value of P / A / G lives in the arena: found by pushing the values 1, 2, 3, ... through the host path of the single-QP setup
+    // (make_sparse_host_data: upper-triangle extraction, transposes, disabled rows of G zeroed).  h_l .. x_u: instance 0's bound vectors (host).
+    void build_update_maps(const int* Pp, const int* Pi, const int* Ap, const int* Ai, const int* Gp, const int* Gi, const double* h_l, const double* h_u, const double* x_l,
+                           const double* x_u, const HostData& d0)
     {
+        const int n = n_, p = p_, m = m_;
         nzP_in_ = Pp[n]; nzA_in_ = Ap ? Ap[n] : 0; nzG_in_ = Gp ? Gp[n] : 0;
         Vec iP(std::max(nzP_in_, 1)), iA(std::max(nzA_in_, 1)), iG(std::max(nzG_in_, 1));
         for (int k = 0; k < nzP_in_; ++k) iP[k] = k + 1;
@@ -2441,7 +2385,7 @@ private:
         for (int k = 0; k < nzG_in_; ++k) iG[k] = k + 1;
         // (per-instance bound sets: no row of the probe is dropped -- finite bounds everywhere --, k_batch_assign tests the row of an entry against the instance's table)
         const Vec hfin(std::max(m, 1), 0.0);
-        auto probe = make_sparse_host_data(n, p, m, Pp, Pi, iP.data(), c, Ap, Ai, Ap ? iA.data() : nullptr, b, Gp, Gi, Gp ? iG.data() : nullptr, per_inst_ ? hfin.data() : h_l,
+        auto probe = make_sparse_host_data(n, p, m, Pp, Pi, iP.data(), nullptr, Ap, Ai, Ap ? iA.data() : nullptr, nullptr, Gp, Gi, Gp ? iG.data() : nullptr, per_inst_ ? hfin.data() : h_l,
                                            per_inst_ ? hfin.data() : h_u, x_l, x_u);
         Grow_ = (per_inst_ && Gp && nzG_in_ > 0) ? up(sbufs_->i, std::vector<int>(Gi, Gi + nzG_in_)) : nullptr;
         auto invert = [&](const Vec& stored, int nz_in) {
@@ -2455,15 +2399,6 @@ private:
         std::vector<int> dis(std::max(m_, 1), 0);
         for (int i = 0; i < m_; ++i) dis[i] = !fin_hl_[i] && !fin_hu_[i];
         disabled_d_ = up(sbufs_->i, dis);
-        if (fin_ready) {
-            const int* f[4];
-            for (int k = 0; k < 4; ++k) { sbufs_->i.push_back(std::move((*fin_ready)[(size_t)k])); f[k] = sbufs_->i.back().p; }
-            fin_hl_d_ = f[0]; fin_hu_d_ = f[1]; fin_xl_d_ = f[2]; fin_xu_d_ = f[3];
-        } else {
-            fin_hl_d_ = up(sbufs_->i, finite_as_int(fin_hl_)); fin_hu_d_ = up(sbufs_->i, finite_as_int(fin_hu_));
-            fin_xl_d_ = up(sbufs_->i, finite_as_int(fin_xl_)); fin_xu_d_ = up(sbufs_->i, finite_as_int(fin_xu_));
-            fin_flag_.alloc(1);
-        }
         rzPp_ = up(sbufs_->i, d0.sP_utri.colptr);
         rzPi_ = up(sbufs_->i, d0.sP_utri.rowind.empty() ? std::vector<int>(1, 0) : d0.sP_utri.rowind);
         stream_wait(st_);
@@ -2490,33 +2425,6 @@ private:
         launch_ruiz_sparse(a, rows, n_ + p_ + m_ <= 512 ? 64 : 256, st_);
     }
 
-    // PQ_BOUND_SETS_PER_INSTANCE: the table of every instance's lists from its own HostData (rows as bl_off says), and the descriptor that points to it
-    void build_bound_table(const std::vector<std::unique_ptr<HostData>>& data, const double* h_l, const double* h_u)
-    {
-        const int n = n_, m = m_;
-        const long long R = bl_row_ints(n, m);
-        std::vector<int> tab((size_t)R * batch_, 0);
-        for (int q = 0; q < batch_; ++q) {
-            const HostData& d = *data[(size_t)q];
-            int* r = tab.data() + (size_t)R * q;
-            r[0] = d.n_h_l; r[1] = d.n_h_u; r[2] = d.n_x_l; r[3] = d.n_x_u;
-            int *hli = r + bl_off(BL_H_L_IDX, n, m), *hui = r + bl_off(BL_H_U_IDX, n, m), *has_l = r + bl_off(BL_HAS_L, n, m), *has_u = r + bl_off(BL_HAS_U, n, m);
-            int *dropped = r + bl_off(BL_DROPPED, n, m), *xli = r + bl_off(BL_X_L_IDX, n, m), *xui = r + bl_off(BL_X_U_IDX, n, m);
-            int *pos_l = r + bl_off(BL_POS_L, n, m), *pos_u = r + bl_off(BL_POS_U, n, m);
-            for (int i = 0; i < d.n_h_l; ++i) { hli[i] = d.h_l_idx[i]; has_l[d.h_l_idx[i]] = 1; }
-            for (int i = 0; i < d.n_h_u; ++i) { hui[i] = d.h_u_idx[i]; has_u[d.h_u_idx[i]] = 1; }
-            // a dropped row is one the caller gave no finite bound (disable_inf_constraints has set its bounds to -1 / 1 in d: they no longer tell)
-            for (int i = 0; i < m; ++i) dropped[i] = !(h_l && h_l[(size_t)q * m + i] > -1e30) && !(h_u && h_u[(size_t)q * m + i] < 1e30);
-            for (int j = 0; j < n; ++j) pos_l[j] = pos_u[j] = -1;
-            for (int i = 0; i < d.n_x_l; ++i) { xli[i] = d.x_l_idx[i]; pos_l[d.x_l_idx[i]] = i; }
-            for (int i = 0; i < d.n_x_u; ++i) { xui[i] = d.x_u_idx[i]; pos_u[d.x_u_idx[i]] = i; }
-        }
-        upload_vec(bl_tab_, tab, st_);
-        shared_h_.bl_tab = bl_tab_.p;
-        shared_h_.bl_stride = R;
-        PQ_HIP(hipMemcpyAsync(shared_.p, &shared_h_, sizeof(BatchShared), hipMemcpyHostToDevice, st_));
-        stream_wait(st_);
-    }
     void launch_bound_lists(const double* h_l, const double* h_u, const double* x_l, const double* x_u, bool scaled, const int* list, int rows)
     {
         if (!per_inst_ || (!h_l && !h_u && !x_l && !x_u)) return;
@@ -2538,8 +2446,6 @@ private:
         BatchShared& S = shared_h_;
         S = BatchShared{};
         S.n = n; S.p = p; S.m = m; S.n_h_l = d.n_h_l; S.n_h_u = d.n_h_u; S.n_x_l = d.n_x_l; S.n_x_u = d.n_x_u;
-        sbufs_ = std::make_shared<StructBufs>();  // (a clone may still hold the set of the last setup)
-        sbufs_->i.reserve(64); sbufs_->l.reserve(16);
         std::vector<int> has_l(std::max(m, 1), 0), has_u(std::max(m, 1), 0), pos_l(n, -1), pos_u(n, -1);
         for (int i = 0; i < d.n_h_l; ++i) has_l[d.h_l_idx[i]] = 1;
         for (int i = 0; i < d.n_h_u; ++i) has_u[d.h_u_idx[i]] = 1;
@@ -2741,13 +2647,6 @@ private:
         stream_wait(st_);
     }
 
-    void pack_instance(const HostData& d, double* dst) const
-    {
-        auto cp = [&](int slot, const Vec& v, size_t cnt) { if (cnt) std::copy(v.begin(), v.begin() + cnt, dst + layout_.off[slot]); };
-        cp(D_PX, d.sP_utri.val, d.sP_utri.val.size()); cp(D_ATX, d.sAT.val, d.sAT.val.size()); cp(D_GTX, d.sGT.val, d.sGT.val.size());
-        cp(D_C, d.c, n_); cp(D_B, d.b, p_); cp(D_HL, d.h_l, m_); cp(D_HU, d.h_u, m_); cp(D_XL, d.x_l, n_); cp(D_XU, d.x_u, n_); cp(D_XBS, d.x_b_scaling, n_);
-    }
-
     void launch_prepare(const int* list = nullptr, int rows = 0)
     {
         if (!list) rows = batch_;
@@ -2816,7 +2715,7 @@ private:
     const int *mapP_ = nullptr, *mapA_ = nullptr, *mapG_ = nullptr, *disabled_d_ = nullptr, *rzPp_ = nullptr, *rzPi_ = nullptr;  // device, owned by sbufs_->i
     double last_kernel_ms_ = 0.0;
     double clone_ms_[2] = {0.0, 0.0};  // of the clone call that made this handle: wall, device time of the gathers (pq_batch_clone_ms)
-    double setup_ms_[3] = {0.0, 0.0, 0.0};  // of the last setup: wall, host analysis (symbolic, maps, tables), device time from the fill of the arena to prepare (pq_batch_setup_ms)
+    double setup_ms_[3] = {0.0, 0.0, 0.0};  // of the last setup: wall, host analysis (symbolic, maps, tables), device time from the fill of the arena (host arrays: from their upload) to prepare (pq_batch_setup_ms)
     long long ingest_[2] = {0, 0};           // of the last setup / update: note_ingest (pq_batch_last_ingest)
     bool lpt_ = true;
     pq_settings settings_;
@@ -2897,12 +2796,9 @@ int pq_batch_clone(const pq_batch* s, pq_batch** out)
 int pq_batch_clone_select(const pq_batch* s, const int* idx, int count, pq_batch** out)
 {
     if (!s || !out) return fail(PQ_ERR_INVALID, "pq_batch_clone_select: null argument");
-    if (!idx) return fail(PQ_ERR_INVALID, "pq_batch_clone_select: idx is null");
-    if (count < 1) return fail(PQ_ERR_INVALID, "pq_batch_clone_select: count = %d, count >= 1 wanted", count);
-    if (!s->impl->is_set_up()) return fail(PQ_ERR_INVALID, "pq_batch_clone_select: the handle has no problem (no setup yet)");
-    const int batch = s->impl->batch();
-    for (int j = 0; j < count; ++j)
-        if (idx[j] < 0 || idx[j] >= batch) return fail(PQ_ERR_INVALID, "pq_batch_clone_select: idx[%d] = %d outside [0, %d)", j, idx[j], batch);
+    const char* fn = "pq_batch_clone_select";
+    if (int rc = select_args(fn, s, idx, count)) return rc;
+    if (int rc = select_entries(fn, s, idx, count, false)) return rc;
     return guarded([&] {
         std::unique_ptr<pq_batch> h(new pq_batch);
         h->impl.reset(new BatchSolver(*s->impl, idx, count));

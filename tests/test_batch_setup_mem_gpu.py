@@ -1,6 +1,7 @@
 """BatchSparseSolver.setup() from problem data in GPU memory (pq_batch_setup_sparse_mem with PQ_MEM_DEVICE): every test sets up twin handles on the same data, one
-host-fed and one device-fed, and asks for equality of bits -- the kernels behind the arena are the same, so there is no tolerance anywhere in this file.  The host-fed
-twin is the unchanged path the other test_batch_* files hold to the oracle."""
+host-fed and one device-fed, and asks for equality of bits -- there is no tolerance anywhere in this file.  The twins are two entries into one setup path: the
+host-fed one uploads the caller's arrays into a staging buffer and checks the shared finiteness pattern on the host, the device-fed one fetches instance 0's bound
+vectors and checks the pattern with a kernel; from there both run the same kernels.  The host-fed setup is the one the other test_batch_* files hold to the oracle."""
 import ctypes as C
 
 import numpy as np
@@ -257,6 +258,27 @@ def test_a_second_setup_on_the_same_handle(hip, kkt):
     same_twins(dh, hd, kkt)
 
 
+@pytest.mark.parametrize("bounds", ["shared", "per_instance"])
+@pytest.mark.parametrize("kkt", KKTS)
+def test_a_host_setup_over_another_problem_is_a_fresh_one(hip, kkt, bounds):
+    """the re-setup path of the host mode: the handle holds another problem -- other data, another shape, more instances, the list buffer of a solve by list -- when
+    it is set up from host arrays.  Nothing of the old table of lists, list buffer or finiteness copies may show: every arena row and every bound list is bitwise a
+    fresh handle's, and so is what an update (checked against the finiteness copies) and a solve by list (through the list buffer) make of them"""
+    old, bt = (batch("random", 33, 67), batch("random", 16, 5)) if bounds == "shared" else (batch("mixed", 33, 9), batch("mixed", 16, 5))
+    s, fresh = new_solver(hip, kkt, bounds), new_solver(hip, kkt, bounds)
+    assert s.setup(*args_of(old, False))
+    s.solve(instances=[1, 0])
+    assert s.setup(*args_of(bt, False)) and fresh.setup(*args_of(bt, False))
+    same_structure(s, fresh)
+    for i in range(bt["B"]):
+        assert np.array_equal(_bits(s.arena_row(i)), _bits(fresh.arena_row(i))), i
+    for h in (s, fresh):
+        assert h.update(x_l=bt["x_l"], h_u=bt["h_u"])
+        h.solve(instances=[4, 2])
+    for i in range(bt["B"]):
+        assert np.array_equal(_bits(s.arena_row(i)), _bits(fresh.arena_row(i))), i
+
+
 # ---- 5. refusals ------------------------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("key,value", [("h_l", -np.inf), ("h_u", np.inf), ("x_l", -np.inf), ("x_u", 1.0)])
 def test_shared_mode_refuses_an_instance_with_another_finiteness(hip, key, value):
@@ -356,17 +378,18 @@ def test_last_ingest_and_the_allocation_count(hip, bounds):
         moved.append(count() - c0)
         n, m = s.n, s.m
         got = s.last_ingest()
+        # header: what the ingest kernels write, 8 x B x (the stored nonzeros of upper(P), A', G' + the lengths of the given c, b, x_l, x_u + 2 m + n)
+        K = 8 * B * (sp.triu(bt["P"]).nnz + bt["A"].nnz + bt["G"].nnz + sum(bt[k].shape[1] for k in ("c", "b", "x_l", "x_u")) + 2 * m + n)
         if device:
             # header: the fetch of instance 0's h_l, h_u, x_l, x_u, and not a byte of the matrices
-            assert got["link_bytes"] == 8 * (2 * m + 2 * n)
-            assert got["kernel_bytes"] > 0
+            assert got == dict(link_bytes=8 * (2 * m + 2 * n), kernel_bytes=K)
         else:
             given = sum(bt[k].shape[1] for k in STACKS)
-            assert got == dict(link_bytes=8 * B * given, kernel_bytes=0)
+            assert got == dict(link_bytes=8 * B * given, kernel_bytes=K)
         ms = s.setup_ms()
         assert ms["wall_ms"] > 0 and 0 < ms["analysis_ms"] < ms["wall_ms"] and 0 < ms["device_ms"] < ms["wall_ms"]
-    # the host mode stages in host memory, so there is nothing to subtract: the two modes allocate the same number of device buffers
-    assert moved[0] == moved[1] > 0
+    # the host mode uploads the caller's arrays into one staging buffer; every other device buffer of a setup is made by both modes
+    assert moved[0] == moved[1] + 1 > 1
     # only the vectors that are given are fetched; an update in device mode moves nothing
     s = new_solver(hip, "SPARSE_LDLT", bounds)
     assert s.setup(*args_of(_without(bt, "h_l", "x_u"), True))

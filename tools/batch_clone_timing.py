@@ -12,7 +12,7 @@ released before the next one.
   solve    pq_batch_last_kernel_ms, the hipEvent time of the solve kernel, of the whole clone and of the source; the margin is the source's spread over its rounds.
            Beside it the second solve of the same clone and the second solve of the handle that setup() made in the same round: the source's arena was allocated
            once, before everything else, theirs in this round
-setup() runs host threads, staged uploads and two launches and has no single device interval: wall time only.  The source's solve kernel against the parent commit is
+setup() is a host check, an upload, host analysis and several launches: wall time only.  The source's solve kernel against the parent commit is
 the business of tools/batch_bounds_timing.py --shared-only, run on both trees beside this tool.  No ratio is fixed in advance."""
 import ctypes as C
 import os
