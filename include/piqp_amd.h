@@ -888,6 +888,44 @@ const pq_info *pq_solver_batch_info(const pq_solver_batch *s, int instance);
 /* field 0..9 of Variables of ALL instances into a host or device array [batch][len], len as in the single solver's result (the box vectors at full length n,
  * restore_dual applied).  Device mode makes no allocation. */
 int pq_solver_batch_get_result_mem(pq_solver_batch *s, int field, double *out, int mem);
+/* ACTING ON A LIST OF INSTANCES, IN PLACE (the _select forms of pq_solver_batch_solve, pq_solver_batch_update_dense and pq_solver_batch_get_result_mem): the same
+ * handle, the same buffers, the same result arrays -- no second handle as with pq_solver_batch_clone_select.  idx: `count` instances in HOST memory; the value arrays
+ * and out are [count][...], row j belongs to instance idx[j]; mem and order mean what they mean in the whole-batch calls.
+ * A LISTED instance ends in the state the whole-batch call would leave it in when given the same row, bit for bit: the ten result vectors, status, iter and every
+ * non-time info field (n_factor, n_solve, n_backend_solve), every trace row and the row count, the 13 items of pq_solver_batch_scaled_data, its lists with
+ * PQ_BOUND_SETS_PER_INSTANCE, and the state of the borrowed KKT system (pq_kktsys_batch_state, pq_kktsys_batch_info, pq_kkt_batch_internal_factor).  The same device
+ * functions run on the same row: every launch is sized by the list, one workgroup per listed instance (in the packed factor kernel of n < 32 one wave), which
+ * reads its instance from the list; the activity words of an instance that is not listed are never read.
+ * Of an UNLISTED instance no observable byte changes: the results handed out, pq_info with its times, the trace, the scaled data and scalings, its bound lists, the
+ * KKT system's state and factor.  No workgroup runs on it.  (Host images travel whole where the whole-batch calls move them whole -- the state records around a
+ * solve, the bound tables of PQ_BOUND_SETS_PER_INSTANCE in an update: an unlisted row gets the bytes it holds.)
+ * _solve_select: returns how many of the listed instances ended PQ_SOLVED.  The settings are read as they stand at the call (stragglers are run again in place
+ * under a larger max_iter).  Every listed instance starts from INIT as in pq_solver_batch_solve (no warm start) and its trace at row 0.  The rounds end when every
+ * listed instance is done; their bound is pq_solver_batch_solve's: when it is reached PQ_ERR_INTERNAL is returned and only the listed unfinished instances become
+ * PQ_UNSOLVED.  Settings that verify_settings refuses: the listed infos alone become PQ_INVALID_SETTINGS, no launch, PQ_ERR_INVALID.  solve_time and run_time are
+ * written to the listed infos only; run_time keeps the handle-wide rule of pq_solver_batch_solve -- updated (any update call since the setup) ? update_time :
+ * setup_time, plus solve_time -- where update_time is that of the instance's OWN last update (0 if it never had one).  pq_solver_batch_last_ms reports this
+ * call.  Afterwards pq_solver_batch_get_result_mem, _get_trace and _info work for the whole batch: an instance that was never solved reads zeros, the status its
+ * setup left and 0 trace rows.
+ * _update_dense_select: the sequence of pq_solver_batch_update_dense (bound lists on the host, unscale, assign, rescale or re-equilibrate, P_diag, A'A under the A'A
+ * rule above, x_b_scaling into the KKT system) on the listed rows only.  Shared bound sets: the finiteness check runs over the `count` rows given; a mismatch is
+ * refused with pq_solver_batch_update_dense's text, naming the instance (not j), and the handle stays as it was.  Sets per instance: the lists of the listed
+ * instances are rebuilt and no others; the borrowed KKT system then refuses its solve, mul and state calls (as after pq_kktsys_batch_set_lists) until EVERY instance
+ * whose lists were replaced has been solved again, by list or whole -- a solve of other instances does not end that.  All pointers NULL: an unscale and rescale of the listed rows.  update_time goes to the listed infos,
+ * pq_solver_batch_last_update_ms reports this call.  An updated instance keeps the results, info and trace of its last solve until it is solved again.  Returns 1.
+ * _get_result_select_mem: field 0..9 of the listed instances -> out [count][len] by one gather kernel per `batch` entries of the list; repeats are allowed and
+ * count may exceed the batch; a field of length 0 writes nothing and returns PQ_OK; it needs a previous solve, as pq_solver_batch_get_result_mem does.
+ * ALLOCATION: the first _select call on a handle allocates one device int buffer of `batch` entries for the list (setup and clone allocate nothing for it).  After
+ * that _solve_select, _update_dense_select from host or device memory and the device-memory result allocate nothing (pq_debug_alloc_count does not move); a
+ * host-memory result stages [count][len].
+ * REFUSED with PQ_ERR_INVALID before any device call, the handle untouched, the text opening with the call's name and naming j and the value where there is one:
+ * a NULL s, idx or out; count < 1; a bad mem, order or field; a handle that is not set up; an idx[j] outside [0, batch); -- _solve_select and
+ * _update_dense_select only -- an instance listed twice (two workgroups on one instance would race); the refusals of pq_solver_batch_update_dense (A or b with
+ * p = 0; G, h_l or h_u with m = 0); for the result: no solve yet. */
+int pq_solver_batch_solve_select(pq_solver_batch *s, const int *idx, int count);
+int pq_solver_batch_update_dense_select(pq_solver_batch *s, const int *idx, int count, const double *P, const double *c, const double *A, const double *b,
+                                        const double *G, const double *h_l, const double *h_u, const double *x_l, const double *x_u, int mem, int order);
+int pq_solver_batch_get_result_select_mem(pq_solver_batch *s, const int *idx, int count, int field, double *out, int mem);
 /* the 11-column table of solver.hpp:590-602 per instance, kept in device memory during the solve.  set_trace: rows per instance, before the setup (which sizes the
  * buffer; afterwards only a smaller number is accepted); every solve starts at row 0.  get_trace: rows_out rows of 11 doubles to HOST memory (out_host may be NULL) */
 int pq_solver_batch_set_trace(pq_solver_batch *s, int max_rows);

@@ -131,6 +131,7 @@ SYMBOLS = [
     "pq_solver_batch_get_result_mem", "pq_solver_batch_set_trace", "pq_solver_batch_get_trace", "pq_solver_batch_dims", "pq_solver_batch_last_ms", "pq_solver_batch_scaled_data",
     "pq_solver_batch_kktsys", "pq_solver_batch_update_dense", "pq_solver_batch_last_update_ms", "pq_solver_batch_set_bound_sets", "pq_debug_bound_lists",
     "pq_kkt_batch_clone_select", "pq_kktsys_batch_clone_select", "pq_solver_batch_clone", "pq_solver_batch_clone_select", "pq_solver_batch_clone_ms",
+    "pq_solver_batch_solve_select", "pq_solver_batch_update_dense_select", "pq_solver_batch_get_result_select_mem",
     "pq_debug_alloc_count", "pq_debug_chol_plan", "pq_debug_syrk_plan", "pq_debug_device_sqrt", "pq_kkt_set_exchange_norm", "pq_kkt_sharded_calls", "pq_kkt_sharded_solve_calls", "pq_solver_sharded_solve_calls", "pq_solver_set_exchange_norm", "pq_solver_sharded_calls", "pq_microbench_mfma_f64", "pq_microbench_hbm_copy", "pq_microbench_potrf_block", "pq_debug_potrf_block", "pq_debug_csc_ops", "pq_debug_ruiz","pq_rccl_unique_id", "pq_kkt_set_comm_rccl", "pq_solver_set_comm_rccl", "pq_kkt_native_exchange_calls", "pq_kkt_min_abs_pivot", "pq_solver_native_exchange_calls",
     "pq_solver_setup_sparse_mem", "pq_solver_update_sparse_mem", "pq_debug_sparse_ingest_maps",
     "pq_solver_setup_dense_mem", "pq_solver_update_dense_mem", "pq_solver_get_result_mem", "pq_solver_last_ingest", "pq_batch_update_mem", "pq_batch_update_data_mem",
@@ -288,6 +289,9 @@ def load():
     L.pq_solver_batch_info.argtypes = [vp, C.c_int]
     L.pq_solver_batch_info.restype = C.POINTER(Info)
     L.pq_solver_batch_get_result_mem.argtypes = [vp, C.c_int, vp, C.c_int]
+    L.pq_solver_batch_solve_select.argtypes = [vp, vp, C.c_int]
+    L.pq_solver_batch_update_dense_select.argtypes = [vp, vp, C.c_int] + [vp] * 9 + [C.c_int, C.c_int]
+    L.pq_solver_batch_get_result_select_mem.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int]
     L.pq_solver_batch_set_trace.argtypes = [vp, C.c_int]
     L.pq_solver_batch_set_bound_sets.argtypes = [vp, C.c_int]
     L.pq_debug_bound_lists.argtypes = [C.c_int, C.c_int] + [vp] * 18

@@ -38,7 +38,14 @@ class BatchDenseSolver(_BatchHandle):
     the arguments, under the rules of setup; with shared bounds the set of finite bounds must stay the setup's (RuntimeError otherwise, the handle is as it was).
     s.clone(instances=None): a second solver in the state of this one, without a new setup -- whole, or instance j of the clone being instance instances[j] of this
     one (repeats allowed, any length >= 1): settings, scaled data, stored scalings, bound sets, statuses, results and traces go along, so update() on the clone gives
-    each copy its scenario and a clone of the instances that did not end SOLVED can be solved again with other settings."""
+    each copy its scenario and a clone of the instances that did not end SOLVED can be solved again with other settings.
+    IN PLACE ON A LIST OF INSTANCES (pq_solver_batch_*_select): s.solve(instances=...), s.update(..., instances=...) and s.result(name, instances=...) act on the listed
+    instances of this solver -- no second handle, no gather of its buffers.  instances: anything np.asarray makes a one-dimensional, non-empty list of integers of;
+    for solve and update the entries are distinct.  update takes arrays [len(instances), ...], row j for instance instances[j], NumPy or torch CUDA tensors under
+    the rules of setup; the listed instances end bit for bit where the whole-batch call given the same rows would leave them, and nothing of any other instance is
+    written.  solve runs the listed instances again from the start with the settings as they stand (stragglers: raise settings.max_iter, then
+    s.solve(instances=np.flatnonzero(s.statuses() != SOLVED))) and returns how many of them ended SOLVED; the others keep results, info and trace.  result gives
+    [len(instances), len], repeats allowed.  A fleet of which a fraction gets new measurements: s.update(c=c_new, b=b_new, instances=ids); s.solve(instances=ids)."""
     _destroy = "pq_solver_batch_destroy"
 
     def __init__(self, device=0, kkt_solver=DENSE_CHOLESKY, bounds="shared"):
@@ -93,9 +100,23 @@ class BatchDenseSolver(_BatchHandle):
         m = 0 if G is None else int(G.shape[1])
         return (b, n, p, m), dict(P=(b, n, n), c=(b, n), A=(b, p, n), b=(b, p), G=(b, m, n), h_l=(b, m), h_u=(b, m), x_l=(b, n), x_u=(b, n))
 
+    @staticmethod
+    def _instances(instances, unique):
+        """the list of a call with instances (select_list); unique: ValueError for an instance listed twice -- two workgroups would work on one instance.  No
+        library call in here: the range of the entries is the library's check."""
+        idx = select_list(instances)
+        if unique and len(np.unique(idx)) != len(idx):
+            seen = {}
+            for j, i in enumerate(idx.tolist()):
+                if i in seen:
+                    raise ValueError(f"instances[{j}] = {i} is listed twice (instances[{seen[i]}] too)")
+                seen[i] = j
+        return idx
+
     def _prepare(self, args, dims=None):
         """(dims, mem, order, the arrays to pass in the order of _NAMES); raises before any library call.  dims: None for a setup, which takes them from P, A and G;
-        the (batch, n, p, m) of the setup for an update, where every argument is optional"""
+        the (batch, n, p, m) of the setup for an update, where every argument is optional -- for an update of a list of instances the leading one is the length of
+        the list"""
         a = dict(zip(_NAMES, args))
         if dims is None:
             if a["P"] is None or a["c"] is None:
@@ -146,13 +167,20 @@ class BatchDenseSolver(_BatchHandle):
         check(self.L.pq_solver_batch_setup_dense(self.h, *dims, *[self._p(v) for v in arrs], mem, order), "pq_solver_batch_setup_dense")
         self.batch, self.n, self.p, self.m = dims
 
-    def update(self, P=None, c=None, A=None, b=None, G=None, h_l=None, h_u=None, x_l=None, x_u=None):
+    def update(self, P=None, c=None, A=None, b=None, G=None, h_l=None, h_u=None, x_l=None, x_u=None, instances=None):
+        """instances: a list of distinct instances -- the arrays are [len(instances), ...], row j for instance instances[j]; those instances alone are updated, in
+        place (pq_solver_batch_update_dense_select)"""
         if self.batch is None:
             raise RuntimeError("update before setup")
-        _, mem, order, arrs = self._prepare((P, c, A, b, G, h_l, h_u, x_l, x_u), (self.batch, self.n, self.p, self.m))
+        idx = None if instances is None else self._instances(instances, unique=True)
+        rows = self.batch if idx is None else len(idx)
+        _, mem, order, arrs = self._prepare((P, c, A, b, G, h_l, h_u, x_l, x_u), (rows, self.n, self.p, self.m))
         if mem == MEM_DEVICE:
             sync_current_stream(self.device)
-        return check(self.L.pq_solver_batch_update_dense(self.h, *[self._p(v) for v in arrs], mem, order), "pq_solver_batch_update_dense") == 1
+        ptrs = [self._p(v) for v in arrs]
+        if idx is not None:
+            return check(self.L.pq_solver_batch_update_dense_select(self.h, idx.ctypes.data, rows, *ptrs, mem, order), "pq_solver_batch_update_dense_select") == 1
+        return check(self.L.pq_solver_batch_update_dense(self.h, *ptrs, mem, order), "pq_solver_batch_update_dense") == 1
 
     def clone_ms(self):
         """of the clone() that made this solver: dict(wall_ms, device_ms); zeros on a solver that is no clone"""
@@ -166,7 +194,12 @@ class BatchDenseSolver(_BatchHandle):
         check(self.L.pq_solver_batch_last_update_ms(self.h, o.ctypes.data), "pq_solver_batch_last_update_ms")
         return dict(wall_ms=float(o[0]), device_ms=float(o[1]))
 
-    def solve(self):
+    def solve(self, instances=None):
+        """returns the number of instances that ended SOLVED.  instances: a list of distinct instances -- they alone are solved again, in place, with the settings as
+        they stand; the count is of the listed ones (pq_solver_batch_solve_select)"""
+        if instances is not None:
+            idx = self._instances(instances, unique=True)
+            return check(self.L.pq_solver_batch_solve_select(self.h, idx.ctypes.data, len(idx)), "pq_solver_batch_solve_select")
         return check(self.L.pq_solver_batch_solve(self.h), "pq_solver_batch_solve")
 
     def info(self, i):
@@ -181,18 +214,24 @@ class BatchDenseSolver(_BatchHandle):
     def iterations(self):
         return np.array([self.info(i).iter for i in range(self.batch)], dtype=np.int32)
 
-    def result(self, name, device=False):
-        """field `name` of Variables of all instances, [batch, len]: a NumPy array, or with device=True a torch CUDA tensor (no copy across the link)"""
+    def result(self, name, device=False, instances=None):
+        """field `name` of Variables of all instances, [batch, len]: a NumPy array, or with device=True a torch CUDA tensor (no copy across the link).
+        instances: a list of instances, repeats allowed -- [len(instances), len], row j of instance instances[j] (pq_solver_batch_get_result_select_mem)"""
         field = VAR_NAMES.index(name)
-        shape = var_shapes(self.batch, self.n, self.p, self.m)[name]
+        idx = None if instances is None else self._instances(instances, unique=False)
+        shape = var_shapes(self.batch if idx is None else len(idx), self.n, self.p, self.m)[name]
         if device:
             import torch
             out = torch.empty(shape, dtype=torch.float64, device=f"cuda:{self.device}")
             sync_current_stream(self.device)
-            check(self.L.pq_solver_batch_get_result_mem(self.h, field, out.data_ptr(), MEM_DEVICE), "pq_solver_batch_get_result_mem")
-            return out
-        out = np.zeros(shape)
-        check(self.L.pq_solver_batch_get_result_mem(self.h, field, out.ctypes.data, MEM_HOST), "pq_solver_batch_get_result_mem")
+            ptr, mem = out.data_ptr(), MEM_DEVICE
+        else:
+            out = np.zeros(shape)
+            ptr, mem = out.ctypes.data, MEM_HOST
+        if idx is None:
+            check(self.L.pq_solver_batch_get_result_mem(self.h, field, ptr, mem), "pq_solver_batch_get_result_mem")
+        else:  # (an empty torch tensor has no address to give: a field of length 0 is checked like any other and nothing is written, so any address stands for it)
+            check(self.L.pq_solver_batch_get_result_select_mem(self.h, idx.ctypes.data, len(idx), field, ptr or idx.ctypes.data, mem), "pq_solver_batch_get_result_select_mem")
         return out
 
     def trace(self, i):

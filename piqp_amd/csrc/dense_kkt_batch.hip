@@ -93,17 +93,19 @@ __global__ __launch_bounds__(DFB_THREADS) void k_kb_factor(const KbFactorArgs A)
 }
 
 // The assemble-only instantiation: the lower triangle of  init + M diag(w) M'  of every instance to memory (out: [batch][n n], leading dimension n).  AT_A at
-// create / update_data (Pu = null, M = AT, no weights) and the test hook pq_kkt_batch_internal_kkt_mat (one instance, the stored scalings).
+// create / update_data (Pu = null, M = AT, no weights) and the test hook pq_kkt_batch_internal_kkt_mat (one instance, the stored scalings).  list: null = slot s of
+// the grid is instance s; else `batch` counts the slots and slot s works on instance list[s] -- M, w, Pu, x_reg, ATA, delta and out are all reached by INSTANCE.
 template <int G>
 __global__ __launch_bounds__(DFB_THREADS) void k_kb_assemble(int n, int ld, int batch, int kdim, const double* __restrict__ M, const double* __restrict__ w,
                                                             const double* __restrict__ Pu, const double* __restrict__ x_reg, const double* __restrict__ ATA,
-                                                            const double* __restrict__ delta, double* __restrict__ out)
+                                                            const double* __restrict__ delta, double* __restrict__ out, const int* __restrict__ list)
 {
     extern __shared__ double kb_lds[];
     constexpr int MPW = DFB_THREADS / G;
     const int g = threadIdx.x / G, t = threadIdx.x % G;
-    const long long inst = (long long)blockIdx.x * MPW + g;
-    const bool have = inst < batch;
+    const long long slot = (long long)blockIdx.x * MPW + g;
+    const bool have = slot < batch;
+    const long long inst = list && have ? list[slot] : slot;
     double* a = kb_lds + (size_t)g * ((size_t)n * ld + (size_t)(KB_SLICE + 1) * n + KB_SLICE);
     double* dacc = a + (size_t)n * ld;
     double* gs = dacc + n;
@@ -221,24 +223,24 @@ void kb_alloc(pq_kkt_batch* k)
 
 // launches the assemble-only kernel over `count` instances with the factorisation's launch shape
 void kb_launch_assemble(const pq_kkt_batch* k, int count, int kdim, const double* M, const double* w, const double* Pu, const double* x_reg, const double* ATA,
-                        const double* delta, double* out)
+                        const double* delta, double* out, const int* list = nullptr)
 {
     const int n = k->n, ld = dfb_ld(n);
     const size_t lds = kb_factor_lds_bytes(n);
-    if (n < 32) k_kb_assemble<64><<<div_up(count, DFB_THREADS / 64), DFB_THREADS, lds, k->st>>>(n, ld, count, kdim, M, w, Pu, x_reg, ATA, delta, out);
-    else k_kb_assemble<DFB_THREADS><<<count, DFB_THREADS, lds, k->st>>>(n, ld, count, kdim, M, w, Pu, x_reg, ATA, delta, out);
+    if (n < 32) k_kb_assemble<64><<<div_up(count, DFB_THREADS / 64), DFB_THREADS, lds, k->st>>>(n, ld, count, kdim, M, w, Pu, x_reg, ATA, delta, out, list);
+    else k_kb_assemble<DFB_THREADS><<<count, DFB_THREADS, lds, k->st>>>(n, ld, count, kdim, M, w, Pu, x_reg, ATA, delta, out, list);
     PQ_HIP(hipGetLastError());
 }
 
-// dense/kkt.hpp:53: AT_A.lower = AT * AT^T of every instance
-void kb_compute_ata(pq_kkt_batch* k)
+// dense/kkt.hpp:53: AT_A.lower = AT * AT^T of every instance, or of the `count` instances of a device list
+void kb_compute_ata(pq_kkt_batch* k, const int* list = nullptr, int count = 0)
 {
-    if (k->p > 0) kb_launch_assemble(k, k->batch, k->p, k->AT.p, nullptr, nullptr, nullptr, nullptr, nullptr, k->ATA.p);
+    if (k->p > 0) kb_launch_assemble(k, list ? count : k->batch, k->p, k->AT.p, nullptr, nullptr, nullptr, nullptr, nullptr, k->ATA.p, list);
 }
 
 }  // namespace
 
-void pq::kb_refresh_ata(pq_kkt_batch* k) { kb_compute_ata(k); }
+void pq::kb_refresh_ata(pq_kkt_batch* k, const int* list, int count) { kb_compute_ata(k, list, count); }
 
 int pq::kb_factor_done(pq_kkt_batch* k, const std::chrono::steady_clock::time_point* w0, const KbReadback* more, int n_more)
 {

@@ -245,4 +245,36 @@ __global__ __launch_bounds__(KB_GATHER_THREADS) void k_kb_gather_rows(W* __restr
     }
 }
 
+// ---- the mirror, for the calls that act on a list of instances in place (pq_solver_batch_*_select): row idx[j] of dst is row j of src -- or, with same_row, row
+// idx[j] of src: the listed rows of one [batch][len] array into another.  The same word-width rule (kb_scatter_rows), the same two walks, a copy of bits.  The
+// entries of idx are distinct (checked on the host), so no two rows of a launch write the same place.
+template <class W>
+__global__ __launch_bounds__(KB_GATHER_THREADS) void k_kb_scatter_rows(W* __restrict__ dst, const W* __restrict__ src, const int* __restrict__ idx, size_t count,
+                                                                       size_t wpr, int same_row)
+{
+    const unsigned t = threadIdx.x;
+    if (wpr >= (size_t)KB_GATHER_THREADS) {
+        const size_t cpr = (wpr + KB_GATHER_CHUNK - 1) / KB_GATHER_CHUNK, units = count * cpr;
+        for (size_t u = blockIdx.x; u < units; u += gridDim.x) {
+            const size_t row = u / cpr, w0 = (u % cpr) * KB_GATHER_CHUNK;
+            const size_t w1 = w0 + KB_GATHER_CHUNK < wpr ? w0 + KB_GATHER_CHUNK : wpr;
+            const size_t to = (size_t)idx[row];
+            const W* s = src + (same_row ? to : row) * wpr;
+            W* d = dst + to * wpr;
+            for (size_t w = w0 + t; w < w1; w += KB_GATHER_THREADS) d[w] = s[w];
+        }
+        return;
+    }
+    const unsigned len = (unsigned)wpr, rpb = KB_GATHER_THREADS / len, r = t / len, w = t % len;
+    if (r >= rpb) return;  // (the lanes past the last whole row; no barrier below)
+    const size_t groups = (count + rpb - 1) / rpb;
+    for (size_t g = blockIdx.x; g < groups; g += gridDim.x) {
+        const size_t row = g * rpb + r;
+        if (row < count) {
+            const size_t to = (size_t)idx[row];
+            dst[to * wpr + w] = src[(same_row ? to : row) * wpr + w];
+        }
+    }
+}
+
 }  // namespace pq

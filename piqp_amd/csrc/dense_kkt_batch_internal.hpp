@@ -106,6 +106,26 @@ inline void kb_gather_rows(hipStream_t st, void* dst, const void* src, const int
     else if (a % 4 == 0) kb_gather_launch<unsigned>(st, dst, src, idx_d, count, row_bytes);
     else throw std::runtime_error("gather: a row that is no multiple of 4 bytes");
 }
+// the mirror: dst[idx_d[j]][0 .. row_bytes) = src[j][0 .. row_bytes) -- with same_row src[idx_d[j]] -- for j < count, the entries of idx_d distinct
+template <class W>
+void kb_scatter_launch(hipStream_t st, void* dst, const void* src, const int* idx_d, size_t count, size_t row_bytes, bool same_row)
+{
+    const size_t wpr = row_bytes / sizeof(W);
+    const size_t work = wpr >= (size_t)KB_GATHER_THREADS ? count * ((wpr + KB_GATHER_CHUNK - 1) / KB_GATHER_CHUNK)
+                                                         : (count + KB_GATHER_THREADS / wpr - 1) / (KB_GATHER_THREADS / wpr);
+    const unsigned grid = (unsigned)(work < (size_t)KB_GATHER_MAX_GRID ? work : (size_t)KB_GATHER_MAX_GRID);
+    k_kb_scatter_rows<W><<<grid, KB_GATHER_THREADS, 0, st>>>((W*)dst, (const W*)src, idx_d, count, wpr, same_row ? 1 : 0);
+    PQ_HIP(hipGetLastError());
+}
+inline void kb_scatter_rows(hipStream_t st, void* dst, const void* src, const int* idx_d, size_t count, size_t row_bytes, bool same_row = false)
+{
+    if (!count || !row_bytes) return;
+    const size_t a = row_bytes | (size_t)(uintptr_t)dst | (size_t)(uintptr_t)src;
+    if (a % 16 == 0) kb_scatter_launch<uint4>(st, dst, src, idx_d, count, row_bytes, same_row);
+    else if (a % 8 == 0) kb_scatter_launch<unsigned long long>(st, dst, src, idx_d, count, row_bytes, same_row);
+    else if (a % 4 == 0) kb_scatter_launch<unsigned>(st, dst, src, idx_d, count, row_bytes, same_row);
+    else throw std::runtime_error("scatter: a row that is no multiple of 4 bytes");
+}
 template <class T>
 void kb_gather_host(T* dst, const T* src, const int* idx, int count, size_t len)
 {
@@ -136,14 +156,22 @@ int kb_factor_done(pq_kkt_batch* k, const std::chrono::steady_clock::time_point*
 // The two heavy launches of a pq_kktsys_batch (dense_kktsys_batch.hip) on their own, for dense_solver_batch.hip, which clocks them in rounds: every pointer is
 // device memory, the launch goes on the handle's stream, nothing is read back and nothing waits.  active: null = every instance; else int [batch], an instance
 // whose word is 0 is left out (it reads nothing, writes nothing, and in the n < 32 variant its wave still reaches every barrier of its workgroup).
-void ksb_launch_factor(pq_kktsys_batch* k, const int* flags, const double* rho, const double* delta, const pq_vars& v, const int* active);
-void ksb_launch_solve(pq_kktsys_batch* k, const pq_vars& rhs, const pq_vars& lhs, const int* active);
+// list, count: null and the batch = every instance, slot s of the grid is instance s (the code of before).  Else `count` distinct instances in device memory: the
+// grid is sized by count and slot s works on instance list[s]; every array, `active` included, stays indexed by INSTANCE, and the words of an instance that is not
+// listed are not read (they are stale from earlier solves).
+void ksb_launch_factor(pq_kktsys_batch* k, const int* flags, const double* rho, const double* delta, const pq_vars& v, const int* active, const int* list, int count);
+void ksb_launch_solve(pq_kktsys_batch* k, const pq_vars& rhs, const pq_vars& lhs, const int* active, const int* list, int count);
+// After pq_kktsys_batch_set_lists the system is `stale` (its solve, mul and state calls are refused) until a factorisation.  A factor launch over the whole batch ends
+// that; one over a list does not, because an instance outside the list may still hold a factor of its old lists.  The caller that launches by list keeps count and
+// says here when every instance whose lists were replaced has been factored since.
+void ksb_lists_factored(pq_kktsys_batch* k);
 // The one writer of the backend's data outside dense_kkt_batch.hip: pq_solver_batch_update_dense (dense_solver_batch.hip) unscales, assigns and rescales Pu, AT and
 // GT where they stand, by kernels on the handle's stream, and then says so here.  options: the PQ_KKT_UPDATE_* flags of the matrices its caller gave (P: the
 // system's P_diag is taken again, as KKTSystem::update_data does); refresh_ata: A'A is computed again from AT (kb_refresh_ata, dense_kkt_batch.hip);
-// x_b_scaling: device, [batch][n], copied into the system's own.  Everything goes on the stream, nothing waits.
-void ksb_data_rewritten(pq_kktsys_batch* k, int options, bool refresh_ata, const double* x_b_scaling);
-void kb_refresh_ata(pq_kkt_batch* k);
+// x_b_scaling: device, [batch][n], copied into the system's own.  Everything goes on the stream, nothing waits.  list, count as above: with a list P_diag, A'A
+// and the rows of x_b_scaling of the listed instances alone are taken again, each by a launch sized by count.
+void ksb_data_rewritten(pq_kktsys_batch* k, int options, bool refresh_ata, const double* x_b_scaling, const int* list, int count);
+void kb_refresh_ata(pq_kkt_batch* k, const int* list, int count);
 hipStream_t ksb_stream(pq_kktsys_batch* k);
 const int* ksb_factor_status(const pq_kktsys_batch* k);  // device, [batch]: 0 = the instance's last factorisation succeeded
 const int* ksb_solve_info(const pq_kktsys_batch* k);     // device, [3][batch]: solve_ok, refine steps, backend solves of the instance's last solve

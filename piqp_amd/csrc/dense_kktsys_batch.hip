@@ -68,18 +68,19 @@ __device__ __forceinline__ double ksb_wave_max(double a)
 }
 
 // ---- extract_P_diag (kkt_system.hpp:430-453): the diagonal the refinement's max_diag reads is the one of the last update_data that carried P, not the live one
-__global__ void k_ksb_pdiag(const double* __restrict__ Pu, double* __restrict__ out, int n, long long total)
+// list: null = every instance; else total = count n and element e belongs to instance list[e / n]
+__global__ void k_ksb_pdiag(const double* __restrict__ Pu, double* __restrict__ out, int n, long long total, const int* __restrict__ list)
 {
     const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= total) return;
-    const long long inst = e / n;
+    const long long inst = list ? list[e / n] : e / n;
     const int i = (int)(e % n);
-    out[e] = Pu[inst * (size_t)n * n + i + (size_t)i * n];
+    out[inst * n + i] = Pu[inst * (size_t)n * n + i + (size_t)i * n];
 }
 
 // ---- update_scalings_and_factor
 struct KsbFactorArgs {
-    int n, p, m, ld, width, batch;
+    int n, p, m, ld, width, count;  // count: the slots of the grid -- the batch, or the length of `list`
     KbBounds bd;                  // row i has a lower / upper bound (has_* >= 0); variable i is entry pos_* of the lower / upper box list (or -1)
     const double *Pu, *ATA, *GT;  // the backend's data
     const int* flags;             // [batch] or null (off everywhere)
@@ -93,9 +94,12 @@ struct KsbFactorArgs {
     int* use_ref;
     double *delta_s, *x_reg_s, *zinv_s, *F;  // the backend's stored scalings (delta_reg, x_reg with reg, 1 / z_reg_iter_ref) and factor store
     int *info, *badcol;
+    const int* list;  // SEL only: slot s works on instance list[s] (distinct entries); every array above is indexed by INSTANCE
 };
 
-template <int KIND, int G, bool PER>
+// SEL = false: slot s of the grid is instance s -- the code of before lists of instances existed (the one read of A.list is not compiled).  SEL = true: the grid is
+// sized by the list and a slot learns its instance from it, nothing else differs.
+template <int KIND, int G, bool PER, bool SEL>
 __global__ __launch_bounds__(DFB_THREADS) void k_ksb_factor(const KsbFactorArgs A)
 {
     extern __shared__ double ksb_lds[];
@@ -104,8 +108,11 @@ __global__ __launch_bounds__(DFB_THREADS) void k_ksb_factor(const KsbFactorArgs 
     __shared__ double s_md[DFB_THREADS / 64], s_zm[DFB_THREADS / 64];
     const int n = A.n, m = A.m, ld = A.ld;
     const int g = threadIdx.x / G, t = threadIdx.x % G;
-    const long long inst = (long long)blockIdx.x * MPW + g;
-    const bool have = inst < A.batch && (!A.active || A.active[inst] != 0);  // (an instance left out is an empty slot: it still reaches every barrier)
+    const long long slot = (long long)blockIdx.x * MPW + g;
+    const bool in = slot < A.count;
+    // (the slot is the same in every lane of a wave, so the list is read once per wave through a uniform address; without a list the slot is the instance)
+    const long long inst = SEL && in ? (long long)A.list[G == 64 ? __builtin_amdgcn_readfirstlane((int)slot) : (int)slot] : slot;
+    const bool have = in && (!A.active || A.active[inst] != 0);  // (an instance left out is an empty slot: it still reaches every barrier)
     double* a = ksb_lds + (size_t)g * ((size_t)n * ld + (size_t)(KB_SLICE + 2) * n + KB_SLICE);
     double* dacc = a + (size_t)n * ld;
     double* gs = dacc + n;
@@ -221,6 +228,7 @@ struct KsbSolveArgs {
     double *wy, *wz;                 // workspace: [batch][3][p], [batch][3][m] (lhs, ref_lhs, err)
     int* sinfo;                      // [3][batch]: solve_ok, refine steps, backend solves
     double* dinfo;                   // [2][batch]: refine error, rhs norm
+    const int* list;                 // SEL only: the grid has one workgroup per entry and workgroup s works on instance list[s]
 };
 
 // what one instance's workgroup keeps at hand
@@ -280,12 +288,12 @@ __device__ __forceinline__ double ksb_refine_error(const KsbInst& I, const doubl
 
 __device__ __forceinline__ void ksb_swap(double*& a, double*& b) { double* c = a; a = b; b = c; }
 
-template <int KIND, bool PER>
+template <int KIND, bool PER, bool SEL>  // (SEL: as at k_ksb_factor)
 __global__ __launch_bounds__(KB_SOLVE_THREADS) void k_ksb_solve(const KsbSolveArgs A)
 {
     extern __shared__ double ksb_lds[];
     __shared__ double s_red[KB_SOLVE_THREADS / 64];
-    const long long inst = blockIdx.x;
+    const long long inst = SEL ? (long long)A.list[blockIdx.x] : (long long)blockIdx.x;  // (one scalar read per workgroup)
     const int n = A.n, p = A.p, m = A.m, ld = A.ld, t = threadIdx.x, T = blockDim.x;
     if (A.active && A.active[inst] == 0) return;  // (uniform: before any barrier)
     if (A.info[inst] != 0) {  // (uniform: before any barrier) the factorisation failed: the lhs blocks are not touched
@@ -590,9 +598,13 @@ void ksb_raise_lds()
     static PerDeviceOnce once;
     once([&] {
         const int fb = (int)ksb_factor_lds_bytes(PQ_KKT_BATCH_DENSE_MAX_N), sb = (int)ksb_solve_lds_bytes(PQ_KKT_BATCH_DENSE_MAX_N);
-        const void* const factor[4] = {(const void*)k_ksb_factor<0, DFB_THREADS, false>, (const void*)k_ksb_factor<1, DFB_THREADS, false>,
-                                       (const void*)k_ksb_factor<0, DFB_THREADS, true>, (const void*)k_ksb_factor<1, DFB_THREADS, true>};
-        const void* const solve[4] = {(const void*)k_ksb_solve<0, false>, (const void*)k_ksb_solve<1, false>, (const void*)k_ksb_solve<0, true>, (const void*)k_ksb_solve<1, true>};
+        const void* const factor[8] = {(const void*)k_ksb_factor<0, DFB_THREADS, false, false>, (const void*)k_ksb_factor<1, DFB_THREADS, false, false>,
+                                       (const void*)k_ksb_factor<0, DFB_THREADS, true, false>,  (const void*)k_ksb_factor<1, DFB_THREADS, true, false>,
+                                       (const void*)k_ksb_factor<0, DFB_THREADS, false, true>,  (const void*)k_ksb_factor<1, DFB_THREADS, false, true>,
+                                       (const void*)k_ksb_factor<0, DFB_THREADS, true, true>,   (const void*)k_ksb_factor<1, DFB_THREADS, true, true>};
+        const void* const solve[8] = {(const void*)k_ksb_solve<0, false, false>, (const void*)k_ksb_solve<1, false, false>, (const void*)k_ksb_solve<0, true, false>,
+                                      (const void*)k_ksb_solve<1, true, false>,  (const void*)k_ksb_solve<0, false, true>,  (const void*)k_ksb_solve<1, false, true>,
+                                      (const void*)k_ksb_solve<0, true, true>,   (const void*)k_ksb_solve<1, true, true>};
         for (const void* fn : factor) PQ_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, fb));
         for (const void* fn : solve) PQ_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, sb));
     });
@@ -638,10 +650,10 @@ void ksb_upload_tables(pq_kktsys_batch* k)
     stream_wait(k->kb->st);
 }
 // P_diag of every instance from the backend's P, on the handle's stream (nothing waits)
-void ksb_extract_pdiag(pq_kktsys_batch* k)
+void ksb_extract_pdiag(pq_kktsys_batch* k, const int* list = nullptr, int count = 0)
 {
-    const long long total = (long long)k->batch * k->n;
-    k_ksb_pdiag<<<(unsigned)((total + 255) / 256), 256, 0, k->kb->st>>>(k->kb->Pu.p, k->state[S_PDIAG].p, k->n, total);
+    const long long total = (long long)(list ? count : k->batch) * k->n;
+    k_ksb_pdiag<<<(unsigned)((total + 255) / 256), 256, 0, k->kb->st>>>(k->kb->Pu.p, k->state[S_PDIAG].p, k->n, total, list);
     PQ_HIP(hipGetLastError());
 }
 KbBounds ksb_bounds(const pq_kktsys_batch* k)
@@ -736,14 +748,32 @@ void ksb_take_lists(pq_kktsys_batch* k, const int* counts, const int* h_l_idx, c
 // handle's stream and nothing waits for it.
 namespace pq {
 
-void ksb_launch_factor(pq_kktsys_batch* k, const int* flags, const double* rho, const double* delta, const pq_vars& v, const int* active)
+namespace {
+// the kernel with or without a list, at one (KIND, G, PER)
+template <int KIND, int G, bool PER>
+void ksb_factor_go(bool sel, int grid, size_t lds, hipStream_t st, const KsbFactorArgs& a)
+{
+    if (sel) k_ksb_factor<KIND, G, PER, true><<<grid, DFB_THREADS, lds, st>>>(a);
+    else k_ksb_factor<KIND, G, PER, false><<<grid, DFB_THREADS, lds, st>>>(a);
+}
+template <int KIND, bool PER>
+void ksb_solve_go(bool sel, int grid, int threads, size_t lds, hipStream_t st, const KsbSolveArgs& a)
+{
+    if (sel) k_ksb_solve<KIND, PER, true><<<grid, threads, lds, st>>>(a);
+    else k_ksb_solve<KIND, PER, false><<<grid, threads, lds, st>>>(a);
+}
+}  // namespace
+
+void ksb_launch_factor(pq_kktsys_batch* k, const int* flags, const double* rho, const double* delta, const pq_vars& v, const int* active, const int* list, int count)
 {
     pq_kkt_batch* kb = k->kb.get();
-    const int n = k->n, batch = k->batch;
+    const int n = k->n, batch = k->batch, slots = list ? count : batch;
     hipStream_t st = kb->st;
     KsbFactorArgs a;
-    k->stale = false;  // (also for a launch masked by `active`: the one caller that masks, the solver's rounds, factors every instance in its first round)
-    a.n = n; a.p = k->p; a.m = k->m; a.ld = dfb_ld(n); a.width = n < 32 ? n : dfb_block_size_rule(n); a.batch = batch; a.bd = ksb_bounds(k);
+    // (also for a launch masked by `active`: the one caller that masks, the solver's rounds, factors every instance in its first round.  A launch sized by a list
+    // leaves the flag alone: instances outside the list may still wait with replaced lists and an old factor; the solver says when none does, ksb_lists_factored)
+    if (!list) k->stale = false;
+    a.n = n; a.p = k->p; a.m = k->m; a.ld = dfb_ld(n); a.width = n < 32 ? n : dfb_block_size_rule(n); a.count = slots; a.list = list; a.bd = ksb_bounds(k);
     a.Pu = kb->Pu.p; a.ATA = k->p > 0 ? kb->ATA.p : nullptr; a.GT = kb->GT.p;
     a.flags = flags; a.active = active; a.rho = rho; a.delta = delta;
     a.v_s_l = v.s_l; a.v_z_l = v.z_l; a.v_s_u = v.s_u; a.v_z_u = v.z_u; a.v_s_bl = v.s_bl; a.v_z_bl = v.z_bl; a.v_s_bu = v.s_bu; a.v_z_bu = v.z_bu;
@@ -755,33 +785,33 @@ void ksb_launch_factor(pq_kktsys_batch* k, const int* flags, const double* rho, 
     a.delta_s = kb->delta_s.p; a.x_reg_s = kb->x_reg_s.p; a.zinv_s = kb->zinv_s.p; a.F = kb->fac.p; a.info = kb->status.p; a.badcol = kb->status.p + batch;
     const size_t lds = ksb_factor_lds_bytes(n);
     if (n < 32) {
-        const int grid = div_up(batch, DFB_THREADS / 64);
+        const int grid = div_up(slots, DFB_THREADS / 64);
         if (k->per_inst) {
-            if (kb->kind == PQ_DENSE_CHOLESKY) k_ksb_factor<0, 64, true><<<grid, DFB_THREADS, lds, st>>>(a);
-            else k_ksb_factor<1, 64, true><<<grid, DFB_THREADS, lds, st>>>(a);
-        } else if (kb->kind == PQ_DENSE_CHOLESKY) k_ksb_factor<0, 64, false><<<grid, DFB_THREADS, lds, st>>>(a);
-        else k_ksb_factor<1, 64, false><<<grid, DFB_THREADS, lds, st>>>(a);
+            if (kb->kind == PQ_DENSE_CHOLESKY) ksb_factor_go<0, 64, true>(list != nullptr, grid, lds, st, a);
+            else ksb_factor_go<1, 64, true>(list != nullptr, grid, lds, st, a);
+        } else if (kb->kind == PQ_DENSE_CHOLESKY) ksb_factor_go<0, 64, false>(list != nullptr, grid, lds, st, a);
+        else ksb_factor_go<1, 64, false>(list != nullptr, grid, lds, st, a);
     } else {
         if (k->per_inst) {
-            if (kb->kind == PQ_DENSE_CHOLESKY) k_ksb_factor<0, DFB_THREADS, true><<<batch, DFB_THREADS, lds, st>>>(a);
-            else k_ksb_factor<1, DFB_THREADS, true><<<batch, DFB_THREADS, lds, st>>>(a);
-        } else if (kb->kind == PQ_DENSE_CHOLESKY) k_ksb_factor<0, DFB_THREADS, false><<<batch, DFB_THREADS, lds, st>>>(a);
-        else k_ksb_factor<1, DFB_THREADS, false><<<batch, DFB_THREADS, lds, st>>>(a);
+            if (kb->kind == PQ_DENSE_CHOLESKY) ksb_factor_go<0, DFB_THREADS, true>(list != nullptr, slots, lds, st, a);
+            else ksb_factor_go<1, DFB_THREADS, true>(list != nullptr, slots, lds, st, a);
+        } else if (kb->kind == PQ_DENSE_CHOLESKY) ksb_factor_go<0, DFB_THREADS, false>(list != nullptr, slots, lds, st, a);
+        else ksb_factor_go<1, DFB_THREADS, false>(list != nullptr, slots, lds, st, a);
     }
     PQ_HIP(hipGetLastError());
 }
 
-void ksb_launch_solve(pq_kktsys_batch* k, const pq_vars& rhs, const pq_vars& lhs, const int* active)
+void ksb_launch_solve(pq_kktsys_batch* k, const pq_vars& rhs, const pq_vars& lhs, const int* active, const int* list, int count)
 {
     pq_kkt_batch* kb = k->kb.get();
-    const int n = k->n, batch = k->batch;
+    const int n = k->n, batch = k->batch, slots = list ? count : batch;
     hipStream_t st = kb->st;
     KsbSolveArgs a;
     a.n = n; a.p = k->p; a.m = k->m; a.ld = dfb_ld(n); a.bd = ksb_bounds(k); a.max_iter = k->settings.iterative_refinement_max_iter; a.batch = batch;
     a.eps_abs = k->settings.iterative_refinement_eps_abs; a.eps_rel = k->settings.iterative_refinement_eps_rel;
     a.min_rate = k->settings.iterative_refinement_min_improvement_rate;
     a.Pu = kb->Pu.p; a.AT = kb->AT.p; a.GT = kb->GT.p; a.F = kb->fac.p; a.delta_s = kb->delta_s.p; a.x_reg_s = kb->x_reg_s.p; a.zinv_s = kb->zinv_s.p; a.info = kb->status.p;
-    a.active = active;
+    a.active = active; a.list = list;
     a.s_l = k->state[S_SL].p; a.zinv_l = k->state[S_ZIL].p; a.s_u = k->state[S_SU].p; a.zinv_u = k->state[S_ZIU].p;
     a.s_bl = k->state[S_SBL].p; a.zinv_bl = k->state[S_ZIBL].p; a.s_bu = k->state[S_SBU].p; a.zinv_bu = k->state[S_ZIBU].p;
     a.z_reg = k->state[S_ZREG].p; a.mdelta_s = k->state[S_MDELTA].p; a.xbs = k->state[S_XBS].p;
@@ -791,20 +821,22 @@ void ksb_launch_solve(pq_kktsys_batch* k, const pq_vars& rhs, const pq_vars& lhs
     const int threads = n <= 64 ? 64 : KB_SOLVE_THREADS;
     const size_t lds = ksb_solve_lds_bytes(n);
     if (k->per_inst) {
-        if (kb->kind == PQ_DENSE_CHOLESKY) k_ksb_solve<0, true><<<batch, threads, lds, st>>>(a);
-        else k_ksb_solve<1, true><<<batch, threads, lds, st>>>(a);
-    } else if (kb->kind == PQ_DENSE_CHOLESKY) k_ksb_solve<0, false><<<batch, threads, lds, st>>>(a);
-    else k_ksb_solve<1, false><<<batch, threads, lds, st>>>(a);
+        if (kb->kind == PQ_DENSE_CHOLESKY) ksb_solve_go<0, true>(list != nullptr, slots, threads, lds, st, a);
+        else ksb_solve_go<1, true>(list != nullptr, slots, threads, lds, st, a);
+    } else if (kb->kind == PQ_DENSE_CHOLESKY) ksb_solve_go<0, false>(list != nullptr, slots, threads, lds, st, a);
+    else ksb_solve_go<1, false>(list != nullptr, slots, threads, lds, st, a);
     PQ_HIP(hipGetLastError());
 }
 
-void ksb_data_rewritten(pq_kktsys_batch* k, int options, bool refresh_ata, const double* x_b_scaling)
+void ksb_data_rewritten(pq_kktsys_batch* k, int options, bool refresh_ata, const double* x_b_scaling, const int* list, int count)
 {
-    if (options & PQ_KKT_UPDATE_P) ksb_extract_pdiag(k);
-    if (refresh_ata) kb_refresh_ata(k->kb.get());
-    copy_in(k->state[S_XBS].p, x_b_scaling, k->state[S_XBS].bytes(), PQ_MEM_DEVICE, k->kb->st);
+    if (options & PQ_KKT_UPDATE_P) ksb_extract_pdiag(k, list, count);
+    if (refresh_ata) kb_refresh_ata(k->kb.get(), list, count);
+    if (list) kb_scatter_rows(k->kb->st, k->state[S_XBS].p, x_b_scaling, list, (size_t)count, sizeof(double) * (size_t)k->n, true);
+    else copy_in(k->state[S_XBS].p, x_b_scaling, k->state[S_XBS].bytes(), PQ_MEM_DEVICE, k->kb->st);
 }
 
+void ksb_lists_factored(pq_kktsys_batch* k) { k->stale = false; }
 hipStream_t ksb_stream(pq_kktsys_batch* k) { return k->kb->st; }
 const int* ksb_factor_status(const pq_kktsys_batch* k) { return k->kb->status.p; }
 const int* ksb_solve_info(const pq_kktsys_batch* k) { return k->sinfo.p; }
@@ -1071,7 +1103,7 @@ int pq_kktsys_batch_update_scalings_and_factor(pq_kktsys_batch* k, const int* it
         const double* delta_d = kb_in(k->stage_in, st, delta, (size_t)batch, mem, off);
         const pq_vars v = ksb_vars_in(k, vars, 2, mem, off);
         PQ_HIP(hipEventRecord(kb->ev[0], st));
-        ksb_launch_factor(k, flags, rho_d, delta_d, v, nullptr);
+        ksb_launch_factor(k, flags, rho_d, delta_d, v, nullptr, nullptr, k->batch);
         PQ_HIP(hipEventRecord(kb->ev[1], st));
         good = kb_factor_done(kb, &w0);  // the backend handle: as its own update_scalings_and_factor leaves it
         return (int)PQ_OK;
@@ -1097,7 +1129,7 @@ int pq_kktsys_batch_solve(pq_kktsys_batch* k, const pq_vars* rhs, pq_vars* lhs, 
         const pq_vars r = ksb_vars_in(k, rhs, 0, mem, off);
         const pq_vars l = ksb_vars_out(k, lhs, mem, kb->n_ok < batch);
         PQ_HIP(hipEventRecord(k->ev[0], st));
-        ksb_launch_solve(k, r, l, nullptr);
+        ksb_launch_solve(k, r, l, nullptr, nullptr, k->batch);
         PQ_HIP(hipEventRecord(k->ev[1], st));
         ksb_vars_back(k, lhs, l, mem);
         PQ_HIP(hipMemcpyAsync(k->sinfo_h.p, k->sinfo.p, sizeof(int) * 3 * batch, hipMemcpyDeviceToHost, st));

@@ -137,6 +137,8 @@ struct DsbArgs {
     int *flags, *act_f, *act_s, *counters;                // counters: [2][4], the slot of this round and the one zeroed for the next
     const int *fstatus, *sinfo;                           // the factor launch's status, the solve launch's diagnostics
     double* trace;                                        // [batch][trace_max][11]
+    const int* list;                                      // SEL only: one workgroup per entry, workgroup s is instance list[s] (distinct entries).  Every array above,
+                                                          // the activity words and the state included, is indexed by INSTANCE
 };
 
 // what one instance's workgroup keeps at hand
@@ -505,17 +507,19 @@ __device__ __forceinline__ int dsb_loop_head(const DsbCtx& C, const DsbArgs& A, 
     return WANT_FACTOR;
 }
 
-template <bool PER>
+// SEL = false: workgroup s is instance s -- the code of before lists of instances existed (A.list is not read).  SEL = true: the grid is sized by the list and a
+// workgroup learns its instance from it, by one scalar read; nothing else differs.
+template <bool PER, bool SEL>
 __global__ __launch_bounds__(DSB_T) void k_dsb_advance(const DsbArgs A)
 {
     __shared__ DsbState S;
     __shared__ double sc[16];
     __shared__ double red[DSB_RED];
     __shared__ int s_flag[2];
-    const long long inst = blockIdx.x;
+    const long long inst = SEL ? (long long)A.list[blockIdx.x] : (long long)blockIdx.x;
     const int t = threadIdx.x, n = A.n, p = A.p, m = A.m;
     int* counters = A.counters + 4 * A.slot;
-    if (inst == 0 && t < 4) A.counters[4 * (A.slot ^ 1) + t] = 0;  // (nobody else touches the other slot during this launch)
+    if (blockIdx.x == 0 && t < 4) A.counters[4 * (A.slot ^ 1) + t] = 0;  // (nobody else touches the other slot during this launch; instance 0 need not be listed)
     {
         const int* src = reinterpret_cast<const int*>(A.state + inst);
         int* dst = reinterpret_cast<int*>(&S);
@@ -780,11 +784,12 @@ struct DsbFinishArgs {
     KbBounds bd;
     const double *pd, *pdb, *pdi, *pdbi, *pc_inv;
     pq_vars r, out;
+    const int* list;  // null: workgroup s is instance s; else one workgroup per entry, workgroup s is instance list[s]
 };
 template <bool PER>
 __global__ __launch_bounds__(DSB_T) void k_dsb_finish(const DsbFinishArgs A)
 {
-    const long long inst = blockIdx.x;
+    const long long inst = A.list ? (long long)A.list[blockIdx.x] : (long long)blockIdx.x;
     const int t = threadIdx.x, n = A.n, p = A.p, m = A.m;
     const size_t on = (size_t)inst * n, op = (size_t)inst * p, om = (size_t)inst * m;
     const DsbVars r = dsb_at(A.r, on, op, om), o = dsb_at(A.out, on, op, om);
@@ -819,38 +824,42 @@ __global__ __launch_bounds__(DSB_T) void k_dsb_finish(const DsbFinishArgs A)
 
 // ---- the data of a setup: upper(P), A' and G' column-major from the caller's stacks
 // mode 0: dst = src (a row-major A is the column-major A'); 1: transpose of a column-major rows x n matrix; 2: upper triangle of a column-major P; 3: of a row-major P.
-// dead: columns of the result that are zeroed (rows of G without a finite bound); instance `inst` reads dead[inst * dead_stride + column]: stride 0 at setup, where
-// the batch shares the mask, `cols` at an update, where an instance may give both bounds of a row infinite and another not
+// dead: columns of the result that are zeroed (rows of G without a finite bound); row `row` of the call reads dead[row * dead_stride + column]: stride 0 at setup, where
+// the batch shares the mask, `cols` at an update, where an instance may give both bounds of a row infinite and another not.
+// list: null = row `row` of src is instance `row`; else total counts the rows of the list and row `row` of src goes to instance list[row].  ONE indexing for the
+// mask in every kernel of an update: `dead` goes by the ROW OF THE CALL, like src (without a list that is the instance); dst alone goes by instance.
 __global__ void k_dsb_ingest(const double* __restrict__ src, double* __restrict__ dst, int n, int cols, long long total, int mode, const int* __restrict__ dead,
-                             int dead_stride)
+                             int dead_stride, const int* __restrict__ list)
 {
     const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= total) return;
-    const long long per = (long long)n * cols, inst = e / per;
+    const long long per = (long long)n * cols, row = e / per;
     const int q = (int)(e % per), i = q % n, j = q / n;
-    const double* s = src + inst * per;
+    const double* s = src + row * per;
     double v;
     if (mode == 0) v = s[q];
     else if (mode == 1) v = s[j + (size_t)i * cols];
     else if (mode == 2) v = i <= j ? s[q] : 0.0;
     else v = i <= j ? s[j + (size_t)i * n] : 0.0;
-    if (dead && dead[inst * dead_stride + j]) v = 0.0;
-    dst[e] = v;
+    if (dead && dead[row * dead_stride + j]) v = 0.0;
+    dst[(list ? (long long)list[row] : row) * per + q] = v;
 }
 
 // ---- RuizEquilibration::unscale_data, dense (orc_solver.c:243-256), one workgroup per instance, in place: the first step of an update
-// dead: null, or [batch][m]: the columns of G' that disable_inf_constraints zeroes in this update (a row whose two bounds are both given infinite)
+// dead: null, or [rows of the call][m]: the columns of G' that disable_inf_constraints zeroes in this update (a row whose two bounds are both given infinite); it
+// goes by the row of the call (blockIdx.x), as in k_dsb_ingest.  list: as DsbFinishArgs::list
 struct DsbUnscaleArgs {
     int n, p, m;
     KbBounds bd;  // the tables as they stood BEFORE this update: the stored box vectors are packed to them
     double *Pu, *AT, *GT, *c, *b, *h_l, *h_u, *x_l, *x_u, *xbs;
     const double *pdi, *pdbi, *pc_inv;
     const int* dead;
+    const int* list;
 };
 template <bool PER>
 __global__ __launch_bounds__(DSB_RUIZ_T) void k_dsb_unscale(const DsbUnscaleArgs A)
 {
-    const long long inst = blockIdx.x;
+    const long long inst = A.list ? (long long)A.list[blockIdx.x] : (long long)blockIdx.x;
     const int t = threadIdx.x, T = DSB_RUIZ_T, n = A.n, p = A.p, m = A.m, N = n + p + m;
     double* P = A.Pu + inst * (size_t)n * n;
     double* AT = A.AT + inst * (size_t)n * p;
@@ -858,7 +867,7 @@ __global__ __launch_bounds__(DSB_RUIZ_T) void k_dsb_unscale(const DsbUnscaleArgs
     double *c = A.c + inst * (size_t)n, *b = A.b + inst * (size_t)p, *h_l = A.h_l + inst * (size_t)m, *h_u = A.h_u + inst * (size_t)m;
     double *x_l = A.x_l + inst * (size_t)n, *x_u = A.x_u + inst * (size_t)n, *xbs = A.xbs + inst * (size_t)n;
     const double *di = A.pdi + inst * (size_t)N, *dib = A.pdbi + inst * (size_t)n;
-    const int* dead = A.dead ? A.dead + inst * (size_t)m : nullptr;
+    const int* dead = A.dead ? A.dead + blockIdx.x * (size_t)m : nullptr;
     const double ci = A.pc_inv[inst];
     const KbBounds R = kb_bound_row<PER>(A.bd, inst);
     for (int e = t; e < n * n; e += T) {  // scale_P_scalar, then scale_P: the column pass, the row pass (the lower triangle is zero and stays zero)
@@ -890,16 +899,17 @@ struct DsbRuizArgs {
     double epsilon;
     double *Pu, *AT, *GT, *c, *b, *h_l, *h_u, *x_l, *x_u, *xbs;
     double *pd, *pdb, *pdi, *pdbi, *pc, *pc_inv;
+    const int* list;  // as DsbArgs::list
 };
 __device__ __forceinline__ double dsb_limit_scaling(double d) { return d < 1e-4 ? 1.0 : (d > 1e4 ? 1e4 : d); }
 
-template <bool PER>
+template <bool PER, bool SEL>  // (SEL: as at k_dsb_advance)
 __global__ __launch_bounds__(DSB_RUIZ_T) void k_dsb_ruiz(const DsbRuizArgs A)
 {
     __shared__ double red[DSB_RED];
     __shared__ double colmax[PQ_KKT_BATCH_DENSE_MAX_N];
     __shared__ double s_gamma;
-    const long long inst = blockIdx.x;
+    const long long inst = SEL ? (long long)A.list[blockIdx.x] : (long long)blockIdx.x;
     const int t = threadIdx.x, T = DSB_RUIZ_T, n = A.n, p = A.p, m = A.m, N = n + p + m;
     double* P = A.Pu + inst * (size_t)n * n;
     double* AT = A.AT + inst * (size_t)n * p;
@@ -1052,6 +1062,8 @@ struct DsbProblem {
     std::vector<int> try_h;      // 2 m + 2 n + 4: the lists and counts of one instance while they are compared with the shared ones
     std::vector<int> dead_h;     // [batch][m]
     std::vector<int> keep_h;     // per instance only: cnt_h and lists_h as they stood before an update, put back if the update fails on its way
+    std::vector<char> relisted_h;  // per instance only, [batch]: the instance's lists were replaced by an update and it has not been factored since (a solve that
+                                   // includes it factors it in its first round); while any is set the KKT system stays `stale`
     VarSet sets[6];  // result, res_nr, res, step, prox, the results handed out
     DBuf<double> c, b, h_l, h_u, x_l, x_u, xbs, pd, pdb, pdi, pdbi, pc, pc_inv, rho, delta, trace;
     DBuf<int> tab, cnt_d, flags, act, counters;  // tab: has_l[m], has_u[m], x_l_idx, x_u_idx (KbBounds without pos_*); cnt_d: [batch][4], per instance only
@@ -1060,6 +1072,7 @@ struct DsbProblem {
     DBuf<double> raw;
     DBuf<int> dead_d;
     HBuf<double> bnd_h;
+    DBuf<int> sel;  // the list of a call that acts on a list of instances (pq_solver_batch_*_select): `batch` ints, allocated by the first such call -- a setup and a clone leave it empty
     DBuf<DsbState> state;
     HBuf<DsbState> state_h;
     HBuf<int> counters_h;
@@ -1141,37 +1154,71 @@ int dsb_check_refine_cap(const pq_settings& s)
     return PQ_OK;
 }
 
-void dsb_ingest(hipStream_t st, const double* src, double* dst, int batch, int n, int cols, int mode, const int* dead, int dead_stride)
+// the instances a call acts on: the whole batch (dev = null: row j of the call is instance j), or the list of a _select call -- host: the caller's, checked;
+// dev: its copy in the problem's `sel`
+struct DsbRows {
+    const int *host, *dev;
+    int count;
+    int inst(int j) const { return host ? host[j] : j; }
+};
+// the rows of a _select call: the list goes up into `sel`, which the first such call on a problem allocates
+DsbRows dsb_rows_select(DsbProblem* q, hipStream_t st, const int* idx, int count)
 {
-    const long long total = (long long)batch * n * cols;
+    if (!q->sel.p) q->sel.alloc((size_t)q->batch);
+    PQ_HIP(hipMemcpyAsync(q->sel.p, idx, sizeof(int) * (size_t)count, hipMemcpyHostToDevice, st));
+    return DsbRows{idx, q->sel.p, count};
+}
+
+void dsb_ingest(hipStream_t st, const double* src, double* dst, int rows, int n, int cols, int mode, const int* dead, int dead_stride, const int* list)
+{
+    const long long total = (long long)rows * n * cols;
     if (total == 0) return;
-    k_dsb_ingest<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(src, dst, n, cols, total, mode, dead, dead_stride);
+    k_dsb_ingest<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(src, dst, n, cols, total, mode, dead, dead_stride, list);
     PQ_HIP(hipGetLastError());
 }
 
-// one of the caller's matrix stacks into upper(P), A' or G' at `dst` (device): a host stack goes through the problem's staging first
-void dsb_matrix(DsbProblem* q, hipStream_t st, const double* src, double* dst, int cols, int mode, const int* dead, int dead_stride, int mem)
+// one of the caller's matrix stacks (a row per row of the call) into upper(P), A' or G' at `dst` (device, by instance): a host stack goes through the problem's
+// staging first
+void dsb_matrix(DsbProblem* q, hipStream_t st, const DsbRows& rw, const double* src, double* dst, int cols, int mode, const int* dead, int dead_stride, int mem)
 {
     if (!cols) return;
     const double* from = src;
     if (mem == PQ_MEM_HOST) {
-        PQ_HIP(hipMemcpyAsync(q->raw.p, src, sizeof(double) * (size_t)q->batch * q->n * cols, hipMemcpyHostToDevice, st));
+        PQ_HIP(hipMemcpyAsync(q->raw.p, src, sizeof(double) * (size_t)rw.count * q->n * cols, hipMemcpyHostToDevice, st));
         from = q->raw.p;
     }
-    dsb_ingest(st, from, dst, q->batch, q->n, cols, mode, dead, dead_stride);
+    dsb_ingest(st, from, dst, rw.count, q->n, cols, mode, dead, dead_stride, rw.dev);
 }
 
-// scale_data of every instance on the matrices at Pu, AT, GT (device), with the settings as they stand
-void dsb_launch_ruiz(const pq_solver_batch* s, DsbProblem* q, hipStream_t st, double* Pu, double* AT, double* GT, int reuse)
+// one of the caller's vector stacks, [rows of the call][len], into the [batch][len] array at `dst`: the whole batch by one copy; a list by k_kb_scatter_rows,
+// a host stack through the problem's staging first (`raw` holds a matrix stack of the batch, so a vector stack of at most `batch` rows fits)
+void dsb_vector(DsbProblem* q, hipStream_t st, const DsbRows& rw, const double* src, double* dst, size_t len, int mem)
+{
+    const size_t bytes = sizeof(double) * (size_t)rw.count * len;
+    if (!bytes) return;
+    if (!rw.dev) { copy_in(dst, src, bytes, mem, st); return; }
+    const double* from = src;
+    if (mem == PQ_MEM_HOST) {
+        PQ_HIP(hipMemcpyAsync(q->raw.p, src, bytes, hipMemcpyHostToDevice, st));
+        from = q->raw.p;
+    }
+    kb_scatter_rows(st, dst, from, rw.dev, (size_t)rw.count, sizeof(double) * len);
+}
+
+// scale_data of every instance of `rw` on the matrices at Pu, AT, GT (device), with the settings as they stand
+void dsb_launch_ruiz(const pq_solver_batch* s, DsbProblem* q, hipStream_t st, const DsbRows& rw, double* Pu, double* AT, double* GT, int reuse)
 {
     DsbRuizArgs r;
     r.n = q->n; r.p = q->p; r.m = q->m; r.bd = q->bounds(); r.max_iter = s->settings.preconditioner_iter; r.scale_cost = s->settings.preconditioner_scale_cost;
-    r.reuse = reuse;
+    r.reuse = reuse; r.list = rw.dev;
     r.epsilon = 1e-3;
     r.Pu = Pu; r.AT = AT; r.GT = GT; r.c = q->c.p; r.b = q->b.p; r.h_l = q->h_l.p; r.h_u = q->h_u.p; r.x_l = q->x_l.p; r.x_u = q->x_u.p; r.xbs = q->xbs.p;
     r.pd = q->pd.p; r.pdb = q->pdb.p; r.pdi = q->pdi.p; r.pdbi = q->pdbi.p; r.pc = q->pc.p; r.pc_inv = q->pc_inv.p;
-    if (q->per_inst) k_dsb_ruiz<true><<<q->batch, DSB_RUIZ_T, 0, st>>>(r);
-    else k_dsb_ruiz<false><<<q->batch, DSB_RUIZ_T, 0, st>>>(r);
+    if (q->per_inst) {
+        if (rw.dev) k_dsb_ruiz<true, true><<<rw.count, DSB_RUIZ_T, 0, st>>>(r);
+        else k_dsb_ruiz<true, false><<<rw.count, DSB_RUIZ_T, 0, st>>>(r);
+    } else if (rw.dev) k_dsb_ruiz<false, true><<<rw.count, DSB_RUIZ_T, 0, st>>>(r);
+    else k_dsb_ruiz<false, false><<<rw.count, DSB_RUIZ_T, 0, st>>>(r);
     PQ_HIP(hipGetLastError());
 }
 
@@ -1219,6 +1266,30 @@ void dsb_bound_lists(int m, int n, const double* h_l, const double* h_u, const d
         if (out && (setup || v))
             for (int j = cnt[k]; j < n; ++j) out[j] = 0.0;
     }
+}
+
+// ---- the checks of the calls that act on a list of instances, before any device call.  fn: the call's name, which opens every text
+int dsb_check_list(const char* fn, const pq_solver_batch* s, const int* idx, int count)
+{
+    if (!s) return fail(PQ_ERR_INVALID, "%s: null handle", fn);
+    if (!idx) return fail(PQ_ERR_INVALID, "%s: idx is null", fn);
+    if (count < 1) return fail(PQ_ERR_INVALID, "%s: count = %d, count >= 1 wanted", fn, count);
+    return PQ_OK;
+}
+// the handle is set up, every entry is an instance, and -- unique -- none is listed twice (two workgroups on one instance would race)
+int dsb_check_entries(const char* fn, const pq_solver_batch* s, const int* idx, int count, bool unique)
+{
+    if (!s->pr) return fail(PQ_ERR_INVALID, "%s: the handle is not set up (there is no instance to list)", fn);
+    const int batch = s->pr->batch;
+    for (int j = 0; j < count; ++j)
+        if (idx[j] < 0 || idx[j] >= batch) return fail(PQ_ERR_INVALID, "%s: idx[%d] = %d outside [0, %d)", fn, j, idx[j], batch);
+    if (!unique) return PQ_OK;
+    std::vector<int> first((size_t)batch, -1);
+    for (int j = 0; j < count; ++j) {
+        if (first[idx[j]] >= 0) return fail(PQ_ERR_INVALID, "%s: idx[%d] = %d is listed twice (idx[%d] too)", fn, j, idx[j], first[idx[j]]);
+        first[idx[j]] = j;
+    }
+    return PQ_OK;
 }
 
 void dsb_reset_state(pq_solver_batch* s)
@@ -1272,6 +1343,8 @@ void dsb_clone_problem(const pq_solver_batch* s, pq_solver_batch* c, const int* 
     if (q->per_inst) {
         d->cnt_h.resize(4 * (size_t)R); d->lists_h.resize((size_t)R * (2 * (size_t)m + 2 * (size_t)n)); d->fin_h.resize(d->lists_h.size());
         d->keep_h.assign(d->cnt_h.size() + d->lists_h.size(), 0);
+        d->relisted_h.resize(B);
+        kb_gather_host(d->relisted_h.data(), q->relisted_h.data(), idx, count, 1);
         kb_gather_host(d->cnt_h.data(), q->cnt_h.data(), idx, count, 4);
         for (int k = 0; k < 4; ++k) {
             kb_gather_host(d->list(k, 0), q->list(k, 0), idx, count, (size_t)(k < 2 ? m : n));
@@ -1447,7 +1520,7 @@ int pq_solver_batch_setup_dense(pq_solver_batch* s, int batch, int n, int p, int
         const int R = q->rows = q->per_inst ? batch : 1;
         q->cnt_h.assign(4 * (size_t)R, 0); q->lists_h.assign((size_t)R * (2 * (size_t)m + 2 * (size_t)n), 0); q->fin_h.assign(q->lists_h.size(), 0);
         q->try_h.assign(2 * (size_t)m + 2 * (size_t)n + 4, 0); q->dead_h.assign(B * m, 0);
-        if (q->per_inst) q->keep_h.assign(q->cnt_h.size() + q->lists_h.size(), 0);
+        if (q->per_inst) { q->keep_h.assign(q->cnt_h.size() + q->lists_h.size(), 0); q->relisted_h.assign(B, 0); }
         std::vector<double> vhl(B * m), vhu(B * m), vxl(B * n, 0.0), vxu(B * n, 0.0);
         for (size_t i = 0; i < B; ++i) {
             // the lists of instance i: its own row, or with shared sets those of instance 0, which every other instance must reproduce (with the rows it drops)
@@ -1476,9 +1549,10 @@ int pq_solver_batch_setup_dense(pq_solver_batch* s, int batch, int n, int p, int
         if (q->per_inst) PQ_HIP(hipMemcpyAsync(q->cnt_d.p, q->cnt_h.data(), sizeof(int) * 4 * B, hipMemcpyHostToDevice, st));
         const int dead_stride = q->per_inst ? m : 0;  // (shared sets: every instance drops the rows instance 0 drops)
         if (m > 0) PQ_HIP(hipMemcpyAsync(q->dead_d.p, q->dead_h.data(), sizeof(int) * (size_t)R * m, hipMemcpyHostToDevice, st));
-        dsb_matrix(q.get(), st, P, Pu.p, n, order == PQ_COL_MAJOR ? 2 : 3, nullptr, 0, mem);
-        dsb_matrix(q.get(), st, A, AT.p, p, order == PQ_COL_MAJOR ? 1 : 0, nullptr, 0, mem);
-        dsb_matrix(q.get(), st, G, GT.p, m, order == PQ_COL_MAJOR ? 1 : 0, q->dead_d.p, dead_stride, mem);
+        const DsbRows all{nullptr, nullptr, batch};
+        dsb_matrix(q.get(), st, all, P, Pu.p, n, order == PQ_COL_MAJOR ? 2 : 3, nullptr, 0, mem);
+        dsb_matrix(q.get(), st, all, A, AT.p, p, order == PQ_COL_MAJOR ? 1 : 0, nullptr, 0, mem);
+        dsb_matrix(q.get(), st, all, G, GT.p, m, order == PQ_COL_MAJOR ? 1 : 0, q->dead_d.p, dead_stride, mem);
         auto up = [&](DBuf<double>& d, const std::vector<double>& v, size_t count) {
             d.alloc(count);
             if (count) PQ_HIP(hipMemcpyAsync(d.p, v.data(), sizeof(double) * count, hipMemcpyHostToDevice, st));
@@ -1486,7 +1560,7 @@ int pq_solver_batch_setup_dense(pq_solver_batch* s, int batch, int n, int p, int
         const std::vector<double> ones(B * n, 1.0);
         up(q->c, hc, B * n); up(q->b, hb, B * p); up(q->h_l, vhl, B * m); up(q->h_u, vhu, B * m); up(q->x_l, vxl, B * n); up(q->x_u, vxu, B * n); up(q->xbs, ones, B * n);
         q->pd.alloc(B * N); q->pdi.alloc(B * N); q->pdb.alloc(B * n); q->pdbi.alloc(B * n); q->pc.alloc(B); q->pc_inv.alloc(B);
-        dsb_launch_ruiz(s, q.get(), st, Pu.p, AT.p, GT.p, 0);
+        dsb_launch_ruiz(s, q.get(), st, all, Pu.p, AT.p, GT.p, 0);
         stream_wait(st);
         pq_kktsys_batch* ks = nullptr;
         const int* cn = q->cnt_h.data();
@@ -1514,6 +1588,152 @@ int pq_solver_batch_setup_dense(pq_solver_batch* s, int batch, int n, int p, int
     });
 }
 
+// ---- update: pq_solver_batch_update_dense (idx = null: row j of every array is instance j, `count` is the batch) and pq_solver_batch_update_dense_select (row j is
+// instance idx[j]; the list has been checked) are this one sequence.  Everything of the call goes by its ROWS: the fetched and the packed bound vectors, the mask of
+// the rows of G it drops (dead_h, dead_d); what is kept per instance -- lists, tables, data -- is reached through the row's instance.  With a list every launch is
+// sized by it and no workgroup runs on an instance that is not listed.
+static int dsb_update(pq_solver_batch* s, const int* idx, int count, const double* P, const double* c, const double* A, const double* b, const double* G, const double* h_l,
+                      const double* h_u, const double* x_l, const double* x_u, int mem, int order)
+{
+    DsbProblem* q = s->pr.get();
+    return guarded([&] {
+        PQ_HIP(hipSetDevice(s->device));
+        const auto w0 = std::chrono::steady_clock::now();
+        const int batch = q->batch, n = q->n, p = q->p, m = q->m;
+        const size_t B = (size_t)batch, R = (size_t)count, half = B * (2 * (size_t)m + 2 * (size_t)n);
+        pq_kktsys_batch* ks = q->ks.get();
+        pq_kkt_batch* kb = pq_kktsys_batch_backend(ks);
+        hipStream_t st = ksb_stream(ks);
+        DsbRows rw{idx, nullptr, count};  // (the list goes up behind the host's checks: a refused call has done nothing on the device and allocated nothing)
+        // ---- the host: the lists the reference would hold after this call (dsb_bound_lists): with shared sets they must be the setup's, else they replace the instance's own
+        const double* given[4] = {h_l, h_u, x_l, x_u};
+        const double* hv[4];
+        double* packed[4];
+        bool fetched = false;
+        for (int k = 0; k < 4; ++k) {
+            const size_t off = k == 0 ? 0 : k == 1 ? B * m : k == 2 ? 2 * B * m : 2 * B * m + B * n, cnt = R * (k < 2 ? m : n);
+            packed[k] = q->bnd_h.p + half + off;
+            hv[k] = given[k];
+            if (given[k] && mem == PQ_MEM_DEVICE && cnt) {
+                PQ_HIP(hipMemcpyAsync(q->bnd_h.p + off, given[k], sizeof(double) * cnt, hipMemcpyDeviceToHost, st));
+                hv[k] = q->bnd_h.p + off;
+                fetched = true;
+            }
+        }
+        if (fetched) stream_wait(st);
+        const bool rows = h_l || h_u;
+        // sets per instance: the host images of the call's instances are rewritten below, before the device and the KKT system follow.  Should a call on the way fail,
+        // those rows go back to what the device still holds (a failure after the new tables are on their way leaves the device ahead of the host: then only a new
+        // setup helps).  Only what the call touches is kept and put back.
+        struct Keep {
+            DsbProblem* q;
+            const DsbRows& rw;
+            bool done = false;
+            void move(bool back)
+            {
+                int* kc = q->keep_h.data();
+                int* kl = kc + q->cnt_h.size();
+                for (int j = 0; j < rw.count; ++j) {
+                    const size_t i = (size_t)rw.inst(j);
+                    int* a = q->cnt_h.data() + 4 * i;
+                    if (back) std::copy(kc + 4 * i, kc + 4 * i + 4, a);
+                    else std::copy(a, a + 4, kc + 4 * i);
+                    for (int k = 0; k < 4; ++k) {
+                        int* l = q->list(k, i);
+                        int* kp = kl + (l - q->lists_h.data());
+                        const int len = k < 2 ? q->m : q->n;
+                        if (back) std::copy(kp, kp + len, l);
+                        else std::copy(l, l + len, kp);
+                    }
+                }
+            }
+            Keep(DsbProblem* p, const DsbRows& r) : q(p), rw(r)
+            {
+                if (q->per_inst) move(false);
+            }
+            ~Keep()
+            {
+                if (done || !q->per_inst) return;
+                move(true);
+                q->fill_fin();
+                q->fill_tab();
+            }
+        } keep(q, rw);
+        bool any_dead = false;
+        for (size_t j = 0; j < R; ++j) {
+            const size_t i = (size_t)rw.inst((int)j), r = q->per_inst ? i : 0;
+            const int* fin[4] = {q->fin(0, r), q->fin(1, r), q->fin(2, r), q->fin(3, r)};
+            int* t = q->try_h.data();
+            int* lst[4] = {q->per_inst ? q->list(0, i) : t, q->per_inst ? q->list(1, i) : t + m, q->per_inst ? q->list(2, i) : t + 2 * (size_t)m,
+                           q->per_inst ? q->list(3, i) : t + 2 * (size_t)m + n};
+            int* cnt = q->per_inst ? q->cnt_h.data() + 4 * i : t + 2 * (size_t)m + 2 * (size_t)n;
+            double* out[4] = {packed[0] + j * m, packed[1] + j * m, packed[2] + j * n, packed[3] + j * n};
+            dsb_bound_lists(m, n, h_l ? hv[0] + j * m : nullptr, h_u ? hv[1] + j * m : nullptr, x_l ? hv[2] + j * n : nullptr, x_u ? hv[3] + j * n : nullptr, fin, cnt, lst,
+                            q->dead_h.data() + j * m, out);
+            for (int e = 0; e < m && rows && !any_dead; ++e) any_dead = q->dead_h[j * m + e] != 0;
+            if (q->per_inst) continue;
+            for (int k = 0; k < 4; ++k) {  // shared sets: the lists are the setup's, which the KKT system and `tab` carry
+                const int* old = q->list(k, 0);
+                const int co = q->cnt_h[k];
+                int e = 0;
+                while (e < cnt[k] && e < co && lst[k][e] == old[e]) ++e;
+                if (e == cnt[k] && e == co) continue;
+                const int at = e == cnt[k] ? old[e] : e == co ? lst[k][e] : std::min(lst[k][e], old[e]);
+                return fail(PQ_ERR_INVALID, "dense solver batch: update: the set of finite bounds of %s %d%s changes in instance %zu (it is fixed at setup)", k < 2 ? "row" : "variable", at,
+                            k < 2 ? " of G" : "", i);
+            }
+        }
+        if (q->per_inst) {
+            q->fill_fin(); q->fill_tab();
+            for (int j = 0; j < count; ++j) q->relisted_h[rw.inst(j)] = 1;
+        }
+        // ---- the device: unscale, assign, rescale, all where the data stand
+        if (idx) rw = dsb_rows_select(q, st, idx, count);
+        PQ_HIP(hipEventRecord(q->ev[0], st));
+        const int* dd = nullptr;
+        if (any_dead) {
+            PQ_HIP(hipMemcpyAsync(q->dead_d.p, q->dead_h.data(), sizeof(int) * R * m, hipMemcpyHostToDevice, st));
+            dd = q->dead_d.p;
+        }
+        DsbUnscaleArgs u;
+        u.n = n; u.p = p; u.m = m; u.list = rw.dev; u.bd = q->bounds();  // (the device still holds the tables of before this call)
+        u.Pu = kb->Pu.p; u.AT = kb->AT.p; u.GT = kb->GT.p; u.c = q->c.p; u.b = q->b.p; u.h_l = q->h_l.p; u.h_u = q->h_u.p; u.x_l = q->x_l.p; u.x_u = q->x_u.p; u.xbs = q->xbs.p;
+        u.pdi = q->pdi.p; u.pdbi = q->pdbi.p; u.pc_inv = q->pc_inv.p; u.dead = dd;
+        if (q->per_inst) k_dsb_unscale<true><<<count, DSB_RUIZ_T, 0, st>>>(u);
+        else k_dsb_unscale<false><<<count, DSB_RUIZ_T, 0, st>>>(u);
+        PQ_HIP(hipGetLastError());
+        if (q->per_inst) {  // the sets of after this call: the tables here (behind the unscaling on the stream) and the KKT system's.  (The whole host images go up:
+                            // the rows of the instances the call does not act on are the bytes the device holds already)
+            PQ_HIP(hipMemcpyAsync(q->tab.p, q->tab_h.data(), sizeof(int) * q->tab_h.size(), hipMemcpyHostToDevice, st));
+            PQ_HIP(hipMemcpyAsync(q->cnt_d.p, q->cnt_h.data(), sizeof(int) * 4 * B, hipMemcpyHostToDevice, st));
+            if (int rc = pq_kktsys_batch_set_lists(ks, q->cnt_h.data(), q->list(0, 0), q->list(1, 0), q->list(2, 0), q->list(3, 0))) return rc;
+        }
+        int opt = PQ_KKT_UPDATE_NONE;
+        if (P) { dsb_matrix(q, st, rw, P, kb->Pu.p, n, order == PQ_COL_MAJOR ? 2 : 3, nullptr, 0, mem); opt |= PQ_KKT_UPDATE_P; }
+        if (A) { dsb_matrix(q, st, rw, A, kb->AT.p, p, order == PQ_COL_MAJOR ? 1 : 0, nullptr, 0, mem); opt |= PQ_KKT_UPDATE_A; }
+        if (G) { dsb_matrix(q, st, rw, G, kb->GT.p, m, order == PQ_COL_MAJOR ? 1 : 0, dd, m, mem); opt |= PQ_KKT_UPDATE_G; }
+        if (c) dsb_vector(q, st, rw, c, q->c.p, (size_t)n, mem);
+        if (b) dsb_vector(q, st, rw, b, q->b.p, (size_t)p, mem);
+        DBuf<double>* dst[4] = {&q->h_l, &q->h_u, &q->x_l, &q->x_u};
+        for (int k = 0; k < 4; ++k)
+            if (given[k]) dsb_vector(q, st, rw, packed[k], dst[k]->p, (size_t)(k < 2 ? m : n), PQ_MEM_HOST);
+        const bool reuse = s->settings.preconditioner_reuse_on_update || opt == PQ_KKT_UPDATE_NONE;
+        dsb_launch_ruiz(s, q, st, rw, kb->Pu.p, kb->AT.p, kb->GT.p, reuse);
+        // A'A: the reference takes it again only with A; with new scalings it has to follow A' (the header says why)
+        ksb_data_rewritten(ks, opt, A != nullptr || !reuse, q->xbs.p, rw.dev, count);
+        PQ_HIP(hipEventRecord(q->ev[1], st));
+        stream_wait(st);
+        float ms = 0.f;
+        PQ_HIP(hipEventElapsedTime(&ms, q->ev[0], q->ev[1]));
+        const double wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
+        for (int j = 0; j < count; ++j) q->state_h.p[rw.inst(j)].info.update_time = wall * 1e-3;  // (the call's)
+        s->update_wall_ms = wall; s->update_device_ms = ms;
+        s->updated = true;
+        keep.done = true;
+        return 1;
+    });
+}
+
 int pq_solver_batch_update_dense(pq_solver_batch* s, const double* P, const double* c, const double* A, const double* b, const double* G, const double* h_l,
                                  const double* h_u, const double* x_l, const double* x_u, int mem, int order)
 {
@@ -1524,119 +1744,21 @@ int pq_solver_batch_update_dense(pq_solver_batch* s, const double* P, const doub
     if (!q) return fail(PQ_ERR_INVALID, "dense solver batch: update before setup");
     if (q->p == 0 && (A || b)) return fail(PQ_ERR_INVALID, "dense solver batch: update: A or b given, p = 0");
     if (q->m == 0 && (G || h_l || h_u)) return fail(PQ_ERR_INVALID, "dense solver batch: update: G, h_l or h_u given, m = 0");
-    return guarded([&] {
-        PQ_HIP(hipSetDevice(s->device));
-        const auto w0 = std::chrono::steady_clock::now();
-        const int batch = q->batch, n = q->n, p = q->p, m = q->m;
-        const size_t B = (size_t)batch, half = B * (2 * (size_t)m + 2 * (size_t)n);
-        pq_kktsys_batch* ks = q->ks.get();
-        pq_kkt_batch* kb = pq_kktsys_batch_backend(ks);
-        hipStream_t st = ksb_stream(ks);
-        // ---- the host: the lists the reference would hold after this call (dsb_bound_lists): with shared sets they must be the setup's, else they replace the instance's own
-        const double* given[4] = {h_l, h_u, x_l, x_u};
-        const double* hv[4];
-        double* packed[4];
-        bool fetched = false;
-        for (int k = 0; k < 4; ++k) {
-            const size_t off = k == 0 ? 0 : k == 1 ? B * m : k == 2 ? 2 * B * m : 2 * B * m + B * n, count = B * (k < 2 ? m : n);
-            packed[k] = q->bnd_h.p + half + off;
-            hv[k] = given[k];
-            if (given[k] && mem == PQ_MEM_DEVICE && count) {
-                PQ_HIP(hipMemcpyAsync(q->bnd_h.p + off, given[k], sizeof(double) * count, hipMemcpyDeviceToHost, st));
-                hv[k] = q->bnd_h.p + off;
-                fetched = true;
-            }
-        }
-        if (fetched) stream_wait(st);
-        const bool rows = h_l || h_u;
-        // sets per instance: the host images are rewritten below, before the device and the KKT system follow.  Should a call on the way fail, they go back to what
-        // the device still holds (a failure after the new tables are on their way leaves the device ahead of the host: then only a new setup helps)
-        struct Keep {
-            DsbProblem* q;
-            bool done = false;
-            explicit Keep(DsbProblem* p) : q(p)
-            {
-                if (!q->per_inst) return;
-                std::copy(q->cnt_h.begin(), q->cnt_h.end(), q->keep_h.begin());
-                std::copy(q->lists_h.begin(), q->lists_h.end(), q->keep_h.begin() + q->cnt_h.size());
-            }
-            ~Keep()
-            {
-                if (done || !q->per_inst) return;
-                std::copy(q->keep_h.begin(), q->keep_h.begin() + q->cnt_h.size(), q->cnt_h.begin());
-                std::copy(q->keep_h.begin() + q->cnt_h.size(), q->keep_h.end(), q->lists_h.begin());
-                q->fill_fin();
-                q->fill_tab();
-            }
-        } keep(q);
-        bool any_dead = false;
-        for (size_t i = 0; i < B; ++i) {
-            const size_t r = q->per_inst ? i : 0;
-            const int* fin[4] = {q->fin(0, r), q->fin(1, r), q->fin(2, r), q->fin(3, r)};
-            int* t = q->try_h.data();
-            int* idx[4] = {q->per_inst ? q->list(0, i) : t, q->per_inst ? q->list(1, i) : t + m, q->per_inst ? q->list(2, i) : t + 2 * (size_t)m,
-                           q->per_inst ? q->list(3, i) : t + 2 * (size_t)m + n};
-            int* cnt = q->per_inst ? q->cnt_h.data() + 4 * i : t + 2 * (size_t)m + 2 * (size_t)n;
-            double* out[4] = {packed[0] + i * m, packed[1] + i * m, packed[2] + i * n, packed[3] + i * n};
-            dsb_bound_lists(m, n, h_l ? hv[0] + i * m : nullptr, h_u ? hv[1] + i * m : nullptr, x_l ? hv[2] + i * n : nullptr, x_u ? hv[3] + i * n : nullptr, fin, cnt, idx,
-                            q->dead_h.data() + i * m, out);
-            for (int j = 0; j < m && rows && !any_dead; ++j) any_dead = q->dead_h[i * m + j] != 0;
-            if (q->per_inst) continue;
-            for (int k = 0; k < 4; ++k) {  // shared sets: the lists are the setup's, which the KKT system and `tab` carry
-                const int* old = q->list(k, 0);
-                const int co = q->cnt_h[k];
-                int e = 0;
-                while (e < cnt[k] && e < co && idx[k][e] == old[e]) ++e;
-                if (e == cnt[k] && e == co) continue;
-                const int j = e == cnt[k] ? old[e] : e == co ? idx[k][e] : std::min(idx[k][e], old[e]);
-                return fail(PQ_ERR_INVALID, "dense solver batch: update: the set of finite bounds of %s %d%s changes in instance %zu (it is fixed at setup)", k < 2 ? "row" : "variable", j,
-                            k < 2 ? " of G" : "", i);
-            }
-        }
-        if (q->per_inst) { q->fill_fin(); q->fill_tab(); }
-        // ---- the device: unscale, assign, rescale, all where the data stand
-        PQ_HIP(hipEventRecord(q->ev[0], st));
-        const int* dd = nullptr;
-        if (any_dead) {
-            PQ_HIP(hipMemcpyAsync(q->dead_d.p, q->dead_h.data(), sizeof(int) * B * m, hipMemcpyHostToDevice, st));
-            dd = q->dead_d.p;
-        }
-        DsbUnscaleArgs u;
-        u.n = n; u.p = p; u.m = m; u.bd = q->bounds();  // (the device still holds the tables of before this call)
-        u.Pu = kb->Pu.p; u.AT = kb->AT.p; u.GT = kb->GT.p; u.c = q->c.p; u.b = q->b.p; u.h_l = q->h_l.p; u.h_u = q->h_u.p; u.x_l = q->x_l.p; u.x_u = q->x_u.p; u.xbs = q->xbs.p;
-        u.pdi = q->pdi.p; u.pdbi = q->pdbi.p; u.pc_inv = q->pc_inv.p; u.dead = dd;
-        if (q->per_inst) k_dsb_unscale<true><<<batch, DSB_RUIZ_T, 0, st>>>(u);
-        else k_dsb_unscale<false><<<batch, DSB_RUIZ_T, 0, st>>>(u);
-        PQ_HIP(hipGetLastError());
-        if (q->per_inst) {  // the sets of after this call: the tables here (behind the unscaling on the stream) and the KKT system's
-            PQ_HIP(hipMemcpyAsync(q->tab.p, q->tab_h.data(), sizeof(int) * q->tab_h.size(), hipMemcpyHostToDevice, st));
-            PQ_HIP(hipMemcpyAsync(q->cnt_d.p, q->cnt_h.data(), sizeof(int) * 4 * B, hipMemcpyHostToDevice, st));
-            if (int rc = pq_kktsys_batch_set_lists(ks, q->cnt_h.data(), q->list(0, 0), q->list(1, 0), q->list(2, 0), q->list(3, 0))) return rc;
-        }
-        int opt = PQ_KKT_UPDATE_NONE;
-        if (P) { dsb_matrix(q, st, P, kb->Pu.p, n, order == PQ_COL_MAJOR ? 2 : 3, nullptr, 0, mem); opt |= PQ_KKT_UPDATE_P; }
-        if (A) { dsb_matrix(q, st, A, kb->AT.p, p, order == PQ_COL_MAJOR ? 1 : 0, nullptr, 0, mem); opt |= PQ_KKT_UPDATE_A; }
-        if (G) { dsb_matrix(q, st, G, kb->GT.p, m, order == PQ_COL_MAJOR ? 1 : 0, dd, m, mem); opt |= PQ_KKT_UPDATE_G; }
-        if (c) copy_in(q->c.p, c, sizeof(double) * B * n, mem, st);
-        if (b) copy_in(q->b.p, b, sizeof(double) * B * p, mem, st);
-        DBuf<double>* dst[4] = {&q->h_l, &q->h_u, &q->x_l, &q->x_u};
-        for (int k = 0; k < 4; ++k)
-            if (given[k]) copy_in(dst[k]->p, packed[k], dst[k]->bytes(), PQ_MEM_HOST, st);
-        const bool reuse = s->settings.preconditioner_reuse_on_update || opt == PQ_KKT_UPDATE_NONE;
-        dsb_launch_ruiz(s, q, st, kb->Pu.p, kb->AT.p, kb->GT.p, reuse);
-        // A'A: the reference takes it again only with A; with new scalings it has to follow A' (the header says why)
-        ksb_data_rewritten(ks, opt, A != nullptr || !reuse, q->xbs.p);
-        PQ_HIP(hipEventRecord(q->ev[1], st));
-        stream_wait(st);
-        float ms = 0.f;
-        PQ_HIP(hipEventElapsedTime(&ms, q->ev[0], q->ev[1]));
-        const double wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
-        for (int i = 0; i < batch; ++i) q->state_h.p[i].info.update_time = wall * 1e-3;  // (the batch's)
-        s->update_wall_ms = wall; s->update_device_ms = ms;
-        s->updated = true;
-        keep.done = true;
-        return 1;
-    });
+    return dsb_update(s, nullptr, q->batch, P, c, A, b, G, h_l, h_u, x_l, x_u, mem, order);
+}
+
+int pq_solver_batch_update_dense_select(pq_solver_batch* s, const int* idx, int count, const double* P, const double* c, const double* A, const double* b, const double* G,
+                                        const double* h_l, const double* h_u, const double* x_l, const double* x_u, int mem, int order)
+{
+    static const char* const fn = "pq_solver_batch_update_dense_select";
+    if (int rc = dsb_check_list(fn, s, idx, count)) return rc;
+    if (kb_bad_mem(mem)) return fail(PQ_ERR_INVALID, "%s: bad mem %d", fn, mem);
+    if (order != PQ_COL_MAJOR && order != PQ_ROW_MAJOR) return fail(PQ_ERR_INVALID, "%s: bad order %d", fn, order);
+    if (int rc = dsb_check_entries(fn, s, idx, count, true)) return rc;
+    const DsbProblem* q = s->pr.get();
+    if (q->p == 0 && (A || b)) return fail(PQ_ERR_INVALID, "%s: A or b given, p = 0", fn);
+    if (q->m == 0 && (G || h_l || h_u)) return fail(PQ_ERR_INVALID, "%s: G, h_l or h_u given, m = 0", fn);
+    return dsb_update(s, idx, count, P, c, A, b, G, h_l, h_u, x_l, x_u, mem, order);
 }
 
 int pq_solver_batch_last_update_ms(const pq_solver_batch* s, double out2[2])
@@ -1646,17 +1768,17 @@ int pq_solver_batch_last_update_ms(const pq_solver_batch* s, double out2[2])
     return PQ_OK;
 }
 
-int pq_solver_batch_solve(pq_solver_batch* s)
+// ---- solve: pq_solver_batch_solve (idx = null, `count` is the batch) and pq_solver_batch_solve_select (the `count` distinct instances idx[..], checked) are this
+// one loop.  With a list every launch has one workgroup (in the packed factor kernel one wave) per listed instance, the round loop ends when the DONE counter
+// reaches count, and only the listed infos are written on the host.  The state records travel whole in both forms: the host image goes up before the first round and
+// comes back after the last -- between the two no workgroup has touched the record of an instance that is not listed, so its host record gets its own bytes back.
+static int dsb_solve(pq_solver_batch* s, const int* idx, int count)
 {
-    if (!s) return fail(PQ_ERR_INVALID, "null argument");
     DsbProblem* q = s->pr.get();
-    if (!q) {
-        s->invalid_info.status = PQ_UNSOLVED;
-        return fail(PQ_ERR_INVALID, "dense solver batch: solve before setup");
-    }
+    const DsbRows on_host{idx, nullptr, count};
     if (int rc = dsb_check_refine_cap(s->settings)) return rc;
     if (!dsb_verify_settings(s->settings)) {  // solver.hpp:75-79: no launch
-        for (int i = 0; i < q->batch; ++i) q->state_h.p[i].info.status = PQ_INVALID_SETTINGS;
+        for (int j = 0; j < count; ++j) q->state_h.p[on_host.inst(j)].info.status = PQ_INVALID_SETTINGS;
         return fail(PQ_ERR_INVALID, "dense solver batch: invalid settings");
     }
     int solved = 0, rc_loop = PQ_OK;
@@ -1671,12 +1793,13 @@ int pq_solver_batch_solve(pq_solver_batch* s)
         }
         hipStream_t st = ksb_stream(ks);
         pq_kkt_batch* kb = pq_kktsys_batch_backend(ks);
-        // every instance starts at INIT (the info fields a solve does not reset keep their values)
-        for (int i = 0; i < batch; ++i) q->state_h.p[i].stage = ST_INIT;
+        const DsbRows rw = idx ? dsb_rows_select(q, st, idx, count) : DsbRows{nullptr, nullptr, batch};
+        // every instance of the call starts at INIT (the info fields a solve does not reset keep their values)
+        for (int j = 0; j < count; ++j) q->state_h.p[rw.inst(j)].stage = ST_INIT;
         PQ_HIP(hipMemcpyAsync(q->state.p, q->state_h.p, sizeof(DsbState) * batch, hipMemcpyHostToDevice, st));
         PQ_HIP(hipMemsetAsync(q->counters.p, 0, sizeof(int) * 8, st));
         DsbArgs a;
-        a.n = n; a.p = p; a.m = m; a.bd = q->bounds(); a.batch = batch; a.trace_max = q->trace_max; a.slot = 0;
+        a.n = n; a.p = p; a.m = m; a.bd = q->bounds(); a.batch = batch; a.trace_max = q->trace_max; a.slot = 0; a.list = rw.dev;
         a.set = s->settings;
         a.Pu = kb->Pu.p; a.AT = kb->AT.p; a.GT = kb->GT.p;
         a.c = q->c.p; a.b = q->b.p; a.h_l = q->h_l.p; a.h_u = q->h_u.p; a.x_l = q->x_l.p; a.x_u = q->x_u.p; a.xbs = q->xbs.p;
@@ -1699,8 +1822,11 @@ int pq_solver_batch_solve(pq_solver_batch* s)
         for (; round < bound && !done; ++round) {
             a.slot = (int)(round & 1);
             PQ_HIP(hipEventRecord(q->ev[0], st));
-            if (q->per_inst) k_dsb_advance<true><<<batch, DSB_T, 0, st>>>(a);
-            else k_dsb_advance<false><<<batch, DSB_T, 0, st>>>(a);
+            if (q->per_inst) {
+                if (rw.dev) k_dsb_advance<true, true><<<count, DSB_T, 0, st>>>(a);
+                else k_dsb_advance<true, false><<<count, DSB_T, 0, st>>>(a);
+            } else if (rw.dev) k_dsb_advance<false, true><<<count, DSB_T, 0, st>>>(a);
+            else k_dsb_advance<false, false><<<count, DSB_T, 0, st>>>(a);
             PQ_HIP(hipGetLastError());
             PQ_HIP(hipEventRecord(q->ev[1], st));
             PQ_HIP(hipMemcpyAsync(q->counters_h.p, q->counters.p + 4 * a.slot, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
@@ -1710,31 +1836,31 @@ int pq_solver_batch_solve(pq_solver_batch* s)
             if (pend_f) { const double t = elapsed(2); dev_ms += t; f_ms += t; pend_f = false; }
             if (pend_s) { const double t = elapsed(4); dev_ms += t; s_ms += t; pend_s = false; }
             const int nf = q->counters_h.p[WANT_FACTOR], ns = q->counters_h.p[WANT_SOLVE], nd = q->counters_h.p[WANT_DONE];
-            if (nd == batch) { done = true; continue; }
+            if (nd == count) { done = true; continue; }
             if (nf > 0) {
                 PQ_HIP(hipEventRecord(q->ev[2], st));
-                // (any factor launch, masked or not, ends the KKT system's `stale` state after pq_kktsys_batch_set_lists: right here, because after an update every
-                // instance starts at INIT and the first round's launch factors them all)
-                ksb_launch_factor(ks, q->flags.p, q->rho.p, q->delta.p, q->sets[0].v, a.act_f);
+                // (a factor launch over the whole batch ends the KKT system's `stale` state after pq_kktsys_batch_set_lists: right here, because after an update every
+                // instance starts at INIT and the first round's launch factors them all; one over a list leaves it to the end of this call)
+                ksb_launch_factor(ks, q->flags.p, q->rho.p, q->delta.p, q->sets[0].v, a.act_f, rw.dev, count);
                 PQ_HIP(hipEventRecord(q->ev[3], st));
                 pend_f = true;
                 ++launches;
             }
             if (ns > 0) {
                 PQ_HIP(hipEventRecord(q->ev[4], st));
-                ksb_launch_solve(ks, q->sets[2].v, q->sets[3].v, a.act_s);
+                ksb_launch_solve(ks, q->sets[2].v, q->sets[3].v, a.act_s, rw.dev, count);
                 PQ_HIP(hipEventRecord(q->ev[5], st));
                 pend_s = true;
                 ++launches;
             }
         }
         DsbFinishArgs f;
-        f.n = n; f.p = p; f.m = m; f.bd = q->bounds();
+        f.n = n; f.p = p; f.m = m; f.list = rw.dev; f.bd = q->bounds();
         f.pd = q->pd.p; f.pdb = q->pdb.p; f.pdi = q->pdi.p; f.pdbi = q->pdbi.p; f.pc_inv = q->pc_inv.p;
         f.r = q->sets[0].v; f.out = q->sets[5].v;
         PQ_HIP(hipEventRecord(q->ev[6], st));
-        if (q->per_inst) k_dsb_finish<true><<<batch, DSB_T, 0, st>>>(f);
-        else k_dsb_finish<false><<<batch, DSB_T, 0, st>>>(f);
+        if (q->per_inst) k_dsb_finish<true><<<count, DSB_T, 0, st>>>(f);
+        else k_dsb_finish<false><<<count, DSB_T, 0, st>>>(f);
         PQ_HIP(hipGetLastError());
         PQ_HIP(hipEventRecord(q->ev[7], st));
         ++launches;
@@ -1744,12 +1870,17 @@ int pq_solver_batch_solve(pq_solver_batch* s)
         if (pend_s) { const double t = elapsed(4); dev_ms += t; s_ms += t; }
         dev_ms += elapsed(6);
         const double wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
-        for (int i = 0; i < batch; ++i) {
-            pq_info& I = q->state_h.p[i].info;
-            if (!done && q->state_h.p[i].stage != ST_DONE) I.status = PQ_UNSOLVED;
+        for (int j = 0; j < count; ++j) {
+            DsbState& S = q->state_h.p[rw.inst(j)];
+            pq_info& I = S.info;
+            if (!done && S.stage != ST_DONE) I.status = PQ_UNSOLVED;
             solved += I.status == PQ_SOLVED;
-            I.solve_time = wall * 1e-3;  // (the batch's)
+            I.solve_time = wall * 1e-3;  // (the call's)
             I.run_time = (s->updated ? I.update_time : I.setup_time) + I.solve_time;
+        }
+        if (q->per_inst) {  // every instance of the call was factored in the first round; the KKT system's lists are all in use again once no other one waits
+            for (int j = 0; j < count; ++j) q->relisted_h[rw.inst(j)] = 0;
+            if (round > 0 && std::find(q->relisted_h.begin(), q->relisted_h.end(), (char)1) == q->relisted_h.end()) ksb_lists_factored(ks);
         }
         s->wall_ms = wall; s->device_ms = dev_ms; s->factor_ms = f_ms; s->solve_ms = s_ms; s->rounds = (int)round; s->launches = launches;
         s->solved = true;
@@ -1758,6 +1889,24 @@ int pq_solver_batch_solve(pq_solver_batch* s)
     });
     if (rc != PQ_OK) return rc;
     return rc_loop != PQ_OK ? rc_loop : solved;
+}
+
+int pq_solver_batch_solve(pq_solver_batch* s)
+{
+    if (!s) return fail(PQ_ERR_INVALID, "null argument");
+    if (!s->pr) {
+        s->invalid_info.status = PQ_UNSOLVED;
+        return fail(PQ_ERR_INVALID, "dense solver batch: solve before setup");
+    }
+    return dsb_solve(s, nullptr, s->pr->batch);
+}
+
+int pq_solver_batch_solve_select(pq_solver_batch* s, const int* idx, int count)
+{
+    static const char* const fn = "pq_solver_batch_solve_select";
+    if (int rc = dsb_check_list(fn, s, idx, count)) return rc;
+    if (int rc = dsb_check_entries(fn, s, idx, count, true)) return rc;
+    return dsb_solve(s, idx, count);
 }
 
 const pq_info* pq_solver_batch_info(const pq_solver_batch* s, int instance)
@@ -1780,6 +1929,36 @@ int pq_solver_batch_get_result_mem(pq_solver_batch* s, int field, double* out, i
         const size_t count = (size_t)q->batch * dsb_field_len(q, field);
         hipStream_t st = ksb_stream(q->ks.get());
         if (count) PQ_HIP(hipMemcpyAsync(out, (&q->sets[5].v.x)[field], sizeof(double) * count, mem == PQ_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+        stream_wait(st);
+        return (int)PQ_OK;
+    });
+}
+
+int pq_solver_batch_get_result_select_mem(pq_solver_batch* s, const int* idx, int count, int field, double* out, int mem)
+{
+    static const char* const fn = "pq_solver_batch_get_result_select_mem";
+    if (int rc = dsb_check_list(fn, s, idx, count)) return rc;
+    if (!out) return fail(PQ_ERR_INVALID, "%s: out is null", fn);
+    if (field < 0 || field > 9) return fail(PQ_ERR_INVALID, "%s: field %d: 0 .. 9 wanted", fn, field);
+    if (kb_bad_mem(mem)) return fail(PQ_ERR_INVALID, "%s: bad mem %d", fn, mem);
+    if (int rc = dsb_check_entries(fn, s, idx, count, false)) return rc;
+    if (!s->solved) return fail(PQ_ERR_INVALID, "%s: no solve yet", fn);
+    return guarded([&] {
+        PQ_HIP(hipSetDevice(s->device));
+        DsbProblem* q = s->pr.get();
+        const size_t len = dsb_field_len(q, field);
+        if (!len) return (int)PQ_OK;
+        hipStream_t st = ksb_stream(q->ks.get());
+        DBuf<double> stage;  // a host out: [count][len] on the device first
+        if (mem == PQ_MEM_HOST) stage.alloc((size_t)count * len);
+        double* to = mem == PQ_MEM_HOST ? stage.p : out;
+        const double* from = (&q->sets[5].v.x)[field];
+        for (int j0 = 0; j0 < count; j0 += q->batch) {  // (the list's buffer holds `batch` entries: a longer list goes up in pieces, each read by its gather before the next)
+            const int part = std::min(q->batch, count - j0);
+            const DsbRows rw = dsb_rows_select(q, st, idx + j0, part);
+            kb_gather_rows(st, to + (size_t)j0 * len, from, rw.dev, (size_t)part, sizeof(double) * len);
+        }
+        if (mem == PQ_MEM_HOST) PQ_HIP(hipMemcpyAsync(out, stage.p, sizeof(double) * (size_t)count * len, hipMemcpyDeviceToHost, st));
         stream_wait(st);
         return (int)PQ_OK;
     });
